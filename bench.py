@@ -24,11 +24,16 @@ process group it ends up in does not have N ranks.  Two modes (--mgpu-mode):
       i % N, factorised there and its factor broadcast, every column loop runs row-sharded and the codes / scales are
       all-gathered; every rank ends with the same packed block.
 Total work is fixed -> "strong" scaling; nothing is divided by N.
+A plain run sets up, warms up, times the K steps and prints the one JSON line (`roofline` there describes the kernel that
+dominates the step, from the timed steps' own breakdown).  Everything else runs only with --full (each part can still be switched
+off there by its --no-* flag):
 `e2e` times the thing the north_star names once more, without extrapolation: a full 32-block model through
 prepare -> run_fn (calibration capture) -> convert, wall-clock.  The second half of the metric, the fused INT4->bf16
-dequant-GEMM, is timed on the BASELINE shapes and reported in `dequant_gemm`; `roofline` describes the kernel that
-dominates the step (chosen from the measured breakdown); `awq_block` / `smoothquant_block` are BASELINE configs #3 / #4
-at full layer size (one block each).
+dequant-GEMM, is timed on the BASELINE shapes and reported in `dequant_gemm`; `awq_block` / `smoothquant_block` are BASELINE
+configs #3 / #4 at full layer size (one block each); `ceilings` / `per_layer` come from a fresh child process; `cpu_baseline`
+times the oracle on the host's cores.  With N > 1 ranks a plain run keeps `e2e`, because the headline `value` is its wall-clock.
+--dump-outputs DIR writes what the last timed step produced as float32 .npy files (dump_outputs); the inputs are seeded, so
+two builds run with the same arguments can be compared output for output.
 """
 
 import argparse
@@ -1023,6 +1028,46 @@ def _run_child(mode, timeout_s=600):
         return None
 
 
+DUMP_MAX_ELEMS = 1 << 19  # per array: larger outputs are dumped as a fixed, seeded sample of this many elements (2 MiB in float32)
+
+
+def dump_outputs(out_dir, block, hidden):
+    """--dump-outputs: what the last timed step handed its caller, as float32 DIR/<name>.npy.  Per packed Linear of the quantised block
+    (MI355XWeightOnlyLinear.unpack()): `<module>.codes`, `<module>.scales`, `<module>.zeros`; `hidden_states` = the block's outputs on the
+    calibration set (the next block's inputs; None in the layer-per-GPU mode, where they are the float model's).  An array of more than
+    DUMP_MAX_ELEMS elements is replaced by the elements at fixed indices (`<name>.sample<n>`, drawn from a seeded generator), so the same
+    arguments always dump the same positions: at most 22 arrays x 2 MiB in all."""
+    import numpy as np
+
+    from neural_compressor_amd.torch.algorithms.weight_only.modules import MI355XWeightOnlyLinear
+
+    os.makedirs(out_dir, exist_ok=True)
+    g = torch.Generator().manual_seed(20240)
+    written = 0
+
+    def save(name, t):
+        nonlocal written
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = torch.randint(0, t.numel(), (DUMP_MAX_ELEMS,), generator=g).to(t.device)
+            t, name = t.reshape(-1)[idx], f"{name}.sample{DUMP_MAX_ELEMS}"
+        a = t.detach().float().cpu().numpy()
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+        written += a.nbytes
+
+    for name, m in block.named_modules():
+        if isinstance(m, MI355XWeightOnlyLinear):
+            p = m.unpack()
+            for key, out in (("int_weight", "codes"), ("scales", "scales"), ("zp", "zeros")):
+                if p[key] is not None:
+                    save(f"{name}.{out}", p[key])
+    if hidden is not None:
+        # the same number of fixed positions from every calibration sample's output (one tensor per sample)
+        per = max(1, DUMP_MAX_ELEMS // len(hidden))
+        save("hidden_states.sample", torch.cat([h.reshape(-1)[torch.randint(0, h.numel(), (per,), generator=g).to(h.device)] for h in hidden]))
+    torch.cuda.synchronize()
+    assert written <= 64 << 20, f"dump of {written} bytes exceeds 64 MiB"
+
+
 def compact_line(full):
     """The ONE stdout line: the contract's keys, `roofline` and `cpu_baseline` as flat scalars (the driver's record keeps the scalars of
     these two objects and drops nested lists), everything else in short form.  The full record goes to --detail-file."""
@@ -1120,15 +1165,22 @@ def main():
     ap.add_argument("--no-e2e", action="store_true")
     ap.add_argument("--no-extra-configs", action="store_true")
     ap.add_argument("--no-per-layer", action="store_true")
-    ap.add_argument("--e2e-configs", action="store_true", help="also run BASELINE configs #3 (AWQ, 32 blocks) and #4 (SmoothQuant, 40 blocks) end to end (~4 min)")
+    ap.add_argument("--full", action="store_true", help="also run everything beyond the headline: e2e, dequant-GEMM / W8A8 shapes, ceilings + per-layer "
+                                                          "child, AWQ / SmoothQuant / RTN configs, CPU baseline; off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps write what the last one produced to DIR/<name>.npy "
+                                                                          "(float32, a fixed seeded sample of the large arrays; see dump_outputs)")
+    ap.add_argument("--e2e-configs", action="store_true", help="with --full: also run BASELINE configs #3 (AWQ, 32 blocks) and #4 (SmoothQuant, 40 blocks) end to end (~4 min)")
     ap.add_argument("--mgpu-mode", choices=("layer", "exact"), default="layer", help="N > 1: one block per GPU on float activations (north_star) | exact reference semantics")
     ap.add_argument("--layer-on-one-gpu", action="store_true", help="N = 1: time the layer-per-GPU mode's round (float forward + quantise, no exchange)")
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="llama2-7b", help="llama2-70b: BASELINE config #5's block shape (hidden 8192, ffn 28672, GQA 64:8)")
-    ap.add_argument("--detail-file", default=os.path.join(ROOT, "gpurun_out", "bench_detail.json"),
-                    help="the full per-row record (cold / graph / cache-resident variants of every row); the stdout line is its compact form")
+    ap.add_argument("--detail-file", default=None,
+                    help="the full per-row record (cold / graph / cache-resident variants of every row); the stdout line is its compact form "
+                         "(default with --full: bench_out/bench_detail.json; a plain run writes one only when this is given)")
     ap.add_argument("--full-line", action="store_true", help="print the full record on stdout instead of the compact line")
     ap.add_argument("--child", choices=("per_layer",), default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.child == "per_layer":
         # a fresh process on an otherwise idle chip (the parent waits): the measured ceilings and the per-layer calls
         device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
@@ -1173,6 +1225,10 @@ def main():
     # `live`: the multi-GPU paths run -- N > 1 ranks, or ONE rank with INC_MI355X_DIST_SINGLE_RANK=1 (RCCL bring-up on a 1-GPU box: the
     # process group, the collective wrappers and the drivers' exchange / broadcast code execute over a world of one rank)
     live = D.live()
+    if not args.full:
+        # a plain run measures the headline only; with N > 1 ranks that includes e2e, whose wall-clock is the headline `value` there
+        args.no_gemm = args.no_per_layer = args.no_extra_configs = args.no_cpu_baseline = True
+        args.no_e2e = args.no_e2e or not live
     layer_mode = args.mgpu_mode == "layer" and (live or args.layer_on_one_gpu)
     if live:
         # ONE model, N ranks.  layer: one block per rank on the float model's activations; exact: samples sharded, Hessians reduced to
@@ -1333,6 +1389,12 @@ def main():
     )
     if round_timing:
         result["layer_round_ms"] = {k.replace("_s", ""): round(v * 1e3 / args.steps, 2) for k, v in round_timing.items() if k != "_"}
+    if args.dump_outputs and rank == 0:
+        last = args.warmup + args.steps - 1
+        if layer_mode:  # the block this rank quantised in the last timed round; the cached hidden states are float-model activations there
+            last = next(b for b in range(last * world, (last + 1) * world) if D.owner_of_block(b, world) == rank)
+        dump_outputs(args.dump_outputs, blocks[last], None if layer_mode else rq._hidden_list())
+        note(f"outputs of the last timed step written to {args.dump_outputs}")
     del model, rq, blocks
     torch.cuda.empty_cache()
     if not args.no_e2e:
@@ -1400,14 +1462,16 @@ def main():
             result["rtn_config1"]["cpu_port_s"] = cpu["t_rtn_config1"]
     if rank == 0:
         line = result if args.full_line else compact_line(result)
-        try:
-            os.makedirs(os.path.dirname(args.detail_file), exist_ok=True)
-            with open(args.detail_file, "w") as f:
-                json.dump(result, f, indent=1)
-            if not args.full_line:
-                line["detail_file"] = os.path.relpath(args.detail_file, ROOT)
-        except OSError as e:  # a read-only checkout: the compact line is still complete on its own
-            print(f"[bench] could not write {args.detail_file}: {e}", file=sys.stderr)
+        detail_file = args.detail_file or (os.path.join(ROOT, "bench_out", "bench_detail.json") if args.full else None)
+        if detail_file:
+            try:
+                os.makedirs(os.path.dirname(os.path.abspath(detail_file)), exist_ok=True)
+                with open(detail_file, "w") as f:
+                    json.dump(result, f, indent=1)
+                if not args.full_line:
+                    line["detail_file"] = os.path.relpath(detail_file, ROOT)
+            except OSError as e:  # a read-only checkout: the compact line is still complete on its own
+                print(f"[bench] could not write {detail_file}: {e}", file=sys.stderr)
         print(json.dumps(line))
     if live:
         torch.distributed.barrier()
