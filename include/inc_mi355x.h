@@ -150,6 +150,31 @@ int inc_woq_gemm_multi(int n, const void* x, int xdtype, const int32_t* const* q
                        const int32_t* const* qzeros, const void* const* bias, void* const* y, int64_t M, const int64_t* N,
                        int64_t K, int group_size, int bits, void* workspace, int64_t workspace_bytes, inc_stream_t stream);
 
+/* ---- K4d: fused 4-bit code-book / row-packed integer dequant + GEMM ------------------------ *
+ * == INCWeightOnlyLinear.forward (modules.py:594-610) for the layouts that are not the optimum one: F.linear(x, recover(x.dtype), bias)
+ *   with recover (modules.py:413-443) done in registers, the dense weight never materialised.  NF4 / FP4 code books and integer
+ *   modules packed with use_optimum_format=False, compression_dim = 1, bits = 4:
+ *     qweight [N, row_bytes] bytes (any of the int8 / 16 / 32 / 64 containers of pack_rows: field k of row n is the low nibble of byte
+ *       n * row_bytes + k/2 for even k, the high one for odd k);  row_bytes >= K/2, a multiple of 16
+ *     table16 [16] fp32 in HOST memory, indexed by the field f: LUT[(f + 8) & 15] for a code book, f sign-extended for sym
+ *       integers, f for asym integers
+ *     scales [N,G] of scale_dtype (fp32 / fp16 / bf16);  qzeros NULL or [N, zrow_bytes] bytes with the 4-bit zero point of group g
+ *       at byte g/2 (same nibble order)
+ *     W[n,k] = rx( rs( (table16[f] - zp[n,g]) * scales[n,g] ) ), g = k / group_size, in fp32; rs rounds to scale_dtype when
+ *       `scale_round` is set (integers: inc_dequant_ints's rule; with fp32 scales and an fp16 xdtype that rule rounds the exact
+ *       product once to fp16) and is the identity otherwise (code books: the product stays fp32); rx rounds to xdtype.  So
+ *       W == recover(dtype=xdtype) bit for bit.  The fused route serves up to 256 rows of x (MI355XWeightOnlyLinear.LUT_MAX_M).
+ *   x [M,K], y [M,N] and bias [N] (or NULL) of `xdtype` (INC_BF16 / INC_F16), fp32 accumulate in a fixed order: repeated calls are
+ *   bit-identical.  INC_ERR_UNSUPPORTED (nothing launched) unless K % 32 == 0, group_size a multiple of 32 or one group
+ *   (-1 / >= K), x and qweight 16-byte aligned.
+ *   `workspace` (inc_woq_gemm_lut_workspace_bytes bytes; 0 = none needed): its first 16 KiB are split-K arrival counters that
+ *   MUST BE ZERO when the workspace is first used (the kernel re-arms them, as inc_woq_gemm's), the fp32 partials follow.  One
+ *   workspace must not be shared by calls that may run concurrently (different streams).                                   */
+int64_t inc_woq_gemm_lut_workspace_bytes(int64_t M, int64_t N, int64_t K);
+int inc_woq_gemm_lut(const void* x, int xdtype, const uint8_t* qweight, int64_t row_bytes, const float* table16, const void* scales,
+                     int scale_dtype, int scale_round, const uint8_t* qzeros, int64_t zrow_bytes, const void* bias, void* y, int64_t M,
+                     int64_t N, int64_t K, int64_t G, int group_size, void* workspace, int64_t workspace_bytes, inc_stream_t stream);
+
 /* ---- K7: group-wise round-to-nearest quantisation ------------------------------------------ *
  * == quant_tensor / qdq_weight_sym / qdq_weight_asym (weight_only/utility.py:272-436, :199, :162).
  *   w [N,K] of `wdtype`, quantised per row in groups of `group_size` along K (tail group = the

@@ -265,6 +265,7 @@ class WoqGemmCall:
 
     __slots__ = ("dev", "dev_index", "dtype", "dt", "N", "K", "G", "gs", "bits", "qw", "sc", "qz", "gi", "bi", "keep", "need", "fn",
                  "bias_conv", "versions", "tag")
+    lut = False  # (WoqGemmLutCall: True)
 
     def __init__(self, qweight, scales, qzeros, bias, N, K, group_size, bits, dtype, g_idx=None):
         dev = _dev(qweight, scales, qzeros, bias, g_idx)
@@ -322,6 +323,88 @@ class WoqGemmCall:
                              self.G, self.gs, self.bits, wp, wn, stream)
         if rc != 0:
             check(rc, "inc_woq_gemm")
+        return y
+
+
+def woq_gemm_lut(x2d, qweight, table16, scales, qzeros, bias, N, K, group_size, scale_round):
+    """y[M,N] = x[M,K] @ recover(x.dtype)^T + bias for 4-bit row-packed modules (NF4 / FP4 code books, integer modules with
+    use_optimum_format=False, compression_dim = 1), fused (include/inc_mi355x.h: inc_woq_gemm_lut; reference modules.py:594-610).
+
+    qweight [N, words] of any integer container, scales [N,G] fp32 / fp16 / bf16, qzeros [N, words] or None; table16: 16 floats on
+    the host, indexed by the stored 4-bit field (see the header); scale_round: round (table - zp) * scale to the scale dtype first
+    (the integer formats' rule) or not (code books)."""
+    return WoqGemmLutCall(qweight, table16, scales, qzeros, bias, N, K, group_size, scale_round, x2d.dtype)(x2d)
+
+
+class WoqGemmLutCall:
+    """inc_woq_gemm_lut with the module side resolved once (the decode path, like WoqGemmCall): the bias converted to the compute
+    dtype, the table as a host array, the row sizes in bytes; per call only x, y, the stream and the (device, stream) workspace.
+    `current()` has WoqGemmCall's contract (same tensors, version counters unchanged)."""
+
+    lut = True
+
+    def __init__(self, qweight, table16, scales, qzeros, bias, N, K, group_size, scale_round, dtype):
+        import ctypes
+
+        dev = _dev(qweight, scales, qzeros, bias)
+        if dtype is not torch.bfloat16 and dtype is not torch.float16:
+            raise TypeError("woq_gemm_lut computes in bf16 or fp16")
+        if len(table16) != 16:
+            raise ValueError("table16 holds the 16 values of a 4-bit field")
+        self.keep = (qweight, scales, qzeros, bias)
+        self.versions = tuple(None if t is None else t._version for t in self.keep)
+        if bias is not None and bias.dtype != dtype:
+            bias = bias.to(dtype)  # converted once
+        self.bias_conv = bias
+        self.dev, self.dev_index, self.dtype = dev, dev.index if dev.index is not None else torch.cuda.current_device(), dtype
+        self.dt = INC_BF16 if dtype is torch.bfloat16 else INC_F16
+        self.N, self.K, self.G, self.gs = N, K, scales.shape[1], group_size
+        self.table = (ctypes.c_float * 16)(*[float(v) for v in table16])
+        self.sdt, self.rnd = dtype_code(scales.dtype), int(bool(scale_round))
+        self.qw, self.row_bytes = qweight.data_ptr(), qweight.shape[1] * qweight.element_size()
+        self.qz, self.zrow_bytes = (None, 0) if qzeros is None else (qzeros.data_ptr(), qzeros.shape[1] * qzeros.element_size())
+        self.sc, self.bi = scales.data_ptr(), _ptr(bias)
+        self.need = {}
+
+    # a cache, not state: copies and pickles of the owning module start without it
+    def __deepcopy__(self, memo):
+        return None
+
+    def __reduce__(self):
+        return (_none, ())
+
+    def current(self, qweight, scales, qzeros, bias, owner_g_idx=None):
+        k, v = self.keep, self.versions
+        return (k[0] is qweight and k[1] is scales and k[2] is qzeros and k[3] is bias and owner_g_idx is None
+                and qweight._version == v[0] and scales._version == v[1] and (qzeros is None or qzeros._version == v[2])
+                and (bias is None or bias._version == v[3]))
+
+    def __call__(self, x2d):
+        """x2d: contiguous [M, K] of the call's dtype on the call's device."""
+        M = x2d.shape[0]
+        if x2d.data_ptr() % 16:
+            x2d = x2d.clone()  # the kernel reads x in 16-byte pieces; a fresh allocation is aligned
+        y = torch.empty((M, self.N), dtype=self.dtype, device=self.dev)
+        need = self.need.get(M)
+        if need is None:
+            need = self.need[M] = lib.inc_woq_gemm_lut_workspace_bytes(M, self.N, self.K)
+        idx = self.dev_index
+        stream = _raw_stream(idx)
+        wp, wn = None, 0
+        if need > 0:
+            buf = _ws_cache.get((idx, stream))
+            if buf is None or buf.numel() < need:
+                buf = _workspace(self.dev, need)
+            wp, wn = buf.data_ptr(), buf.numel()
+        args = (x2d.data_ptr(), self.dt, self.qw, self.row_bytes, self.table, self.sc, self.sdt, self.rnd, self.qz, self.zrow_bytes,
+                self.bi, y.data_ptr(), M, self.N, self.K, self.G, self.gs, wp, wn, stream)
+        if _cur_device() == idx:
+            rc = lib.inc_woq_gemm_lut(*args)
+        else:
+            with torch.cuda.device(self.dev):
+                rc = lib.inc_woq_gemm_lut(*args)
+        if rc != 0:
+            check(rc, "inc_woq_gemm_lut")
         return y
 
 

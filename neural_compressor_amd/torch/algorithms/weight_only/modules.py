@@ -281,7 +281,8 @@ class MI355XWeightOnlyLinear(WeightOnlyLinear):
         call = d.get("_call")
         if call is not None and x.dtype is call.dtype and x.device == call.dev and x.is_contiguous() and x.numel() > 0 and x.shape[-1] == call.K:
             bufs = self._buffers
-            if call.current(bufs["qweight"], bufs["scales"], bufs["qzeros"], bufs.get("bias", d.get("bias")), bufs.get("g_idx", d.get("g_idx"))):
+            if (call.current(bufs["qweight"], bufs["scales"], bufs.get("qzeros"), bufs.get("bias", d.get("bias")), bufs.get("g_idx", d.get("g_idx")))
+                    and (not call.lut or (self.LUT_FUSED and x.numel() <= self.LUT_MAX_M * call.K))):
                 y = call(x if x.dim() == 2 else x.view(-1, call.K))
                 return y if x.dim() == 2 else y.view(*x.shape[:-1], call.N)
         if x.dtype not in (torch.bfloat16, torch.float16):
@@ -296,6 +297,8 @@ class MI355XWeightOnlyLinear(WeightOnlyLinear):
         d["_call"] = None
         if plan == "fused" and self._fused_max_m is not None and x2d.shape[0] > self._fused_max_m:
             plan = "dense"  # (a group size the fast kernels do not take: see _forward_plan)
+        if plan == "fused_lut" and x2d.shape[0] > self.LUT_MAX_M:
+            plan = "dense"  # (prefill-sized batches: see LUT_MAX_M)
         if plan == "fused" and self._fused_max_m is not None:
             y = ops.woq_gemm(x2d, self.qweight, self.scales, self.qzeros, self.bias, self.out_features, self.in_features, self.group_size, self.bits)
         elif plan == "fused":
@@ -310,6 +313,12 @@ class MI355XWeightOnlyLinear(WeightOnlyLinear):
                 x2d.index_select(1, self._k_order), self._qweight_sorted, self.scales, self.qzeros, self.bias,
                 self.out_features, self.in_features, self.group_size, self.bits,
             )
+        elif plan == "fused_lut":
+            # 4-bit row-packed modules (NF4 / FP4 code books, non-optimum integers): inc_woq_gemm_lut decodes the fields through a
+            # 16-entry table per (row, group) in registers; recover() never runs
+            call = d["_call"] = ops.WoqGemmLutCall(self.qweight, self._lut_table, self.scales, getattr(self, "qzeros", None), self.bias,
+                                                   self.out_features, self.in_features, self.group_size, self._lut is None, x2d.dtype)
+            y = call(x2d)
         elif plan == "fused_g_idx":
             # an irregular g_idx (not a permutation of whole groups): inc_woq_gemm's general tile kernel reads scale / zero of
             # group g_idx[k] per element (reference modules.py:427-431 semantics), still without a dense weight
@@ -327,6 +336,13 @@ class MI355XWeightOnlyLinear(WeightOnlyLinear):
     # widths other than 4 / 8 bits: True = multiply through inc_woq_gemm's per-element tile form (no dense weight ever exists; 8-10 x
     # slower), False = HIP recover() into a transient dense weight + the library GEMM (what the reference's forward does on its CPU)
     ODD_WIDTH_FUSED = False
+    # 4-bit row-packed modules (compression_dim = 1, dtype int / nf4 / fp4 / fp4_e2m1 / fp4_e2m1_bnb, no g_idx, K % 32 == 0, groups of
+    # 32 k multiples): True = inc_woq_gemm_lut, False = HIP recover() into a transient dense weight + the library GEMM
+    LUT_FUSED = True
+    # ... up to this many rows of x: NF4 g32 through inc_woq_gemm_lut is 2.2-3.1 x faster than the dense route at M = 256 and as fast or
+    # slower from M = 1024 on (272.1 vs 260.2 us at 4096^2, 759.3 vs 736.6 us at 11008 x 4096; 2.8-3.5 x slower at M = 4096:
+    # profiles/r7/lut_gemm_time.log), so larger batches keep HIP recover() + the library GEMM
+    LUT_MAX_M = 256
 
     def _forward_plan(self):
         """Pick the forward route once per packed state.  A per-element `g_idx` (GPTQ act_order, HF desc_act
@@ -335,7 +351,7 @@ class MI355XWeightOnlyLinear(WeightOnlyLinear):
         K-sorted copy of the packed words with only an activation gather per call."""
         # in-place re-packing / load_state_dict bump the tensors' version counters -> the plan is rebuilt
         key = (self.qweight.data_ptr(), self.qweight._version,
-               None if self.g_idx is None else (self.g_idx.data_ptr(), self.g_idx._version), self.ODD_WIDTH_FUSED)
+               None if self.g_idx is None else (self.g_idx.data_ptr(), self.g_idx._version), self.ODD_WIDTH_FUSED, self.LUT_FUSED)
         if getattr(self, "_plan_key", None) == key:
             return self._plan
         plan = "dense"
@@ -377,8 +393,31 @@ class MI355XWeightOnlyLinear(WeightOnlyLinear):
                         plan = "fused_g_idx"  # groups of uneven size: the library's general kernel looks the group up per k
                 else:
                     plan = "fused_g_idx"
+        if not self.use_optimum_format and self.LUT_FUSED and self._lut_eligible():
+            plan = "fused_lut"
         self._plan_key, self._plan = key, plan
         return plan
+
+    def _lut_eligible(self):
+        """inc_woq_gemm_lut takes the module (and self._lut_table is its field -> value table)?"""
+        K, gs = self.in_features, self.group_size
+        gs_eff = K if (gs == -1 or gs >= K) else gs
+        has_zp = hasattr(self, "qzeros")
+        if (self.compression_dim != 1 or self.bits != 4 or self.g_idx is not None or K % 32 != 0 or (gs_eff != K and gs_eff % 32 != 0)
+                or self.scales.dtype not in (torch.float32, torch.float16, torch.bfloat16) or not self.scales.is_contiguous()
+                or not self.qweight.is_contiguous() or self.qweight.data_ptr() % 16 or (has_zp and not self.qzeros.is_contiguous())):
+            return False
+        f = list(range(16))
+        if self._lut is not None:  # code book: the stored code is sign-extended, then +8 (unpack)
+            if has_zp:
+                return False  # (recover() of a code book has no zero point)
+            lut = self._lut.cpu().tolist()
+            self._lut_table = [lut[(v + 8) & 15] for v in f]
+        elif "int" in self.dtype:
+            self._lut_table = [float(v) for v in f] if has_zp else [float(v - 16 if v >= 8 else v) for v in f]
+        else:
+            return False
+        return True
 
     def extra_repr(self):
         s = super().extra_repr()
