@@ -175,6 +175,40 @@ int inc_woq_gemm_lut(const void* x, int xdtype, const uint8_t* qweight, int64_t 
                      int scale_dtype, int scale_round, const uint8_t* qzeros, int64_t zrow_bytes, const void* bias, void* y, int64_t M,
                      int64_t N, int64_t K, int64_t G, int group_size, void* workspace, int64_t workspace_bytes, inc_stream_t stream);
 
+/* ---- K4e: weight-only INT4 fused MoE experts ------------------------------------------------- *
+ * == transformers' MixtralExperts.forward (also Qwen2-MoE / Qwen3-MoE / OLMoE experts): for every expert that was hit, gather its
+ *   tokens, act_fn(x Wg^T) * (x Wu^T), times Wd^T, times the routing weight, index_add_ into the output.  Four launches, no host wait:
+ *   inc_moe_route -> inc_woq_moe_gemm(mode 0) -> inc_woq_moe_gemm(mode 1) -> inc_moe_combine, all on `stream`.
+ *   S = T * top_k slots, slot t*k+s = token t, choice s.  E <= 512, S <= 2^22.
+ *
+ *   inc_moe_route: top_k_index [T, top_k] int32 / int64 (index_bytes 4 / 8) -> `route` (inc_moe_route_bytes bytes, int32):
+ *     [0] number of 64-row tiles, then offsets [E+1] (the slots of expert e are positions offsets[e] .. offsets[e+1]-1 of the sorted
+ *     order; offsets[E] = slots with an id in 0..E-1, other ids contribute nothing), order [S] (sorted position -> slot; ascending slot
+ *     inside an expert), pos [S] (slot -> sorted position), tiles [2 * (ceil(S/64) + min(E, S))] (expert, first position).
+ *   inc_woq_moe_gemm: per-expert optimum layout stacked on the expert axis -- qweight [E, K/8, N] int32, scales [E, G, N] fp16,
+ *     qzeros [E, G, N/8] int32 (slice e == MI355XWeightOnlyLinear's buffers for expert e) -- dequantised as inc_woq_dequant (the weight
+ *     equals recover(xdtype) bit for bit), fp32 accumulate in a fixed order (repeated calls are bit-identical):
+ *       mode 0 (gate_up, N = 2I): a = x [T, K]; out [S, I] xdtype, out[p, j] = silu(g) * u, g / u = row order[p]/top_k of x times
+ *              weight rows j / I+j of the expert of position p
+ *       mode 1 (down): a = [S, K] in sorted order (mode 0's output); out [S, N] fp32 = routing_weights[order[p]] * (a[p] . W[n])
+ *              (routing_weights [T, top_k] of wdtype INC_F32 / INC_F16 / INC_BF16)
+ *       mode 2 (plain): a = x [T, K]; out [S, N] fp32 = x[order[p]/top_k] . W[n]
+ *     INC_ERR_UNSUPPORTED (nothing launched) unless xdtype is INC_BF16 / INC_F16, K % 32 == 0, N % 8 == 0, group_size a power of two
+ *     >= 32 dividing K or one group (-1 / >= K), a / qweight / out 16-byte and scales 8-byte aligned.
+ *     `workspace` (inc_woq_moe_gemm_workspace_bytes; 0 = none needed): its first 4 KiB are split-K arrival counters, which MUST BE
+ *     ZERO when the workspace is first used (the kernel re-arms them), then fp32 partials.  One workspace of the largest size serves
+ *     every call shape and both modes in stream order; calls that may run concurrently need their own.
+ *   inc_moe_combine: out [T, H] xdtype, out[t] = sum over s = 0 .. top_k-1 of y[pos[t*k+s]] (y = mode 1's output) in fp32, one rounding. */
+int64_t inc_moe_route_bytes(int64_t T, int top_k, int64_t E);
+int inc_moe_route(const void* top_k_index, int index_bytes, int64_t T, int top_k, int64_t E, int32_t* route, int64_t route_bytes,
+                  inc_stream_t stream);
+int64_t inc_woq_moe_gemm_workspace_bytes(int mode, int64_t T, int top_k, int64_t E, int64_t N, int64_t K);
+int inc_woq_moe_gemm(int mode, const void* a, int xdtype, const int32_t* route, const int32_t* qweight, const uint16_t* scales,
+                     const int32_t* qzeros, const void* routing_weights, int wdtype, void* out, int64_t T, int top_k, int64_t E, int64_t N,
+                     int64_t K, int64_t G, int group_size, void* workspace, int64_t workspace_bytes, inc_stream_t stream);
+int inc_moe_combine(const float* y, const int32_t* route, void* out, int xdtype, int64_t T, int top_k, int64_t E, int64_t H,
+                    inc_stream_t stream);
+
 /* ---- K7: group-wise round-to-nearest quantisation ------------------------------------------ *
  * == quant_tensor / qdq_weight_sym / qdq_weight_asym (weight_only/utility.py:272-436, :199, :162).
  *   w [N,K] of `wdtype`, quantised per row in groups of `group_size` along K (tail group = the

@@ -10,7 +10,7 @@ from ctypes import c_char_p, c_float, c_int, c_int64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libinc_mi355x.so")
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 INC_OK = 0
 INC_F32, INC_F16, INC_BF16 = 0, 1, 2
@@ -38,6 +38,14 @@ SIGNATURES = {
         c_int,
         [_P, c_int, _P, c_int64, _P, _P, c_int, c_int, _P, c_int64, _P, _P, c_int64, c_int64, c_int64, c_int64, c_int, _P, c_int64, _P],
     ),
+    "inc_moe_route_bytes": (c_int64, [c_int64, c_int, c_int64]),
+    "inc_moe_route": (c_int, [_P, c_int, c_int64, c_int, c_int64, _P, c_int64, _P]),
+    "inc_woq_moe_gemm_workspace_bytes": (c_int64, [c_int, c_int64, c_int, c_int64, c_int64, c_int64]),
+    "inc_woq_moe_gemm": (
+        c_int,
+        [c_int, _P, c_int, _P, _P, _P, _P, _P, c_int, _P, c_int64, c_int, c_int64, c_int64, c_int64, c_int64, c_int, _P, c_int64, _P],
+    ),
+    "inc_moe_combine": (c_int, [_P, _P, _P, c_int, c_int64, c_int, c_int64, c_int64, _P]),
     "inc_woq_gemm_multi_workspace_bytes": (c_int64, [c_int, c_int64, _P, c_int64]),
     "inc_woq_gemm_multi": (c_int, [c_int, _P, c_int, _P, _P, _P, _P, _P, c_int64, _P, c_int64, c_int, c_int, _P, c_int64, _P]),
     "inc_groupwise_quant": (

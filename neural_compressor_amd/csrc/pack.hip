@@ -505,7 +505,7 @@ extern "C" {
 // 4: inc_gptq_quantize_layer (the column loop as one call)
 // 8: + inc_codebook_quant_with_scale (quantize_4bit with the caller's scale)
 // 10: + inc_woq_gemm_lut (4-bit code-book / row-packed integer dequant-GEMM)
-int inc_abi_version(void) { return 10; }
+int inc_abi_version(void) { return 11; }
 const char* inc_target_arch(void) { return "gfx950"; }
 const char* inc_error_string(int code) {
   switch (code) {

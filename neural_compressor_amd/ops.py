@@ -473,6 +473,137 @@ class WoqGemmGroupCall:
 
 
 # ---------------------------------------------------------------------------------------------------
+# K4e fused MoE experts (INT4, optimum layout stacked on the expert axis)
+# ---------------------------------------------------------------------------------------------------
+def _index_bytes(top_k_index):
+    if top_k_index.dtype not in (torch.int64, torch.int32):
+        raise TypeError(f"top_k_index must be int64 or int32, got {top_k_index.dtype}")
+    return top_k_index.element_size()
+
+
+def moe_route(top_k_index, num_experts, route=None):
+    """inc_moe_route: top_k_index [T, k] -> the int32 route buffer (offsets, sorted slot order, inverse map, tile table; see the header)."""
+    top_k_index = top_k_index.contiguous()
+    dev = _dev(top_k_index)
+    T, k = top_k_index.shape
+    nbytes = lib.inc_moe_route_bytes(T, k, num_experts)
+    if route is None:
+        route = torch.empty(nbytes // 4, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.inc_moe_route(_ptr(top_k_index), _index_bytes(top_k_index), T, k, num_experts, _ptr(route), route.numel() * 4, _stream()),
+              "inc_moe_route")
+    return route
+
+
+def woq_moe_gemm(mode, a, route, qweight, scales, qzeros, T, top_k, group_size, routing_weights=None, out=None, workspace=None):
+    """inc_woq_moe_gemm.  mode 0: gate_up + SiLU product -> [T*k, N/2] of a.dtype; mode 1: down x routing weight -> fp32 [T*k, N];
+    mode 2: plain -> fp32 [T*k, N] (rows in the route's sorted order).  qweight [E, K/8, N], scales [E, G, N] fp16, qzeros [E, G, N/8]."""
+    dev = _dev(a, route, qweight, scales, qzeros, routing_weights)
+    if a.dtype not in (torch.bfloat16, torch.float16):
+        raise TypeError("woq_moe_gemm computes in bf16 or fp16")
+    E, K8, N = qweight.shape
+    K, G, S = K8 * 8, scales.shape[1], T * top_k
+    if out is None:
+        out = (torch.empty((S, N // 2), dtype=a.dtype, device=dev) if mode == 0 else torch.empty((S, N), dtype=torch.float32, device=dev))
+    need = lib.inc_woq_moe_gemm_workspace_bytes(mode, T, top_k, E, N, K)
+    if need > 0 and (workspace is None or workspace.numel() < need):
+        workspace = torch.zeros(need, dtype=torch.uint8, device=dev)  # counters must start at zero
+    wdt = dtype_code(routing_weights.dtype) if routing_weights is not None else INC_F32
+    with torch.cuda.device(dev):
+        check(lib.inc_woq_moe_gemm(mode, _ptr(a), dtype_code(a.dtype), _ptr(route), _ptr(qweight), _ptr(scales), _ptr(qzeros),
+                                   _ptr(routing_weights), wdt, _ptr(out), T, top_k, E, N, K, G, group_size,
+                                   _ptr(workspace) if need > 0 else None, workspace.numel() if need > 0 else 0, _stream()),
+              "inc_woq_moe_gemm")
+    return out
+
+
+def moe_combine(y, route, T, top_k, num_experts, dtype, out=None):
+    """inc_moe_combine: out[t] = sum_s y[pos(t, s)] in fp32, rounded once to `dtype`."""
+    dev = _dev(y, route)
+    H = y.shape[1]
+    if out is None:
+        out = torch.empty((T, H), dtype=dtype, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.inc_moe_combine(_ptr(y), _ptr(route), _ptr(out), dtype_code(dtype), T, top_k, num_experts, H, _stream()), "inc_moe_combine")
+    return out
+
+
+class WoqMoeCall:
+    """One fused experts forward (route -> gate_up -> down -> combine, four launches, no host wait) with the module side resolved once.
+    The route buffer and the two intermediates are allocated per call (the caching allocator makes that free of device allocations, and
+    inside a graph capture they come from the graph's pool).  Only the split-K workspace is kept: one zero-initialised buffer per call
+    object that serves every call shape (its counters sit in a fixed region) and only grows.  A grown-out buffer is retired, never freed,
+    because a captured graph may still write to it; growth at least doubles the size, so the retired buffers add up to less than the
+    current one, which is below 2 x the largest need: what is held stays below 4 x the largest need.
+    Calls that share the workspace run in stream order (one module, one stream).  `current()` has WoqGemmCall's contract for the six
+    packed buffers."""
+
+    def __init__(self, gate_up, down, E, H, I, group_size):
+        self.keep = tuple(gate_up) + tuple(down)
+        self.versions = tuple(t._version for t in self.keep)
+        self.dev = _dev(*self.keep)
+        self.dev_index = self.dev.index if self.dev.index is not None else torch.cuda.current_device()
+        self.gu, self.dn = [t.data_ptr() for t in gate_up], [t.data_ptr() for t in down]
+        self.E, self.H, self.I, self.gs = E, H, I, group_size
+        self.Gh, self.Gi = gate_up[1].shape[1], down[1].shape[1]
+        self.workspace = None
+        self.retired = []  # grown-out workspaces, kept alive for graphs that captured them
+
+    # a cache, not state: copies and pickles of the owning module start without it
+    def __deepcopy__(self, memo):
+        return None
+
+    def __reduce__(self):
+        return (_none, ())
+
+    def current(self, gate_up, down):
+        tensors = tuple(gate_up) + tuple(down)
+        return all(a is b for a, b in zip(tensors, self.keep)) and tuple(t._version for t in tensors) == self.versions
+
+    def held_bytes(self):
+        """Device memory this call keeps between calls (the workspace and the retired ones)."""
+        return sum(t.numel() for t in ([self.workspace] if self.workspace is not None else []) + self.retired)
+
+    def _workspace(self, T, k):
+        need = max(lib.inc_woq_moe_gemm_workspace_bytes(0, T, k, self.E, 2 * self.I, self.H),
+                   lib.inc_woq_moe_gemm_workspace_bytes(1, T, k, self.E, self.H, self.I))
+        ws = self.workspace
+        if need > 0 and (ws is None or ws.numel() < need):
+            if ws is not None:
+                self.retired.append(ws)
+            size = max(need, 2 * ws.numel() if ws is not None else 0)
+            ws = self.workspace = torch.zeros(size, dtype=torch.uint8, device=self.dev)  # counters must start at zero
+        return ws
+
+    def __call__(self, x2d, top_k_index, top_k_weights):
+        """x2d [T, H] bf16 / fp16, top_k_index [T, k] int64 / int32, top_k_weights [T, k] fp32 / bf16 / fp16, all contiguous on the call's
+        device -> [T, H] of x2d's dtype."""
+        T, k = top_k_index.shape
+        dt = dtype_code(x2d.dtype)
+        E, H, I = self.E, self.H, self.I
+        ws = self._workspace(T, k)
+        wp, wn = (None, 0) if ws is None else (ws.data_ptr(), ws.numel())
+        route = torch.empty(lib.inc_moe_route_bytes(T, k, E) // 4, dtype=torch.int32, device=self.dev)
+        h = torch.empty((T * k, I), dtype=x2d.dtype, device=self.dev)
+        y = torch.empty((T * k, H), dtype=torch.float32, device=self.dev)
+        out = torch.empty((T, H), dtype=x2d.dtype, device=self.dev)
+        stream = _raw_stream(self.dev_index)
+        with torch.cuda.device(self.dev):
+            rc = lib.inc_moe_route(top_k_index.data_ptr(), top_k_index.element_size(), T, k, E, route.data_ptr(), route.numel() * 4, stream)
+            if rc == 0:
+                rc = lib.inc_woq_moe_gemm(0, x2d.data_ptr(), dt, route.data_ptr(), self.gu[0], self.gu[1], self.gu[2], None, INC_F32,
+                                          h.data_ptr(), T, k, E, 2 * I, H, self.Gh, self.gs, wp, wn, stream)
+            if rc == 0:
+                rc = lib.inc_woq_moe_gemm(1, h.data_ptr(), dt, route.data_ptr(), self.dn[0], self.dn[1], self.dn[2], top_k_weights.data_ptr(),
+                                          dtype_code(top_k_weights.dtype), y.data_ptr(), T, k, E, H, I, self.Gi, self.gs, wp, wn, stream)
+            if rc == 0:
+                rc = lib.inc_moe_combine(y.data_ptr(), route.data_ptr(), out.data_ptr(), dt, T, k, E, H, stream)
+        if rc != 0:
+            check(rc, "fused MoE experts forward")
+        return out
+
+
+# ---------------------------------------------------------------------------------------------------
 # K7 group-wise RTN
 # ---------------------------------------------------------------------------------------------------
 def groupwise_quant(w, bits, group_size, scheme, quantile=1.0, full_range=False, return_int=False, inplace=True):

@@ -9,8 +9,9 @@ Per nn.Linear / transformers.Conv1D found in `quant_config`: optional clip searc
 import torch
 
 from ....common.utils import logger
-from ...utils.utility import WOQ_WHITE_LIST, get_accelerator, get_model_device, set_module
+from ...utils.utility import WOQ_WHITE_LIST, get_accelerator, get_model_device, is_fused_experts, set_module
 from ..base_algorithm import Quantizer
+from .experts import quantize_experts, unsupported_reason
 from .modules import MI355XWeightOnlyLinear
 from .utility import FLOAT_MAPPING, quant_tensor, search_clip
 
@@ -46,6 +47,9 @@ class RTNQuantizer(Quantizer):
             logger.debug("use_layer_wise is ignored on MI355X")
         assert isinstance(model, torch.nn.Module), "only support torch module"
         for name, m in list(model.named_modules()):
+            if name in weight_config and is_fused_experts(m):
+                self._convert_experts(model, name, m, weight_config[name], device, use_optimum_format)
+                continue
             if not isinstance(m, WOQ_WHITE_LIST) or name not in weight_config:
                 continue
             cfg = weight_config[name]
@@ -110,3 +114,19 @@ class RTNQuantizer(Quantizer):
             logger.info("RTN: moving the quantised model from %s to %s", model_device, device)
         model.to(device)
         return model
+
+    @staticmethod
+    def _convert_experts(model, name, m, cfg, device, use_optimum_format):
+        """Fused MoE experts (is_fused_experts): INT4 RTN -> MI355XWeightOnlyExperts; anything else stays float with one warning."""
+        cfg = dict(cfg)
+        dtype = cfg.get("dtype", "int")
+        if dtype == "fp32":
+            return
+        if dtype != "int" and "int" in dtype:
+            cfg["bits"], cfg["dtype"] = int(dtype.lstrip("int")), "int"
+        reason = unsupported_reason(m, cfg) or (None if use_optimum_format else "use_optimum_format=False")
+        if reason is not None:
+            logger.warning("RTN leaves %s (%s) in float: %s", name, type(m).__name__, reason)
+            return
+        m.to(device)
+        set_module(model, name, quantize_experts(m, cfg, device))

@@ -24,7 +24,8 @@ import torch
 
 from .... import ops
 from ....common.utils import logger
-from ...utils.utility import set_module
+from ...utils.utility import is_fused_experts, set_module
+from .experts import MI355XWeightOnlyExperts
 from .modules import MI355XWeightOnlyLinear, MulLinear
 
 WEIGHT_NAME = "quantized_weight.pt"  # reference torch/utils/utility.py:56
@@ -78,6 +79,8 @@ def save(model, output_dir="./saved_results", format="default", **kwargs):
     # flags of its own process); the huggingface format IS the optimum (AutoGPTQ) layout and cannot hold them
     layout = {}
     for name, mod in model.named_modules():
+        if isinstance(mod, MI355XWeightOnlyExperts) and fmt == "huggingface":
+            raise ValueError(f"{name} holds packed MoE experts; the huggingface (AutoGPTQ) format has no layout for them")
         if isinstance(mod, MI355XWeightOnlyLinear) and not getattr(mod, "use_optimum_format", True):
             if fmt == "huggingface":
                 raise ValueError(f"{name} was packed with use_optimum_format=False; the huggingface format is the optimum layout")
@@ -134,6 +137,9 @@ def _build(original_model, state, quantization_config, device, layout=None):
     except Exception:  # pragma: no cover
         Conv1D = ()
     for name, module in list(original_model.named_modules()):
+        if is_fused_experts(module) and name + ".gate_up_qweight" in keys:
+            _build_experts(original_model, name, module, state, quantization_config, device)
+            continue
         if not isinstance(module, (torch.nn.Linear, Conv1D) if Conv1D else torch.nn.Linear):
             continue
         if name + ".qweight" not in keys and name + ".linear.qweight" not in keys:
@@ -178,10 +184,23 @@ def _build(original_model, state, quantization_config, device, layout=None):
         if "qweight" in missing.missing_keys or "scales" in missing.missing_keys:
             raise RuntimeError(f"checkpoint is missing packed buffers of {target}")
         set_module(original_model, target, new)
-    left = sorted(k for k in state if k.endswith(".qweight"))
+    left = sorted(k for k in state if k.endswith((".qweight", "_qweight")))
     if left:  # e.g. a module type this loader does not rebuild: never hand back a silently-float model
         raise RuntimeError(f"checkpoint holds packed weights that no module of the model consumed: {left[:4]}{' ...' if len(left) > 4 else ''}")
     return original_model
+
+
+def _build_experts(model, name, module, state, quantization_config, device):
+    """Rebuild MI355XWeightOnlyExperts from its saved buffers (the float module gives E, H, I and the activation)."""
+    E, N2, H = module.gate_up_proj.shape
+    cfg = _module_config(quantization_config, name, module)
+    new = MI355XWeightOnlyExperts(E, H, N2 // 2, bits=cfg.get("bits", 4), group_size=cfg.get("group_size", 32), act_fn=module.act_fn,
+                                  device=device)
+    own = {k: state.pop(f"{name}.{k}").to(device) for k in list(new.state_dict()) if f"{name}.{k}" in state}
+    missing = new.load_state_dict(own, strict=False)
+    if missing.missing_keys:
+        raise RuntimeError(f"checkpoint is missing packed buffers of {name}: {missing.missing_keys}")
+    set_module(model, name, new)
 
 
 def load(model_name_or_path, original_model=None, format="default", device="cuda", **kwargs):

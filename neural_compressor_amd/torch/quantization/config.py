@@ -13,7 +13,9 @@ import torch
 
 from ...common.base_config import BaseConfig, register_config
 from ...common.utils import AWQ, DEFAULT_WHITE_LIST, GPTQ, RTN, SMOOTH_QUANT
-from ..utils.utility import LM_HEAD_NAMES, PRIORITY_AWQ, PRIORITY_GPTQ, PRIORITY_RTN, PRIORITY_SMOOTH_QUANT, WOQ_WHITE_LIST
+from ..utils.utility import (
+    LM_HEAD_NAMES, PRIORITY_AWQ, PRIORITY_GPTQ, PRIORITY_RTN, PRIORITY_SMOOTH_QUANT, WOQ_WHITE_LIST, is_fused_experts,
+)
 
 FRAMEWORK_NAME = "torch"
 
@@ -87,6 +89,11 @@ class RTNConfig(TorchBaseConfig):
         if not self.quant_lm_head:
             self.set_local(LM_HEAD_NAMES, self._fp32_for_lm_head(use_layer_wise=self.use_layer_wise, model_path=self.model_path))
         return super().to_config_mapping(config_list, model_info)
+
+    @staticmethod
+    def get_model_info(model: torch.nn.Module):
+        """Every Linear / Conv1D, and the fused MoE experts modules (is_fused_experts), which only RTN packs."""
+        return [(name, type(m).__name__) for name, m in model.named_modules() if isinstance(m, WOQ_WHITE_LIST) or is_fused_experts(m)]
 
     @classmethod
     def get_config_set_for_tuning(cls):

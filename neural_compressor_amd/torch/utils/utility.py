@@ -20,6 +20,21 @@ except Exception:  # pragma: no cover
     transformers = None
     WOQ_WHITE_LIST = (torch.nn.Linear,)
 
+def is_fused_experts(module):
+    """A transformers MoE experts module that RTN packs (Mixtral / Qwen2-MoE / Qwen3-MoE / OLMoE `*Experts`), recognised by shape:
+    3-D `gate_up_proj [E, 2I, H]` and `down_proj [E, H, I]`, no bias parameters, an `act_fn`.  GPT-OSS experts ([E, H, 2I] with
+    `*_bias`) do not match."""
+    gu, dn = getattr(module, "gate_up_proj", None), getattr(module, "down_proj", None)
+    if not isinstance(gu, torch.Tensor) or not isinstance(dn, torch.Tensor) or gu.dim() != 3 or dn.dim() != 3:
+        return False
+    E, N2, H = gu.shape
+    if N2 % 2 or tuple(dn.shape) != (E, H, N2 // 2):
+        return False
+    if any("bias" in n for n, _ in module.named_parameters(recurse=False)):
+        return False
+    return hasattr(module, "act_fn")
+
+
 LM_HEAD_NAMES = [".*lm_head", ".*output_layer", ".*embed_out"]  # reference torch/utils/constants.py:69
 PRIORITY_GPTQ, PRIORITY_RTN, PRIORITY_AWQ = 90, 80, 70  # reference torch/utils/constants.py:45-48
 PRIORITY_SMOOTH_QUANT = 60

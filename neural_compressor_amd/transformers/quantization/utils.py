@@ -17,6 +17,7 @@ import torch
 
 from ...common.utils import logger
 from ...torch.quantization import AWQConfig, GPTQConfig, RTNConfig, convert, prepare
+from ...torch.utils.utility import is_fused_experts
 
 
 def _as_batches(dataset, tokenizer, max_length, n_samples, batch_size):
@@ -88,6 +89,9 @@ def convert_to_quantized_model(model, config, device="cuda", for_inference=True)
         quant_config = RTNConfig(dtype=dtype, bits=config.bits, use_sym=config.sym, group_size=config.group_size,
                                  use_layer_wise=False, model_path=config.model_path, quant_lm_head=config.quant_lm_head)
         _exclude(quant_config, RTNConfig, config.modules_to_not_convert)
+        for experts_type in {type(m) for m in model.modules() if is_fused_experts(m)}:
+            # the front-end's models and save_pretrained checkpoints are AutoGPTQ-shaped, which has no layout for fused experts
+            quant_config.set_local(experts_type, RTNConfig(dtype="fp32"))
         logger.info("Do RTN algorithm with config %s", quant_config)
         model = convert(prepare(model, quant_config))
     elif method == "gptq":
