@@ -274,6 +274,20 @@ int inc_gptq_hessian_accum_multi(int n, const void* const* xs, int xdtype, int64
                                  const int64_t* ldxs, float* const* Hs, const float* betas, const float* alphas,
                                  void* workspace, int64_t workspace_bytes, inc_stream_t stream);
 
+/* ---- K5e: the same update for ALL experts of a fused MoE module, from routed rows ------------ *
+ * == GPTQ.add_batch (weight_only/gptq.py:1111-1141) of every expert as if it were an nn.Linear fed the rows routed to it.
+ *   `route` is the buffer inc_moe_route wrote for top_k_index [T, top_k] and E experts (offsets [E+1], order [S]; K4e above).
+ *   mode 0 (gather): a = x [T, K]; the rows of expert e are x[order[p] / top_k], p = offsets[e] .. offsets[e+1]-1 (gate_up Hessian)
+ *   mode 1 (sorted): a [S, K] already in the route's sorted order (down Hessian, fed with silu(g) * u)
+ *   H [E, K, K] fp32, rows [E] int64 (device): rows folded so far.  Per expert with c_new = offsets[e+1] - offsets[e] > 0, c = rows[e]:
+ *     H[e] <- H[e] * c/(c+c_new) + 2/(c+c_new) * X_e^T X_e  (c = 0: H[e] is overwritten, not read),  rows[e] <- c + c_new
+ *   on the tiles on / above the diagonal only (inc_gptq_hessian_finalize works on each H[e] unchanged).  An expert with c_new = 0 is
+ *   not touched.  In stream order, no host wait (the grid depends on E and K only); fixed summation order, no atomics: repeated calls
+ *   on the same inputs are bit-identical.  16-bit inputs: bf16 / f16 MFMA, fp32 accumulation; fp32 inputs: exact-fp32 MFMA (untuned).
+ *   INC_ERR_UNSUPPORTED (nothing launched): E > 512, T * top_k > 2^22, K % 32 != 0, a / H not 16-byte aligned.              */
+int inc_gptq_hessian_accum_routed(const void* a, int xdtype, int mode, const int32_t* route, int64_t T, int top_k, int64_t E,
+                                  int64_t K, float* H, int64_t* rows, inc_stream_t stream);
+
 /* == GPTQ.fasterquant prologue (gptq.py:1186-1189, 1221-1227): mirror the upper triangle to the
  *   lower, dead[i] = (H[i,i]==0) -> H[i,i]=1, damp = percdamp*mean(diag(H)), H[i,i] += damp.
  *   dead: uint8 [K] out.  workspace: >= 16 bytes.                                               */

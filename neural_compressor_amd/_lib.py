@@ -10,7 +10,7 @@ from ctypes import c_char_p, c_float, c_int, c_int64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libinc_mi355x.so")
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 INC_OK = 0
 INC_F32, INC_F16, INC_BF16 = 0, 1, 2
@@ -59,6 +59,7 @@ SIGNATURES = {
     "inc_gptq_hessian_accum": (c_int, [_P, c_int, c_int64, c_int64, c_int64, _P, c_float, c_float, _P]),
     "inc_gptq_hessian_accum_multi": (c_int, [c_int, _P, c_int, c_int64, _P, _P, _P, _P, _P, _P, c_int64, _P]),
     "inc_gptq_hessian_accum_multi_workspace_bytes": (c_int64, []),
+    "inc_gptq_hessian_accum_routed": (c_int, [_P, c_int, c_int, _P, c_int64, c_int, c_int64, c_int64, _P, _P, _P]),
     "inc_gptq_hessian_finalize": (c_int, [_P, c_int64, c_float, _P, _P, _P]),
     "inc_gptq_prepare_weight": (c_int, [_P, c_int, _P, _P, c_int64, c_int64, _P]),
     "inc_gptq_find_params": (

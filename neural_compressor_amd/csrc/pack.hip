@@ -505,7 +505,8 @@ extern "C" {
 // 4: inc_gptq_quantize_layer (the column loop as one call)
 // 8: + inc_codebook_quant_with_scale (quantize_4bit with the caller's scale)
 // 10: + inc_woq_gemm_lut (4-bit code-book / row-packed integer dequant-GEMM)
-int inc_abi_version(void) { return 11; }
+// 12: + inc_gptq_hessian_accum_routed (GPTQ Hessians of fused MoE experts from routed rows)
+int inc_abi_version(void) { return 12; }
 const char* inc_target_arch(void) { return "gfx950"; }
 const char* inc_error_string(int code) {
   switch (code) {

@@ -517,6 +517,38 @@ def woq_moe_gemm(mode, a, route, qweight, scales, qzeros, T, top_k, group_size, 
     return out
 
 
+def gptq_hessian_accum_routed(H, rows, a, route, T, top_k, sorted_rows=False):
+    """inc_gptq_hessian_accum_routed: the GPTQ Hessians of all experts of one fused module from one forward, in stream order.
+    H [E, K, K] fp32, rows [E] int64 (rows folded so far, advanced by the call), route = moe_route(top_k_index [T, top_k], E).
+    sorted_rows=False: a = x [T, K], expert e folds the rows x[order[p] // top_k] of its range (gate_up); True: a [T * top_k, K] in the
+    route's sorted order (down).  Returns False (nothing launched) when the library declines the shape: the caller then loops over
+    gptq_hessian_accum on host-sliced ranges."""
+    if H.dim() != 3 or H.shape[1] != H.shape[2] or H.dtype != torch.float32:
+        raise ValueError(f"H must be fp32 [E, K, K], got {tuple(H.shape)} {H.dtype}")
+    E, K = H.shape[0], H.shape[1]
+    if rows.dtype != torch.int64 or rows.shape != (E,):
+        raise ValueError(f"rows must be int64 [{E}], got {tuple(rows.shape)} {rows.dtype}")
+    if route.dtype != torch.int32 or route.dim() != 1:
+        raise TypeError("route must be the int32 buffer moe_route returns")
+    T, top_k = int(T), int(top_k)
+    if T <= 0 or top_k <= 0:
+        raise ValueError("T and top_k must be positive")
+    want = (T * top_k, K) if sorted_rows else (T, K)
+    if a.dim() != 2 or tuple(a.shape) != want:
+        raise ValueError(f"a must be {list(want)} for sorted_rows={bool(sorted_rows)}, got {tuple(a.shape)}")
+    code = dtype_code(a.dtype)
+    if route.numel() * 4 < lib.inc_moe_route_bytes(T, top_k, E):
+        raise ValueError("route is smaller than inc_moe_route_bytes(T, top_k, E)")
+    dev = _dev(H, rows, a, route)
+    with torch.cuda.device(dev):
+        rc = lib.inc_gptq_hessian_accum_routed(_ptr(a), code, 1 if sorted_rows else 0, _ptr(route), T, top_k, E, K, _ptr(H), _ptr(rows),
+                                               _stream())
+    if rc == -2:  # INC_ERR_UNSUPPORTED: nothing was launched
+        return False
+    check(rc, "inc_gptq_hessian_accum_routed")
+    return True
+
+
 def moe_combine(y, route, T, top_k, num_experts, dtype, out=None):
     """inc_moe_combine: out[t] = sum_s y[pos(t, s)] in fp32, rounded once to `dtype`."""
     dev = _dev(y, route)

@@ -74,6 +74,14 @@ class MI355XWeightOnlyExperts(torch.nn.Module):
                 ops.woq_pack(iw[e].contiguous(), sc[e], None if zp is None else zp[e], self.bits, shift, qweight=qw[e], qzeros=qz[e],
                              scales_out=scales[e])
 
+    def pack_codes(self, prefix, expert, codes, scales, zp):
+        """GPTQ's entry (mirrors MI355XWeightOnlyLinear.pack_codes): the already-offset codes 0..15 (uint8 [N, K], what the column loop
+        emits) of matrix `prefix` ("gate_up" / "down") of one expert, scales [N, G] fp32, zp [N, G] or None (sym) -> that expert's
+        slices, bit-identical to `pack` on `codes - 8` (sym) / `codes` with zp (asym)."""
+        self.__dict__["_call"] = None
+        qw, sc, qz = self._bufs(prefix)
+        ops.woq_pack(codes, scales, zp, self.bits, 0, qweight=qw[expert], qzeros=qz[expert], scales_out=sc[expert])
+
     def recover(self, dtype=None, expert=None):
         """Dense weights (gate_up [E, 2I, H], down [E, H, I]) of `dtype` (default fp16), or expert `expert`'s two matrices [2I, H], [H, I]:
         inc_woq_dequant on every slice, so each equals MI355XWeightOnlyLinear.recover() of that expert's matrix."""

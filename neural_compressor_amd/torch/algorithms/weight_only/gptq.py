@@ -1492,6 +1492,11 @@ class RAWGPTQuantizer(object):
     @torch.no_grad()
     def quantize_block(self, block, block_idx, seq_map=None, propagate=True):
         sub_layers = find_layers(block)
+        # fused MoE experts with a config entry (GPTQConfig(quant_experts=True)) are calibrated, solved and packed by experts_gptq.py
+        # before the Linear flow below, which neither sees them nor depends on them
+        from .experts_gptq import quantize_block_experts
+
+        quantize_block_experts(self, block, block_idx)
         sequentials = seq_map if seq_map else [list(sub_layers.keys())]
         for sequential in sequentials:
             layers = {}

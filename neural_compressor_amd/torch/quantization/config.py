@@ -135,6 +135,7 @@ class GPTQConfig(TorchBaseConfig):
         block_size: int = 2048,
         static_groups: bool = False,
         true_sequential: bool = False,
+        quant_experts: bool = False,
         white_list: Optional[List] = DEFAULT_WHITE_LIST,
         **kwargs,
     ):
@@ -143,9 +144,19 @@ class GPTQConfig(TorchBaseConfig):
             "dtype", "bits", "use_sym", "group_size", "use_mse_search", "use_layer_wise", "use_block_wise",
             "model_path", "use_double_quant", "double_quant_bits", "double_quant_dtype", "double_quant_use_sym",
             "double_quant_group_size", "act_order", "hybrid_order", "fp8_aware", "percdamp", "block_size",
-            "static_groups", "true_sequential", "quant_lm_head",
+            "static_groups", "true_sequential", "quant_lm_head", "quant_experts",
         ])
         self._post_init()
+
+    def extend_model_info(self, model, model_info):
+        """`quant_experts=True` (an extension of the reference's fields; off by default): the fused MoE experts modules
+        (is_fused_experts) join the Linears, so they get (name, type) keys in the config mapping and GPTQ packs them
+        (algorithms/weight_only/experts_gptq.py).  `get_model_info` itself keeps returning the Linears only."""
+        if not self.quant_experts:
+            return model_info
+        have = set(model_info)
+        extra = [(name, type(m).__name__) for name, m in model.named_modules() if is_fused_experts(m)]
+        return list(model_info) + [e for e in extra if e not in have]
 
     def to_config_mapping(self, config_list=None, model_info=None):
         if not self.quant_lm_head:

@@ -25,9 +25,16 @@ def _as_config(quant_config):
     return quant_config
 
 
+def _model_info(quant_config, model):
+    """The config's model info, extended by what the instance opts into (GPTQConfig(quant_experts=True): the fused MoE experts)."""
+    info = quant_config.get_model_info(model=model)
+    extend = getattr(quant_config, "extend_model_info", None)
+    return extend(model, info) if callable(extend) else info
+
+
 def preprocess_quant_config(model, quant_config, mode="prepare", example_inputs=None, run_fn=None):
     quant_config = _as_config(quant_config)
-    model_info = quant_config.get_model_info(model=model)
+    model_info = _model_info(quant_config, model)
     if (getattr(quant_config, "model_path", None) == "" or isinstance(quant_config, ComposableConfig)) and hasattr(model, "name_or_path"):
         quant_config.model_path = model.name_or_path
     return model, quant_config.to_config_mapping(model_info=model_info)
@@ -76,7 +83,7 @@ def convert(model, quant_config=None, inplace=True, **kwargs):
             quant_config = model.quant_config
     example_inputs = model.example_inputs if is_prepared else None
     quant_config = _as_config(quant_config)
-    configs_mapping = quant_config.to_config_mapping(model_info=quant_config.get_model_info(model=q_model))
+    configs_mapping = quant_config.to_config_mapping(model_info=_model_info(quant_config, q_model))
     for algo_name, algo_func in algos_mapping.items():
         if need_apply(configs_mapping, algo_name):
             logger.info("Start to convert model with %s.", algo_name)
