@@ -117,13 +117,16 @@ int inc_dequant_ints(const int16_t* int_weight, const void* scales, int scale_dt
  *   (act_order / HF desc_act checkpoints, modules.py:341-344, 427-431); with a g_idx the general 128x128 tile
  *   kernel (or the M <= 16 split-K kernel) looks scale / zero up per element.  A g_idx that permutes whole groups
  *   is faster through a K-sorted copy of the words and a gather of x, which MI355XWeightOnlyLinear does once per module.
- *   The library picks the kernel itself: 256x256x64 LDS-DMA tile kernel (4-bit, M >= 128, K % 64 == 0,
- *   power-of-two group_size >= 32 or one group), split-K MFMA GEMV (M <= 16), or the generic 128x128
- *   tile kernel for everything else.
- *   `workspace` (inc_woq_gemm_workspace_bytes bytes; may be 0).  Medium M (fewer 256x256 tiles than CUs): fp32
- *   split-K slabs, summed in a fixed order by a second small kernel; without a workspace the call still works,
- *   single pass.  M <= 16:
- *   its first 16 KiB hold the per-strip arrival counters of the in-kernel split-K reduction and MUST BE
+ *   The library picks the kernel itself from (M, N, K, group_size, bits, g_idx) and the alignment of x / y / bias; inc_woq_gemm_route
+ *   below reports the choice (INC_WOQ_ROUTE_*).  In short, for 4 / 8 bits without g_idx and a power-of-two group_size >= 32 (or one
+ *   group): M <= 64 streams the packed weights once (GEMV16 / STREAM_*), 64 < M <= 1024 with few 256x256 tiles takes the strip
+ *   kernels (STRIP8 / STRIP), everything larger a 256-row tile kernel (D2R, 3A2B_*, BIG); whatever those do not take (g_idx, other
+ *   group sizes, K % 32 != 0, N < 64 or N % 4 != 0, unaligned x) runs on the general 128x128 tile kernel (TILE, M > 16) or the
+ *   generic split-K kernel (SMALL, M <= 16).
+ *   `workspace` (inc_woq_gemm_workspace_bytes bytes; may be 0).  STRIP / D2R / 3A2B_* with too few tiles to fill the chip: fp32
+ *   split-K slabs, summed in a fixed order (by the last-arriving workgroup, or by a second small kernel); without a workspace the
+ *   call still works, single pass.  STREAM_* and SMALL need it (INC_ERR_WORKSPACE without, nothing launched).
+ *   Its first 16 KiB hold the per-strip arrival counters of the in-kernel split-K reductions and MUST BE
  *   ZERO when the workspace is first used (the last-arriving workgroup re-arms them, so a workspace that
  *   is only ever handed to this function stays valid); the fp32 partials follow.  One workspace must not
  *   be shared by calls that may run concurrently (different streams).
@@ -133,6 +136,34 @@ int inc_woq_gemm(const void* x, int xdtype, const int32_t* qweight, const uint16
                  const int32_t* qzeros, const int32_t* g_idx, const void* bias, void* y, int64_t M,
                  int64_t N, int64_t K, int64_t G, int group_size, int bits, void* workspace,
                  int64_t workspace_bytes, inc_stream_t stream);
+
+/* Which kernel inc_woq_gemm launches for a call: the dispatcher's own decision (inc_woq_gemm branches on the result of the same
+ * function), computed on the host without touching the GPU or dereferencing a pointer -- of x, y, bias and workspace only the
+ * alignment / being NULL is used.  Returns an INC_WOQ_ROUTE_* value, or a negative INC_ERR_* code where inc_woq_gemm would reject
+ * the shape.  Out-parameters (each may be NULL):
+ *   splitk       K-slices actually used with the given workspace (1 = single pass).  The tile-shaped routes (STRIP, D2R, 3A2B_*)
+ *                fall back to 1 when the workspace is NULL or smaller than *workspace_need; STREAM_* and SMALL cannot, and
+ *                inc_woq_gemm returns INC_ERR_WORKSPACE there (compare *workspace_need with workspace_bytes).
+ *   row_blocks   STREAM_*: 16-row blocks per workgroup (1 / 2 / 4); 0 elsewhere.
+ *   steps        STREAM_*: K-steps of 32 per wave (4 / 8); D2R / 3A2B_*: K-steps of 64 per slab; 0 elsewhere.
+ *   y_vec_ok     D2R: bit 0 = 8-byte stores, bit 1 = 16-byte stores; 3A2B_* / BIG: 0 / 1; -1 elsewhere.
+ *   x_vec_ok     TILE / TILE_ANYW: 16-byte loads of x possible (0 / 1); -1 elsewhere.
+ *   workspace_need  bytes of workspace the route uses when it is given enough (0 = none).                                    */
+#define INC_WOQ_ROUTE_TILE_ANYW 1 /* 128x128 tile kernel, per-element form: 1 / 2 / 3 / 5 / 6 / 7 bits                   */
+#define INC_WOQ_ROUTE_STRIP8 2    /* 128-row four-wave strip kernel (gemm_strip8.hip), no K-slices                       */
+#define INC_WOQ_ROUTE_STRIP 3     /* 64-row strip kernel, <= 4 K-slices handed over in the kernel                        */
+#define INC_WOQ_ROUTE_3A2B_W8 4   /* 256x256 3A2B tile kernel, 8-bit words (+ slab reduce)                               */
+#define INC_WOQ_ROUTE_D2R 5       /* 256x256 direct-to-register kernel (gemm_d2r.hip) (+ slab reduce)                    */
+#define INC_WOQ_ROUTE_3A2B_W4 6   /* 256x256 3A2B tile kernel, 4-bit words (+ slab reduce)                               */
+#define INC_WOQ_ROUTE_BIG 7       /* the older 256x256 kernel (K % 128 == 64)                                            */
+#define INC_WOQ_ROUTE_TILE 8      /* general 128x128 tile kernel, 4 / 8 bits, M > 16                                     */
+#define INC_WOQ_ROUTE_GEMV16 9    /* decode kernel without split-K (M <= 4)                                              */
+#define INC_WOQ_ROUTE_STREAM_W4 10 /* streaming decode kernel, 4-bit                                                     */
+#define INC_WOQ_ROUTE_STREAM_W8 11 /* streaming decode kernel, 8-bit                                                     */
+#define INC_WOQ_ROUTE_SMALL 12    /* generic split-K kernel + reduce, M <= 16                                            */
+int inc_woq_gemm_route(int64_t M, int64_t N, int64_t K, int group_size, int bits, int xdtype, int has_g_idx, const void* x,
+                       const void* y, const void* bias, const void* workspace, int64_t workspace_bytes, int* splitk,
+                       int* row_blocks, int* steps, int* y_vec_ok, int* x_vec_ok, int64_t* workspace_need);
 
 /* Several packed modules that multiply the SAME x, in ONE launch -- the decode path of q / k / v (and of gate / up): n calls of
  * INCWeightOnlyLinear.forward (modules.py:594-610) on one activation, which the reference issues one F.linear after the other.

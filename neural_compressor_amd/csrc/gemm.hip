@@ -1775,12 +1775,185 @@ constexpr int64_t GEMV_MAX_M = 64;  // M <= 64 streams the weights once (woq_gem
 // (scripts/w8_gemm_time.py: 4096^2 M = 48 / 64: 17.3 / 18.5 vs 24.4 us; 11008 x 4096 M = 32: 18.7 vs 32.7 us, M = 48 / 64: 40.8 / 43.8 vs 32.7 us)
 constexpr int64_t GEMV8_MAX_M = 64, GEMV8_WIDE_MAX_M = 32, GEMV8_WIDE_ELEMS = (int64_t)1 << 25;
 
+// ---- routing: which kernel a call takes, decided once, on the host -----------------------------------------------------------------
+// woq_gemm_plan is the ONLY place that decides; inc_woq_gemm launches what it says and inc_woq_gemm_route reports it (the route table
+// of tests/test_gemm_routes_cpu.py pins every threshold below: a retuned one has to be acknowledged there).
+// <woq-gemm-plan>
+// harness-build routes (tools/kbench flags; never returned by libinc_mi355x.so)
+constexpr int WOQ_ROUTE_DBG_PC = 100, WOQ_ROUTE_DBG_GEMV16_NT = 103, WOQ_ROUTE_DBG_STREAM_NT = 104;
+
+struct WoqGemmPlan {
+  int route = 0;
+  int splitk = 1;          // K-slices launched
+  int steps = 0;           // streaming: K-steps per wave (4 / 8); 256-row kernels: K-steps of TK per slab
+  int mb = 0;              // streaming: 16-row blocks per workgroup
+  int y_vec_ok = -1, x_vec_ok = -1;
+  int g_shift = -2;        // group lookup by shift: log2(group_size), -1 = one group, -2 = not a power of two >= 32
+  int kw_per_slice = 0;    // small kernel: packed rows per K-slice
+  int64_t need = 0;        // workspace bytes the route uses when it is given enough
+};
+
+// of x / y / bias only the alignment is used, of workspace only whether it is NULL: nothing is dereferenced, no HIP call is made
+static int woq_gemm_plan(int64_t M, int64_t N, int64_t K, int group_size, int bits, int xdtype, bool has_g_idx, uintptr_t x, uintptr_t y,
+                         uintptr_t bias, bool has_ws, int64_t workspace_bytes, WoqGemmPlan* p) {
+  if (bits < 1 || bits > 8) return INC_ERR_UNSUPPORTED;
+  // g_idx (per-element groups: GPTQ act_order / HF desc_act): the general tile kernel and the small kernel look the group up per k; every
+  // other kernel assumes contiguous groups (the module sorts K by group once and calls them without g_idx, modules.py)
+  if (!(xdtype == INC_BF16 || xdtype == INC_F16)) return INC_ERR_UNSUPPORTED;
+  const int np = 32 / bits;
+  // a packed word must not straddle two groups unless g_idx is given per element... (word-granular
+  // group lookup): require group boundaries on word boundaries.
+  const bool anyw = !(bits == 4 || bits == 8);  // 1 / 2 / 3 / 5 / 6 / 7 bits: the tile kernel's per-element form, any group_size
+  if (!anyw && !has_g_idx && (group_size % np) != 0 && group_size < K) return INC_ERR_UNSUPPORTED;
+  if (anyw && K >= ((int64_t)1 << 31)) return INC_ERR_UNSUPPORTED;
+  // group lookup by shift: group_size a power of two >= 32, or a single group (group_size >= K)
+  int g_shift = -2;
+  if (group_size >= K) g_shift = -1;
+  else if (group_size >= 32 && (group_size & (group_size - 1)) == 0) { g_shift = 0; while ((1 << g_shift) < group_size) ++g_shift; }
+  p->g_shift = g_shift;
+  const bool x16 = (x & 15) == 0;
+  const int64_t slices512 = ceil_div64(K, 32 * 4 * 4);  // K-slices of the streaming kernel at 4 steps per wave (<= 64 for its row-blocked form)
+  const int dbg = inc_small_tiles_flag(-1);
+  // 4-bit, M <= 64: the streaming kernel (16 < M <= 64 while its K-slices fit the plan, else a 256-row kernel with most rows clamped)
+  const bool gemv_ok = !has_g_idx && bits == 4 && g_shift != -2 && (K % 32) == 0 && (N % 4) == 0 && N >= 64 && ceil_div64(N, 64) * 4 <= WS_COUNTER_BYTES &&
+                       x16 && !inc_force_small_tiles() && M <= GEMV_MAX_M && dbg != 42;
+  const bool big_ok = !has_g_idx && bits == 4 && (K % TK) == 0 && g_shift != -2 && M > 16 && N >= 64 && !(gemv_ok && slices512 <= 64) &&
+                      x16 && N * (K / 8) < (int64_t)1 << 31;
+  // weight-only INT8 at M <= 64: the streaming kernel's 8-bit form (M <= 16 whatever K; 16 < M <= 64 while its K-slices fit the counters' plan);
+  // above that the 3A2B kernel's 8-bit instantiation, same tiling and split-K plan as the 4-bit one
+  const bool gemv8_ok = !has_g_idx && bits == 8 && g_shift != -2 && (K % 32) == 0 && (N % 4) == 0 && N >= 64 && M <= GEMV8_MAX_M && dbg == 0 &&
+                        (M <= GEMV8_WIDE_MAX_M || N * K <= GEMV8_WIDE_ELEMS) && (M <= 16 || slices512 <= 64) && ceil_div64(N, 64) * 4 <= WS_COUNTER_BYTES && x16;
+  const bool big8_ok = !gemv8_ok && !has_g_idx && bits == 8 && (K % 128) == 0 && g_shift != -2 && M > 16 && N >= 64 && dbg == 0 &&
+                       x16 && N * (K / 4) < (int64_t)1 << 31;
+  if (anyw) {
+    p->route = INC_WOQ_ROUTE_TILE_ANYW;
+    p->x_vec_ok = (K % 8 == 0) && x16;
+    return INC_OK;
+  }
+  // 64 < M <= 1024 with at most 64 tiles of 256 x 256: the strip kernels (no 256-row tiles, no slab passes).  With more tiles the
+  // 256-row kernels fill the chip with <= 2 slabs and win (M = 512, N = 11008: 71 vs 81 us; tools/kbench strip).
+  // 32 < M <= 64 on the larger layers too (M = 64, 11008 x 4096: 21 vs 29 us for the streaming kernel, whose x fragments are
+  // per-lane 16-byte gathers; at 4096^2 the streaming kernel keeps a 1 us lead).  Harness flags 42 / 40 / 4 / 6 select the tile paths, 83 this kernel for any M > 16.
+  const bool strip_ok = !has_g_idx && bits == 4 && g_shift != -2 && (K % 32) == 0 && (N % 4) == 0 && N >= 64 && (M > GEMV_MAX_M || (M > 32 && N * K > ((int64_t)24 << 20)) || (dbg == 83 && M > 16)) && M <= STRIP_MAX_M &&
+                        ceil_div64(M, TM) * ceil_div64(N, TN) <= 64 && x16 && (y & 7) == 0 &&
+                        (bias & 7) == 0 && (dbg == 0 || (dbg >= 83 && dbg <= 89) || (dbg >= 100 && dbg <= 102));
+  // the 256-row kernels' split-K plan: slabs only with 8-byte stores possible and a workspace that holds them
+  auto slab_plan = [&](int y_vec_bit) {
+    p->steps = (int)(K / TK);
+    const int want = big_splitk(M, N, K, &p->steps);
+    if (want > 1) {
+      p->need = WS_COUNTER_BYTES + (int64_t)want * M * N * 4;
+      if (y_vec_bit && has_ws && workspace_bytes >= p->need) p->splitk = want;
+      else p->steps = (int)(K / TK);  // no workspace given: single pass (still correct, fewer workgroups)
+    }
+  };
+  if (strip_ok && dbg == 0 && M > 128 && M * N < ((int64_t)1 << 30) && inc_woq_gemm_strip8_splitk(M, N, K) == 1) {
+    // enough 128 x 128 tiles to fill the chip without K-slices (>= 192): the four-wave kernel that dequantises every weight once per
+    // 128 rows (gemm_strip8.hip).  tools/midm_lab, 4096 x 4096: M = 1024 46 vs 57 us; 11008 x 4096, M = 256: 40 vs 48 us.  With K-slices
+    // its larger partial tiles lose to the 64-row strips below (M = 512: 34 vs 30 us), so those keep this kernel's predecessor.
+    p->route = INC_WOQ_ROUTE_STRIP8;
+  } else if (strip_ok && M * N < ((int64_t)1 << 30)) {
+    p->route = INC_WOQ_ROUTE_STRIP;
+    const int want = strip_splitk(M, N, K);
+    const int64_t wgs = ceil_div64(M, 64) * ceil_div64(N, 128);
+    if (want > 1 && wgs * 4 <= WS_COUNTER_BYTES) {
+      p->need = WS_COUNTER_BYTES + (int64_t)want * M * N * 4;
+      if (has_ws && workspace_bytes >= p->need) p->splitk = want;
+    }
+  } else if (big8_ok) {
+    p->route = INC_WOQ_ROUTE_3A2B_W8;
+    p->y_vec_ok = (N % 4 == 0) && ((y & 7) == 0);
+    slab_plan(p->y_vec_ok);
+  } else if (big_ok && (K % 128) == 0 && (g_shift == -1 || g_shift >= 6) && (N % 2) == 0 && ((dbg == 0 && INC_GEMM_DEFAULT_D2R) || (dbg >= 90 && dbg <= 99))) {
+    // weights direct to registers (gemm_d2r.hip): four waves, one per SIMD, no dequantised tile in LDS
+    p->route = INC_WOQ_ROUTE_D2R;
+    // bit 0: 8-byte stores possible; bit 1: 16-byte stores possible
+    p->y_vec_ok = (((N % 4 == 0) && ((y & 7) == 0)) ? 1 : 0) | (((N % 8 == 0) && ((y & 15) == 0)) ? 2 : 0);
+    slab_plan(p->y_vec_ok & 1);
+#ifdef INC_KBENCH
+  } else if (big_ok && (K % 128) == 0 && (g_shift == -1 || g_shift >= 6) && (dbg == 0 || dbg == 42 || (dbg >= 51 && dbg <= 74)) && INC_GEMM_DEFAULT_PC) {
+    p->route = WOQ_ROUTE_DBG_PC;  // harness: the producer / consumer kernel (tools/kbench_gemm_2.inc)
+    p->y_vec_ok = (((N % 4 == 0) && ((y & 7) == 0)) ? 1 : 0) | (((N % 8 == 0) && ((y & 15) == 0)) ? 2 : 0);
+    slab_plan(p->y_vec_ok & 1);
+#endif
+  } else if (big_ok && (K % 128) == 0 && (dbg == 0 || dbg == 40 || dbg == 4 || dbg == 6 || (dbg >= 20 && dbg <= 30) || (dbg >= 31 && dbg <= 37))) {
+    // what the direct-to-register kernel does not take: groups of 32 (two scales per K-step) and odd N
+    p->route = INC_WOQ_ROUTE_3A2B_W4;
+    p->y_vec_ok = (N % 4 == 0) && ((y & 7) == 0);
+    slab_plan(p->y_vec_ok);
+  } else if (big_ok && !inc_force_small_tiles()) {
+    p->route = INC_WOQ_ROUTE_BIG;  // K % 128 == 64: the two-stage 256x256 kernel, K-steps of 64, no split-K
+    p->y_vec_ok = (N % 4 == 0) && ((y & 7) == 0);
+  } else if (M > 16 && !gemv8_ok && !(gemv_ok && slices512 <= 64)) {
+    p->route = INC_WOQ_ROUTE_TILE;
+    p->x_vec_ok = (K % 8 == 0) && x16;
+#ifdef INC_KBENCH
+  } else if (gemv_ok && M <= 16 && K <= GEMV16_MAX_K && xdtype == INC_BF16 && dbg == 103) {  // harness: the no-split decode kernel with non-temporal weight loads
+    p->route = WOQ_ROUTE_DBG_GEMV16_NT;
+  } else if (gemv_ok && M <= 16 && xdtype == INC_BF16 && dbg == 104 && (g_shift == -1 || g_shift >= 7)) {  // harness: the streaming kernel, non-temporal weight loads
+    p->route = WOQ_ROUTE_DBG_STREAM_NT;
+    const bool vs4 = ceil_div64(N, 64) * ceil_div64(K, 32 * 8 * 4) < 512 && slices512 <= 64;
+    p->steps = vs4 ? 4 : 8;
+    p->mb = 1;
+    p->splitk = (int)ceil_div64(K, 32 * p->steps * 4);
+    p->need = WS_COUNTER_BYTES + (int64_t)p->splitk * M * N * 4;
+#endif
+  } else if (gemv_ok && M <= 16 && K <= GEMV16_MAX_K && (dbg == 85 || (dbg == 0 && M <= 4 && N <= 4096 && K <= 4096))) {
+    // decode without split-K: one workgroup of 16 waves per 16 columns, the whole of K.  Wins where its N / 16 workgroups are a
+    // single round on the chip and x is <= 4 rows (M = 1, 4096^2: 5.9 vs 6.8 us); elsewhere the streaming kernel's 64-column
+    // requests and K-slices use the HBM better (M = 1, 11008 x 4096: 8.5 vs 15.9 us; tools/kbench decode; harness flag 85 forces it)
+    p->route = INC_WOQ_ROUTE_GEMV16;
+  } else if (gemv_ok && (M <= 16 || slices512 <= 64)) {
+    p->route = INC_WOQ_ROUTE_STREAM_W4;
+    // 8 steps per wave when that still gives every SIMD two waves (>= 512 workgroups), else 4; row-blocked (M > 16): always 4
+    const bool vs4 = M > 16 || (ceil_div64(N, 64) * ceil_div64(K, 32 * 8 * 4) < 512 && slices512 <= 64);
+    p->steps = vs4 ? 4 : 8;
+    p->mb = M > 32 ? 4 : M > 16 ? 2 : 1;
+    p->splitk = (int)ceil_div64(K, 32 * p->steps * 4);
+    p->need = WS_COUNTER_BYTES + (int64_t)p->splitk * M * N * 4;
+  } else if (gemv8_ok) {
+    // weight-only INT8 decode (BASELINE config #1's format): the streaming kernel's 8-bit form -- 64-column strips x K-slices of 512 k,
+    // every wave's 8 KiB of packed weights requested before the first use, same hand-off.  (The generic split-K kernel it replaces
+    // here read 16.8 MB in 20.6 us at 4096^2 and 45 MB in 46.7 us at 11008 x 4096: scripts/w8_gemm_time.py.)
+    p->route = INC_WOQ_ROUTE_STREAM_W8;
+    p->steps = 4;
+    p->mb = M > 32 ? 4 : M > 16 ? 2 : 1;
+    p->splitk = (int)slices512;
+    p->need = WS_COUNTER_BYTES + (int64_t)p->splitk * M * N * 4;
+  } else {
+    p->route = INC_WOQ_ROUTE_SMALL;
+    p->splitk = small_slices(N, K, bits, &p->kw_per_slice);
+    p->need = WS_COUNTER_BYTES + (int64_t)p->splitk * M * N * 4;
+  }
+  return INC_OK;
+}
+// </woq-gemm-plan>
+
+int inc_woq_gemm_route(int64_t M, int64_t N, int64_t K, int group_size, int bits, int xdtype, int has_g_idx, const void* x,
+                       const void* y, const void* bias, const void* workspace, int64_t workspace_bytes, int* splitk,
+                       int* row_blocks, int* steps, int* y_vec_ok, int* x_vec_ok, int64_t* workspace_need) {
+  INC_CHECK_ARG(M > 0 && N > 0 && K > 0 && group_size > 0);
+  WoqGemmPlan p;
+  const int rc = woq_gemm_plan(M, N, K, group_size, bits, xdtype, has_g_idx != 0, reinterpret_cast<uintptr_t>(x), reinterpret_cast<uintptr_t>(y),
+                               reinterpret_cast<uintptr_t>(bias), workspace != nullptr, workspace_bytes, &p);
+  if (rc != INC_OK) return rc;
+  if (splitk) *splitk = p.splitk;
+  if (row_blocks) *row_blocks = p.mb;
+  if (steps) *steps = p.steps;
+  if (y_vec_ok) *y_vec_ok = p.y_vec_ok;
+  if (x_vec_ok) *x_vec_ok = p.x_vec_ok;
+  if (workspace_need) *workspace_need = p.need;
+  return p.route;
+}
+
 int64_t inc_woq_gemm_workspace_bytes(int64_t M, int64_t N, int64_t K) {
   // an upper bound over the routes inc_woq_gemm can take for (M, N, K) (it does not know bits / group size here)
   int64_t need = 0;
   auto at_least = [&](int64_t v) { if (v > need) need = v; };
   if (M > 16) {
-    if (N >= 64) {  // 256-row tiles (producer / consumer, 3A2B incl. its 8-bit form): split-K slabs behind the counter block
+    // 256-row tiles (direct-to-register, 3A2B incl. its 8-bit form): split-K slabs behind the counter block.  They split only K % 128 == 0
+    // (big_splitk divides by K / 64: K < 64 must not reach it)
+    if (N >= 64 && (K % 128) == 0) {
       int steps;
       const int splits = big_splitk(M, N, K, &steps);
       if (splits > 1) at_least(WS_COUNTER_BYTES + (int64_t)splits * M * N * 4);
@@ -1804,16 +1977,13 @@ int inc_woq_gemm(const void* x, int xdtype, const int32_t* qweight, const uint16
                  int64_t N, int64_t K, int64_t G, int group_size, int bits, void* workspace,
                  int64_t workspace_bytes, inc_stream_t stream) {
   INC_CHECK_ARG(x && qweight && scales && qzeros && y && M > 0 && N > 0 && K > 0 && G > 0 && group_size > 0);
-  if (bits < 1 || bits > 8) return INC_ERR_UNSUPPORTED;
-  // g_idx (per-element groups: GPTQ act_order / HF desc_act): the general tile kernels below look the group up per k; the
-  // 256-row kernels assume contiguous groups (the module sorts K by group once and calls them without g_idx, modules.py)
-  if (!(xdtype == INC_BF16 || xdtype == INC_F16)) return INC_ERR_UNSUPPORTED;
+  // the kernel, its K-slices and its store / load forms: decided by woq_gemm_plan (above), launched here
+  WoqGemmPlan plan;
+  const int plan_rc = woq_gemm_plan(M, N, K, group_size, bits, xdtype, g_idx != nullptr, reinterpret_cast<uintptr_t>(x), reinterpret_cast<uintptr_t>(y),
+                                    reinterpret_cast<uintptr_t>(bias), workspace != nullptr, workspace_bytes, &plan);
+  if (plan_rc != INC_OK) return plan_rc;
+  const int route = plan.route, g_shift = plan.g_shift;
   const int np = 32 / bits;
-  // a packed word must not straddle two groups unless g_idx is given per element... (word-granular
-  // group lookup): require group boundaries on word boundaries.
-  const bool anyw = !(bits == 4 || bits == 8);  // 1 / 2 / 3 / 5 / 6 / 7 bits: the tile kernel's per-element form, any group_size
-  if (!anyw && !g_idx && (group_size % np) != 0 && group_size < K) return INC_ERR_UNSUPPORTED;
-  if (anyw && K >= ((int64_t)1 << 31)) return INC_ERR_UNSUPPORTED;
   const int64_t KW = ceil_div64(K, np), NW = ceil_div64(N, np);
   hipStream_t s = inc_s(stream);
   const uint16_t* xp = (const uint16_t*)x;
@@ -1822,29 +1992,15 @@ int inc_woq_gemm(const void* x, int xdtype, const int32_t* qweight, const uint16
   const uint16_t* bp = (const uint16_t*)bias;
   uint16_t* yp = (uint16_t*)y;
   const bool bf = xdtype == INC_BF16;
-  // group lookup by shift: group_size a power of two >= 32, or a single group (group_size >= K)
-  int g_shift = -2;
-  if (group_size >= K) g_shift = -1;
-  else if (group_size >= 32 && (group_size & (group_size - 1)) == 0) { g_shift = 0; while ((1 << g_shift) < group_size) ++g_shift; }
-  // 16 < M < 128 (batched decode) runs the same 256-row tile with most rows clamped: with split-K over up to 16 slabs that is
-  // 30 us at 64 x 4096 x 4096 where the 128x128 register-staged kernel needed 208 us (and 615 us at 17 x 4096 x 11008)
-  const bool gemv_ok = !g_idx && bits == 4 && g_shift != -2 && (K % 32) == 0 && (N % 4) == 0 && N >= 64 && ceil_div64(N, 64) * 4 <= WS_COUNTER_BYTES &&
-                       (reinterpret_cast<uintptr_t>(x) & 15) == 0 && !inc_force_small_tiles() && M <= GEMV_MAX_M && inc_small_tiles_flag(-1) != 42;
-  const bool big_ok = !g_idx && bits == 4 && (K % TK) == 0 && g_shift != -2 && M > 16 && N >= 64 && !(gemv_ok && ceil_div64(K, 32 * 4 * 4) <= 64) &&
-                      (reinterpret_cast<uintptr_t>(x) & 15) == 0 && N * (K / 8) < (int64_t)1 << 31;
-  const int dbg = inc_small_tiles_flag(-1);
-  // weight-only INT8 (BASELINE config #1's layers): the 3A2B kernel's 8-bit instantiation, same tiling and split-K plan
-  // weight-only INT8 at M <= 64: the streaming kernel's 8-bit form (M <= 16 whatever K; 16 < M <= 64 while its K-slices fit the counters' plan)
-  const bool gemv8_ok = !g_idx && bits == 8 && g_shift != -2 && (K % 32) == 0 && (N % 4) == 0 && N >= 64 && M <= GEMV8_MAX_M && dbg == 0 &&
-                        (M <= GEMV8_WIDE_MAX_M || N * K <= GEMV8_WIDE_ELEMS) && (M <= 16 || ceil_div64(K, 32 * 4 * 4) <= 64) && ceil_div64(N, 64) * 4 <= WS_COUNTER_BYTES && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
-  const bool big8_ok = !gemv8_ok && !g_idx && bits == 8 && (K % 128) == 0 && g_shift != -2 && M > 16 && N >= 64 && dbg == 0 &&
-                       (reinterpret_cast<uintptr_t>(x) & 15) == 0 && N * (K / 4) < (int64_t)1 << 31;
-  // 64 < M <= 1024 with at most 64 tiles of 256 x 256: the strip kernel (no 256-row tiles, no slab passes).  With more tiles the
-  // producer / consumer kernel fills the chip with <= 2 slabs and wins (M = 512, N = 11008: 71 vs 81 us; tools/kbench strip).
-  // 32 < M <= 64 on the larger layers too (M = 64, 11008 x 4096: 21 vs 29 us for the streaming kernel, whose x fragments are
-  // per-lane 16-byte gathers; at 4096^2 the streaming kernel keeps a 1 us lead).  Harness flags 42 / 40 / 4 / 6 select the tile paths, 83 this kernel for any M > 16.
-  if (anyw) {
-    const int x_vec_ok = (K % 8 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0);
+  const int dbg = inc_small_tiles_flag(-1);  // harness build: which A/B partner or ablation of the chosen route to launch (0 in the product)
+  // the routes that cannot run without their K-slices
+  if ((route == INC_WOQ_ROUTE_STREAM_W4 || route == INC_WOQ_ROUTE_STREAM_W8 || route == INC_WOQ_ROUTE_SMALL || route == WOQ_ROUTE_DBG_STREAM_NT) &&
+      (!workspace || workspace_bytes < plan.need))
+    return INC_ERR_WORKSPACE;
+  // the strip / 256-row kernels' fp32 slabs sit behind the counter block (never touch the streaming kernels' arrival counters)
+  float* const slabs = plan.splitk > 1 ? (float*)((char*)workspace + WS_COUNTER_BYTES) : nullptr;
+  if (route == INC_WOQ_ROUTE_TILE_ANYW) {
+    const int x_vec_ok = plan.x_vec_ok;
     const size_t smem = (size_t)2 * 2 * GM * GP * sizeof(uint16_t);
     const unsigned grid = (unsigned)(ceil_div64(M, GM) * ceil_div64(N, GN));
 #define INC_TILE_W(B)                                                                                                                 \
@@ -1869,19 +2025,10 @@ int inc_woq_gemm(const void* x, int xdtype, const int32_t* qweight, const uint16
 #undef INC_TILE_W
     INC_LAUNCH_RETURN();
   }
-  const bool strip_ok = !g_idx && bits == 4 && g_shift != -2 && (K % 32) == 0 && (N % 4) == 0 && N >= 64 && (M > GEMV_MAX_M || (M > 32 && N * K > ((int64_t)24 << 20)) || (dbg == 83 && M > 16)) && M <= STRIP_MAX_M &&
-                        ceil_div64(M, TM) * ceil_div64(N, TN) <= 64 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(y) & 7) == 0 &&
-                        (reinterpret_cast<uintptr_t>(bias) & 7) == 0 && (dbg == 0 || (dbg >= 83 && dbg <= 89) || (dbg >= 100 && dbg <= 102));
-  if (strip_ok && dbg == 0 && M > 128 && M * N < ((int64_t)1 << 30) && inc_woq_gemm_strip8_splitk(M, N, K) == 1) {
-    // enough 128 x 128 tiles to fill the chip without K-slices (>= 192): the four-wave kernel that dequantises every weight once per
-    // 128 rows (gemm_strip8.hip).  tools/midm_lab, 4096 x 4096: M = 1024 46 vs 57 us; 11008 x 4096, M = 256: 40 vs 48 us.  With K-slices
-    // its larger partial tiles lose to the 64-row strips below (M = 512: 34 vs 30 us), so those keep this kernel's predecessor.
+  if (route == INC_WOQ_ROUTE_STRIP8)
     return inc_launch_woq_gemm_strip8(xp, qw, scales, qz, bp, yp, M, N, K, NW, g_shift, nullptr, nullptr, 1, bf, s);
-  }
-  if (strip_ok && M * N < ((int64_t)1 << 30)) {
-    int splitk = strip_splitk(M, N, K);
-    const int64_t wgs = ceil_div64(M, 64) * ceil_div64(N, 128);
-    if (splitk > 1 && (!workspace || workspace_bytes < WS_COUNTER_BYTES + (int64_t)splitk * M * N * 4 || wgs * 4 > WS_COUNTER_BYTES)) splitk = 1;
+  if (route == INC_WOQ_ROUTE_STRIP) {
+    const int splitk = plan.splitk;
     static std::atomic<uint64_t> strip_attr_set{0};
     if (inc_attr_needed(strip_attr_set)) {
       (void)hipFuncSetAttribute((const void*)woq_gemm_w4_strip_kernel<true, STRIP_WAVES, STRIP_RING>, hipFuncAttributeMaxDynamicSharedMemorySize, STRIP_SMEM_BYTES);
@@ -1889,7 +2036,7 @@ int inc_woq_gemm(const void* x, int xdtype, const int32_t* qweight, const uint16
       inc_attr_done(strip_attr_set);
     }
     unsigned* counters = (unsigned*)workspace;
-    float* part = splitk > 1 ? (float*)((char*)workspace + WS_COUNTER_BYTES) : nullptr;
+    float* part = slabs;
     dim3 grid((unsigned)ceil_div64(N, 128), (unsigned)ceil_div64(M, 64), (unsigned)splitk);
 #ifdef INC_KBENCH
     {
@@ -1919,7 +2066,7 @@ int inc_woq_gemm(const void* x, int xdtype, const int32_t* qweight, const uint16
     else woq_gemm_w4_strip_kernel<false, STRIP_WAVES, STRIP_RING><<<grid, 64 * STRIP_WAVES, STRIP_SMEM_BYTES, s>>>(xp, qw, scales, qz, bp, yp, part, counters, (int)M, N, K, NW, g_shift, splitk);
     INC_LAUNCH_RETURN();
   }
-  if (big8_ok) {
+  if (route == INC_WOQ_ROUTE_3A2B_W8) {
     const size_t smem = (size_t)3 * T_ASTAGE + 2 * T_BSTAGE;
     static std::atomic<uint64_t> a8_attr_set{0};
     if (inc_attr_needed(a8_attr_set)) {
@@ -1928,15 +2075,8 @@ int inc_woq_gemm(const void* x, int xdtype, const int32_t* qweight, const uint16
       inc_attr_done(a8_attr_set);
     }
     const unsigned grid = (unsigned)(ceil_div64(M, TM) * ceil_div64(N, TN));
-    const int y_vec_ok = (N % 4 == 0) && ((reinterpret_cast<uintptr_t>(y) & 7) == 0);
-    int steps = (int)(K / TK);
-    int splits = big_splitk(M, N, K, &steps);
-    float* part = nullptr;
-    if (splits > 1) {
-      if (y_vec_ok && workspace && workspace_bytes >= WS_COUNTER_BYTES + (int64_t)splits * M * N * 4)
-        part = (float*)((char*)workspace + WS_COUNTER_BYTES);
-      else { splits = 1; steps = (int)(K / TK); }
-    }
+    const int y_vec_ok = plan.y_vec_ok, steps = plan.steps, splits = plan.splitk;
+    float* const part = slabs;
     dim3 g2(grid, (unsigned)splits);
     if (bf) woq_gemm_w4_3a2b_kernel<true, INC_3A2B_DEFAULT_SCHED, 8><<<g2, 512, smem, s>>>(xp, qw, scales, qz, bp, yp, M, N, K, NW, g_shift, y_vec_ok, part, steps);
     else woq_gemm_w4_3a2b_kernel<false, INC_3A2B_DEFAULT_SCHED, 8><<<g2, 512, smem, s>>>(xp, qw, scales, qz, bp, yp, M, N, K, NW, g_shift, y_vec_ok, part, steps);
@@ -1946,18 +2086,9 @@ int inc_woq_gemm(const void* x, int xdtype, const int32_t* qweight, const uint16
       if (bf) splitk_slab_reduce_kernel<true><<<(unsigned)rb, 256, 0, s>>>(part, bp, yp, M, N, splits);
       else splitk_slab_reduce_kernel<false><<<(unsigned)rb, 256, 0, s>>>(part, bp, yp, M, N, splits);
     }
-  } else if (big_ok && (K % 128) == 0 && (g_shift == -1 || g_shift >= 6) && (N % 2) == 0 && ((dbg == 0 && INC_GEMM_DEFAULT_D2R) || (dbg >= 90 && dbg <= 99))) {
-    // weights direct to registers (gemm_d2r.hip): four waves, one per SIMD, no dequantised tile in LDS
-    const int y_vec_ok = (((N % 4 == 0) && ((reinterpret_cast<uintptr_t>(y) & 7) == 0)) ? 1 : 0) |
-                         (((N % 8 == 0) && ((reinterpret_cast<uintptr_t>(y) & 15) == 0)) ? 2 : 0);
-    int steps = (int)(K / TK);
-    int splits = big_splitk(M, N, K, &steps);
-    float* part = nullptr;
-    if (splits > 1) {
-      if ((y_vec_ok & 1) && workspace && workspace_bytes >= WS_COUNTER_BYTES + (int64_t)splits * M * N * 4)
-        part = (float*)((char*)workspace + WS_COUNTER_BYTES);
-      else { splits = 1; steps = (int)(K / TK); }
-    }
+  } else if (route == INC_WOQ_ROUTE_D2R) {
+    const int y_vec_ok = plan.y_vec_ok, steps = plan.steps, splits = plan.splitk;
+    float* const part = slabs;
     static const int d2r_abl[10] = {0, 0, 4, 8, 12, 76, 128, 0, 256, 0};  // harness flags 90..96 (91: three x stages; 92..96 timing-only), 98: time stamps
     const int abl = dbg >= 90 ? d2r_abl[dbg - 90] : 0;
 #ifdef INC_KBENCH
@@ -1977,7 +2108,7 @@ int inc_woq_gemm(const void* x, int xdtype, const int32_t* qweight, const uint16
 #ifdef INC_KBENCH
 #include "../../tools/kbench_gemm_2.inc"
 #endif  // INC_KBENCH
-  } else if (big_ok && (K % 128) == 0 && (dbg == 0 || dbg == 40 || dbg == 4 || dbg == 6 || (dbg >= 20 && dbg <= 30) || (dbg >= 31 && dbg <= 37))) {
+  } else if (route == INC_WOQ_ROUTE_3A2B_W4) {
     const size_t smem = (size_t)3 * T_ASTAGE + 2 * T_BSTAGE;  // 160 KiB: the whole LDS of a CU
     static std::atomic<uint64_t> a3_attr_set{0};
     if (inc_attr_needed(a3_attr_set)) {
@@ -1993,15 +2124,8 @@ int inc_woq_gemm(const void* x, int xdtype, const int32_t* qweight, const uint16
       inc_attr_done(a3_attr_set);
     }
     const unsigned grid = (unsigned)(ceil_div64(M, TM) * ceil_div64(N, TN));
-    const int y_vec_ok = (N % 4 == 0) && ((reinterpret_cast<uintptr_t>(y) & 7) == 0);
-    int steps = (int)(K / TK);
-    int splits = big_splitk(M, N, K, &steps);
-    float* part = nullptr;
-    if (splits > 1) {
-      if (y_vec_ok && workspace && workspace_bytes >= WS_COUNTER_BYTES + (int64_t)splits * M * N * 4)
-        part = (float*)((char*)workspace + WS_COUNTER_BYTES);  // never touch the GEMV's arrival counters
-      else { splits = 1; steps = (int)(K / TK); }  // no workspace given: single pass (still correct, fewer workgroups)
-    }
+    const int y_vec_ok = plan.y_vec_ok, steps = plan.steps, splits = plan.splitk;
+    float* const part = slabs;
     dim3 g2(grid, (unsigned)splits);
 #define INC_A3(B, S) woq_gemm_w4_3a2b_kernel<B, S><<<g2, 512, smem, s>>>(xp, qw, scales, qz, bp, yp, M, N, K, NW, g_shift, y_vec_ok, part, steps)
     if (!bf) INC_A3(false, INC_3A2B_DEFAULT_SCHED);
@@ -2033,7 +2157,7 @@ int inc_woq_gemm(const void* x, int xdtype, const int32_t* qweight, const uint16
       if (bf) splitk_slab_reduce_kernel<true><<<(unsigned)rb, 256, 0, s>>>(part, bp, yp, M, N, splits);
       else splitk_slab_reduce_kernel<false><<<(unsigned)rb, 256, 0, s>>>(part, bp, yp, M, N, splits);
     }
-  } else if (big_ok && !inc_force_small_tiles()) {
+  } else if (route == INC_WOQ_ROUTE_BIG) {
     const size_t smem = (size_t)2 * T_ASTAGE + 2 * T_BSTAGE;  // 128 KiB
     static std::atomic<uint64_t> big_attr_set{0};
     if (inc_attr_needed(big_attr_set)) {
@@ -2042,11 +2166,11 @@ int inc_woq_gemm(const void* x, int xdtype, const int32_t* qweight, const uint16
       inc_attr_done(big_attr_set);
     }
     const unsigned grid = (unsigned)(ceil_div64(M, TM) * ceil_div64(N, TN));
-    const int y_vec_ok = (N % 4 == 0) && ((reinterpret_cast<uintptr_t>(y) & 7) == 0);
+    const int y_vec_ok = plan.y_vec_ok;
     if (bf) woq_gemm_w4_big_kernel<true><<<grid, 512, smem, s>>>(xp, qw, scales, qz, bp, yp, M, N, K, NW, g_shift, y_vec_ok);
     else woq_gemm_w4_big_kernel<false><<<grid, 512, smem, s>>>(xp, qw, scales, qz, bp, yp, M, N, K, NW, g_shift, y_vec_ok);
-  } else if (M > 16 && !gemv8_ok && !(gemv_ok && ceil_div64(K, 32 * 4 * 4) <= 64)) {
-    const int x_vec_ok = (K % 8 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0);
+  } else if (route == INC_WOQ_ROUTE_TILE) {
+    const int x_vec_ok = plan.x_vec_ok;
     const size_t smem = (size_t)2 * 2 * GM * GP * sizeof(uint16_t);
     static std::atomic<uint64_t> attr_set{0};
     if (inc_attr_needed(attr_set)) {
@@ -2062,31 +2186,24 @@ int inc_woq_gemm(const void* x, int xdtype, const int32_t* qweight, const uint16
     else { if (bf) INC_TILE(8, true); else INC_TILE(8, false); }
 #undef INC_TILE
 #ifdef INC_KBENCH
-  } else if (gemv_ok && M <= 16 && K <= GEMV16_MAX_K && bf && dbg == 103) {  // harness: the no-split decode kernel with non-temporal weight loads
+  } else if (route == WOQ_ROUTE_DBG_GEMV16_NT) {  // harness: the no-split decode kernel with non-temporal weight loads
     woq_gemv16_w4_kernel<true, true><<<(unsigned)ceil_div64(N, 16), 64 * GEMV16_WAVES, 0, s>>>(xp, qw, scales, qz, bp, yp, (int)M, N, K, NW, g_shift);
-  } else if (gemv_ok && M <= 16 && bf && dbg == 104 && (g_shift == -1 || g_shift >= 7)) {  // harness: the streaming kernel, non-temporal weight loads
-    const bool vs4 = ceil_div64(N, 64) * ceil_div64(K, 32 * 8 * 4) < 512 && ceil_div64(K, 32 * 4 * 4) <= 64;
-    const int splitk = (int)ceil_div64(K, 32 * (vs4 ? 4 : 8) * 4);
-    if (!workspace || workspace_bytes < WS_COUNTER_BYTES + (int64_t)splitk * M * N * 4) return INC_ERR_WORKSPACE;
+  } else if (route == WOQ_ROUTE_DBG_STREAM_NT) {  // harness: the streaming kernel, non-temporal weight loads
+    const bool vs4 = plan.steps == 4;
+    const int splitk = plan.splitk;
     unsigned* counters = (unsigned*)workspace;
     float* part = (float*)((char*)workspace + WS_COUNTER_BYTES);
     dim3 grid((unsigned)ceil_div64(N, 64), (unsigned)splitk);
     if (vs4) woq_gemv_w4_kernel<true, true, 4, 1, true><<<grid, 256, 0, s>>>(xp, qw, scales, qz, bp, yp, part, counters, (int)M, N, K, NW, G, g_shift, splitk);
     else woq_gemv_w4_kernel<true, true, 8, 1, true><<<grid, 256, 0, s>>>(xp, qw, scales, qz, bp, yp, part, counters, (int)M, N, K, NW, G, g_shift, splitk);
 #endif
-  } else if (gemv_ok && M <= 16 && K <= GEMV16_MAX_K && (dbg == 85 || (dbg == 0 && M <= 4 && N <= 4096 && K <= 4096))) {
-    // decode without split-K: one workgroup of 16 waves per 16 columns, the whole of K.  Wins where its N / 16 workgroups are a
-    // single round on the chip and x is <= 4 rows (M = 1, 4096^2: 5.9 vs 6.8 us); elsewhere the streaming kernel's 64-column
-    // requests and K-slices use the HBM better (M = 1, 11008 x 4096: 8.5 vs 15.9 us; tools/kbench decode; harness flag 85 forces it)
+  } else if (route == INC_WOQ_ROUTE_GEMV16) {
     const unsigned grid = (unsigned)ceil_div64(N, 16);
     if (bf) woq_gemv16_w4_kernel<true><<<grid, 64 * GEMV16_WAVES, 0, s>>>(xp, qw, scales, qz, bp, yp, (int)M, N, K, NW, g_shift);
     else woq_gemv16_w4_kernel<false><<<grid, 64 * GEMV16_WAVES, 0, s>>>(xp, qw, scales, qz, bp, yp, (int)M, N, K, NW, g_shift);
-  } else if (gemv_ok && (M <= 16 || ceil_div64(K, 32 * 4 * 4) <= 64)) {
-    // 8 steps per wave when that still gives every SIMD two waves (>= 512 workgroups), else 4; row-blocked (M > 16): always 4
-    const bool vs4 = M > 16 || (ceil_div64(N, 64) * ceil_div64(K, 32 * 8 * 4) < 512 && ceil_div64(K, 32 * 4 * 4) <= 64);
-    const int vsteps = vs4 ? 4 : 8;
-    const int splitk = (int)ceil_div64(K, 32 * vsteps * 4);
-    if (!workspace || workspace_bytes < WS_COUNTER_BYTES + (int64_t)splitk * M * N * 4) return INC_ERR_WORKSPACE;
+  } else if (route == INC_WOQ_ROUTE_STREAM_W4) {
+    const bool vs4 = plan.steps == 4;
+    const int splitk = plan.splitk;
     unsigned* counters = (unsigned*)workspace;
     float* part = (float*)((char*)workspace + WS_COUNTER_BYTES);
     dim3 grid((unsigned)ceil_div64(N, 64), (unsigned)splitk);
@@ -2097,12 +2214,8 @@ int inc_woq_gemm(const void* x, int xdtype, const int32_t* qweight, const uint16
     else { if (g128) INC_GEMV2(false, true) else INC_GEMV2(false, false) }
 #undef INC_GEMV2
 #undef INC_GEMV
-  } else if (gemv8_ok) {
-    // weight-only INT8 decode (BASELINE config #1's format): the streaming kernel's 8-bit form -- 64-column strips x K-slices of 512 k,
-    // every wave's 8 KiB of packed weights requested before the first use, same hand-off.  (The generic split-K kernel it replaces
-    // here read 16.8 MB in 20.6 us at 4096^2 and 45 MB in 46.7 us at 11008 x 4096: scripts/w8_gemm_time.py.)
-    const int splitk = (int)ceil_div64(K, 32 * 4 * 4);
-    if (!workspace || workspace_bytes < WS_COUNTER_BYTES + (int64_t)splitk * M * N * 4) return INC_ERR_WORKSPACE;
+  } else if (route == INC_WOQ_ROUTE_STREAM_W8) {
+    const int splitk = plan.splitk;
     unsigned* counters = (unsigned*)workspace;
     float* part = (float*)((char*)workspace + WS_COUNTER_BYTES);
     dim3 grid((unsigned)ceil_div64(N, 64), (unsigned)splitk);
@@ -2114,10 +2227,8 @@ int inc_woq_gemm(const void* x, int xdtype, const int32_t* qweight, const uint16
     else { if (g128) INC_GEMV8(false, true) else INC_GEMV8(false, false) }
 #undef INC_GEMV8
 #undef INC_GEMV8B
-  } else {
-    int kw_per_slice = 0;
-    const int slices = small_slices(N, K, bits, &kw_per_slice);
-    if (!workspace || workspace_bytes < WS_COUNTER_BYTES + (int64_t)slices * M * N * 4) return INC_ERR_WORKSPACE;
+  } else {  // INC_WOQ_ROUTE_SMALL
+    const int kw_per_slice = plan.kw_per_slice, slices = plan.splitk;
     float* part = (float*)((char*)workspace + WS_COUNTER_BYTES);
     dim3 grid((unsigned)ceil_div64(N, SN), (unsigned)slices);
 #define INC_SMALL(B, F) woq_gemm_small_kernel<B, F><<<grid, 256, 0, s>>>(xp, qw, scales, qz, g_idx, part, M, N, K, KW, NW, group_size, kw_per_slice)

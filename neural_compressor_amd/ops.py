@@ -249,6 +249,29 @@ def woq_gemm(x2d, qweight, scales, qzeros, bias, N, K, group_size, bits, g_idx=N
     return y
 
 
+WOQ_GEMM_ROUTES = {
+    1: "TILE_ANYW", 2: "STRIP8", 3: "STRIP", 4: "3A2B_W8", 5: "D2R", 6: "3A2B_W4", 7: "BIG", 8: "TILE", 9: "GEMV16", 10: "STREAM_W4",
+    11: "STREAM_W8", 12: "SMALL",
+}  # INC_WOQ_ROUTE_* of include/inc_mi355x.h
+
+
+def woq_gemm_route(M, N, K, group_size, bits, dtype, has_g_idx=False, x_ptr=0, y_ptr=0, bias_ptr=0, ws_ptr=None, ws_bytes=0):
+    """Which kernel inc_woq_gemm launches for this call (inc_woq_gemm_route: the dispatcher's own decision, computed on the host --
+    works without a GPU).  Of the addresses only the alignment is used, of `ws_ptr` only whether it is None.  Returns a dict:
+    route (a name of WOQ_GEMM_ROUTES), splitk, row_blocks, steps, y_vec_ok, x_vec_ok, need (workspace bytes the route uses).  Not on
+    the forward path: woq_gemm / WoqGemmCall never call it."""
+    import ctypes
+
+    o = [ctypes.c_int() for _ in range(5)]
+    need = ctypes.c_int64()
+    rc = lib.inc_woq_gemm_route(M, N, K, group_size, bits, dtype_code(dtype), int(bool(has_g_idx)), x_ptr or None, y_ptr or None,
+                                bias_ptr or None, ws_ptr or None, ws_bytes, *[ctypes.byref(v) for v in o], ctypes.byref(need))
+    if rc < 0:
+        check(rc, "inc_woq_gemm_route")
+    return dict(route=WOQ_GEMM_ROUTES[rc], splitk=o[0].value, row_blocks=o[1].value, steps=o[2].value, y_vec_ok=o[3].value,
+                x_vec_ok=o[4].value, need=need.value)
+
+
 _raw_stream = torch._C._cuda_getCurrentRawStream  # (device index) -> hipStream_t of torch's current stream, no Stream object
 _cur_device = torch._C._cuda_getDevice
 

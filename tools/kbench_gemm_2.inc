@@ -1,6 +1,6 @@
 // harness-only code of gemm.hip (superseded kernel generations / timing-only ablations; tools/Makefile builds
 // them into tools/libinc_mi355x_kbench.so with -DINC_KBENCH; they are NOT part of libinc_mi355x.so).  Included in place by gemm.hip.
-  } else if (big_ok && (K % 128) == 0 && (g_shift == -1 || g_shift >= 6) && (dbg == 0 || dbg == 42 || (dbg >= 51 && dbg <= 74)) && INC_GEMM_DEFAULT_PC) {
+  } else if (route == WOQ_ROUTE_DBG_PC) {
     // producer / consumer specialisation of the 3A2B tile (one scale per column and K-step: group_size >= 64)
     const size_t smem = (size_t)3 * T_ASTAGE + 2 * T_BSTAGE;  // 160 KiB: the whole LDS of a CU
     static std::atomic<uint64_t> pc_attr_set{0};
@@ -10,17 +10,9 @@
       inc_attr_done(pc_attr_set);
     }
     const unsigned grid = (unsigned)(ceil_div64(M, TM) * ceil_div64(N, TN));
-    // bit 0: 8-byte stores possible; bit 1: 16-byte stores possible (full tiles then leave through LDS)
-    const int y_vec_ok = (((N % 4 == 0) && ((reinterpret_cast<uintptr_t>(y) & 7) == 0)) ? 1 : 0) |
-                         (((N % 8 == 0) && ((reinterpret_cast<uintptr_t>(y) & 15) == 0)) ? 2 : 0);
-    int steps = (int)(K / TK);
-    int splits = big_splitk(M, N, K, &steps);
-    float* part = nullptr;
-    if (splits > 1) {
-      if ((y_vec_ok & 1) && workspace && workspace_bytes >= WS_COUNTER_BYTES + (int64_t)splits * M * N * 4)
-        part = (float*)((char*)workspace + WS_COUNTER_BYTES);  // never touch the GEMV's arrival counters
-      else { splits = 1; steps = (int)(K / TK); }
-    }
+    // woq_gemm_plan: y_vec_ok bit 0: 8-byte stores possible; bit 1: 16-byte stores possible (full tiles then leave through LDS)
+    const int y_vec_ok = plan.y_vec_ok, steps = plan.steps, splits = plan.splitk;
+    float* const part = slabs;
     dim3 g2(grid, (unsigned)splits);
 #define INC_PC(B, A) woq_gemm_w4_pc_kernel<B, A><<<g2, PC_THREADS, smem, s>>>(xp, qw, scales, qz, bp, yp, M, N, K, NW, g_shift, y_vec_ok, part, steps)
     if (!bf) INC_PC(false, 0);
