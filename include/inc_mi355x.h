@@ -226,9 +226,10 @@ int inc_woq_gemm_lut(const void* x, int xdtype, const uint8_t* qweight, int64_t 
  *       mode 2 (plain): a = x [T, K]; out [S, N] fp32 = x[order[p]/top_k] . W[n]
  *     INC_ERR_UNSUPPORTED (nothing launched) unless xdtype is INC_BF16 / INC_F16, K % 32 == 0, N % 8 == 0, group_size a power of two
  *     >= 32 dividing K or one group (-1 / >= K), a / qweight / out 16-byte and scales 8-byte aligned.
- *     `workspace` (inc_woq_moe_gemm_workspace_bytes; 0 = none needed): its first 4 KiB are split-K arrival counters, which MUST BE
- *     ZERO when the workspace is first used (the kernel re-arms them), then fp32 partials.  One workspace of the largest size serves
- *     every call shape and both modes in stream order; calls that may run concurrently need their own.
+ *     `workspace` (inc_woq_moe_gemm_workspace_bytes; 0 = none needed, also for N % 8 != 0 or K % 32 != 0, which the GEMM rejects): its
+ *     first 4 KiB are split-K arrival counters, which MUST BE ZERO when the workspace is first used (the kernel re-arms them), then
+ *     fp32 partials.  One workspace of the largest size serves every call shape and both modes in stream order; calls that may run
+ *     concurrently need their own.
  *   inc_moe_combine: out [T, H] xdtype, out[t] = sum over s = 0 .. top_k-1 of y[pos[t*k+s]] (y = mode 1's output) in fp32, one rounding. */
 int64_t inc_moe_route_bytes(int64_t T, int top_k, int64_t E);
 int inc_moe_route(const void* top_k_index, int index_bytes, int64_t T, int top_k, int64_t E, int32_t* route, int64_t route_bytes,

@@ -403,6 +403,8 @@ int inc_moe_route(const void* top_k_index, int index_bytes, int64_t T, int top_k
 
 int64_t inc_woq_moe_gemm_workspace_bytes(int mode, int64_t T, int top_k, int64_t E, int64_t N, int64_t K) {
   if (mode < 0 || mode > 2 || T <= 0 || top_k <= 0 || E <= 0 || N <= 0 || K < 32) return 0;
+  // shapes inc_woq_moe_gemm rejects before it plans need no workspace (mode 0 with N = 1 has no column, so no strip to plan over)
+  if (N % 8 != 0 || K % 32 != 0) return 0;
   const int64_t S = T * top_k;
   return moe_ws_bytes(moe_plan(mode, S, E, N, K), S, N);
 }
