@@ -165,6 +165,22 @@ int inc_woq_gemm_route(int64_t M, int64_t N, int64_t K, int group_size, int bits
                        const void* y, const void* bias, const void* workspace, int64_t workspace_bytes, int* splitk,
                        int* row_blocks, int* steps, int* y_vec_ok, int* x_vec_ok, int64_t* workspace_need);
 
+/* act_order (HF desc_act) decode in ONE launch: y = x[:, k_order] . W_sorted^T + bias -- INCWeightOnlyLinear.forward (modules.py:594-610)
+ * on a module whose g_idx permutes whole groups (modules.py:427-431 looks the group up per element).  `qweight` is the packed weight
+ * with its K axis sorted by group (row k of the sorted fields is row k_order[k] of the module's), so scales / qzeros are the module's own
+ * and the groups are contiguous; k_order [K] int32, 16-byte aligned, is that order.  The activations are gathered inside the decode
+ * kernels (x needs only 2-byte alignment); every entry of k_order is clamped to [0, K-1] before it is used, so no array can send a
+ * read outside x.  The result is bit-identical to inc_woq_gemm(x.index_select(1, k_order), qweight, ..., g_idx = NULL) with the
+ * same workspace size: the same kernel body, the same plan.
+ *   Planned as inc_woq_gemm_route plans (M, N, K, group_size, bits, no g_idx) for a 16-byte aligned x; launched only on the routes
+ *   GEMV16, STREAM_W4 and STREAM_W8.  INC_ERR_UNSUPPORTED (nothing launched) on every other route -- every M > 64 among them --
+ *   and for a k_order that is not 16-byte aligned: gather x and call inc_woq_gemm then.
+ *   `workspace`: inc_woq_gemm_workspace_bytes(M, N, K) bytes, with inc_woq_gemm's rules (zeroed arrival counters in the first
+ *   16 KiB; INC_ERR_WORKSPACE where a STREAM_* route gets too little).                                                        */
+int inc_woq_gemm_perm(const void* x, int xdtype, const int32_t* k_order, const int32_t* qweight, const uint16_t* scales,
+                      const int32_t* qzeros, const void* bias, void* y, int64_t M, int64_t N, int64_t K, int64_t G,
+                      int group_size, int bits, void* workspace, int64_t workspace_bytes, inc_stream_t stream);
+
 /* Several packed modules that multiply the SAME x, in ONE launch -- the decode path of q / k / v (and of gate / up): n calls of
  * INCWeightOnlyLinear.forward (modules.py:594-610) on one activation, which the reference issues one F.linear after the other.
  *   x [M,K] of `xdtype`, M <= 64; module i: qweight[i] [K/8,N[i]], scales[i] [G,N[i]] fp16, qzeros[i] [G,ceil(N[i]/8)], bias[i] [N[i]] of

@@ -37,6 +37,10 @@ SIGNATURES = {
         c_int,
         [c_int64, c_int64, c_int64, c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_int64, _P, _P, _P, _P, _P, _P],
     ),
+    "inc_woq_gemm_perm": (
+        c_int,
+        [_P, c_int, _P, _P, _P, _P, _P, _P, c_int64, c_int64, c_int64, c_int64, c_int, c_int, _P, c_int64, _P],
+    ),
     "inc_woq_gemm_lut_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64]),
     "inc_woq_gemm_lut": (
         c_int,

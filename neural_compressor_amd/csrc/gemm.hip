@@ -1098,12 +1098,36 @@ constexpr int VS = 8;   // largest VSTEPS (sizes the workspace)
 // BITS = 8 (weight-only INT8, round 6): a step's 32 k of four columns are TWO packed rows per lane (a word = 4 k of one column), the
 // integer -> float step is the int8 wrap of dequant8_from_bytes (bit-identical to inc_woq_dequant); always 4 steps per wave, so a wave
 // streams the same 8 KiB as the 4-bit form with 8 steps.  `NW` = words per row of qzeros (N / 8 for 4 bits, N / 4 for 8).
-template <bool IS_BF16, bool G128, int VSTEPS, int MB, bool NT = false, int BITS = 4>
+// PERM (inc_woq_gemm_perm: act_order modules, whose packed words are sorted along K by group once): the A operand of a step is
+// x[row, k_order[k]] for the step's k instead of x[row, k] -- a lane reads its 8 entries of k_order (two 16-byte loads; k_order is
+// 16-byte aligned and the offset a multiple of 8 entries), clamps them to [0, K-1] so that no array can send a read outside x, and
+// packs eight 2-byte loads into the uint4 the plain form gets from one 16-byte load.  Nothing else differs: the same values reach
+// the same MFMAs in the same order, so the result equals the plain form's on x.index_select(1, k_order) bit for bit.  x is at
+// most 64 x K 16-bit values and is read by every workgroup: it stays in L2.
+// Order of issue: the entries of k_order for all of a wave's steps first, then the weights, then the gathers -- vector loads
+// return in order, so the gathers wait for the indices alone while the weights are on their way from HBM.  An index register is
+// done once its gather is issued; x is addressed by 32-bit byte offsets (the entry point requires M * K < 2^31).
+struct PermIdx8 { int4 lo, hi; };
+__device__ __forceinline__ PermIdx8 perm_load8(const int32_t* __restrict__ ko) {
+  return PermIdx8{*reinterpret_cast<const int4*>(ko), *reinterpret_cast<const int4*>(ko + 4)};
+}
+__device__ __forceinline__ uint4 perm_gather8(const uint16_t* __restrict__ x, uint32_t row_bytes, const PermIdx8& p, int kmax) {
+  const int raw[8] = {p.lo.x, p.lo.y, p.lo.z, p.lo.w, p.hi.x, p.hi.y, p.hi.z, p.hi.w};
+  uint32_t v[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int k = raw[j] < 0 ? 0 : (raw[j] > kmax ? kmax : raw[j]);
+    v[j] = *reinterpret_cast<const uint16_t*>(reinterpret_cast<const char*>(x) + (row_bytes + 2u * (uint32_t)k));
+  }
+  return make_uint4(v[0] | (v[1] << 16), v[2] | (v[3] << 16), v[4] | (v[5] << 16), v[6] | (v[7] << 16));
+}
+
+template <bool IS_BF16, bool G128, int VSTEPS, int MB, bool NT = false, int BITS = 4, bool PERM = false>
 __device__ __forceinline__ void woq_gemv_w4_body(
     const uint16_t* __restrict__ x, const uint32_t* __restrict__ qweight, const uint16_t* __restrict__ scales,
     const uint32_t* __restrict__ qzeros, const uint16_t* __restrict__ bias, uint16_t* __restrict__ y,
     float* __restrict__ partial, unsigned* __restrict__ counter, int M, int64_t N, int64_t K, int64_t NW,
-    int g_shift, int splitk, int strip, int slice) {
+    int g_shift, int splitk, int strip, int slice, const int32_t* __restrict__ k_order = nullptr) {
   constexpr int VS = VSTEPS;  // shadows the file-level maximum inside this kernel
   constexpr int ROWS = 16 * MB;
   constexpr int NOUT = ROWS * 64 / 256;  // outputs per thread of the strip
@@ -1121,6 +1145,16 @@ __device__ __forceinline__ void woq_gemv_w4_body(
   constexpr int WPS = BITS == 8 ? 2 : 1;  // 16-byte weight requests per lane and step
   static_assert(BITS == 4 || (BITS == 8 && !NT), "4- or 8-bit words");
   uint4 w[VS * WPS], a[MB][VS];
+  PermIdx8 kraw[PERM ? VS : 1];
+  if constexpr (PERM) {
+#pragma unroll
+    for (int s = 0; s < VS; ++s) {
+      int st = step0 + s;
+      if (st > steps_total - 1) st = steps_total - 1;  // (clamped like the weights' step: inside k_order)
+      kraw[s] = perm_load8(k_order + (int64_t)st * 32 + 8 * oct);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
 #pragma unroll
   for (int s = 0; s < VS; ++s) {
     int st = step0 + s;
@@ -1138,7 +1172,8 @@ __device__ __forceinline__ void woq_gemv_w4_body(
 #pragma unroll
     for (int b = 0; b < MB; ++b) {
       const int am = 16 * b + jn < M ? 16 * b + jn : M - 1;  // A row (clamped; rows >= M are zeroed below)
-      a[b][s] = *reinterpret_cast<const uint4*>(x + (int64_t)am * K + (int64_t)st * 32 + 8 * oct);
+      if constexpr (PERM) a[b][s] = perm_gather8(x, 2u * (uint32_t)am * (uint32_t)K, kraw[s], (int)(K - 1));
+      else a[b][s] = *reinterpret_cast<const uint4*>(x + (int64_t)am * K + (int64_t)st * 32 + 8 * oct);
     }
   }
   // group parameters: G128 -> one group per 4 steps (step0 is a multiple of 4)
@@ -1269,6 +1304,17 @@ __global__ __launch_bounds__(256) void woq_gemv_w4_kernel(
     int64_t G, int g_shift, int splitk) {
   woq_gemv_w4_body<IS_BF16, G128, VSTEPS, MB, NT, BITS>(x, qweight, scales, qzeros, bias, y, partial, counters + blockIdx.x, M, N, K, NW, g_shift, splitk,
                                                  (int)blockIdx.x, (int)blockIdx.y);
+}
+
+// the same workgroup with the activations gathered through k_order (PERM above)
+template <bool IS_BF16, bool G128, int VSTEPS, int MB, int BITS = 4>
+__global__ __launch_bounds__(256) void woq_gemv_w4_perm_kernel(
+    const uint16_t* __restrict__ x, const int32_t* __restrict__ k_order, const uint32_t* __restrict__ qweight,
+    const uint16_t* __restrict__ scales, const uint32_t* __restrict__ qzeros, const uint16_t* __restrict__ bias,
+    uint16_t* __restrict__ y, float* __restrict__ partial, unsigned* __restrict__ counters, int M, int64_t N, int64_t K, int64_t NW,
+    int g_shift, int splitk) {
+  woq_gemv_w4_body<IS_BF16, G128, VSTEPS, MB, false, BITS, true>(x, qweight, scales, qzeros, bias, y, partial, counters + blockIdx.x, M, N, K, NW, g_shift,
+                                                                 splitk, (int)blockIdx.x, (int)blockIdx.y, k_order);
 }
 
 // Several packed modules that multiply the SAME x (q / k / v of an attention block; gate / up of an MLP) in ONE launch
@@ -1661,12 +1707,15 @@ constexpr int GEMV16_WAVES = 16;
 constexpr int GEMV16_CH = 12;                                              // K-steps per wave and pass whose loads are issued up front
 constexpr int64_t GEMV16_MAX_K = (int64_t)32 * GEMV16_WAVES * 2 * GEMV16_CH;  // two passes: K <= 12288
 
-template <bool IS_BF16, bool NT = false>
+// PERM: x is gathered through k_order (perm_load8 / perm_gather8 above the streaming body; inc_woq_gemm_perm)
+template <bool IS_BF16, bool NT = false, bool PERM = false>
 __global__ __launch_bounds__(64 * GEMV16_WAVES) void woq_gemv16_w4_kernel(
     const uint16_t* __restrict__ x, const uint32_t* __restrict__ qweight, const uint16_t* __restrict__ scales,
     const uint32_t* __restrict__ qzeros, const uint16_t* __restrict__ bias, uint16_t* __restrict__ y, int M, int64_t N, int64_t K,
-    int64_t NW, int g_shift) {
-  constexpr int WAVES = GEMV16_WAVES, CH = GEMV16_CH;
+    int64_t NW, int g_shift, const int32_t* __restrict__ k_order = nullptr) {
+  // PERM: 8 steps per pass (the product routes K <= 4096 here: at most 8 steps per wave) -- the indices of a pass are in flight next
+  // to its weights, and a workgroup of 16 waves leaves a lane 128 registers.  The order of the MFMAs does not depend on CH.
+  constexpr int WAVES = GEMV16_WAVES, CH = PERM ? 8 : GEMV16_CH;
   __shared__ float red[WAVES * 16 * 17];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1687,6 +1736,16 @@ __global__ __launch_bounds__(64 * GEMV16_WAVES) void woq_gemv16_w4_kernel(
     uint32_t w[CH], zraw[CH];
     uint16_t sraw[CH];
     uint4 a[CH];
+    PermIdx8 kraw[PERM ? CH : 1];
+    if constexpr (PERM) {
+#pragma unroll
+      for (int s = 0; s < CH; ++s) {
+        int st = c0 + s;
+        if (st > hi - 1) st = hi - 1;
+        kraw[s] = perm_load8(k_order + (int64_t)st * 32 + 8 * kg);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
 #pragma unroll
     for (int s = 0; s < CH; ++s) {
       int st = c0 + s;
@@ -1695,7 +1754,8 @@ __global__ __launch_bounds__(64 * GEMV16_WAVES) void woq_gemv16_w4_kernel(
       w[s] = NT ? __builtin_nontemporal_load(wcol + (int64_t)st * 4 * N) : wcol[(int64_t)st * 4 * N];
       sraw[s] = scales[g * N + ncol];
       zraw[s] = qzeros[g * NW + (ncol >> 3)];
-      a[s] = *reinterpret_cast<const uint4*>(xrow + (int64_t)st * 32);
+      if constexpr (PERM) a[s] = perm_gather8(x, 2u * (uint32_t)am * (uint32_t)K, kraw[s], (int)(K - 1));
+      else a[s] = *reinterpret_cast<const uint4*>(xrow + (int64_t)st * 32);
     }
     __builtin_amdgcn_sched_barrier(0);  // everything above is in flight before the first use below
 #pragma unroll
@@ -2240,6 +2300,56 @@ int inc_woq_gemm(const void* x, int xdtype, const int32_t* qweight, const uint16
     if (bf) splitk_reduce_kernel<true><<<(unsigned)rb, 256, 0, s>>>(part, bp, yp, M, N, slices);
     else splitk_reduce_kernel<false><<<(unsigned)rb, 256, 0, s>>>(part, bp, yp, M, N, slices);
   }
+  INC_LAUNCH_RETURN();
+}
+
+// ---- act_order decode in one launch: y = x[:, k_order] W_sorted^T + bias ------------------------------------------------------
+// The plan is woq_gemm_plan's for the same shape without g_idx and a 16-byte aligned x (the gathered x is read 2 bytes at a time);
+// only the three streaming routes have a PERM form, everything else is the caller's index_select + inc_woq_gemm.
+int inc_woq_gemm_perm(const void* x, int xdtype, const int32_t* k_order, const int32_t* qweight, const uint16_t* scales,
+                      const int32_t* qzeros, const void* bias, void* y, int64_t M, int64_t N, int64_t K, int64_t G,
+                      int group_size, int bits, void* workspace, int64_t workspace_bytes, inc_stream_t stream) {
+  INC_CHECK_ARG(x && k_order && qweight && scales && qzeros && y && M > 0 && N > 0 && K > 0 && G > 0 && group_size > 0);
+  INC_CHECK_ARG((reinterpret_cast<uintptr_t>(x) & 1) == 0);
+  if ((reinterpret_cast<uintptr_t>(k_order) & 15) != 0 || M * K >= ((int64_t)1 << 31)) return INC_ERR_UNSUPPORTED;  // (x by 32-bit byte offsets)
+  WoqGemmPlan plan;
+  const int plan_rc = woq_gemm_plan(M, N, K, group_size, bits, xdtype, false, 0, reinterpret_cast<uintptr_t>(y), reinterpret_cast<uintptr_t>(bias),
+                                    workspace != nullptr, workspace_bytes, &plan);
+  if (plan_rc != INC_OK) return plan_rc;
+  const int route = plan.route, g_shift = plan.g_shift;
+  if (route != INC_WOQ_ROUTE_GEMV16 && route != INC_WOQ_ROUTE_STREAM_W4 && route != INC_WOQ_ROUTE_STREAM_W8) return INC_ERR_UNSUPPORTED;
+  if (route != INC_WOQ_ROUTE_GEMV16 && (!workspace || workspace_bytes < plan.need)) return INC_ERR_WORKSPACE;
+  hipStream_t s = inc_s(stream);
+  const uint16_t* xp = (const uint16_t*)x;
+  const uint32_t* qw = (const uint32_t*)qweight;
+  const uint32_t* qz = (const uint32_t*)qzeros;
+  const uint16_t* bp = (const uint16_t*)bias;
+  uint16_t* yp = (uint16_t*)y;
+  const bool bf = xdtype == INC_BF16;
+  if (route == INC_WOQ_ROUTE_GEMV16) {
+    const unsigned grid = (unsigned)ceil_div64(N, 16);
+    const int64_t NW = ceil_div64(N, 8);
+    if (bf) woq_gemv16_w4_kernel<true, false, true><<<grid, 64 * GEMV16_WAVES, 0, s>>>(xp, qw, scales, qz, bp, yp, (int)M, N, K, NW, g_shift, k_order);
+    else woq_gemv16_w4_kernel<false, false, true><<<grid, 64 * GEMV16_WAVES, 0, s>>>(xp, qw, scales, qz, bp, yp, (int)M, N, K, NW, g_shift, k_order);
+    INC_LAUNCH_RETURN();
+  }
+  const int splitk = plan.splitk;
+  unsigned* counters = (unsigned*)workspace;
+  float* part = (float*)((char*)workspace + WS_COUNTER_BYTES);
+  dim3 grid((unsigned)ceil_div64(N, 64), (unsigned)splitk);
+  const bool g128 = g_shift == -1 || g_shift >= 7;
+  const bool vs4 = plan.steps == 4;
+  const int64_t NW = ceil_div64(N, 32 / bits);
+#define INC_GEMVP(F, GG, V, B, W) woq_gemv_w4_perm_kernel<F, GG, V, B, W><<<grid, 256, 0, s>>>(xp, k_order, qw, scales, qz, bp, yp, part, counters, (int)M, N, K, NW, g_shift, splitk)
+#define INC_GEMVP2(F, GG)                                                                                                             \
+  {                                                                                                                                   \
+    if (route == INC_WOQ_ROUTE_STREAM_W8) { if (M > 32) INC_GEMVP(F, GG, 4, 4, 8); else if (M > 16) INC_GEMVP(F, GG, 4, 2, 8); else INC_GEMVP(F, GG, 4, 1, 8); } \
+    else if (M > 32) INC_GEMVP(F, GG, 4, 4, 4); else if (M > 16) INC_GEMVP(F, GG, 4, 2, 4); else if (vs4) INC_GEMVP(F, GG, 4, 1, 4); else INC_GEMVP(F, GG, 8, 1, 4);      \
+  }
+  if (bf) { if (g128) INC_GEMVP2(true, true) else INC_GEMVP2(true, false) }
+  else { if (g128) INC_GEMVP2(false, true) else INC_GEMVP2(false, false) }
+#undef INC_GEMVP2
+#undef INC_GEMVP
   INC_LAUNCH_RETURN();
 }
 

@@ -249,6 +249,44 @@ def woq_gemm(x2d, qweight, scales, qzeros, bias, N, K, group_size, bits, g_idx=N
     return y
 
 
+def woq_gemm_perm(x2d, k_order, qweight_sorted, scales, qzeros, bias, N, K, group_size, bits):
+    """y[M,N] = x[:, k_order] @ dequant(qweight_sorted)^T + bias in ONE launch (inc_woq_gemm_perm: the decode form of act_order /
+    HF desc_act modules, reference modules.py:427-431, 594-610).
+
+    `qweight_sorted` is the packed weight with its K axis sorted by group and `k_order` [K] int32 that order (what
+    MI355XWeightOnlyLinear builds once per packed state); the activations are gathered inside the decode kernels, entries of
+    k_order outside [0, K-1] are clamped.  Bit-identical to woq_gemm(x2d.index_select(1, k_order), qweight_sorted, ...).  Only the
+    streaming decode routes have this form (M <= 64; ops.woq_gemm_route says GEMV16 / STREAM_W4 / STREAM_W8 for the shape):
+    anything else raises -- gather x and call woq_gemm there, which WoqGemmCall(k_order=...) does by itself."""
+    if k_order.dtype is not torch.int32:
+        raise TypeError(f"k_order must be int32, got {k_order.dtype}")
+    if k_order.dim() != 1 or k_order.shape[0] != K or x2d.dim() != 2 or x2d.shape[1] != K:
+        raise ValueError(f"k_order must hold K = {K} entries and x2d be [M, {K}]; got {tuple(k_order.shape)} and {tuple(x2d.shape)}")
+    dev = x2d.device
+    if k_order.device != dev:
+        raise RuntimeError(f"tensors on different devices: {dev} vs {k_order.device}")
+    if dev.type != "cuda" or qweight_sorted.device != dev or not x2d.is_contiguous():
+        _dev(x2d, k_order, qweight_sorted, scales, qzeros, bias)  # raises the descriptive error
+    if x2d.dtype is not torch.bfloat16 and x2d.dtype is not torch.float16:
+        raise TypeError("woq_gemm computes in bf16 or fp16")
+    if bias is not None and bias.dtype != x2d.dtype:
+        bias = bias.to(x2d.dtype)
+    M = x2d.shape[0]
+    y = torch.empty((M, N), dtype=x2d.dtype, device=dev)
+    nbytes = _ws_bytes_cache.get((M, N, K))
+    if nbytes is None:
+        nbytes = _ws_bytes_cache[(M, N, K)] = lib.inc_woq_gemm_workspace_bytes(M, N, K)
+    with torch.cuda.device(dev):
+        ws = _workspace(dev, nbytes) if nbytes > 0 else None
+        rc = lib.inc_woq_gemm_perm(
+            x2d.data_ptr(), INC_BF16 if x2d.dtype is torch.bfloat16 else INC_F16, k_order.data_ptr(), qweight_sorted.data_ptr(),
+            scales.data_ptr(), qzeros.data_ptr(), _ptr(bias), y.data_ptr(), M, N, K, scales.shape[0], group_size, bits, _ptr(ws),
+            0 if ws is None else ws.numel(), torch.cuda.current_stream(dev).cuda_stream)
+    if rc != 0:
+        check(rc, "inc_woq_gemm_perm")
+    return y
+
+
 WOQ_GEMM_ROUTES = {
     1: "TILE_ANYW", 2: "STRIP8", 3: "STRIP", 4: "3A2B_W8", 5: "D2R", 6: "3A2B_W4", 7: "BIG", 8: "TILE", 9: "GEMV16", 10: "STREAM_W4",
     11: "STREAM_W8", 12: "SMALL",
@@ -284,17 +322,34 @@ class WoqGemmCall:
     """inc_woq_gemm with everything that does not change between calls resolved once (the decode path: the kernel is ~6 us,
     so the host side counts).  Built by MI355XWeightOnlyLinear for its packed buffers; per call only the activation pointer,
     the output, the stream and the (device, stream) workspace are looked up.  Holds references to the tensors whose addresses
-    it caches; the owner rebuilds it when a buffer is replaced."""
+    it caches; the owner rebuilds it when a buffer is replaced.
+
+    With `k_order` (int32 [K]; act_order modules) `qweight` is the K-sorted packed weight and the call computes x[:, k_order] W^T:
+    up to 64 rows through inc_woq_gemm_perm wherever the shape takes a streaming decode route (the gather happens inside the
+    kernel: one launch), otherwise x2d.index_select(1, k_order) and the ordinary launch.  `owner_qweight` is the buffer the sorted
+    copy was made from: current() is asked about that one."""
 
     __slots__ = ("dev", "dev_index", "dtype", "dt", "N", "K", "G", "gs", "bits", "qw", "sc", "qz", "gi", "bi", "keep", "need", "fn",
-                 "bias_conv", "versions", "tag")
+                 "bias_conv", "versions", "tag", "ko", "perm_keep", "perm_versions", "perm_ok")
     lut = False  # (WoqGemmLutCall: True)
+    PERM_ROUTES = (9, 10, 11)  # GEMV16, STREAM_W4, STREAM_W8: the routes inc_woq_gemm_perm launches
 
-    def __init__(self, qweight, scales, qzeros, bias, N, K, group_size, bits, dtype, g_idx=None):
-        dev = _dev(qweight, scales, qzeros, bias, g_idx)
+    def __init__(self, qweight, scales, qzeros, bias, N, K, group_size, bits, dtype, g_idx=None, k_order=None, owner_qweight=None):
         if dtype is not torch.bfloat16 and dtype is not torch.float16:
             raise TypeError("woq_gemm computes in bf16 or fp16")
-        self.keep = (qweight, scales, qzeros, bias, g_idx)
+        if k_order is not None:
+            if k_order.dtype is not torch.int32:
+                raise TypeError(f"k_order must be int32, got {k_order.dtype}")
+            if k_order.dim() != 1 or k_order.shape[0] != K:
+                raise ValueError(f"k_order must hold K = {K} entries, got {tuple(k_order.shape)}")
+            if g_idx is not None:
+                raise ValueError("k_order goes with the K-sorted weight, whose groups are contiguous: no g_idx")
+        dev = _dev(qweight, scales, qzeros, bias, g_idx, k_order, owner_qweight)
+        self.ko = _ptr(k_order)
+        self.perm_keep = (qweight, k_order)
+        self.perm_versions = (qweight._version, None if k_order is None else k_order._version)
+        self.perm_ok = {}  # M -> inc_woq_gemm_perm takes it
+        self.keep = (qweight if owner_qweight is None else owner_qweight, scales, qzeros, bias, g_idx)
         self.versions = tuple(None if t is None else t._version for t in self.keep)
         if bias is not None and bias.dtype != dtype:
             bias = bias.to(dtype)  # converted once (the packed module stores fp16, a bf16 model multiplies in bf16)
@@ -320,11 +375,29 @@ class WoqGemmCall:
         k, v = self.keep, self.versions
         return (k[0] is qweight and k[1] is scales and k[2] is qzeros and k[3] is bias and qweight._version == v[0]
                 and scales._version == v[1] and qzeros._version == v[2] and (bias is None or bias._version == v[3])
-                and self.tag[0] is owner_g_idx and (owner_g_idx is None or owner_g_idx._version == self.tag[1]))
+                and self.tag[0] is owner_g_idx and (owner_g_idx is None or owner_g_idx._version == self.tag[1])
+                and (self.ko is None or (self.perm_keep[0]._version, self.perm_keep[1]._version) == self.perm_versions))
+
+    def _perm_takes(self, M):
+        """inc_woq_gemm_perm launches for M rows: the dispatcher's own plan for the shape (host only; y comes from torch.empty and
+        is 16-byte aligned, as the planner is told)."""
+        rc = lib.inc_woq_gemm_route(M, self.N, self.K, self.gs, self.bits, self.dt, 0, None, None, self.bi, None, 0, None, None, None,
+                                    None, None, None)
+        return rc in self.PERM_ROUTES
 
     def __call__(self, x2d):
         """x2d: contiguous [M, K] of the call's dtype on the call's device (the owner checks)."""
         M = x2d.shape[0]
+        # the pointers between dtype and bias: (qweight, scales, qzeros, g_idx), or (k_order, qweight, scales, qzeros) for inc_woq_gemm_perm
+        fn, name, a2, a3, a4, a5 = self.fn, "inc_woq_gemm", self.qw, self.sc, self.qz, self.gi
+        if self.ko is not None:
+            ok = self.perm_ok.get(M)
+            if ok is None:
+                ok = self.perm_ok[M] = self._perm_takes(M)
+            if ok:  # the gather happens in the kernel
+                fn, name, a2, a3, a4, a5 = lib.inc_woq_gemm_perm, "inc_woq_gemm_perm", self.ko, self.qw, self.sc, self.qz
+            else:
+                x2d = x2d.index_select(1, self.perm_keep[1])
         y = torch.empty((M, self.N), dtype=self.dtype, device=self.dev)
         need = self.need.get(M)
         if need is None:
@@ -338,14 +411,14 @@ class WoqGemmCall:
                 buf = _workspace(self.dev, need)
             wp, wn = buf.data_ptr(), buf.numel()
         if _cur_device() == idx:
-            rc = self.fn(x2d.data_ptr(), self.dt, self.qw, self.sc, self.qz, self.gi, self.bi, y.data_ptr(), M, self.N, self.K, self.G,
-                         self.gs, self.bits, wp, wn, stream)
+            rc = fn(x2d.data_ptr(), self.dt, a2, a3, a4, a5, self.bi, y.data_ptr(), M, self.N, self.K, self.G,
+                    self.gs, self.bits, wp, wn, stream)
         else:
             with torch.cuda.device(self.dev):
-                rc = self.fn(x2d.data_ptr(), self.dt, self.qw, self.sc, self.qz, self.gi, self.bi, y.data_ptr(), M, self.N, self.K,
-                             self.G, self.gs, self.bits, wp, wn, stream)
+                rc = fn(x2d.data_ptr(), self.dt, a2, a3, a4, a5, self.bi, y.data_ptr(), M, self.N, self.K,
+                        self.G, self.gs, self.bits, wp, wn, stream)
         if rc != 0:
-            check(rc, "inc_woq_gemm")
+            check(rc, name)
         return y
 
 
@@ -365,6 +438,7 @@ class WoqGemmLutCall:
     `current()` has WoqGemmCall's contract (same tensors, version counters unchanged)."""
 
     lut = True
+    ko = None  # (WoqGemmCall: the act_order gather)
 
     def __init__(self, qweight, table16, scales, qzeros, bias, N, K, group_size, scale_round, dtype):
         import ctypes

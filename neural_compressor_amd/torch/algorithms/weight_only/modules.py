@@ -282,7 +282,8 @@ class MI355XWeightOnlyLinear(WeightOnlyLinear):
         if call is not None and x.dtype is call.dtype and x.device == call.dev and x.is_contiguous() and x.numel() > 0 and x.shape[-1] == call.K:
             bufs = self._buffers
             if (call.current(bufs["qweight"], bufs["scales"], bufs.get("qzeros"), bufs.get("bias", d.get("bias")), bufs.get("g_idx", d.get("g_idx")))
-                    and (not call.lut or (self.LUT_FUSED and x.numel() <= self.LUT_MAX_M * call.K))):
+                    and (not call.lut or (self.LUT_FUSED and x.numel() <= self.LUT_MAX_M * call.K))
+                    and (call.ko is None or self.ACT_ORDER_FUSED_GATHER)):
                 y = call(x if x.dim() == 2 else x.view(-1, call.K))
                 return y if x.dim() == 2 else y.view(*x.shape[:-1], call.N)
         if x.dtype not in (torch.bfloat16, torch.float16):
@@ -307,8 +308,16 @@ class MI355XWeightOnlyLinear(WeightOnlyLinear):
             gi = self.g_idx
             call.tag = (gi, None if gi is None else gi._version)
             y = call(x2d)
+        elif plan == "fused_act_order" and self.ACT_ORDER_FUSED_GATHER:
+            # act_order: the K axis is sorted by group once (below); per call only the activations are gathered -- inside the decode
+            # kernels up to 64 rows (inc_woq_gemm_perm: one launch, and the prepared call serves the module from now on)
+            call = d["_call"] = ops.WoqGemmCall(self._qweight_sorted, self.scales, self.qzeros, self.bias, self.out_features, self.in_features,
+                                                self.group_size, self.bits, x2d.dtype, k_order=self._k_order32, owner_qweight=self.qweight)
+            gi = self.g_idx
+            call.tag = (gi, gi._version)
+            y = call(x2d)
         elif plan == "fused_act_order":
-            # act_order: the K axis is sorted by group once (below); per call only the activations are gathered
+            # ... or by a torch kernel in front of the ordinary launch (ACT_ORDER_FUSED_GATHER = False)
             y = ops.woq_gemm(
                 x2d.index_select(1, self._k_order), self._qweight_sorted, self.scales, self.qzeros, self.bias,
                 self.out_features, self.in_features, self.group_size, self.bits,
@@ -333,6 +342,9 @@ class MI355XWeightOnlyLinear(WeightOnlyLinear):
             y = y.float()
         return y.reshape(*lead, self.out_features)
 
+    # act_order modules (plan "fused_act_order"): True = a prepared call that gathers the activations inside the decode kernels
+    # (inc_woq_gemm_perm, up to 64 rows on the streaming routes); False = x.index_select + ops.woq_gemm per call, two launches
+    ACT_ORDER_FUSED_GATHER = True
     # widths other than 4 / 8 bits: True = multiply through inc_woq_gemm's per-element tile form (no dense weight ever exists; 8-10 x
     # slower), False = HIP recover() into a transient dense weight + the library GEMM (what the reference's forward does on its CPU)
     ODD_WIDTH_FUSED = False
@@ -360,7 +372,7 @@ class MI355XWeightOnlyLinear(WeightOnlyLinear):
         # (the per-element form is the memory-saving route, not the fast one: measured 376-480 us against 40-100 us for HIP recover() +
         # the library GEMM at 4096^2 for every M from 1 to 4096, profiles/r6/anyw_route_time.log -- so it is opt-in: ODD_WIDTH_FUSED)
         fusable = self.use_optimum_format and (self.group_size % self.n_pack == 0 if self.bits in (4, 8) else self.ODD_WIDTH_FUSED)
-        self._k_order = self._qweight_sorted = None
+        self._k_order = self._k_order32 = self._qweight_sorted = None
         # group sizes that are neither a power of two >= 32 nor the whole row (e.g. 96) run inc_woq_gemm's general 128 x 128 tile kernel
         # above 16 rows: 190-245 us at 4096 x 4032 against 34-74 us for HIP recover() + the library GEMM (scripts/route_sweep.py) -- such
         # modules keep the fused form for decode-sized batches only
@@ -388,6 +400,7 @@ class MI355XWeightOnlyLinear(WeightOnlyLinear):
                         words = torch.where(words >= 2**31, words - 2**32, words)
                         self._qweight_sorted = words.to(torch.int32).contiguous()
                         self._k_order = order
+                        self._k_order32 = order.to(torch.int32)  # what inc_woq_gemm_perm reads
                         plan = "fused_act_order"
                     else:
                         plan = "fused_g_idx"  # groups of uneven size: the library's general kernel looks the group up per k
