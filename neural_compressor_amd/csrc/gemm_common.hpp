@@ -1,22 +1,54 @@
-// gemm_common.hpp -- helpers shared by the dequant-GEMM translation units (gemm.hip, gemm_d2r.hip): MFMA wrappers,
-// the int4 -> bf16 / f16 dequantisation arithmetic and the 256 x 256 x 64 tile constants.
+// gemm_common.hpp -- shared by the dequant-GEMM translation units: the launchers inc_woq_gemm (gemm.hip) dispatches to, one per
+// kernel family and file, the constants its route planner shares with them, and the device helpers (MFMA wrappers, the int4 / int8
+// -> bf16 / f16 dequantisation arithmetic, the 256 x 256 x 64 tile constants).
 #pragma once
 #include "common.hpp"
 
-// gemm_d2r.hip: launcher of the direct-to-register dequant-GEMM, called by inc_woq_gemm (gemm.hip)
-int inc_launch_woq_gemm_d2r(const uint16_t* x, const uint32_t* qw, const uint16_t* scales, const uint32_t* qz, const uint16_t* bias,
-                            uint16_t* y, int64_t M, int64_t N, int64_t K, int64_t NW, int g_shift, int y_vec_ok, float* part, int steps,
-                            int splits, bool bf, int ns, int abl, hipStream_t s);
-// the same tile with eight waves, two per SIMD (gemm_d2r8.hip)
-int inc_launch_woq_gemm_d2r8(const uint16_t* x, const uint32_t* qw, const uint16_t* scales, const uint32_t* qz, const uint16_t* bias,
-                             uint16_t* y, int64_t M, int64_t N, int64_t K, int64_t NW, int g_shift, int y_vec_ok, float* part, int steps,
-                             int splits, bool bf, hipStream_t s);
+// ---- what the route planner (woq_gemm_plan, gemm.hip) and the kernels' files both need ---------------------------------------------
+// workspace layout : [0, 16 KiB) arrival counters of the fast GEMV (uint32 per 64-column
+// strip; MUST be zero on first use, the kernel re-arms them), then fp32 split-K partials.
+constexpr int64_t WS_COUNTER_BYTES = 16384;
+constexpr int64_t GEMV_MAX_M = 64;          // gemm_stream.hip: M <= 64 streams the weights once (woq_gemv_w4_kernel with 1 / 2 / 4 row blocks)
+constexpr int64_t GEMV16_MAX_K = 12288;     // gemm_stream.hip: the no-split decode kernel's two passes of 12 K-steps per wave
+constexpr int64_t STRIP_MAX_M = 1024;       // gemm_strip.hip: the mid-M strip kernel
+constexpr int64_t STREAM_SLICE_K = 32 * 4 * 4;  // k of one K-slice of the streaming kernel at 4 steps per wave (4 waves x 4 steps x 32 k)
+
+// the tensors of one packed module, the shape and the stream: what every launcher below takes
+struct WoqGemmArgs {
+  const uint16_t* x;
+  const uint32_t* qw;
+  const uint16_t* scales;
+  const uint32_t* qz;
+  const uint16_t* bias;
+  uint16_t* y;
+  int64_t M, N, K, NW;  // NW: words per row of qzeros
+  int g_shift;
+  bool bf;
+  hipStream_t s;
+};
+
+// gemm_tile.hip: the 128 x 128 tile kernel (any width, any group size, g_idx) and the generic split-K kernel for M <= 16 with its plan
+int inc_launch_woq_gemm_tile(const WoqGemmArgs& a, const int32_t* g_idx, int bits, int group_size, int x_vec_ok);
+int inc_woq_gemm_small_slices(int64_t N, int64_t K, int bits, int* kw_per_slice_out);
+int inc_launch_woq_gemm_small(const WoqGemmArgs& a, const int32_t* g_idx, int bits, int group_size, float* part, int slices, int kw_per_slice);
+
+// gemm_tile256.hip: the 256 x 256 kernels (two-stage "big"; 3A2B in 4 / 8 bits, `dbg` = the harness flag); the slab reduce of every split-K 256-row launch
+int inc_launch_woq_gemm_big(const WoqGemmArgs& a, int y_vec_ok);
+int inc_launch_woq_gemm_3a2b(const WoqGemmArgs& a, int bits, int y_vec_ok, float* part, int steps, int splits, int dbg);
+int inc_launch_slab_reduce(const WoqGemmArgs& a, const float* part, int splits);
+int inc_launch_woq_gemm_pc(const WoqGemmArgs& a, int y_vec_ok, float* part, int steps, int splits, int dbg);  // harness only: tools/kbench_gemm_2.inc
+
+// gemm_strip.hip: the 64 x 128 mid-M strip kernel and its split-K plan (`dbg`: harness ablations)
+int inc_woq_gemm_strip_splitk(int64_t M, int64_t N, int64_t K);
+int inc_launch_woq_gemm_strip(const WoqGemmArgs& a, float* part, unsigned* counters, int splitk, int dbg);
+
+// gemm_d2r.hip: the direct-to-register dequant-GEMM; the same tile with eight waves, two per SIMD (tools/gemm_d2r8.hip, harness only)
+int inc_launch_woq_gemm_d2r(const WoqGemmArgs& a, int y_vec_ok, float* part, int steps, int splits, int ns, int abl);
+int inc_launch_woq_gemm_d2r8(const WoqGemmArgs& a, int y_vec_ok, float* part, int steps, int splits);
 
 // gemm_strip8.hip: the 128 x 128 mid-M kernel (four waves, K split inside the workgroup) and its split-K plan
 int inc_woq_gemm_strip8_splitk(int64_t M, int64_t N, int64_t K);
-int inc_launch_woq_gemm_strip8(const uint16_t* x, const uint32_t* qw, const uint16_t* scales, const uint32_t* qz, const uint16_t* bias,
-                               uint16_t* y, int64_t M, int64_t N, int64_t K, int64_t NW, int g_shift, float* part, unsigned* counters,
-                               int splitk, bool bf, hipStream_t s);
+int inc_launch_woq_gemm_strip8(const WoqGemmArgs& a, float* part, unsigned* counters, int splitk);
 
 // modules that share x, one launch (inc_woq_gemm_multi): the per-module tensors of the batch, passed to the kernels by value
 constexpr int GEMV_MAX_BATCH = 8;
@@ -31,6 +63,28 @@ struct GemvBatch {
   int first[GEMV_MAX_BATCH + 1];     // first strip of every module, then the number of strips
   int n;
 };
+
+// gemm_stream.hip: the streaming GEMV (M <= 64) in all its forms, and the no-split decode kernel.  A launch is x, the plan (steps, mb,
+// splitk: woq_gemm_plan / gemv_multi_plan) and the weights: ONE module `mod` (its x, M, K, g_shift, bf, s are not read) -- plain, gathered
+// through `k_order` (inc_woq_gemm_perm) or, in the harness, `nt` (non-temporal loads) -- or the `batch` of inc_woq_gemm_multi.
+struct StreamLaunch {
+  const uint16_t* x;
+  int64_t M, K;
+  int g_shift;
+  bool bf;
+  hipStream_t s;
+  int bits, steps, mb, splitk;
+  int64_t strips;      // 64-column strips: blockIdx.x
+  float* part;
+  unsigned* counters;
+  const WoqGemmArgs* mod = nullptr;
+  int64_t G = 0;       // (an argument the plain kernel takes and does not use)
+  const int32_t* k_order = nullptr;
+  const GemvBatch* batch = nullptr;
+  bool nt = false;
+};
+int inc_launch_woq_gemv_stream(const StreamLaunch& l);
+int inc_launch_woq_gemv16(const WoqGemmArgs& a, const int32_t* k_order, bool nt);
 
 namespace {
 
@@ -255,6 +309,26 @@ __device__ __forceinline__ uint4 dequant8(uint32_t w, float s_over_u, float nzs)
   o.y = cvt_pair<IS_BF16>(e01[1], o01[1]);
   o.z = cvt_pair<IS_BF16>(e23[0], o23[0]);
   o.w = cvt_pair<IS_BF16>(e23[1], o23[1]);
+  return o;
+}
+
+// two 8-bit packed words (k0..3, k4..7 of one column) -> 8 x rn16(int8(q - z) * s).  The difference wraps to int8 exactly like the
+// reference's recover(), which unpacks 8-bit codes and zero points into int8 tensors and subtracts there (modules.py:377-443:
+// an asymmetric code more than 127 away from its zero point flips sign) -- and like inc_woq_dequant / the first-generation
+// kernel (dequant_word).  The product of an int8 and an 11-bit scale is exact in fp32: one rounding, in the 16-bit conversion.
+template <bool IS_BF16>
+__device__ __forceinline__ uint4 dequant8_from_bytes(uint32_t w0, uint32_t w1, float s, int z) {
+  float f[8];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    f[j] = (float)(int)(int8_t)(uint8_t)(((w0 >> (8 * j)) & 0xffu) - (uint32_t)z) * s;
+    f[4 + j] = (float)(int)(int8_t)(uint8_t)(((w1 >> (8 * j)) & 0xffu) - (uint32_t)z) * s;
+  }
+  uint4 o;
+  o.x = cvt_pair<IS_BF16>(f[0], f[1]);
+  o.y = cvt_pair<IS_BF16>(f[2], f[3]);
+  o.z = cvt_pair<IS_BF16>(f[4], f[5]);
+  o.w = cvt_pair<IS_BF16>(f[6], f[7]);
   return o;
 }
 

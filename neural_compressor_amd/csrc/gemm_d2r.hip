@@ -1,7 +1,7 @@
 // gemm_d2r.hip -- K4a, third generation: fused INT4 -> bf16 dequant-GEMM with the weights DIRECT TO REGISTERS.
 //
 // Replaces INCWeightOnlyLinear.forward (reference modules.py:594-610 = recover() once + F.linear) for M > 64 rows, like the
-// producer / consumer kernel in gemm.hip, with the same 256 x 256 x 64 tile and bit-identical outputs (every accumulator
+// producer / consumer kernel (tools/kbench_gemm_1.inc, built into gemm_tile256.hip by the harness), with the same 256 x 256 x 64 tile and bit-identical outputs (every accumulator
 // receives the same MFMAs in the same order).  What changes is who touches the weights:
 //
 //   * a packed word of the optimum layout (8 consecutive k of ONE output column, modules.py:254-260) IS one lane's A operand
@@ -596,10 +596,8 @@ extern "C" int inc_debug_set_d2r_timeline(void* dev_buffer) {  // harness only: 
 #endif
 
 // Launcher used by inc_woq_gemm (gemm.hip).  `abl` selects a timing-only ablation in the harness build (0 in the product).
-int inc_launch_woq_gemm_d2r(const uint16_t* x, const uint32_t* qw, const uint16_t* scales, const uint32_t* qz, const uint16_t* bias,
-                            uint16_t* y, int64_t M, int64_t N, int64_t K, int64_t NW, int g_shift, int y_vec_ok, float* part, int steps,
-                            int splits, bool bf, int ns, int abl, hipStream_t s) {
-  const unsigned grid = (unsigned)(ceil_div64(M, TM) * ceil_div64(N, TN));
+int inc_launch_woq_gemm_d2r(const WoqGemmArgs& a, int y_vec_ok, float* part, int steps, int splits, int ns, int abl) {
+  const unsigned grid = (unsigned)(ceil_div64(a.M, TM) * ceil_div64(a.N, TN));
   dim3 g2(grid, (unsigned)splits);
 #ifdef INC_KBENCH
   if (abl == 256 && g_d2r_abl_override) abl = g_d2r_abl_override;
@@ -612,9 +610,9 @@ int inc_launch_woq_gemm_d2r(const uint16_t* x, const uint32_t* qw, const uint16_
       (void)hipFuncSetAttribute((const void*)woq_gemm_w4_d2r_kernel<B, NS_, A>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);    \
       inc_attr_done(attr_set);                                                                                                         \
     }                                                                                                                                  \
-    woq_gemm_w4_d2r_kernel<B, NS_, A><<<g2, D2R_THREADS, smem, s>>>(x, qw, scales, qz, bias, y, M, N, K, NW, g_shift, y_vec_ok, part, steps); \
+    woq_gemm_w4_d2r_kernel<B, NS_, A><<<g2, D2R_THREADS, smem, a.s>>>(a.x, a.qw, a.scales, a.qz, a.bias, a.y, a.M, a.N, a.K, a.NW, a.g_shift, y_vec_ok, part, steps); \
   }
-  if (!bf) {
+  if (!a.bf) {
     INC_D2R(false, 4, 0)
   }
 #ifdef INC_KBENCH

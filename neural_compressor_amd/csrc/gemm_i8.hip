@@ -10,9 +10,9 @@
 //
 // Tile 256 (M) x 256 (N) x 128 (K bytes) per workgroup, 512 threads = 8 waves as 2 (M) x 4 (N), a wave owns 128 x 64 = 4 x 2
 // MFMA tiles (128 int32 accumulators).  Both operands are K-contiguous int8, so both tiles are 256 rows x 128 B and use the
-// SAME path as the x tile of the 4-bit kernel (gemm.hip): LDS-DMA, 8 full 128-byte rows per instruction, 16-byte chunk
+// SAME path as the x tile of the 4-bit kernels (gemm_tile256.hip): LDS-DMA, 8 full 128-byte rows per instruction, 16-byte chunk
 // index XOR-ed with (row >> 1) & 7 on the source address and again on the ds_read_b128 side (no bank conflicts).  Two 64 KiB
-// stages: the DMA of tile t+1 is issued at the top of step t.  W is the A operand and x the B operand, as in gemm.hip, so a
+// stages: the DMA of tile t+1 is issued at the top of step t.  W is the A operand and x the B operand, as in gemm_tile256.hip, so a
 // lane owns 4 consecutive output columns and the epilogue stores 8 bytes.
 // Tile quantisation: the tiles of the last, partly filled round of workgroups (or all of them when there are fewer tiles
 // than CUs) are split along K into `split` workgroups each; every split stores its int32 tile into its own slab of the

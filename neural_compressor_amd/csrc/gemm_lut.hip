@@ -23,7 +23,7 @@
 // weights once -- split into a low-byte table L and a high-byte table H of four dwords each -- and every nibble is then a byte select:
 // v_perm_b32 picks among 8 entries, one v_bfi_b32 on bit 3 picks the half (sel16 below), two more perms interleave the bytes.
 // Split-K across workgroups: fp32 partial slabs written through (sc1), one relaxed agent-scope ticket per (M tile, column strip) in
-// the workspace's first 16 KiB, the last arriver sums the slabs in slice order, adds the bias and stores (the hand-off of gemm.hip's
+// the workspace's first 16 KiB, the last arriver sums the slabs in slice order, adds the bias and stores (the hand-off of gemm_stream.hip's
 // streaming kernel).
 #include "gemm_common.hpp"
 

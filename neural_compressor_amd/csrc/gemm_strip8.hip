@@ -1,6 +1,6 @@
 // gemm_strip8.hip -- K4c', the mid-M fused INT4 -> bf16 / fp16 dequant-GEMM (128 < M <= 1024, few 256 x 256 tiles), round 6.
 //
-// The strip kernel of round 2 (gemm.hip, woq_gemm_w4_strip_kernel) gives a workgroup 64 rows x 128 columns: every packed weight is
+// The strip kernel of round 2 (gemm_strip.hip, woq_gemm_w4_strip_kernel) gives a workgroup 64 rows x 128 columns: every packed weight is
 // dequantised once per 64 rows, and a K-step's dequantisation (8 words x ~19 VALU instructions) is as long as its 32 MFMAs -- PMC:
 // VALU 27 %, MFMA 28 % of the wave time, the rest waits (profiles/r2_pmc).  This kernel doubles the rows per dequantised weight
 // WITHOUT parking a 256-row tile that such an M would leave half empty:
@@ -342,17 +342,15 @@ int inc_woq_gemm_strip8_splitk(int64_t M, int64_t N, int64_t K) {
 
 // Launcher used by inc_woq_gemm (gemm.hip).  `part` / `counters`: split-K slabs and per-tile arrival counters (zero on first use,
 // re-armed by the kernel) or NULL with splitk = 1.
-int inc_launch_woq_gemm_strip8(const uint16_t* x, const uint32_t* qw, const uint16_t* scales, const uint32_t* qz, const uint16_t* bias,
-                               uint16_t* y, int64_t M, int64_t N, int64_t K, int64_t NW, int g_shift, float* part, unsigned* counters,
-                               int splitk, bool bf, hipStream_t s) {
+int inc_launch_woq_gemm_strip8(const WoqGemmArgs& a, float* part, unsigned* counters, int splitk) {
   static std::atomic<uint64_t> attr_set{0};
   if (inc_attr_needed(attr_set)) {
     (void)hipFuncSetAttribute((const void*)woq_gemm_w4_strip8_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, S8_SMEM_BYTES);
     (void)hipFuncSetAttribute((const void*)woq_gemm_w4_strip8_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, S8_SMEM_BYTES);
     inc_attr_done(attr_set);
   }
-  dim3 grid((unsigned)((N + 127) / 128), (unsigned)((M + 127) / 128), (unsigned)splitk);
-  if (bf) woq_gemm_w4_strip8_kernel<true><<<grid, 64 * S8_WAVES, S8_SMEM_BYTES, s>>>(x, qw, scales, qz, bias, y, part, counters, (int)M, N, K, NW, g_shift, splitk);
-  else woq_gemm_w4_strip8_kernel<false><<<grid, 64 * S8_WAVES, S8_SMEM_BYTES, s>>>(x, qw, scales, qz, bias, y, part, counters, (int)M, N, K, NW, g_shift, splitk);
+  dim3 grid((unsigned)((a.N + 127) / 128), (unsigned)((a.M + 127) / 128), (unsigned)splitk);
+  if (a.bf) woq_gemm_w4_strip8_kernel<true><<<grid, 64 * S8_WAVES, S8_SMEM_BYTES, a.s>>>(a.x, a.qw, a.scales, a.qz, a.bias, a.y, part, counters, (int)a.M, a.N, a.K, a.NW, a.g_shift, splitk);
+  else woq_gemm_w4_strip8_kernel<false><<<grid, 64 * S8_WAVES, S8_SMEM_BYTES, a.s>>>(a.x, a.qw, a.scales, a.qz, a.bias, a.y, part, counters, (int)a.M, a.N, a.K, a.NW, a.g_shift, splitk);
   INC_LAUNCH_RETURN();
 }

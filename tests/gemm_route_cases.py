@@ -2,7 +2,7 @@
 
   * CASES: the route table of the fused weight-only GEMM.  (shape, dtype-independent, alignment) -> the kernel family
     `inc_woq_gemm_route` must report and its variant (K-slices, row blocks, steps, store / load form).  A retuned threshold in
-    neural_compressor_amd/csrc/gemm.hip (woq_gemm_plan) moves a case off the kernel it was written for: the table is where that
+    neural_compressor_amd/csrc/gemm.hip (woq_gemm_plan; the kernels it chooses among are csrc/gemm_*.hip) moves a case off the kernel it was written for: the table is where that
     has to be acknowledged -- move the shape so that the route keeps a case, never drop the route.
   * the inputs of a case (asymmetric weights whose scales and zero points differ clearly between neighbouring columns and
     groups, a bias that is distinct per column, activations with a few large entries) and its float64 reference;

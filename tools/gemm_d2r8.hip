@@ -422,10 +422,8 @@ __global__ __launch_bounds__(D8_THREADS) void woq_gemm_w4_d2r8_kernel(
 
 }  // namespace
 
-int inc_launch_woq_gemm_d2r8(const uint16_t* x, const uint32_t* qw, const uint16_t* scales, const uint32_t* qz, const uint16_t* bias,
-                             uint16_t* y, int64_t M, int64_t N, int64_t K, int64_t NW, int g_shift, int y_vec_ok, float* part, int steps,
-                             int splits, bool bf, hipStream_t s) {
-  const unsigned grid = (unsigned)(ceil_div64(M, TM) * ceil_div64(N, TN));
+int inc_launch_woq_gemm_d2r8(const WoqGemmArgs& a, int y_vec_ok, float* part, int steps, int splits) {
+  const unsigned grid = (unsigned)(ceil_div64(a.M, TM) * ceil_div64(a.N, TN));
   dim3 g2(grid, (unsigned)splits);
   constexpr int smem = D8_NS * T_ASTAGE > TM * D8_CPITCH ? D8_NS * T_ASTAGE : TM * D8_CPITCH;
   static std::atomic<uint64_t> attr_set{0};
@@ -434,7 +432,7 @@ int inc_launch_woq_gemm_d2r8(const uint16_t* x, const uint32_t* qw, const uint16
     (void)hipFuncSetAttribute((const void*)woq_gemm_w4_d2r8_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
     inc_attr_done(attr_set);
   }
-  if (bf) woq_gemm_w4_d2r8_kernel<true><<<g2, D8_THREADS, smem, s>>>(x, qw, scales, qz, bias, y, M, N, K, NW, g_shift, y_vec_ok, part, steps);
-  else woq_gemm_w4_d2r8_kernel<false><<<g2, D8_THREADS, smem, s>>>(x, qw, scales, qz, bias, y, M, N, K, NW, g_shift, y_vec_ok, part, steps);
+  if (a.bf) woq_gemm_w4_d2r8_kernel<true><<<g2, D8_THREADS, smem, a.s>>>(a.x, a.qw, a.scales, a.qz, a.bias, a.y, a.M, a.N, a.K, a.NW, a.g_shift, y_vec_ok, part, steps);
+  else woq_gemm_w4_d2r8_kernel<false><<<g2, D8_THREADS, smem, a.s>>>(a.x, a.qw, a.scales, a.qz, a.bias, a.y, a.M, a.N, a.K, a.NW, a.g_shift, y_vec_ok, part, steps);
   return 0;
 }

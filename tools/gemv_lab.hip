@@ -1,6 +1,6 @@
-// gemv_lab -- the decode (M = 1) streaming body of csrc/gemm.hip with timing-only ablations (WRONG results unless GL_ABL = 0):
+// gemv_lab -- the decode (M = 1) streaming body of csrc/gemm_stream.hip with timing-only ablations (WRONG results unless GL_ABL = 0):
 //   GL_ABL bit 0: no dequantise + MFMA; bit 1: no split-K hand-off (every slice writes y itself); bit 2: all weight requests hit one row.
-// tools/gemv_lab_body.inc is generated from csrc/gemm.hip (see NOTES round 6).  Build:
+// tools/gemv_lab_body.inc is generated from csrc/gemm_stream.hip (see NOTES round 6).  Build:
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -w -DGL_ABL=<n> -Iinclude -Ineural_compressor_amd/csrc tools/gemv_lab.hip -o tools/gemv_lab_a<n>
 #include <hip/hip_runtime.h>
 

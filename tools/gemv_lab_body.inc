@@ -1,4 +1,4 @@
-// generated from csrc/gemm.hip (profiles/NOTES.md round 6): woq_gemv_w4_body with timing-only ablation hooks (GL_ABL)
+// generated from csrc/gemm_stream.hip (then part of gemm.hip; profiles/NOTES.md round 6): woq_gemv_w4_body with timing-only ablation hooks (GL_ABL)
 template <bool IS_BF16, bool G128, int VSTEPS, int MB, bool NT = false>
 __device__ __forceinline__ void woq_gemv_w4_body(
     const uint16_t* __restrict__ x, const uint32_t* __restrict__ qweight, const uint16_t* __restrict__ scales,

@@ -1,5 +1,25 @@
-// harness-only code of gemm.hip (superseded kernel generations / timing-only ablations; tools/Makefile builds
-// them into tools/libinc_mi355x_kbench.so with -DINC_KBENCH; they are NOT part of libinc_mi355x.so).  Included in place by gemm.hip.
+// harness-only code of gemm_tile256.hip (superseded kernel generations / timing-only ablations; tools/Makefile builds
+// them into tools/libinc_mi355x_kbench.so with -DINC_KBENCH; they are NOT part of libinc_mi355x.so).  Included in place by gemm_tile256.hip.
+// =============================================================================================
+// large-M path "PC" (4-bit, K % 128 == 0): the 3A2B tile with PRODUCER / CONSUMER wave specialisation
+// =============================================================================================
+// The 3A2B kernel above is issue-bound, not matrix-pipe-bound (profiles/r1_pmc: MFMA busy 0.49, 52 % of wave time
+// issue-stalled): each of its 8 waves carries ~200 non-MFMA instructions per 32 MFMAs (10 VMEM requests, ~70 VALU of
+// dequantisation, LDS writes, counted waits), and with two such waves per SIMD nothing is left to hide anything.  Here the
+// SAME tile (256 x 256 x 64, three x stages + two dequantised-W stages = 160 KiB) is worked by 12 waves in two roles:
+//   waves 0..7  CONSUMERS (2 x 4, 128 x 64 of the tile each, two per SIMD): per K-step 24 fragment ds_read_b128, 32 MFMAs and
+//               the wave's share of the x tile's LDS-DMA (4 x 1 KiB, issued two steps ahead between the MFMA groups, retired
+//               with a counted vmcnt before the step's barrier) -- no VGPR loads, no dequantisation;
+//   waves 8..11 PRODUCERS (one per SIMD): the weight side.  Per wave and step 8 packed-word loads + scale + zero word of ONE
+//               column per lane (two steps ahead), the int4 -> bf16 arithmetic (fp8-decoder trick of dequant8, bit-identical
+//               to inc_woq_dequant) and 8 fragment-order ds_write_b128, each issued right behind the 15 VALU that produce it.
+// tools/kbench pcablate (profiles/r2b): with everything on the producers their serial chain (0.79 us per step at full clock:
+// x DMA issue 0.19, W loads 0.04, arithmetic 0.17, LDS writes 0.37) is as long as the MFMA work of the step and -- at the
+// ~1.7 GHz the chip sustains under MFMA load -- longer; the consumers alone (reads + MFMA + barrier) run at 1.59 PFLOP/s.
+// One s_barrier per K-step for all 12 waves: step t multiplies x stage t % 3 and W stage t & 1 while the producers dequantise
+// tile t+1 into W stage (t+1) & 1 (read last in step t-1) and the DMA of x tile t+2 fills stage (t+2) % 3 (read last in
+// step t-1).  A wave's 128 fp32 accumulators + one fragment set fit the 168-register budget of three waves per SIMD.
+typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 constexpr int PC_THREADS = 768;
 
 // Epilogue of the producer / consumer kernel for a FULL 256 x 256 tile: the accumulator layout (a lane owns 4 consecutive

@@ -13,12 +13,7 @@
 #include <random>
 #include <vector>
 
-#include "inc_mi355x.h"
-
-int inc_woq_gemm_strip8_splitk(int64_t M, int64_t N, int64_t K);
-int inc_launch_woq_gemm_strip8(const uint16_t* x, const uint32_t* qw, const uint16_t* scales, const uint32_t* qz, const uint16_t* bias,
-                               uint16_t* y, int64_t M, int64_t N, int64_t K, int64_t NW, int g_shift, float* part, unsigned* counters,
-                               int splitk, bool bf, hipStream_t s);
+#include "gemm_common.hpp"  // (the launcher of gemm_strip8.hip and its arguments)
 
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("HIP error %s at %s:%d\n", hipGetErrorString(e), __FILE__, __LINE__); exit(1); } } while (0)
 
@@ -49,7 +44,7 @@ static int run(int64_t M, int64_t N, int64_t K) {
   const int sk = inc_woq_gemm_strip8_splitk(M, N, K);
   auto old_route = [&]() { return inc_woq_gemm(dx, INC_BF16, (const int32_t*)dqw, dsc, (const int32_t*)dqz, nullptr, nullptr, y0, M, N, K, G, gs, 4, ws, wsb, s); };
   auto new_route = [&]() {
-    return inc_launch_woq_gemm_strip8(dx, dqw, dsc, dqz, nullptr, y1, M, N, K, NW, 7, sk > 1 ? (float*)((char*)ws2 + 16384) : nullptr, (unsigned*)ws2, sk, true, s);
+    return inc_launch_woq_gemm_strip8(WoqGemmArgs{dx, dqw, dsc, dqz, nullptr, y1, M, N, K, NW, 7, true, s}, sk > 1 ? (float*)((char*)ws2 + 16384) : nullptr, (unsigned*)ws2, sk);
   };
   if (old_route() != 0 || new_route() != 0) { printf("launch failed\n"); return 1; }
   CK(hipStreamSynchronize(s));

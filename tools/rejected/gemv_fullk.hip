@@ -1,10 +1,10 @@
 // REJECTED EXPERIMENT (round 6, profiles/NOTES.md): correct (all GEMM parity tests green) and SLOWER than the split-K streaming kernel --
 // q+k+v 12.3 vs 11.4 us, gate+up 17.9 vs 17.6, 11008 x 4096 11.7 vs 10.5 us cold.  Kept out of the build; to try it again: put it back into
-// csrc/, add it to the Makefiles and restore the two routing hooks in gemm.hip (git log).
+// csrc/, add it to the Makefiles and restore the two routing hooks in gemm.hip (woq_gemm_plan and the switch of inc_woq_gemm; git log).
 //
 // gemv_fullk.hip -- K4b', decode (M <= 4) of packed 4-bit modules without split-K (round 6).
 //
-// The streaming kernel (gemm.hip, woq_gemv_w4_kernel) cuts K into slices over workgroups to put 512+ of them on the chip and pays for
+// The streaming kernel (gemm_stream.hip, woq_gemv_w4_kernel) cuts K into slices over workgroups to put 512+ of them on the chip and pays for
 // it after the last MFMA: write-through partials, a drain, a ticket, the last arriver's reload.  Timing-only ablations of its body on
 // the cold q+k+v launch (tools/gemv_lab, profiles/NOTES.md round 6) showed four ADDITIVE phases: 3.4 us launch + wave ramp, 3.6 us of HBM
 // streaming, 2.05 us of dequantise + MFMA, 1.65 us of hand-off = 10.8 us -- nothing overlaps, because every wave issues all of its
