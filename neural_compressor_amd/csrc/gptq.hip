@@ -1,31 +1,23 @@
-// gptq.hip -- K5/K6: GPTQ Hessian accumulation (MFMA syrk) and the block-column error-compensation loop.
+// gptq.hip -- K6: the block-column error-compensation loop of GPTQ (the Hessian syrk lives in gptq_hessian.hip).
 //
 // Reference (relative to /root/reference/neural_compressor/torch/algorithms/weight_only/gptq.py):
-//   GPTQ.add_batch      :1111-1141   H <- H*n/(n+b) + (sqrt(2/(n+b)) X)^T (sqrt(2/(n+b)) X)
-//   GPTQ.fasterquant    :1143-1351   dead columns, damping, the blocked column loop, lazy update
+//   GPTQ.fasterquant    :1143-1351   the blocked column loop, lazy update
 //   Quantizer.quantize  :1626-1637   q = clamp(round(x/scale)+zero, 0, maxq); scale*(q-zero)
 //
 // Kernels
-//   hessian_syrk_16bit  bf16/f16 MFMA 32x32x16, fp32 accumulate, 128x128 tile of H per workgroup, upper
-//                       triangle of tiles only.  X is [T,K] row-major (tokens x features) so both MFMA
-//                       operands are X^T: each thread fetches an 8(token) x 8(feature) block with eight
-//                       16-byte row loads (full 128-byte segments per row), transposes it in registers
-//                       and writes eight 16-byte [feature][token] rows into LDS (pitch 144 B: both the
-//                       ds_write_b128 and the fragment ds_read_b128 are bank-conflict free).
-//   hessian_syrk_f32    exact fp32 MFMA 32x32x2 (A/B = one f32 per lane: no transpose needed).
 //   gptq_quant_block    the serial 128-column chain.  One lane owns one weight row; the 128-wide row
 //                       panel lives in 128 VGPRs (fully unrolled), the 128x128 Hinv tile is broadcast
 //                       out of LDS.  Arithmetic is kept un-fused (mul then sub, true divisions) so that
 //                       one block is bit-identical to the reference's torch ops.
 //   gptq_lazy_update    W[:, i2:] -= Err1 @ Hinv[i1:i2, i2:] with the exact fp32 MFMA (first generation here; the product kernels -- tile and
-//                       strip form -- live in gptq_lazy.hip, the Hessian syrk in gptq_hessian.hip).
+//                       strip form -- live in gptq_lazy.hip).
 #include <math.h>
 
+#include <algorithm>
 #include <type_traits>
 
-#include <algorithm>
-
 #include "common.hpp"
+#include "gptq_common.hpp"
 
 namespace {
 
@@ -84,7 +76,6 @@ __global__ __launch_bounds__(256) void gptq_prepare_weight_vec_kernel(const void
 // ---------------------------------------------------------------------------------------------
 // the serial column chain for one 128-column block
 // ---------------------------------------------------------------------------------------------
-constexpr int QB = 128;         // columns per block
 constexpr int QROWS = 64;       // rows per workgroup (one wave)
 constexpr int QPITCH = QB + 1;  // fp32 staging pitch
 
@@ -431,18 +422,46 @@ __global__ __launch_bounds__(256) void gptq_lazy_update_kernel(float* __restrict
     }
 }
 
-constexpr int L2T = 128;  // rows / columns of a lazy-update tile
-
-#ifdef INC_KBENCH  // superseded by the third generation below; harness flag 86, its bitwise A/B partner (tools/kbench colloop / qlayer)
+#ifdef INC_KBENCH  // the second generation of the lazy update (LAB_LAZY_V2, bitwise A/B partner of the product: tools/kbench colloop / qlayer)
 #include "../../tools/kbench_gptq_2.inc"
-#include "../../tools/kbench_gptq_3.inc"  // harness flag 106: the lazy update with split (bf16 x 3) products -- an experiment, not the product
+#include "../../tools/kbench_gptq_3.inc"  // LAB_LAZY_X3: the lazy update with split (bf16 x 3) products -- an experiment, not the product
 #endif  // INC_KBENCH
 
-// third / fourth generation of the lazy update: gptq_lazy.hip
-}  // namespace
-void inc_launch_lazy_update_v3(float* w, const float* Hinv, const float* err, int64_t N, int64_t K, int64_t i1, int64_t c_begin,
-                               int64_t c_end, bool exclusive, hipStream_t s);
-namespace {
+// The quad-per-row chain kernel over one full block on the 128-column grid (chain_block_ok), `gpb` groups per block.  PARAMS: it
+// computes the groups' (scale, zero) itself.
+template <bool PARAMS>
+int launch_quant_block_q4(const float* w, const float* Hinv, float* scale, float* zero, uint8_t* codes, void* q_out, int q_dtype, float* err,
+                          int64_t N, int64_t K, int64_t G, int64_t i1, int64_t g0, int gpb, float maxq, int sym, hipStream_t s) {
+  const size_t smem4 = (size_t)QB * QB * 4;  // 64 KiB: Hinv1 tile, reused as the output stage
+  static std::atomic<uint64_t> attr_set{0};
+  if (inc_attr_needed(attr_set)) {
+    auto lds = [&](auto... kernel) { ((void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem4), ...); };
+    lds(gptq_quant_block_q4_kernel<INC_F32, 1, PARAMS>, gptq_quant_block_q4_kernel<INC_F32, 2, PARAMS>, gptq_quant_block_q4_kernel<INC_F32, 4, PARAMS>);
+    lds(gptq_quant_block_q4_kernel<INC_F16, 1, PARAMS>, gptq_quant_block_q4_kernel<INC_F16, 2, PARAMS>, gptq_quant_block_q4_kernel<INC_F16, 4, PARAMS>);
+    lds(gptq_quant_block_q4_kernel<INC_BF16, 1, PARAMS>, gptq_quant_block_q4_kernel<INC_BF16, 2, PARAMS>, gptq_quant_block_q4_kernel<INC_BF16, 4, PARAMS>);
+    inc_attr_done(attr_set);
+  }
+  const unsigned blocks4 = (unsigned)ceil_div64(N, Q4R * Q4W);
+  auto launch = [&](auto kernel) { kernel<<<blocks4, 64 * Q4W, smem4, s>>>(w, Hinv, scale, zero, codes, q_out, err, N, K, G, i1, g0, maxq, sym); };
+  INC_DISPATCH_DTYPE(q_dtype, DT, {
+    if (gpb == 1) launch(gptq_quant_block_q4_kernel<DT, 1, PARAMS>);
+    else if (gpb == 2) launch(gptq_quant_block_q4_kernel<DT, 2, PARAMS>);
+    else launch(gptq_quant_block_q4_kernel<DT, 4, PARAMS>);
+  })
+  INC_LAUNCH_RETURN();
+}
+
+// The trailing update of block [i1, i1 + count) over the columns [c_begin, c_end) with the product kernels (gptq_lazy.hip).  Returns
+// false, having launched nothing, when the block is not one they take (lazy_block_ok).
+bool lazy_update_range(float* w, const float* Hinv, const float* err, int64_t N, int64_t K, int64_t i1, int count, int64_t c_begin,
+                       int64_t c_end, bool exclusive, hipStream_t s) {
+  if (!lazy_block_ok(K, i1, count)) return false;
+#ifdef INC_KBENCH
+  if (lazy_update_lab_launch(w, Hinv, err, N, K, i1, c_begin, c_end, exclusive, s)) return true;
+#endif
+  inc_launch_lazy_update_v3(w, Hinv, err, N, K, i1, c_begin, c_end, exclusive, s);
+  return true;
+}
 
 }  // namespace
 
@@ -468,10 +487,14 @@ int inc_gptq_quant_block(const float* w, const float* Hinv, const float* scale, 
                          inc_stream_t stream) {
   INC_CHECK_ARG(w && Hinv && scale && zero && err && N > 0 && K > 0 && G > 0);
   INC_CHECK_ARG(i1 >= 0 && count > 0 && count <= QB && i1 + count <= K && bits >= 1 && bits <= 8);
-  const size_t smem = (size_t)QB * QB * 4 + (size_t)QROWS * QPITCH * 4 + (size_t)QROWS * (QB + 4);
-  const unsigned blocks = (unsigned)ceil_div64(N, QROWS);
   const float maxq = (float)((1 << bits) - 1);
   hipStream_t s = inc_s(stream);
+  // second-generation kernel: full 128-column block starting on a 128-column boundary, 1 / 2 / 4 groups per block
+  const int gpb = groups_per_block(group_size, true);
+  if (gpb && chain_block_ok(K, i1, count) && !inc_force_small_tiles())
+    return launch_quant_block_q4<false>(w, Hinv, const_cast<float*>(scale), const_cast<float*>(zero), codes, q_out, q_dtype, err, N, K, G, i1,
+                                        group_size > 0 ? i1 / group_size : 0, gpb, maxq, 0, s);
+  const size_t smem = (size_t)QB * QB * 4 + (size_t)QROWS * QPITCH * 4 + (size_t)QROWS * (QB + 4);
   static std::atomic<uint64_t> attr_set{0};
   if (inc_attr_needed(attr_set)) {
     (void)hipFuncSetAttribute((const void*)gptq_quant_block_kernel<INC_F32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
@@ -479,33 +502,8 @@ int inc_gptq_quant_block(const float* w, const float* Hinv, const float* scale, 
     (void)hipFuncSetAttribute((const void*)gptq_quant_block_kernel<INC_BF16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     inc_attr_done(attr_set);
   }
-  // second-generation kernel: full 128-column block starting on a 128-column boundary, 1 / 2 / 4 groups per block
-  int gpb = 0;
-  if (group_size <= 0 || (group_size % QB) == 0) gpb = 1;
-  else if (group_size == 64) gpb = 2;
-  else if (group_size == 32) gpb = 4;
-  if (gpb && count == QB && (i1 % QB) == 0 && (K % 4) == 0 && K * (int64_t)(QB + 1) * 4 < ((int64_t)1 << 32) && !inc_force_small_tiles()) {
-    const size_t smem4 = (size_t)QB * QB * 4;  // 64 KiB: Hinv1 tile, reused as the output stage
-    static std::atomic<uint64_t> attr4_set{0};
-#define INC_Q4_ATTR(DT, GP) (void)hipFuncSetAttribute((const void*)gptq_quant_block_q4_kernel<DT, GP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem4)
-    if (inc_attr_needed(attr4_set)) {
-      INC_Q4_ATTR(INC_F32, 1); INC_Q4_ATTR(INC_F32, 2); INC_Q4_ATTR(INC_F32, 4);
-      INC_Q4_ATTR(INC_F16, 1); INC_Q4_ATTR(INC_F16, 2); INC_Q4_ATTR(INC_F16, 4);
-      INC_Q4_ATTR(INC_BF16, 1); INC_Q4_ATTR(INC_BF16, 2); INC_Q4_ATTR(INC_BF16, 4);
-      inc_attr_done(attr4_set);
-    }
-#undef INC_Q4_ATTR
-    const unsigned blocks4 = (unsigned)ceil_div64(N, Q4R * Q4W);
-    const int64_t g0 = group_size > 0 ? i1 / group_size : 0;
-#define INC_Q4(GP) gptq_quant_block_q4_kernel<DT, GP><<<blocks4, 64 * Q4W, smem4, s>>>(w, Hinv, const_cast<float*>(scale), const_cast<float*>(zero), codes, q_out, err, N, K, G, i1, g0, maxq, 0)
-    INC_DISPATCH_DTYPE(q_dtype, DT, {
-      if (gpb == 1) INC_Q4(1); else if (gpb == 2) INC_Q4(2); else INC_Q4(4);
-    })
-#undef INC_Q4
-    INC_LAUNCH_RETURN();
-  }
   INC_DISPATCH_DTYPE(q_dtype, DT, {
-    gptq_quant_block_kernel<DT><<<blocks, 64, smem, s>>>(w, Hinv, scale, zero, codes, q_out, err, N, K, G, i1, count, group_size, maxq);
+    gptq_quant_block_kernel<DT><<<(unsigned)ceil_div64(N, QROWS), 64, smem, s>>>(w, Hinv, scale, zero, codes, q_out, err, N, K, G, i1, count, group_size, maxq);
   })
   INC_LAUNCH_RETURN();
 }
@@ -517,32 +515,12 @@ int inc_gptq_quant_block_params(const float* w, const float* Hinv, float* scale,
                                 int bits, int sym, inc_stream_t stream) {
   INC_CHECK_ARG(w && Hinv && scale && zero && err && N > 0 && K > 0 && G > 0);
   INC_CHECK_ARG(i1 >= 0 && count > 0 && count <= QB && i1 + count <= K && bits >= 1 && bits <= 8);
-  int gpb = 0;
-  if (group_size == QB) gpb = 1;
-  else if (group_size == 64) gpb = 2;
-  else if (group_size == 32) gpb = 4;
-  if (!(gpb && count == QB && (i1 % QB) == 0 && (K % 4) == 0 && K * (int64_t)(QB + 1) * 4 < ((int64_t)1 << 32))) return INC_ERR_UNSUPPORTED;
+  const int gpb = groups_per_block(group_size, false);
+  if (!(gpb && chain_block_ok(K, i1, count))) return INC_ERR_UNSUPPORTED;
   const int64_t g0 = i1 / group_size;
   INC_CHECK_ARG(g0 + gpb <= G);
-  const float maxq = (float)((1 << bits) - 1);
-  hipStream_t s = inc_s(stream);
-  const size_t smem4 = (size_t)QB * QB * 4;
-  static std::atomic<uint64_t> attr_set{0};
-#define INC_Q4P_ATTR(DT, GP) (void)hipFuncSetAttribute((const void*)gptq_quant_block_q4_kernel<DT, GP, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem4)
-  if (inc_attr_needed(attr_set)) {
-    INC_Q4P_ATTR(INC_F32, 1); INC_Q4P_ATTR(INC_F32, 2); INC_Q4P_ATTR(INC_F32, 4);
-    INC_Q4P_ATTR(INC_F16, 1); INC_Q4P_ATTR(INC_F16, 2); INC_Q4P_ATTR(INC_F16, 4);
-    INC_Q4P_ATTR(INC_BF16, 1); INC_Q4P_ATTR(INC_BF16, 2); INC_Q4P_ATTR(INC_BF16, 4);
-    inc_attr_done(attr_set);
-  }
-#undef INC_Q4P_ATTR
-  const unsigned blocks4 = (unsigned)ceil_div64(N, Q4R * Q4W);
-#define INC_Q4P(GP) gptq_quant_block_q4_kernel<DT, GP, true><<<blocks4, 64 * Q4W, smem4, s>>>(w, Hinv, scale, zero, codes, q_out, err, N, K, G, i1, g0, maxq, sym)
-  INC_DISPATCH_DTYPE(q_dtype, DT, {
-    if (gpb == 1) INC_Q4P(1); else if (gpb == 2) INC_Q4P(2); else INC_Q4P(4);
-  })
-#undef INC_Q4P
-  INC_LAUNCH_RETURN();
+  return launch_quant_block_q4<true>(w, Hinv, scale, zero, codes, q_out, q_dtype, err, N, K, G, i1, g0, gpb, (float)((1 << bits) - 1), sym,
+                                     inc_s(stream));
 }
 
 int inc_gptq_lazy_update(float* w, const float* Hinv, const float* err, int64_t N, int64_t K,
@@ -550,27 +528,8 @@ int inc_gptq_lazy_update(float* w, const float* Hinv, const float* err, int64_t 
   INC_CHECK_ARG(w && Hinv && err && N > 0 && K > 0 && i1 >= 0 && count > 0 && count <= QB);
   const int64_t i2 = i1 + count;
   if (i2 >= K) return INC_OK;  // nothing to the right of the block
-  if (count == QB && (i1 % 4) == 0 && (K % 4) == 0 && K * (int64_t)(QB + 1) * 4 < ((int64_t)1 << 32) && !inc_force_small_tiles() && inc_small_tiles_flag(-1) != 86) {
-    inc_launch_lazy_update_v3(w, Hinv, err, N, K, i1, i2, K, true, inc_s(stream));
-    INC_LAUNCH_RETURN();
-  }
-#ifdef INC_KBENCH
-  if (count == QB && (i1 % 4) == 0 && (K % 4) == 0 && K * (int64_t)(QB + 1) * 4 < ((int64_t)1 << 32) && !inc_force_small_tiles()) {  // harness flag 86: second generation
-    const int ncol_tiles = (int)ceil_div64(K - i2, L2T);
-    const int row_tiles = (int)ceil_div64(N, L2T);
-    int nchunks = (int)ceil_div64(512, row_tiles);  // ~512 workgroups when the trailing matrix is wide enough
-    if (nchunks > ncol_tiles) nchunks = ncol_tiles;
-    const size_t smem2 = (size_t)2 * L2T * L2T * 4;  // 128 KiB
-    static std::atomic<uint64_t> attr2_set{0};
-    if (inc_attr_needed(attr2_set)) {
-      (void)hipFuncSetAttribute((const void*)gptq_lazy_update_v2_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem2);
-      inc_attr_done(attr2_set);
-    }
-    gptq_lazy_update_v2_kernel<true><<<dim3((unsigned)nchunks, (unsigned)row_tiles), 256, smem2, inc_s(stream)>>>(
-        w, Hinv, err, N, K, i1, i2, nchunks, ncol_tiles);
-    INC_LAUNCH_RETURN();
-  }
-#endif
+  if (!inc_force_small_tiles() && lazy_update_range(w, Hinv, err, N, K, i1, count, i2, K, true, inc_s(stream))) INC_LAUNCH_RETURN();
+  // first generation: any block
   const size_t smem = (size_t)LT * LAP * 4 + (size_t)QB * LT * 4;
   static std::atomic<uint64_t> attr_set{0};
   if (inc_attr_needed(attr_set)) {
@@ -591,28 +550,7 @@ int inc_gptq_lazy_update_cols(float* w, const float* Hinv, const float* err, int
   INC_CHECK_ARG(col_begin >= i2 && col_end <= K && col_begin <= col_end && ((col_begin - i2) % L2T) == 0 &&
                 (col_end == K || ((col_end - col_begin) % L2T) == 0));
   if (col_begin == col_end) return INC_OK;
-  if (!(count == QB && (i1 % 4) == 0 && (K % 4) == 0 && K * (int64_t)(QB + 1) * 4 < ((int64_t)1 << 32))) return INC_ERR_UNSUPPORTED;
-#ifdef INC_KBENCH
-  if (inc_small_tiles_flag(-1) == 106 && launch_lazy_update_x3(w, err, N, K, i1, col_begin, col_end, inc_s(stream))) INC_LAUNCH_RETURN();
-#endif
-  if (inc_small_tiles_flag(-1) != 86) {
-    inc_launch_lazy_update_v3(w, Hinv, err, N, K, i1, col_begin, col_end, false, inc_s(stream));
-    INC_LAUNCH_RETURN();
-  }
-#ifdef INC_KBENCH  // harness flag 86: second generation
-  const int ncol_tiles = (int)ceil_div64(col_end - col_begin, L2T);
-  const int row_tiles = (int)ceil_div64(N, L2T);
-  int nchunks = (int)ceil_div64(512, row_tiles);
-  if (nchunks > ncol_tiles) nchunks = ncol_tiles;
-  const size_t smem2 = (size_t)2 * L2T * L2T * 4;  // 128 KiB
-  static std::atomic<uint64_t> attr2_set{0};
-  if (inc_attr_needed(attr2_set)) {
-    (void)hipFuncSetAttribute((const void*)gptq_lazy_update_v2_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem2);
-    inc_attr_done(attr2_set);
-  }
-  gptq_lazy_update_v2_kernel<true><<<dim3((unsigned)nchunks, (unsigned)row_tiles), 256, smem2, inc_s(stream)>>>(
-      w, Hinv, err, N, K, i1, col_begin, nchunks, ncol_tiles);
-#endif
+  if (!lazy_update_range(w, Hinv, err, N, K, i1, count, col_begin, col_end, false, inc_s(stream))) return INC_ERR_UNSUPPORTED;
   INC_LAUNCH_RETURN();
 }
 
@@ -639,8 +577,7 @@ int inc_gptq_quantize_layer(float* w, const float* Hinv, float* scale, float* ze
   const bool lookahead = aux_stream != nullptr && (flags & INC_GPTQ_NO_LOOKAHEAD) == 0 && K % QB == 0 && blocksize % QB == 0 && K >= 3 * QB;
   // find_params inside the quantisation launch: only when the reference block IS the 128-column block and every group lies inside it
   const bool fuse_params = (flags & INC_GPTQ_NO_FUSED_PARAMS) == 0 && dynamic_groups && !mse && blocksize == QB &&
-                           (group_size == 32 || group_size == 64 || group_size == QB) && K % QB == 0 && own_tables &&
-                           (K % 4) == 0 && K * (int64_t)(QB + 1) * 4 < ((int64_t)1 << 32);
+                           groups_per_block(group_size, false) != 0 && K % QB == 0 && own_tables && chain_block_ok(K, 0, QB);
   float* errs[2] = {err_ws, err_ws + N * QB};
   hipEvent_t ready = nullptr, rest_done = nullptr;
   bool rest_pending = false;

@@ -10,18 +10,21 @@
 //                       operands are X^T: each thread fetches an 8(token) x 8(feature) block with eight
 //                       16-byte row loads (full 128-byte segments per row), transposes it in registers
 //                       and writes eight 16-byte [feature][token] rows into LDS (pitch 144 B: both the
-//                       ds_write_b128 and the fragment ds_read_b128 are bank-conflict free).
+//                       ds_write_b128 and the fragment ds_read_b128 are bank-conflict free).  K < 256, unaligned X.
 //   hessian_syrk_tr_256 the product tile: 256 x 256 of H per workgroup, X staged untouched by LDS-DMA, fragments by
-//                       ds_read_b64_tr_b16 (see below); single and batched (all Hessians of a forward) launches.
+//                       ds_read_b64_tr_b16 (see below); single and batched launches (_multi_kernel: all Hessians of a
+//                       forward; hessian_tail_finalize_kernel folds the split tiles of its last round).
 //   hessian_syrk_f32    exact fp32 MFMA 32x32x2 (A/B = one f32 per lane: no transpose needed).
-// (The column loop lives in gptq.hip; the two were one translation unit until round 6 -- this half alone compiles in a minute.)
+//   hessian_diag / hessian_mirror   dead columns + damping, upper -> lower.
+// Harness only (tools/kbench_gptq_1.inc, kbench_gptq_tile_lab.inc; -DINC_KBENCH): the first 256 x 256 generation (operands transposed
+// in registers), the other forms of the transpose-read tile and their launches by harness flag: one hook per entry point below.
 #include <math.h>
 
+#include <algorithm>
 #include <type_traits>
 
-#include <algorithm>
-
 #include "common.hpp"
+#include "gptq_common.hpp"
 
 namespace {
 
@@ -204,10 +207,6 @@ __global__ __launch_bounds__(256) void hessian_syrk_16bit_kernel(const uint16_t*
 }
 
 constexpr int H2 = 256;  // H tile edge of the 256 x 256 kernels
-
-#ifdef INC_KBENCH  // first 256 x 256 generation (operands transposed in registers): harness flag 45, A/B partner of the kernel below
-#include "../../tools/kbench_gptq_1.inc"
-#endif  // INC_KBENCH
 
 // ---- 256x256 syrk tile, transpose-read generation (round 2) --------------------------------------------------------
 // The kernel above moves X through registers: per 64-token step every thread issues eight 16-byte loads, transposes an 8x8
@@ -401,19 +400,6 @@ __global__ __launch_bounds__(512) void hessian_syrk_tr_256_kernel(const uint16_t
   hessian_syrk_tr_tile<IS_BF16>(x, T, K, ldx, H, beta, alpha, nt, (int)blockIdx.x, (int)gridDim.x);
 }
 
-#ifdef INC_KBENCH  // the tile's other generations and its timing-only ablations: harness code
-#include "../../tools/kbench_gptq_tile_lab.inc"
-#endif
-
-#ifdef INC_KBENCH
-template <bool IS_BF16, bool TAIL>
-__global__ __launch_bounds__(512) void hessian_syrk_16bit_256_kernel(const uint16_t* __restrict__ x, int64_t T,
-                                                                     int64_t K, int64_t ldx, float* __restrict__ H,
-                                                                     float beta, float alpha, int nt) {
-  hessian_syrk_256_tile<IS_BF16, TAIL>(x, T, K, ldx, H, beta, alpha, nt, (int)blockIdx.x, (int)gridDim.x);
-}
-#endif
-
 // Several Hessians of ONE calibration forward in a single launch (same token count T): the three K = 4096 Hessians of a Llama
 // block have 136 tiles each -- alone they leave 120 of the 256 CUs idle for the whole launch (0.395 of peak by the 2*T*K^2
 // convention against 0.64 at K = 11008, profiles/r1l); together with the K = 11008 one they are 1354 tiles of equal length
@@ -448,8 +434,19 @@ __device__ __forceinline__ void hessian_segment(int64_t T, int tok, int seg, int
   tcount = t1 > t0 ? t1 - t0 : 0;
 }
 
-template <bool IS_BF16>
-__global__ __launch_bounds__(512) void hessian_syrk_tr_256_multi_kernel(HessianBatch args, int64_t T) {
+// the problem that owns tile `b` of the batch (wave-uniform)
+__device__ __forceinline__ int hessian_batch_problem(const HessianBatch& args, int b) {
+  int p = 0;
+#pragma unroll
+  for (int i = 1; i < HESSIAN_MAX_BATCH; ++i)
+    if (i < args.n && b >= args.first[i]) p = i;
+  return __builtin_amdgcn_readfirstlane(p);
+}
+
+// One workgroup of the batched launch: its tile and, in the split tail, its token range from the block index, then `tile` (a
+// generation of the 256 x 256 tile with `tok`-token stages) on the problem that owns it.
+template <class Tile>
+__device__ __forceinline__ void hessian_batch_workgroup(const HessianBatch& args, int64_t T, int tok, Tile tile) {
   const int gb = (int)blockIdx.x + args.block0;  // index in the whole call's grid
   int b = gb, seg = 0;
   const bool split = b >= args.full;
@@ -458,68 +455,33 @@ __global__ __launch_bounds__(512) void hessian_syrk_tr_256_multi_kernel(HessianB
     seg = u % args.nseg;
     b = args.full + u / args.nseg;
   }
-  int p = 0;
-#pragma unroll
-  for (int i = 1; i < HESSIAN_MAX_BATCH; ++i)
-    if (i < args.n && b >= args.first[i]) p = i;
-  p = __builtin_amdgcn_readfirstlane(p);
+  const int p = hessian_batch_problem(args, b);
   if (!split) {
-    hessian_syrk_tr_tile<IS_BF16>(args.x[p], T, args.K[p], args.ldx[p], args.H[p], args.beta[p], args.alpha[p], args.nt[p],
-                                  b - args.first[p], args.first[p + 1] - args.first[p]);
+    tile(args.x[p], T, args.K[p], args.ldx[p], args.H[p], args.beta[p], args.alpha[p], args.nt[p], b - args.first[p],
+         args.first[p + 1] - args.first[p], (float*)nullptr);
   } else {
     int64_t t0, tc;
-    hessian_segment(T, TR_TOK, seg, args.nseg, t0, tc);
+    hessian_segment(T, tok, seg, args.nseg, t0, tc);
     float* slab = args.slab + ((int64_t)(gb - args.full)) * (H2 * H2);
     if (tc > 0)
-      hessian_syrk_tr_tile<IS_BF16>(args.x[p] + t0 * args.ldx[p], tc, args.K[p], args.ldx[p], args.H[p], args.beta[p], args.alpha[p],
-                                    args.nt[p], b - args.first[p], args.first[p + 1] - args.first[p], slab);
+      tile(args.x[p] + t0 * args.ldx[p], tc, args.K[p], args.ldx[p], args.H[p], args.beta[p], args.alpha[p], args.nt[p], b - args.first[p],
+           args.first[p + 1] - args.first[p], slab);
     else
       for (int i = threadIdx.x; i < H2 * H2; i += 512) slab[i] = 0.f;
   }
 }
 
-#ifdef INC_KBENCH  // the batched launch over the harness generations of the tile
-template <bool IS_BF16, int TOK = TR_TOK, int NST = TR_NST, int ABL = TR_LAB_ABL>
-__global__ __launch_bounds__(512) void hessian_syrk_tr_256_multi_lab_kernel(HessianBatch args, int64_t T) {
-  const int gb = (int)blockIdx.x + args.block0;  // index in the whole call's grid
-  int b = gb, seg = 0;
-  const bool split = b >= args.full;
-  if (split) {  // a unit of the split tail: tile full + u / nseg, token range u % nseg
-    const int u = b - args.full;
-    seg = u % args.nseg;
-    b = args.full + u / args.nseg;
-  }
-  int p = 0;
-#pragma unroll
-  for (int i = 1; i < HESSIAN_MAX_BATCH; ++i)
-    if (i < args.n && b >= args.first[i]) p = i;
-  p = __builtin_amdgcn_readfirstlane(p);
-  if (!split) {
-    hessian_syrk_tr_tile_lab<IS_BF16, TOK, NST, ABL>(args.x[p], T, args.K[p], args.ldx[p], args.H[p], args.beta[p], args.alpha[p], args.nt[p],
-                                  b - args.first[p], args.first[p + 1] - args.first[p]);
-  } else {
-    int64_t t0, tc;
-    hessian_segment(T, TOK, seg, args.nseg, t0, tc);
-    float* slab = args.slab + ((int64_t)(gb - args.full)) * (H2 * H2);
-    if (tc > 0)
-      hessian_syrk_tr_tile_lab<IS_BF16, TOK, NST, ABL>(args.x[p] + t0 * args.ldx[p], tc, args.K[p], args.ldx[p], args.H[p], args.beta[p], args.alpha[p],
-                                    args.nt[p], b - args.first[p], args.first[p + 1] - args.first[p], slab);
-    else
-      for (int i = threadIdx.x; i < H2 * H2; i += 512) slab[i] = 0.f;
-  }
+template <bool IS_BF16>
+__global__ __launch_bounds__(512) void hessian_syrk_tr_256_multi_kernel(HessianBatch args, int64_t T) {
+  hessian_batch_workgroup(args, T, TR_TOK, [](auto... a) __attribute__((always_inline)) { hessian_syrk_tr_tile<IS_BF16>(a...); });
 }
-#endif
 
 // H tile <- beta * H + alpha * (range 0 + range 1 + ...), ranges added in order: the tiles of the split tail
 // (four workgroups per tile, 64 rows each: a tile per workgroup left 182 of the 256 CUs without work for 0.1 ms per launch)
 __global__ __launch_bounds__(512) void hessian_tail_finalize_kernel(HessianBatch args) {
   const int tile = (int)blockIdx.x >> 2, quarter = (int)blockIdx.x & 3;
   const int b = args.full + tile;
-  int p = 0;
-#pragma unroll
-  for (int i = 1; i < HESSIAN_MAX_BATCH; ++i)
-    if (i < args.n && b >= args.first[i]) p = i;
-  p = __builtin_amdgcn_readfirstlane(p);
+  const int p = hessian_batch_problem(args, b);
   int ti, tj;
   xcd_supertile_decode(b - args.first[p], args.first[p + 1] - args.first[p], args.nt[p], ti, tj);
   const int64_t K = args.K[p], i0 = (int64_t)ti * H2, j0 = (int64_t)tj * H2;
@@ -543,20 +505,6 @@ __global__ __launch_bounds__(512) void hessian_tail_finalize_kernel(HessianBatch
     }
   }
 }
-
-#ifdef INC_KBENCH
-template <bool IS_BF16, bool TAIL>
-__global__ __launch_bounds__(512) void hessian_syrk_16bit_256_multi_kernel(HessianBatch args, int64_t T) {
-  const int b = (int)blockIdx.x;
-  int p = 0;
-#pragma unroll
-  for (int i = 1; i < HESSIAN_MAX_BATCH; ++i)
-    if (i < args.n && b >= args.first[i]) p = i;
-  p = __builtin_amdgcn_readfirstlane(p);
-  hessian_syrk_256_tile<IS_BF16, TAIL>(args.x[p], T, args.K[p], args.ldx[p], args.H[p], args.beta[p], args.alpha[p], args.nt[p],
-                                       b - args.first[p], args.first[p + 1] - args.first[p]);
-}
-#endif
 
 // ---- fp32 inputs: exact fp32 MFMA 32x32x2 ------------------------------------------------------
 constexpr int FK = 32;  // tokens per step
@@ -667,127 +615,18 @@ __global__ __launch_bounds__(256) void hessian_mirror_kernel(float* __restrict__
   }
 }
 
-}  // namespace
+// the 256 x 256 tile needs K >= 256 and 16-byte chunks of eight features: aligned rows of a multiple of eight features
+bool hessian_vec_ok(const void* x, int64_t ldx) { return (ldx % 8 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0); }
+bool hessian_tr_ok(const void* x, int64_t K, int64_t ldx) { return K >= H2 && hessian_vec_ok(x, ldx) && (K % 8) == 0; }
 
-extern "C" {
-
-int inc_gptq_hessian_accum(const void* x, int xdtype, int64_t T, int64_t K, int64_t ldx, float* H,
-                           float beta, float alpha, inc_stream_t stream) {
-  INC_CHECK_ARG(x && H && T > 0 && K > 0 && ldx >= K);
-  const int nt = (int)ceil_div64(K, HB);
-  const int ntiles = nt * (nt + 1) / 2;
-  hipStream_t s = inc_s(stream);
-  if (xdtype == INC_F32) {
-    hessian_syrk_f32_kernel<<<ntiles, 256, 0, s>>>((const float*)x, T, K, ldx, H, beta, alpha, nt);
-  } else if (xdtype == INC_BF16 || xdtype == INC_F16) {
-    const int vec_ok = (ldx % 8 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0);
-    const size_t smem = (size_t)2 * 2 * HB * HPITCH * sizeof(uint16_t);
-    static std::atomic<uint64_t> attr_set{0};
-    if (inc_attr_needed(attr_set)) {
-      (void)hipFuncSetAttribute((const void*)hessian_syrk_16bit_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-      (void)hipFuncSetAttribute((const void*)hessian_syrk_16bit_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-      inc_attr_done(attr_set);
-    }
-    if (K >= H2 && vec_ok && (K % 8) == 0 && !inc_force_small_tiles()) {
-      const int nt2 = (int)ceil_div64(K, H2);
-      const int ntiles2 = nt2 * (nt2 + 1) / 2;
-      const uint16_t* xp = (const uint16_t*)x;
-#ifdef INC_KBENCH
-      if (inc_small_tiles_flag(-1) == 45) {  // harness flag 45: the register-transposing generation
-        const size_t smem2 = (size_t)2 * H2_STAGE * sizeof(uint16_t);  // 144 KiB
-        const bool tail = (T % HK) != 0;
-        (void)hipFuncSetAttribute((const void*)hessian_syrk_16bit_256_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem2);
-        (void)hipFuncSetAttribute((const void*)hessian_syrk_16bit_256_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem2);
-        (void)hipFuncSetAttribute((const void*)hessian_syrk_16bit_256_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem2);
-        (void)hipFuncSetAttribute((const void*)hessian_syrk_16bit_256_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem2);
-#define INC_H2(B, TL) hessian_syrk_16bit_256_kernel<B, TL><<<ntiles2, 512, smem2, s>>>(xp, T, K, ldx, H, beta, alpha, nt2)
-        if (xdtype == INC_BF16) { if (tail) INC_H2(true, true); else INC_H2(true, false); }
-        else { if (tail) INC_H2(false, true); else INC_H2(false, false); }
-#undef INC_H2
-        INC_LAUNCH_RETURN();
-      }
-#endif
-      {  // transpose-read generation
-        const size_t smem3 = (size_t)TR_NST * TR_STAGE;  // 132 KiB
-        static std::atomic<uint64_t> attr3_set{0};
-        if (inc_attr_needed(attr3_set)) {
-          (void)hipFuncSetAttribute((const void*)hessian_syrk_tr_256_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem3);
-          (void)hipFuncSetAttribute((const void*)hessian_syrk_tr_256_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem3);
-          inc_attr_done(attr3_set);
-        }
-#ifdef INC_KBENCH
-        if (inc_small_tiles_flag(-1) == 46 && xdtype == INC_BF16) {  // timing A/B: four 32-token stages
-          (void)hipFuncSetAttribute((const void*)hessian_syrk_tr_256_lab_kernel<true, 32, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem3);
-          hessian_syrk_tr_256_lab_kernel<true, 32, 4><<<ntiles2, 512, smem3, s>>>(xp, T, K, ldx, H, beta, alpha, nt2);
-          INC_LAUNCH_RETURN();
-        }
-        const int habl = inc_small_tiles_flag(-1) - 46;  // 47 / 48 / 49: timing-only, no LDS-DMA / no MFMA + fragment reads / neither
-        if (habl >= 1 && habl <= 3 && xdtype == INC_BF16) {
-#define INC_HABL(A) { (void)hipFuncSetAttribute((const void*)hessian_syrk_tr_256_lab_kernel<true, TR_TOK, TR_NST, A>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem3); \
-                      hessian_syrk_tr_256_lab_kernel<true, TR_TOK, TR_NST, A><<<ntiles2, 512, smem3, s>>>(xp, T, K, ldx, H, beta, alpha, nt2); }
-          if (habl == 1) INC_HABL(1) else if (habl == 2) INC_HABL(2) else INC_HABL(3)
-          INC_LAUNCH_RETURN();
-        }
-        if (habl == 4 && xdtype == INC_BF16) {  // 50: CORRECT results, the DMA requests spread over the step's MFMA rows
-          INC_HABL(4)
-          INC_LAUNCH_RETURN();
-        }
-        if ((habl == 8 || habl == 9) && xdtype == INC_BF16) {  // 54: static priority for waves 4-7; 55: that + spread + rolling fragments
-          if (habl == 8) INC_HABL(16) else INC_HABL(28)
-          INC_LAUNCH_RETURN();
-        }
-        if ((habl == 6 || habl == 7) && xdtype == INC_BF16) {  // 52: spread + row fragments two rows ahead; 53: the rolling fragments alone
-          if (habl == 6) INC_HABL(12) else INC_HABL(8)
-          INC_LAUNCH_RETURN();
-        }
-        if (habl == 13 && xdtype == INC_BF16) {  // 59: the round-4 form of the tile (A/B partner of TR_ABL)
-          INC_HABL(0)
-          INC_LAUNCH_RETURN();
-        }
-        if (habl == 14 && xdtype == INC_BF16) {  // 60: the product tile with its pieces issued from one asm block per step
-          INC_HABL(176)
-          INC_LAUNCH_RETURN();
-        }
-        if (habl >= 10 && habl <= 12 && xdtype == INC_BF16) {  // 56: rolling fragments + priority; 57: one rolling pipeline per step; 58: that + priority
-          if (habl == 10) INC_HABL(24) else if (habl == 11) INC_HABL(32) else INC_HABL(48)
-          INC_LAUNCH_RETURN();
-        }
-        if (habl == 5 && xdtype == INC_BF16) {  // 51: the same with four 32-token stages (three steps in flight)
-          (void)hipFuncSetAttribute((const void*)hessian_syrk_tr_256_lab_kernel<true, 32, 4, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem3);
-          hessian_syrk_tr_256_lab_kernel<true, 32, 4, 4><<<ntiles2, 512, smem3, s>>>(xp, T, K, ldx, H, beta, alpha, nt2);
-          INC_LAUNCH_RETURN();
-        }
-#undef INC_HABL
-#endif
-        if (xdtype == INC_BF16) hessian_syrk_tr_256_kernel<true><<<ntiles2, 512, smem3, s>>>(xp, T, K, ldx, H, beta, alpha, nt2);
-        else hessian_syrk_tr_256_kernel<false><<<ntiles2, 512, smem3, s>>>(xp, T, K, ldx, H, beta, alpha, nt2);
-        INC_LAUNCH_RETURN();
-      }
-    } else if (xdtype == INC_BF16)
-      hessian_syrk_16bit_kernel<true><<<ntiles, 256, smem, s>>>((const uint16_t*)x, T, K, ldx, H, beta, alpha, nt, vec_ok);
-    else
-      hessian_syrk_16bit_kernel<false><<<ntiles, 256, smem, s>>>((const uint16_t*)x, T, K, ldx, H, beta, alpha, nt, vec_ok);
-  } else {
-    return INC_ERR_UNSUPPORTED;
-  }
-  INC_LAUNCH_RETURN();
-}
-
-// Bytes of scratch with which inc_gptq_hessian_accum_multi can split the tiles of its last, partly filled round over idle CUs
-// (at most one round of 256 x 256 fp32 tiles).
-int64_t inc_gptq_hessian_accum_multi_workspace_bytes(void) { return (int64_t)HESSIAN_TAIL_UNITS * H2 * H2 * 4; }
-
-int inc_gptq_hessian_accum_multi(int n, const void* const* xs, int xdtype, int64_t T, const int64_t* Ks, const int64_t* ldxs,
-                                 float* const* Hs, const float* betas, const float* alphas, void* workspace, int64_t workspace_bytes,
-                                 inc_stream_t stream) {
-  INC_CHECK_ARG(n > 0 && xs && Ks && ldxs && Hs && betas && alphas && T > 0);
-  if (n > HESSIAN_MAX_BATCH || !(xdtype == INC_BF16 || xdtype == INC_F16) || inc_force_small_tiles()) return INC_ERR_UNSUPPORTED;
-  HessianBatch a;
+// The batched launch's arguments from the caller's arrays, on a device of `cus` CUs: the problems' block ranges and the tail split.
+// INC_ERR_UNSUPPORTED when a problem cannot take the 256 x 256 tile (the caller falls back to single launches).
+int hessian_batch_fill(HessianBatch& a, int n, const void* const* xs, int64_t T, const int64_t* Ks, const int64_t* ldxs, float* const* Hs,
+                       const float* betas, const float* alphas, void* workspace, int64_t workspace_bytes, int cus) {
   int first = 0;
   for (int i = 0; i < n; ++i) {
     INC_CHECK_ARG(xs[i] && Hs[i] && Ks[i] > 0 && ldxs[i] >= Ks[i]);
-    const bool vec_ok = (ldxs[i] % 8 == 0) && ((reinterpret_cast<uintptr_t>(xs[i]) & 15) == 0);
-    if (!(Ks[i] >= H2 && vec_ok && (Ks[i] % 8) == 0)) return INC_ERR_UNSUPPORTED;  // the caller falls back to single launches
+    if (!hessian_tr_ok(xs[i], Ks[i], ldxs[i])) return INC_ERR_UNSUPPORTED;
     a.x[i] = (const uint16_t*)xs[i];
     a.H[i] = Hs[i];
     a.K[i] = Ks[i];
@@ -800,102 +639,111 @@ int inc_gptq_hessian_accum_multi(int n, const void* const* xs, int xdtype, int64
   }
   for (int i = n; i <= HESSIAN_MAX_BATCH; ++i) a.first[i] = first;
   for (int i = n; i < HESSIAN_MAX_BATCH; ++i) { a.x[i] = a.x[0]; a.H[i] = a.H[0]; a.K[i] = a.K[0]; a.ldx[i] = a.ldx[0]; a.beta[i] = 1.f; a.alpha[i] = 0.f; a.nt[i] = a.nt[0]; }
-  a.n = n;
-  a.full = first;
-  a.nseg = 1;
-  a.slab = nullptr;
-  a.block0 = 0;
-  hipStream_t s = inc_s(stream);
+  a.n = n; a.block0 = 0;
+  a.full = first; a.nseg = 1; a.slab = nullptr;  // no split
   // Tile quantisation: `first` equal tiles on `cus` CUs (one workgroup per CU: 132 KiB of LDS) run in ceil(first / cus) rounds; when the
   // last round fills less than half of the chip its tiles are cut into nseg = cus / tail token ranges, one workgroup each (a Llama
   // block's launch: 1354 tiles = 5 rounds + 74 tiles -> 222 units of a third: 5.4 rounds instead of 6).  The ranges' raw sums go to
   // the caller's workspace and a second, small launch adds them into H in range order: deterministic, and every tile outside the tail
   // is computed exactly as before.
-  {
-    int dev = 0, cus = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    const int tail = cus > 0 ? first % cus : 0;
-    const int steps = (int)ceil_div64(T, TR_TOK);
-    if (workspace && first > cus && tail > 0 && 2 * tail <= cus && inc_small_tiles_flag(-1) != 44) {
-      int nseg = cus / tail;
-      if (nseg > 4) nseg = 4;
-      if (nseg > steps / 16) nseg = steps / 16;  // a range is at least 16 steps long
-      if (nseg >= 2 && tail * nseg <= HESSIAN_TAIL_UNITS && workspace_bytes >= (int64_t)tail * nseg * H2 * H2 * 4 &&
-          (reinterpret_cast<uintptr_t>(workspace) & 15) == 0) {
-        a.full = first - tail;
-        a.nseg = nseg;
-        a.slab = (float*)workspace;
-      }
+  const int tail = cus > 0 ? first % cus : 0;
+  const int steps = (int)ceil_div64(T, TR_TOK);
+  if (workspace && first > cus && tail > 0 && 2 * tail <= cus) {
+    const int nseg = std::min({4, cus / tail, steps / 16});  // a range is at least 16 steps long
+    if (nseg >= 2 && tail * nseg <= HESSIAN_TAIL_UNITS && workspace_bytes >= (int64_t)tail * nseg * H2 * H2 * 4 &&
+        (reinterpret_cast<uintptr_t>(workspace) & 15) == 0) {
+      a.full = first - tail;
+      a.nseg = nseg;
+      a.slab = (float*)workspace;
     }
   }
-  const int grid = a.full + (first - a.full) * a.nseg;
-#ifdef INC_KBENCH
-  if (inc_small_tiles_flag(-1) == 45) {  // harness flag 45: the register-transposing generation
-    a.full = first; a.nseg = 1;
-    const size_t smem2 = (size_t)2 * H2_STAGE * sizeof(uint16_t);  // 144 KiB
-    const bool tail = (T % HK) != 0;
-    (void)hipFuncSetAttribute((const void*)hessian_syrk_16bit_256_multi_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem2);
-    (void)hipFuncSetAttribute((const void*)hessian_syrk_16bit_256_multi_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem2);
-    (void)hipFuncSetAttribute((const void*)hessian_syrk_16bit_256_multi_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem2);
-    (void)hipFuncSetAttribute((const void*)hessian_syrk_16bit_256_multi_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem2);
-#define INC_HM(B, TL) hessian_syrk_16bit_256_multi_kernel<B, TL><<<first, 512, smem2, s>>>(a, T)
-    if (xdtype == INC_BF16) { if (tail) INC_HM(true, true); else INC_HM(true, false); }
-    else { if (tail) INC_HM(false, true); else INC_HM(false, false); }
-#undef INC_HM
+  return INC_OK;
+}
+
+// the second, small launch of a batch with a split tail
+void hessian_tail_finalize(const HessianBatch& a, hipStream_t s) {
+  if (a.nseg > 1) hessian_tail_finalize_kernel<<<4 * (a.first[a.n] - a.full), 512, 0, s>>>(a);
+}
+
+// the LDS size of a kernel's bf16 and f16 forms, once per device
+template <class Kernel>
+void hessian_lds_attr(std::atomic<uint64_t>& done, Kernel bf16, Kernel f16, size_t smem) {
+  if (!inc_attr_needed(done)) return;
+  (void)hipFuncSetAttribute((const void*)bf16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+  (void)hipFuncSetAttribute((const void*)f16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+  inc_attr_done(done);
+}
+
+#ifdef INC_KBENCH  // the 256 x 256 tile's other generations and the launches that reach them by harness flag
+#include "../../tools/kbench_gptq_1.inc"
+#include "../../tools/kbench_gptq_tile_lab.inc"
+#endif
+
+}  // namespace
+
+extern "C" {
+
+int inc_gptq_hessian_accum(const void* x, int xdtype, int64_t T, int64_t K, int64_t ldx, float* H,
+                           float beta, float alpha, inc_stream_t stream) {
+  INC_CHECK_ARG(x && H && T > 0 && K > 0 && ldx >= K);
+  const int nt = (int)ceil_div64(K, HB), ntiles = nt * (nt + 1) / 2;
+  hipStream_t s = inc_s(stream);
+  if (xdtype == INC_F32) {
+    hessian_syrk_f32_kernel<<<ntiles, 256, 0, s>>>((const float*)x, T, K, ldx, H, beta, alpha, nt);
     INC_LAUNCH_RETURN();
   }
+  if (!(xdtype == INC_BF16 || xdtype == INC_F16)) return INC_ERR_UNSUPPORTED;
+  const uint16_t* xp = (const uint16_t*)x;
+  if (hessian_tr_ok(x, K, ldx) && !inc_force_small_tiles()) {
+    const int nt2 = (int)ceil_div64(K, H2), ntiles2 = nt2 * (nt2 + 1) / 2;
+#ifdef INC_KBENCH
+    if (hessian_lab_launch(xp, xdtype, T, K, ldx, H, beta, alpha, nt2, ntiles2, s)) INC_LAUNCH_RETURN();
 #endif
-  {  // transpose-read generation
-    const size_t smem3 = (size_t)TR_NST * TR_STAGE;
+    const size_t smem3 = (size_t)TR_NST * TR_STAGE;  // 132 KiB
     static std::atomic<uint64_t> attr3_set{0};
-    if (inc_attr_needed(attr3_set)) {
-      (void)hipFuncSetAttribute((const void*)hessian_syrk_tr_256_multi_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem3);
-      (void)hipFuncSetAttribute((const void*)hessian_syrk_tr_256_multi_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem3);
-      inc_attr_done(attr3_set);
-    }
-#ifdef INC_KBENCH
-    if (inc_small_tiles_flag(-1) == 46 && xdtype == INC_BF16) {  // timing A/B: four 32-token stages
-      a.full = first; a.nseg = 1;
-      (void)hipFuncSetAttribute((const void*)hessian_syrk_tr_256_multi_lab_kernel<true, 32, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem3);
-      hessian_syrk_tr_256_multi_lab_kernel<true, 32, 4><<<first, 512, smem3, s>>>(a, T);
-      INC_LAUNCH_RETURN();
-    }
-#endif
-#ifdef INC_KBENCH
-    {  // harness flags 53 / 54 / 56 / 57 / 58 / 59: the tile variants of the single-problem launch, in the batched launch
-      const int f = inc_small_tiles_flag(-1);
-      const int mabl = f == 53 ? 8 : f == 54 ? 16 : f == 56 ? 24 : f == 57 ? 32 : f == 58 ? 48 : f == 59 ? 64 : f == 60 ? 176 : 0;  // (64 = ABL 0)
-      if (mabl && xdtype == INC_BF16) {
-#define INC_HMV(A) { (void)hipFuncSetAttribute((const void*)hessian_syrk_tr_256_multi_lab_kernel<true, TR_TOK, TR_NST, A>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem3); \
-                     a.block0 = 0; hessian_syrk_tr_256_multi_lab_kernel<true, TR_TOK, TR_NST, A><<<grid, 512, smem3, s>>>(a, T); }
-        if (mabl == 8) INC_HMV(8) else if (mabl == 16) INC_HMV(16) else if (mabl == 24) INC_HMV(24) else if (mabl == 32) INC_HMV(32) else if (mabl == 64) INC_HMV(0) else if (mabl == 176) INC_HMV(176) else INC_HMV(48)
-#undef INC_HMV
-        if (a.nseg > 1) hessian_tail_finalize_kernel<<<4 * (first - a.full), 512, 0, s>>>(a);
-        INC_LAUNCH_RETURN();
-      }
-    }
-#endif
-    // (one launch per round of one-tile-per-CU, so that the tiles sharing X panels in an XCD's L2 restart together, measured 1 %
-    // slower than this single launch: profiles/NOTES.md round 4; harness flag 43 keeps it as an A/B partner)
-    int chunk = grid;
-#ifdef INC_KBENCH
-    if (inc_small_tiles_flag(-1) == 43) {
-      int dev = 0, cus = 256;
-      (void)hipGetDevice(&dev);
-      (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-      chunk = (cus <= 0 || (cus % 8) != 0) ? 256 : cus;
-    }
-#endif
-    for (int b0 = 0; b0 < grid; b0 += chunk) {
-      a.block0 = b0;
-      const int g = grid - b0 < chunk ? grid - b0 : chunk;
-      if (xdtype == INC_BF16) hessian_syrk_tr_256_multi_kernel<true><<<g, 512, smem3, s>>>(a, T);
-      else hessian_syrk_tr_256_multi_kernel<false><<<g, 512, smem3, s>>>(a, T);
-    }
-    if (a.nseg > 1) hessian_tail_finalize_kernel<<<4 * (first - a.full), 512, 0, s>>>(a);
+    hessian_lds_attr(attr3_set, hessian_syrk_tr_256_kernel<true>, hessian_syrk_tr_256_kernel<false>, smem3);
+    if (xdtype == INC_BF16) hessian_syrk_tr_256_kernel<true><<<ntiles2, 512, smem3, s>>>(xp, T, K, ldx, H, beta, alpha, nt2);
+    else hessian_syrk_tr_256_kernel<false><<<ntiles2, 512, smem3, s>>>(xp, T, K, ldx, H, beta, alpha, nt2);
     INC_LAUNCH_RETURN();
   }
+  const int vec_ok = hessian_vec_ok(x, ldx);
+  const size_t smem = (size_t)2 * 2 * HB * HPITCH * sizeof(uint16_t);
+  static std::atomic<uint64_t> attr_set{0};
+  hessian_lds_attr(attr_set, hessian_syrk_16bit_kernel<true>, hessian_syrk_16bit_kernel<false>, smem);
+  if (xdtype == INC_BF16) hessian_syrk_16bit_kernel<true><<<ntiles, 256, smem, s>>>(xp, T, K, ldx, H, beta, alpha, nt, vec_ok);
+  else hessian_syrk_16bit_kernel<false><<<ntiles, 256, smem, s>>>(xp, T, K, ldx, H, beta, alpha, nt, vec_ok);
+  INC_LAUNCH_RETURN();
+}
+
+// Bytes of scratch with which inc_gptq_hessian_accum_multi can split the tiles of its last, partly filled round over idle CUs
+// (at most one round of 256 x 256 fp32 tiles).
+int64_t inc_gptq_hessian_accum_multi_workspace_bytes(void) { return (int64_t)HESSIAN_TAIL_UNITS * H2 * H2 * 4; }
+
+int inc_gptq_hessian_accum_multi(int n, const void* const* xs, int xdtype, int64_t T, const int64_t* Ks, const int64_t* ldxs,
+                                 float* const* Hs, const float* betas, const float* alphas, void* workspace, int64_t workspace_bytes,
+                                 inc_stream_t stream) {
+  INC_CHECK_ARG(n > 0 && xs && Ks && ldxs && Hs && betas && alphas && T > 0);
+  if (n > HESSIAN_MAX_BATCH || !(xdtype == INC_BF16 || xdtype == INC_F16) || inc_force_small_tiles()) return INC_ERR_UNSUPPORTED;
+  int dev = 0, cus = 0;
+  (void)hipGetDevice(&dev);
+  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  HessianBatch a;
+  const int rc = hessian_batch_fill(a, n, xs, T, Ks, ldxs, Hs, betas, alphas, workspace, workspace_bytes, cus);
+  if (rc != INC_OK) return rc;
+  hipStream_t s = inc_s(stream);
+#ifdef INC_KBENCH
+  if (hessian_batch_lab_launch(a, xdtype, T, cus, s)) INC_LAUNCH_RETURN();
+#endif
+  const size_t smem3 = (size_t)TR_NST * TR_STAGE;
+  static std::atomic<uint64_t> attr3_set{0};
+  hessian_lds_attr(attr3_set, hessian_syrk_tr_256_multi_kernel<true>, hessian_syrk_tr_256_multi_kernel<false>, smem3);
+  // one launch over the whole batch (one launch per round of one-tile-per-CU, so that the tiles sharing X panels in an XCD's L2
+  // restart together, measured 1 % slower: profiles/NOTES.md round 4; the harness keeps it as an A/B partner)
+  const int grid = a.full + (a.first[n] - a.full) * a.nseg;
+  if (xdtype == INC_BF16) hessian_syrk_tr_256_multi_kernel<true><<<grid, 512, smem3, s>>>(a, T);
+  else hessian_syrk_tr_256_multi_kernel<false><<<grid, 512, smem3, s>>>(a, T);
+  hessian_tail_finalize(a, s);
+  INC_LAUNCH_RETURN();
 }
 
 int inc_gptq_hessian_finalize(float* H, int64_t K, float percdamp, uint8_t* dead, void* workspace,

@@ -6,12 +6,11 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "gptq_common.hpp"
 
 namespace {
 
 typedef __attribute__((ext_vector_type(16))) float f32x16;
-constexpr int QB = 128;   // columns per block (gptq.hip)
-constexpr int L2T = 128;  // rows / columns of a lazy-update tile (gptq.hip)
 
 // ---------------------------------------------------------------------------------------------
 // lazy update, third generation: ONE [128 rows x CW columns] tile per workgroup, two workgroups per CU
@@ -162,7 +161,21 @@ __global__ __launch_bounds__(256, 2) void gptq_lazy_update_v3_kernel(float* __re
   }
 }
 
-#ifdef INC_KBENCH  // the same kernel with its timing-only ablations: harness code
+#ifndef INC_LAZY_STRIP_TILES
+#define INC_LAZY_STRIP_TILES 2048
+#endif
+#ifndef INC_LAZY_STRIP_CAP
+#define INC_LAZY_STRIP_CAP 8
+#endif
+// What the harness may change in the launcher below (tools/kbench_gptq_lazy_lab.inc fills it by harness flag); the product's is this default.
+struct LazyLabOverrides {
+  int ablation = 0;                       // a timing-only form of the third generation's whole-tile kernel instead of everything else
+  bool v3_everywhere = false;             // no strip form
+  int64_t strip_cap = INC_LAZY_STRIP_CAP;  // longest short strip, in tiles
+  bool never_one_round = false;           // short strips even where one round of long ones would be taken
+};
+
+#ifdef INC_KBENCH  // the third generation with its timing-only ablations, and the overrides by harness flag
 #include "../../tools/kbench_gptq_lazy_lab.inc"
 #endif
 
@@ -184,12 +197,6 @@ __global__ __launch_bounds__(256, 2) void gptq_lazy_update_v3_kernel(float* __re
 // (A form with two accumulators and the neighbours' epilogue / requests spread over the MFMA shadows is faster alone on the chip and slower
 // inside the step -- 214 registers against 180: tools/rejected/gptq_lazy_strip_pipelined.inc, profiles/NOTES.md.)
 constexpr int L4W = 32;  // columns of a fourth-generation tile
-#ifndef INC_LAZY_STRIP_TILES
-#define INC_LAZY_STRIP_TILES 2048
-#endif
-#ifndef INC_LAZY_STRIP_CAP
-#define INC_LAZY_STRIP_CAP 8
-#endif
 
 __global__ __launch_bounds__(256, 2) void gptq_lazy_update_v4_kernel(float* __restrict__ w, const float* __restrict__ Hinv,
                                                                      const float* __restrict__ err, int64_t N, int64_t K, int64_t i1,
@@ -309,6 +316,28 @@ __global__ __launch_bounds__(256, 2) void gptq_lazy_update_v4_kernel(float* __re
   }
 }
 
+// Strip length of the fourth generation, in 32-column tiles per workgroup, for `row_tiles` x `nt4` tiles.  A strip's start-up (Err1 in,
+// fragment out, first requests: two dependent round trips) costs about three tiles, so long strips are better -- but only when the
+// grid is ONE round of at most two workgroups per CU (a few left-over workgroups in a second round cost a whole strip) AND nothing
+// else needs the CUs meanwhile (`exclusive`): 92 against 78 TFLOP/s alone on the chip at 4096 x 11008, but the look-ahead loop got
+// SLOWER with them (9.45 vs 9.27 ms: the next chain's workgroups wait for a strip to end).  Otherwise short strips (<= `cap` tiles)
+// that the dispatcher balances over several rounds; the busiest CU's work in tiles decides.  (Timing-only ablation, tools/kbench
+// colloop: the strip's MFMA + LDS skeleton alone runs at ~100 TFLOP/s with 8-tile strips against 155 for the bare instruction,
+// tools/f32mfma_lab -- the start-up is the difference; profiles/NOTES.md.)
+int64_t lazy_strip_plan(int64_t row_tiles, int64_t nt4, bool exclusive, int64_t cap, bool force_short) {
+  constexpr int64_t SLOTS = 512, CUS = 256, STARTUP = 3;
+  const int64_t chunks_one = SLOTS / row_tiles > 0 ? SLOTS / row_tiles : 1;
+  int64_t tpw_one = ceil_div64(nt4, chunks_one);
+  if (tpw_one < 4) tpw_one = 4;
+  const int64_t cost_one = ceil_div64(ceil_div64(nt4, tpw_one) * row_tiles, CUS) * (tpw_one + STARTUP);
+  int64_t tpw_short = nt4 / ceil_div64(SLOTS, row_tiles);
+  if (tpw_short > cap) tpw_short = cap;
+  if (tpw_short < 4) tpw_short = 4;
+  const int64_t cost_short = ceil_div64(ceil_div64(nt4, tpw_short) * row_tiles, CUS) * (2 * tpw_short + STARTUP) / 2;
+  const bool one_round = !force_short && exclusive && ceil_div64(nt4, tpw_one) * row_tiles <= SLOTS && cost_one <= cost_short;
+  return one_round ? tpw_one : tpw_short;
+}
+
 }  // namespace
 
 // launch over the columns [c_begin, c_end) of the trailing matrix (c_begin on the 128-column tile grid that starts at i2): the strip
@@ -326,51 +355,21 @@ void inc_launch_lazy_update_v3(float* w, const float* Hinv, const float* err, in
   const int64_t row_tiles = ceil_div64(N, L2T);
   const int64_t col_tiles = ceil_div64(c_end - c_begin, L2T);
 #ifdef INC_KBENCH
-  const int abl = inc_small_tiles_flag(-1) - 86;  // 87 / 88 / 90: timing-only (no MFMAs / no loads / no stores)
-  if (abl == 1 || abl == 2 || abl == 4) {
-#define INC_L3A(A) { (void)hipFuncSetAttribute((const void*)gptq_lazy_update_v3_lab_kernel<128, A>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536); \
-                     gptq_lazy_update_v3_lab_kernel<128, A><<<dim3((unsigned)col_tiles, (unsigned)row_tiles), 256, 65536, s>>>(w, Hinv, err, N, K, i1, c_begin); }
-    if (abl == 1) INC_L3A(1) else if (abl == 2) INC_L3A(2) else INC_L3A(4)
-#undef INC_L3A
-    return;
-  }
+  const LazyLabOverrides lab = lazy_lab_overrides();
+  if (lab.ablation) return lazy_lab_ablation_launch(lab.ablation, w, Hinv, err, N, K, i1, c_begin, col_tiles, row_tiles, s);
+#else
+  constexpr LazyLabOverrides lab;
 #endif
   // the strip form when every one of ~512 workgroups (two per CU) gets at least four 32-column tiles
   const int64_t nt4 = ceil_div64(c_end - c_begin, L4W);
-  if (row_tiles * nt4 >= (int64_t)INC_LAZY_STRIP_TILES && inc_small_tiles_flag(-1) != 107) {  // (harness flag 107: third generation everywhere, the A/B partner)
+  if (row_tiles * nt4 >= (int64_t)INC_LAZY_STRIP_TILES && !lab.v3_everywhere) {
     static std::atomic<uint64_t> attr4_set{0};
     if (inc_attr_needed(attr4_set)) {
       (void)hipFuncSetAttribute((const void*)gptq_lazy_update_v4_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
       inc_attr_done(attr4_set);
     }
-    // Strip length.  A strip's start-up (Err1 in, fragment out, first requests: two dependent round trips) costs about three tiles, so
-    // long strips are better -- but only when the grid is ONE round of at most two workgroups per CU (a few left-over workgroups in a
-    // second round cost a whole strip) AND nothing else needs the CUs meanwhile: 92 against 78 TFLOP/s alone on the chip at 4096 x 11008,
-    // but the look-ahead loop got SLOWER with them (9.45 vs 9.27 ms: the next chain's workgroups wait for a strip to end).  Otherwise
-    // short strips (<= 8 tiles) that the dispatcher balances over several rounds; the busiest CU's work in tiles decides.  (Timing-only
-    // ablation, tools/kbench colloop: the strip's MFMA + LDS skeleton alone runs at ~100 TFLOP/s with 8-tile strips against 155 for the
-    // bare instruction, tools/f32mfma_lab -- the start-up is the difference; profiles/NOTES.md.)
-    constexpr int64_t SLOTS = 512, CUS = 256, STARTUP = 3;
-    const int64_t chunks_one = SLOTS / row_tiles > 0 ? SLOTS / row_tiles : 1;
-    int64_t tpw_one = ceil_div64(nt4, chunks_one);
-    if (tpw_one < 4) tpw_one = 4;
-    const int64_t cost_one = ceil_div64(ceil_div64(nt4, tpw_one) * row_tiles, CUS) * (tpw_one + STARTUP);
-    int64_t cap = INC_LAZY_STRIP_CAP;
-#ifdef INC_KBENCH
-    if (inc_small_tiles_flag(-1) == 108) cap = 4;
-    if (inc_small_tiles_flag(-1) == 109) cap = 16;
-#endif
-    int64_t tpw_short = nt4 / ceil_div64(SLOTS, row_tiles);
-    if (tpw_short > cap) tpw_short = cap;
-    if (tpw_short < 4) tpw_short = 4;
-    const int64_t cost_short = ceil_div64(ceil_div64(nt4, tpw_short) * row_tiles, CUS) * (2 * tpw_short + STARTUP) / 2;
-    bool one_round = exclusive && ceil_div64(nt4, tpw_one) * row_tiles <= SLOTS && cost_one <= cost_short;
-#ifdef INC_KBENCH
-    if (inc_small_tiles_flag(-1) == 108 || inc_small_tiles_flag(-1) == 109 || inc_small_tiles_flag(-1) == 110) one_round = false;  // 110: short strips everywhere
-#endif
-    const int64_t tpw = one_round ? tpw_one : tpw_short;
-    const int64_t chunks = ceil_div64(nt4, tpw);
-    gptq_lazy_update_v4_kernel<<<dim3((unsigned)chunks, (unsigned)row_tiles), 256, 65536, s>>>(w, Hinv, err, N, K, i1, c_begin, c_end, (int)tpw);
+    const int64_t tpw = lazy_strip_plan(row_tiles, nt4, exclusive, lab.strip_cap, lab.never_one_round);
+    gptq_lazy_update_v4_kernel<<<dim3((unsigned)ceil_div64(nt4, tpw), (unsigned)row_tiles), 256, 65536, s>>>(w, Hinv, err, N, K, i1, c_begin, c_end, (int)tpw);
     return;
   }
   if (row_tiles * col_tiles <= 128)
@@ -378,4 +377,3 @@ void inc_launch_lazy_update_v3(float* w, const float* Hinv, const float* err, in
   else
     gptq_lazy_update_v3_kernel<128><<<dim3((unsigned)col_tiles, (unsigned)row_tiles), 256, 65536, s>>>(w, Hinv, err, N, K, i1, c_begin);
 }
-

@@ -140,12 +140,13 @@ def test_hessian_running_mean_and_token_tail(hip):
 
 
 @pytest.mark.parametrize("split", [False, True])
-@pytest.mark.parametrize("shapes,T", [((512, 1024, 768, 256), 1000), ((4096, 4096, 4096, 11008), 16384)])
+@pytest.mark.parametrize("shapes,T", [((512, 1024, 768, 256), 1000), ((4096, 4096, 4096, 11008), 16384), ((2048,) * 8, 2048)])
 def test_hessian_multi_launch_is_bit_identical_to_single_launches(hip, monkeypatch, shapes, T, split):
     """inc_gptq_hessian_accum_multi (all Hessians of one forward in ONE launch -- what the driver issues after every stacked
     calibration forward) computes every tile exactly as inc_gptq_hessian_accum does: same bits, beta != 0 included.  With the
     tail split (default: the tiles of the launch's last, partly filled round are cut into token ranges summed in order) the
-    tiles of that round -- 74 of the 1354 of a Llama block's launch -- carry the rounding of two to four partial sums instead."""
+    tiles of that round -- 74 of the 1354 of a Llama block's launch -- carry the rounding of two to four partial sums instead.
+    The last case is the smallest with a split tail on 256 CUs: 8 x 36 = 288 tiles, 32 of them in the last round, two ranges each."""
     from neural_compressor_amd import ops
 
     monkeypatch.setattr(ops, "HESSIAN_TAIL_SPLIT", split)
@@ -166,8 +167,12 @@ def test_hessian_multi_launch_is_bit_identical_to_single_launches(hip, monkeypat
             n_diff += int((av != bv).sum())
             # (a long fp32 sum against the sum of its three parts: 20 ulps on the diagonal at 16384 tokens; either is 1e-5 from fp64)
             assert float((av - bv).abs().max()) <= 5e-6 * float(av.abs().max()), K
-    if split:  # at most one round's worth of tiles may differ at all (256 CUs x 256 x 256; the small case has no tail to split)
-        assert n_diff <= 128 * 256 * 256 and (n_diff > 0) == (T == 16384)
+    if split:  # at most one round's worth of tiles may differ at all (256 CUs x 256 x 256), and none where the library splits no tail
+        cus = torch.cuda.get_device_properties(hip).multi_processor_count
+        first = sum((-(-K // 256)) * (-(-K // 256) + 1) // 2 for K in shapes)  # 256 x 256 tiles of the upper triangles
+        tail, steps = first % cus, -(-T // 64)
+        has_tail = first > cus and 0 < tail and 2 * tail <= cus and min(4, cus // tail, steps // 16) >= 2
+        assert n_diff <= 128 * 256 * 256 and (n_diff > 0) == has_tail
     # fp32 inputs are declined (nothing launched): the caller falls back to the exact-fp32 single launches
     assert not ops.gptq_hessian_accum_multi([(multi[0], xs[0].float(), 0.5, 0.125), (multi[0], xs[0].float(), 0.5, 0.125)])
 

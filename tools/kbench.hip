@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../include/inc_mi355x.h"
+#include "../neural_compressor_amd/csrc/gptq_common.hpp"  // the harness flag names of the GPTQ kernel families
 
 // A/B switch of the HARNESS build of the library (tools/libinc_mi355x_kbench.so, -DINC_KBENCH): 0 = shipped kernels;
 // 1 = first-generation kernels; 2 = second-generation 256x256 two-stage dequant-GEMM; 4 / 6 = the other instruction
@@ -715,10 +716,10 @@ static int run_hessian_case(int64_t T, int64_t K, bool time_it) {
     const double e = fabs(got - want) / (fabs(want) + 1e-3 * sqrt((double)T));
     if (e > maxrel) maxrel = e;
   }
-  // flags 50 / 52: the same tile with its LDS-DMA requests spread over the step's MFMA rows (and its row fragments requested two rows
+  // correct A/B partners: the same tile with its LDS-DMA requests spread over the step's MFMA rows (and its row fragments requested two rows
   // ahead) -- same arithmetic, same bits
   int64_t spread_differ = 0;
-  for (int flag : {50, 52, 55, 56, 59}) {
+  for (int flag : {LAB_HESSIAN_SPREAD, LAB_HESSIAN_SPREAD_ROLL, LAB_HESSIAN_SPREAD_ROLL_PRIO, LAB_HESSIAN_ROLL_PRIO, LAB_HESSIAN_ROUND4}) {
     if (K % 8 != 0) break;
     Hold.zero();
     inc_debug_set_small_tiles(flag);
@@ -736,7 +737,8 @@ static int run_hessian_case(int64_t T, int64_t K, bool time_it) {
          (long)K, rel, (long)differ, ns, maxrel, (long)spread_differ, ok ? "OK" : "FAIL");
   if (time_it) {
     Timer t;
-    const int modes[14] = {0, 59, 53, 54, 56, 57, 50, 46, 45, 1, 47, 48, 49, 0};
+    const int modes[14] = {0, LAB_HESSIAN_ROUND4, LAB_HESSIAN_ROLL, LAB_HESSIAN_PRIO, LAB_HESSIAN_ROLL_PRIO, LAB_HESSIAN_PIPELINE, LAB_HESSIAN_SPREAD,
+                           LAB_HESSIAN_STAGES_4X32, LAB_HESSIAN_REG_TRANSPOSE, 1, LAB_HESSIAN_NO_DMA, LAB_HESSIAN_NO_MFMA, LAB_HESSIAN_NO_DMA_NO_MFMA, 0};
     const char* labels[14] = {"256x256 TR 2x64 (pipeline + prio)", "256x256 TR 2x64, round-4 form", "256x256 TR 2x64, rolling frags", "256x256 TR 2x64, prio 1 for waves 4-7", "256x256 TR 2x64, rolling + prio",
                               "256x256 TR 2x64, one pipeline per step",
                               "256x256 TR 2x64, DMA spread", "256x256 transpose-read 4x32", "256x256 register transpose", "128x128 tiles",
@@ -779,10 +781,10 @@ static int run_hessian_multi_case(int64_t T) {
   printf("HESSIAN multi T=%ld K=4096+4096+4096+11008 (one launch)\n", (long)T);
   DevBuf<char> hws((size_t)inc_gptq_hessian_accum_multi_workspace_bytes());
   int bad = 0;
-  {  // the split tail against the unsplit launch (harness flag 44): identical outside the tail tiles, fp32 rounding inside
+  {  // the split tail against the unsplit launch (LAB_HESSIAN_NO_TAIL_SPLIT): identical outside the tail tiles, fp32 rounding inside
     std::vector<std::vector<float>> ref;
     for (int pass = 0; pass < 2; ++pass) {
-      inc_debug_set_small_tiles(pass == 0 ? 44 : 0);
+      inc_debug_set_small_tiles(pass == 0 ? LAB_HESSIAN_NO_TAIL_SPLIT : 0);
       for (int i = 0; i < 4; ++i) Hs[i]->zero();
       float b0[4] = {0.f, 0.f, 0.f, 0.f};
       INCCHECK(inc_gptq_hessian_accum_multi(4, xp, INC_BF16, T, Ks, ld, hp, b0, alphas, hws.p, (int64_t)hws.n, nullptr));
@@ -809,7 +811,8 @@ static int run_hessian_multi_case(int64_t T) {
   }
   Timer t;
   const int nm = 10;
-  const int modes[nm] = {0, 59, 53, 54, 56, 57, 44, 46, 45, 0};
+  const int modes[nm] = {0, LAB_HESSIAN_ROUND4, LAB_HESSIAN_ROLL, LAB_HESSIAN_PRIO, LAB_HESSIAN_ROLL_PRIO, LAB_HESSIAN_PIPELINE, LAB_HESSIAN_NO_TAIL_SPLIT,
+                         LAB_HESSIAN_STAGES_4X32, LAB_HESSIAN_REG_TRANSPOSE, 0};
   const char* labels[nm] = {"transpose-read 2x64", "  round-4 form", "  rolling frags", "  prio 1 for waves 4-7", "  rolling + prio", "  one pipeline per step",
                             "  - tail split", "transpose-read 4x32", "register transpose", "transpose-read 2x64 (again)"};
   for (int mi = 0; mi < nm; ++mi) {
@@ -869,7 +872,7 @@ static int run_hessian_pf_case(int64_t T, int passes) {
   DevBuf<char> hws((size_t)inc_gptq_hessian_accum_multi_workspace_bytes());
   DevBuf<unsigned long long> dcount(1);
   constexpr int NM = 4;
-  const int modes[NM] = {0, 58, 59, 58};  // product (one-block issue), the same without it, the round-4 form
+  const int modes[NM] = {0, LAB_HESSIAN_PIPELINE_PRIO, LAB_HESSIAN_ROUND4, LAB_HESSIAN_PIPELINE_PRIO};  // product (one-block issue), the same without it, the round-4 form
   int bad = 0;
   inc_debug_set_small_tiles(0);
   INCCHECK(inc_gptq_hessian_accum_multi(4, xp, INC_BF16, T, Ks, ld, hr, b0, alphas, hws.p, (int64_t)hws.n, nullptr));
@@ -910,7 +913,7 @@ static int run_hessian_pf_case(int64_t T, int passes) {
   return bad;
 }
 
-// ---- GPTQ column loop: quad-per-row quant block + lazy update generations (3rd = default, 2nd = flag 86, 1st = flag 1) --------
+// ---- GPTQ column loop: quad-per-row quant block + lazy update generations (3rd = default, 2nd = LAB_LAZY_V2, 1st = flag 1) --------
 static void colloop_inputs(int64_t N, int64_t K, int gs, std::vector<float>& hw, std::vector<float>& hh, std::vector<float>& hs, std::vector<float>& hz) {
   hw.resize((size_t)N * K); hh.assign((size_t)K * K, 0.f);
   for (auto& v : hw) v = 0.02f * rnd_normal();
@@ -930,7 +933,7 @@ static int run_colloop_case(int64_t N, int64_t K, int gs, int nblocks, bool time
   DevBuf<float> Hinv((size_t)K * K), sc(hs.size()), ze(hz.size());
   Hinv.upload(hh); sc.upload(hs); ze.upload(hz);
   constexpr int NV = 4;
-  const int flag[NV] = {0, 86, 1, 107};
+  const int flag[NV] = {0, LAB_LAZY_V2, 1, LAB_LAZY_V3_ONLY};
   const char* label[NV] = {"product (4th / 3rd)", "second generation", "first generation", "third generation only"};
   std::vector<DevBuf<float>*> W, E;
   std::vector<DevBuf<uint8_t>*> C;
@@ -997,7 +1000,7 @@ static int run_colloop_case(int64_t N, int64_t K, int gs, int nblocks, bool time
              tq / nb, tl / nb, fl / (tl * 1e9), nn ? tn / nn : 0.f);
     }
     // timing-only variants of the third generation's whole-tile kernel
-    const int afl[3] = {87, 88, 90};
+    const int afl[3] = {LAB_LAZY_NO_MFMA, LAB_LAZY_NO_LOADS, LAB_LAZY_NO_STORES};
     const char* alab[3] = {"3rd gen - MFMAs", "3rd gen - loads / DMA", "3rd gen - stores"};
     for (int v = 0; v < 3; ++v) {
       inc_debug_set_small_tiles(afl[v]);
@@ -1024,11 +1027,11 @@ static int run_qlayer_case(int64_t N, int64_t K, int gs) {
   Hinv.upload(hh);
   hipStream_t aux;
   HIPCHECK(hipStreamCreateWithFlags(&aux, hipStreamNonBlocking));
-  // third variant (flag 106, an EXPERIMENT): the lazy update with split (bf16 x 3) products -- not bit-identical by construction; the
+  // third variant (LAB_LAZY_X3, an EXPERIMENT): the lazy update with split (bf16 x 3) products -- not bit-identical by construction; the
   // count of differing codes and the time are the result
   const bool x3 = (K % 128) == 0;
   DevBuf<char> planes((size_t)(x3 ? inc_debug_lazy_x3_bytes(N, K) : 16));
-  const int flag[3] = {0, 86, 106};
+  const int flag[3] = {0, LAB_LAZY_V2, LAB_LAZY_X3};
   std::vector<uint8_t> codes[3];
   std::vector<float> scales[3];
   float ms[3] = {0, 0, 0}, host_ms[3] = {0, 0, 0};
@@ -1056,10 +1059,10 @@ static int run_qlayer_case(int64_t N, int64_t K, int gs) {
     codes[m] = C.download();
     scales[m] = sc.download();
   }
-  // the strip form of the trailing update (fourth generation, the product) against the third generation everywhere (flag 107) and
-  // with short strips everywhere (flag 110) and strips cut at 16 tiles (109): interleaved repeats, codes compared bit for bit
+  // the strip form of the trailing update (fourth generation, the product) against the third generation everywhere (LAB_LAZY_V3_ONLY) and
+  // with short strips everywhere (LAB_LAZY_SHORT_STRIPS) and strips cut at 16 tiles (LAB_LAZY_STRIP_CAP_16): interleaved repeats, codes compared bit for bit
   {
-    const int vflag[4] = {0, 107, 110, 109};
+    const int vflag[4] = {0, LAB_LAZY_V3_ONLY, LAB_LAZY_SHORT_STRIPS, LAB_LAZY_STRIP_CAP_16};
     const char* vname[4] = {"strip form (product)", "third generation everywhere", "short strips (<= 8 tiles) everywhere", "strips <= 16 tiles"};
     std::vector<float> vt[4];
     int64_t vdiff[4] = {0, 0, 0, 0};

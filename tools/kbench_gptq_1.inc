@@ -1,5 +1,5 @@
-// harness-only code of gptq.hip (superseded kernel generations / timing-only ablations; tools/Makefile builds
-// them into tools/libinc_mi355x_kbench.so with -DINC_KBENCH; they are NOT part of libinc_mi355x.so).  Included in place by gptq.hip.
+// kbench_gptq_1.inc -- HARNESS ONLY (tools/libinc_mi355x_kbench.so, -DINC_KBENCH; included by csrc/gptq_hessian.hip inside its anonymous
+// namespace): the first 256 x 256 generation of the Hessian tile, LAB_HESSIAN_REG_TRANSPOSE, A/B partner of the transpose-read tile.
 // ---- 16-bit inputs, 256x256 tile of H per workgroup (K >= 256) --------------------------------------
 // 512 threads = 8 waves as 2 (i) x 4 (j); a wave owns 128 x 64 of H = 4 x 2 MFMA 32x32x16 tiles.
 // Per 64-token step each thread fetches ONE 8(token) x 8(feature) block (eight 16-byte loads, the wave
@@ -136,3 +136,27 @@ __device__ __forceinline__ void hessian_syrk_256_tile(const uint16_t* __restrict
       }
     }
 }
+
+template <bool IS_BF16, bool TAIL>
+__global__ __launch_bounds__(512) void hessian_syrk_16bit_256_kernel(const uint16_t* __restrict__ x, int64_t T,
+                                                                     int64_t K, int64_t ldx, float* __restrict__ H,
+                                                                     float beta, float alpha, int nt) {
+  hessian_syrk_256_tile<IS_BF16, TAIL>(x, T, K, ldx, H, beta, alpha, nt, (int)blockIdx.x, (int)gridDim.x);
+}
+
+template <bool IS_BF16, bool TAIL>
+__global__ __launch_bounds__(512) void hessian_syrk_16bit_256_multi_kernel(HessianBatch args, int64_t T) {
+  const int b = (int)blockIdx.x;
+  const int p = hessian_batch_problem(args, b);
+  hessian_syrk_256_tile<IS_BF16, TAIL>(args.x[p], T, args.K[p], args.ldx[p], args.H[p], args.beta[p], args.alpha[p], args.nt[p],
+                                       b - args.first[p], args.first[p + 1] - args.first[p]);
+}
+
+// `launch(is_bf16, ragged_last_step)` with the two as compile-time constants
+template <class Launch>
+void hessian_256_dispatch(int xdtype, int64_t T, Launch launch) {
+  const bool tail = (T % HK) != 0;
+  if (xdtype == INC_BF16) { if (tail) launch(std::true_type{}, std::true_type{}); else launch(std::true_type{}, std::false_type{}); }
+  else { if (tail) launch(std::false_type{}, std::true_type{}); else launch(std::false_type{}, std::false_type{}); }
+}
+constexpr size_t H2_SMEM = (size_t)2 * H2_STAGE * sizeof(uint16_t);  // 144 KiB

@@ -1,5 +1,5 @@
-// harness-only code of gptq.hip (superseded kernel generations / timing-only ablations; tools/Makefile builds
-// them into tools/libinc_mi355x_kbench.so with -DINC_KBENCH; they are NOT part of libinc_mi355x.so).  Included in place by gptq.hip.
+// kbench_gptq_2.inc -- HARNESS ONLY (included by csrc/gptq.hip under INC_KBENCH, inside its anonymous namespace):
+// the second generation of the lazy update and the hook through which the harness flags reach it and the split-product experiment.
 // ---------------------------------------------------------------------------------------------
 // lazy update, second generation: W[:, i2:] -= Err1 @ Hinv[i1:i2, i2:] with Err1 held in registers
 // ---------------------------------------------------------------------------------------------
@@ -122,4 +122,22 @@ __global__ __launch_bounds__(256) void gptq_lazy_update_v2_kernel(float* __restr
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
   }
+}
+
+// The hook of lazy_update_range (csrc/gptq.hip).  Returns whether it launched.
+bool launch_lazy_update_x3(float* w, const float* err, int64_t N, int64_t K, int64_t i1, int64_t c_begin, int64_t c_end, hipStream_t s);  // kbench_gptq_3.inc
+bool lazy_update_lab_launch(float* w, const float* Hinv, const float* err, int64_t N, int64_t K, int64_t i1, int64_t c_begin, int64_t c_end,
+                            bool exclusive, hipStream_t s) {
+  const int flag = inc_small_tiles_flag(-1);
+  // (the experiment covers the look-ahead loop's column-range calls only)
+  if (flag == LAB_LAZY_X3 && !exclusive) return launch_lazy_update_x3(w, err, N, K, i1, c_begin, c_end, s);
+  if (flag != LAB_LAZY_V2) return false;
+  const int ncol_tiles = (int)ceil_div64(c_end - c_begin, L2T);
+  const int row_tiles = (int)ceil_div64(N, L2T);
+  const int nchunks = std::min((int)ceil_div64(512, row_tiles), ncol_tiles);  // ~512 workgroups when the trailing matrix is wide enough
+  const size_t smem2 = (size_t)2 * L2T * L2T * 4;  // 128 KiB
+  (void)hipFuncSetAttribute((const void*)gptq_lazy_update_v2_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem2);
+  gptq_lazy_update_v2_kernel<true><<<dim3((unsigned)nchunks, (unsigned)row_tiles), 256, smem2, s>>>(w, Hinv, err, N, K, i1, c_begin, nchunks,
+                                                                                                 ncol_tiles);
+  return true;
 }

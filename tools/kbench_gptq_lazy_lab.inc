@@ -1,6 +1,6 @@
-// kbench_gptq_lazy_lab.inc -- the lazy update's third generation WITH its timing-only ablations (harness flags 87 / 88 / 90: no MFMAs /
-// no loads and LDS-DMA / no stores -- WRONG results by construction).  Included by csrc/gptq.hip under INC_KBENCH; the product kernel
-// (gptq_lazy_update_v3_kernel) is this code with ABL = 0 written out.
+// kbench_gptq_lazy_lab.inc -- the lazy update's third generation WITH its timing-only ablations (LAB_LAZY_NO_MFMA / _NO_LOADS / _NO_STORES:
+// WRONG results by construction), and what the harness flags change in the launcher (at the end).  Included by csrc/gptq_lazy.hip under
+// INC_KBENCH; the product kernel (gptq_lazy_update_v3_kernel) is this code with ABL = 0 written out.
 template <int CW, int ABL = 0>  // ABL (harness build, timing only): 1 = no MFMAs, 2 = no loads / LDS-DMA, 4 = no stores
 __global__ __launch_bounds__(256, 2) void gptq_lazy_update_v3_lab_kernel(float* __restrict__ w, const float* __restrict__ Hinv,
                                                                      const float* __restrict__ err, int64_t N, int64_t K,
@@ -150,3 +150,25 @@ __global__ __launch_bounds__(256, 2) void gptq_lazy_update_v3_lab_kernel(float* 
   }
 }
 
+// the launcher's overrides by harness flag (csrc/gptq_lazy.hip, LazyLabOverrides)
+LazyLabOverrides lazy_lab_overrides() {
+  const int f = inc_small_tiles_flag(-1);
+  LazyLabOverrides o;
+  o.ablation = f == LAB_LAZY_NO_MFMA ? 1 : f == LAB_LAZY_NO_LOADS ? 2 : f == LAB_LAZY_NO_STORES ? 4 : 0;
+  o.v3_everywhere = f == LAB_LAZY_V3_ONLY;
+  if (f == LAB_LAZY_STRIP_CAP_4 || f == LAB_LAZY_STRIP_CAP_16) o.strip_cap = f == LAB_LAZY_STRIP_CAP_4 ? 4 : 16;
+  o.never_one_round = f == LAB_LAZY_STRIP_CAP_4 || f == LAB_LAZY_STRIP_CAP_16 || f == LAB_LAZY_SHORT_STRIPS;
+  return o;
+}
+
+// whole tiles of the third generation everywhere, ablation `abl` of the kernel above
+void lazy_lab_ablation_launch(int abl, float* w, const float* Hinv, const float* err, int64_t N, int64_t K, int64_t i1, int64_t c_begin,
+                              int64_t col_tiles, int64_t row_tiles, hipStream_t s) {
+  auto launch = [&](auto kernel) {
+    (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
+    kernel<<<dim3((unsigned)col_tiles, (unsigned)row_tiles), 256, 65536, s>>>(w, Hinv, err, N, K, i1, c_begin);
+  };
+  if (abl == 1) launch(gptq_lazy_update_v3_lab_kernel<128, 1>);
+  else if (abl == 2) launch(gptq_lazy_update_v3_lab_kernel<128, 2>);
+  else launch(gptq_lazy_update_v3_lab_kernel<128, 4>);
+}

@@ -3,12 +3,9 @@
 // without the switches; everything else lives here: ABL bits 0 / 1 are timing-only ablations with WRONG results (no LDS-DMA / no
 // fragment reads and no MFMA), bits 2 / 3 correct A/B partners (requests spread over the step / row fragments two rows ahead), bit 4
 // static priority for waves 4-7, bit 5 one rolling fragment pipeline per step, bit 7 a step's eight LDS-DMA pieces from one asm block;
-// (TOK, NST) other than (64, 2) are the stage-shape A/B partners.  tools/kbench hessian / hpf select them by flag.
+// (TOK, NST) other than (64, 2) are the stage-shape A/B partners.  tools/kbench hessian / hpf select them by flag: the table and the two
+// launch hooks at the end of this file, one per Hessian entry point.  `slab`: as in the product tile.
 constexpr int TR_LAB_ABL = 176;
-// ABL bits 0 / 1 (harness build only, timing-only, WRONG results): no LDS-DMA / no fragment reads and no MFMA; bits 2 / 3 (harness
-// A/B partners, correct results): requests spread over the step / row fragments two rows ahead; bits 4 / 5: see TR_ABL.
-// `slab` != nullptr: the raw sums of this token range go to slab[256][256] instead of into H (a tile of the launch's last, partly
-// filled round computed by several workgroups: hessian_tail_finalize_kernel adds the ranges in order)
 template <bool IS_BF16, int TOK, int NST, int ABL = TR_LAB_ABL>
 __device__ __forceinline__ void hessian_syrk_tr_tile_lab(const uint16_t* __restrict__ x, int64_t T, int64_t K, int64_t ldx,
                                                      float* __restrict__ H, float beta, float alpha, int nt, int block, int nblocks,
@@ -230,3 +227,98 @@ __global__ __launch_bounds__(512) void hessian_syrk_tr_256_lab_kernel(const uint
   hessian_syrk_tr_tile_lab<IS_BF16, TOK, NST, ABL>(x, T, K, ldx, H, beta, alpha, nt, (int)blockIdx.x, (int)gridDim.x);
 }
 
+// the batched launch over the harness generations of the tile
+template <bool IS_BF16, int TOK = TR_TOK, int NST = TR_NST, int ABL = TR_LAB_ABL>
+__global__ __launch_bounds__(512) void hessian_syrk_tr_256_multi_lab_kernel(HessianBatch args, int64_t T) {
+  hessian_batch_workgroup(args, T, TOK, [](auto... a) __attribute__((always_inline)) { hessian_syrk_tr_tile_lab<IS_BF16, TOK, NST, ABL>(a...); });
+}
+
+// ---- harness launches: flag -> form of the tile (bf16 only) ---------------------------------------------------------------------
+struct TileLabForm { int flag, tok, nst, abl; bool batched; };  // batched: also instantiated for the batched launch
+constexpr TileLabForm TILE_LAB_FORMS[] = {
+    {LAB_HESSIAN_STAGES_4X32, 32, 4, TR_LAB_ABL, true},
+    {LAB_HESSIAN_NO_DMA, 64, 2, 1, false},          // timing only
+    {LAB_HESSIAN_NO_MFMA, 64, 2, 2, false},         // timing only
+    {LAB_HESSIAN_NO_DMA_NO_MFMA, 64, 2, 3, false},  // timing only
+    {LAB_HESSIAN_SPREAD, 64, 2, 4, false},
+    {LAB_HESSIAN_SPREAD_4X32, 32, 4, 4, false},     // three steps in flight
+    {LAB_HESSIAN_SPREAD_ROLL, 64, 2, 4 | 8, false},
+    {LAB_HESSIAN_ROLL, 64, 2, 8, true},
+    {LAB_HESSIAN_PRIO, 64, 2, 16, true},
+    {LAB_HESSIAN_SPREAD_ROLL_PRIO, 64, 2, 4 | 8 | 16, false},
+    {LAB_HESSIAN_ROLL_PRIO, 64, 2, 8 | 16, true},
+    {LAB_HESSIAN_PIPELINE, 64, 2, 32, true},
+    {LAB_HESSIAN_PIPELINE_PRIO, 64, 2, 32 | 16, true},
+    {LAB_HESSIAN_ROUND4, 64, 2, 0, true},           // A/B partner of every switch
+    {LAB_HESSIAN_PRODUCT_FORM, 64, 2, TR_LAB_ABL, true},
+};
+// `launch(index)`, the table index of `flag` as a compile-time constant; false when the flag selects no form here.  BATCHED: only the
+// forms with `batched` set are offered, so only those multi_lab_kernel instantiations exist.
+template <bool BATCHED, int I = 0, class Launch>
+bool tile_lab_dispatch(int flag, Launch launch) {
+  if constexpr (I < (int)(sizeof(TILE_LAB_FORMS) / sizeof(TILE_LAB_FORMS[0]))) {
+    if constexpr (!BATCHED || TILE_LAB_FORMS[I].batched)
+      if (flag == TILE_LAB_FORMS[I].flag) return launch(std::integral_constant<int, I>{}), true;
+    return tile_lab_dispatch<BATCHED, I + 1>(flag, launch);
+  }
+  return false;
+}
+
+// a harness launch of 512-thread workgroups: the LDS attribute is set at every launch
+template <class Kernel, class... Args>
+void lab_launch(Kernel kernel, int grid, size_t smem, hipStream_t s, Args... args) {
+  (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+  kernel<<<grid, 512, smem, s>>>(args...);
+}
+
+// The hook of inc_gptq_hessian_accum on the 256 x 256 route.  Returns whether it launched.
+bool hessian_lab_launch(const uint16_t* xp, int xdtype, int64_t T, int64_t K, int64_t ldx, float* H, float beta, float alpha, int nt2,
+                        int ntiles2, hipStream_t s) {
+  const int flag = inc_small_tiles_flag(-1);
+  if (flag == LAB_HESSIAN_REG_TRANSPOSE) {
+    hessian_256_dispatch(xdtype, T, [&](auto bf16, auto tail) {
+      lab_launch(hessian_syrk_16bit_256_kernel<bf16.value, tail.value>, ntiles2, H2_SMEM, s, xp, T, K, ldx, H, beta, alpha, nt2);
+    });
+    return true;
+  }
+  if (xdtype != INC_BF16) return false;
+  return tile_lab_dispatch<false>(flag, [&](auto i) {
+    constexpr TileLabForm F = TILE_LAB_FORMS[i.value];
+    lab_launch(hessian_syrk_tr_256_lab_kernel<true, F.tok, F.nst, F.abl>, ntiles2, (size_t)TR_NST * TR_STAGE, s, xp, T, K, ldx, H, beta, alpha, nt2);
+  });
+}
+
+// The hook of inc_gptq_hessian_accum_multi, after the batch is filled.  Returns whether it launched; LAB_HESSIAN_NO_TAIL_SPLIT only
+// undoes the split and leaves the launch to the product.
+bool hessian_batch_lab_launch(HessianBatch& a, int xdtype, int64_t T, int cus, hipStream_t s) {
+  const int flag = inc_small_tiles_flag(-1), tiles = a.first[a.n];
+  const size_t smem3 = (size_t)TR_NST * TR_STAGE;
+  auto unsplit = [&] { a.full = tiles; a.nseg = 1; a.slab = nullptr; };
+  auto grid = [&] { return a.full + (tiles - a.full) * a.nseg; };
+  if (flag == LAB_HESSIAN_NO_TAIL_SPLIT) { unsplit(); return false; }
+  if (flag == LAB_HESSIAN_REG_TRANSPOSE) {
+    unsplit();
+    hessian_256_dispatch(xdtype, T, [&](auto bf16, auto tail) {
+      lab_launch(hessian_syrk_16bit_256_multi_kernel<bf16.value, tail.value>, tiles, H2_SMEM, s, a, T);
+    });
+    return true;
+  }
+  if (flag == LAB_HESSIAN_ROUND_LAUNCHES) {  // the product kernel, one launch per round of one-tile-per-CU
+    const int chunk = (cus <= 0 || (cus % 8) != 0) ? 256 : cus;
+    for (int b0 = 0; b0 < grid(); b0 += chunk) {
+      a.block0 = b0;
+      const int g = std::min(grid() - b0, chunk);
+      if (xdtype == INC_BF16) lab_launch(hessian_syrk_tr_256_multi_kernel<true>, g, smem3, s, a, T);
+      else lab_launch(hessian_syrk_tr_256_multi_kernel<false>, g, smem3, s, a, T);
+    }
+    hessian_tail_finalize(a, s);
+    return true;
+  }
+  if (xdtype != INC_BF16) return false;
+  return tile_lab_dispatch<true>(flag, [&](auto i) {
+    constexpr TileLabForm F = TILE_LAB_FORMS[i.value];
+    if (F.tok != TR_TOK) unsplit();  // the split's token ranges are whole 64-token steps
+    lab_launch(hessian_syrk_tr_256_multi_lab_kernel<true, F.tok, F.nst, F.abl>, grid(), smem3, s, a, T);
+    hessian_tail_finalize(a, s);
+  });
+}
