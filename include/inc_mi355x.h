@@ -197,6 +197,43 @@ int inc_woq_gemm_multi(int n, const void* x, int xdtype, const int32_t* const* q
                        const int32_t* const* qzeros, const void* const* bias, void* const* y, int64_t M, const int64_t* N,
                        int64_t K, int group_size, int bits, void* workspace, int64_t workspace_bytes, inc_stream_t stream);
 
+/* inc_woq_gemm_multi for act_order (HF desc_act) members: y[i] = x[:, k_order[i]] . W_sorted_i^T + bias_i, all members in ONE launch --
+ * n calls of INCWeightOnlyLinear.forward (modules.py:594-610) whose groups are looked up per element (modules.py:427-431).  The arguments
+ * are inc_woq_gemm_multi's plus `k_order`, a HOST array of n device pointers: k_order[i] [K] int32, 16-byte aligned, never NULL, and
+ * qweight[i] member i's K-sorted words, as for inc_woq_gemm_perm.  A member without a permutation takes the identity (0 .. K-1).  Every
+ * entry of an order is clamped to [0, K-1] before it is used; x needs only 2-byte alignment.
+ *   Contract: y[i] is bit-identical to output i of inc_woq_gemm_multi called with the same n, N[], K, workspace size and
+ *   x.index_select(1, k_order[i]) in place of x -- the same plan, the same rung of the same body, the same MFMAs in the same order.
+ *   INC_ERR_UNSUPPORTED (nothing launched) wherever inc_woq_gemm_multi returns it (an unaligned x excepted: x is read 2 bytes at a
+ *   time here), for M * K >= 2^31 and for an order that is not 16-byte aligned; INC_ERR_BAD_ARG for a NULL k_order or k_order[i].
+ *   `workspace`: inc_woq_gemm_multi_workspace_bytes bytes, with inc_woq_gemm_multi's rules.                                      */
+int inc_woq_gemm_multi_perm(int n, const void* x, int xdtype, const int32_t* const* k_order, const int32_t* const* qweight,
+                            const uint16_t* const* scales, const int32_t* const* qzeros, const void* const* bias, void* const* y, int64_t M,
+                            const int64_t* N, int64_t K, int group_size, int bits, void* workspace, int64_t workspace_bytes,
+                            inc_stream_t stream);
+
+/* gate_proj / up_proj of a dense gated MLP with the SiLU product in the SAME launch: h = act_fn(gate_proj(x)) * up_proj(x), the first half
+ * of transformers' LlamaMLP.forward (models/llama/modeling_llama.py: `down_proj(act_fn(gate_proj(x)) * up_proj(x))`; also Mistral /
+ * Qwen2 / Qwen3), whose two products are INCWeightOnlyLinear.forward (modules.py:594-610) and whose activation and product are two more
+ * torch kernels on 16-bit copies of g and u.  Here
+ *     h[m, j] = rx( g / (1 + expf(-g)) * u ),   g = x[m] . Wg[j],  u = x[m] . Wu[j]
+ *   in fp32 with ONE rounding rx to xdtype (the expression of inc_woq_moe_gemm's mode 0).  g and u are the fixed-order fp32 sums
+ *   inc_woq_gemm_multi forms for the pair (N, N) before it rounds them: deterministic, repeated calls are bit-identical.
+ *   x [M,K] of `xdtype` (INC_BF16 / INC_F16), M <= 16; gate and up: qweight [K/8,N], scales [G,N] fp16, qzeros [G,ceil(N/8)], the same
+ *   N, K and group_size, no bias; h [M,N] of `xdtype`; act: 0 = SiLU.  k_order_gate / k_order_up: both NULL, or both given ([K] int32,
+ *   16-byte aligned; INC_ERR_BAD_ARG for one without the other) -- then the words are the K-sorted ones and each member gathers x through
+ *   its OWN order as inc_woq_gemm_perm does (entries clamped to [0, K-1], x 2-byte aligned, M * K < 2^31).
+ *   INC_ERR_UNSUPPORTED (nothing launched): bits other than 4, act other than 0, M > 16, whatever inc_woq_gemm_multi declines for
+ *   n = 2 and N[] = {N, N}, an unaligned x without orders, a misaligned order.
+ *   `workspace`: inc_woq_gemm_gated_workspace_bytes bytes (0 for a non-positive size; INC_ERR_WORKSPACE for less than the launch needs);
+ *   its first 16 KiB are arrival counters with the rules of inc_woq_gemm's (zero on first use, re-armed by the kernel), so one
+ *   (device, stream) workspace serves this entry and the other inc_woq_gemm* entries in turn.                                       */
+int64_t inc_woq_gemm_gated_workspace_bytes(int64_t M, int64_t N, int64_t K);
+int inc_woq_gemm_gated(const void* x, int xdtype, const int32_t* k_order_gate, const int32_t* k_order_up, const int32_t* gate_qweight,
+                       const uint16_t* gate_scales, const int32_t* gate_qzeros, const int32_t* up_qweight, const uint16_t* up_scales,
+                       const int32_t* up_qzeros, void* h, int64_t M, int64_t N, int64_t K, int group_size, int bits, int act,
+                       void* workspace, int64_t workspace_bytes, inc_stream_t stream);
+
 /* ---- K4d: fused 4-bit code-book / row-packed integer dequant + GEMM ------------------------ *
  * == INCWeightOnlyLinear.forward (modules.py:594-610) for the layouts that are not the optimum one: F.linear(x, recover(x.dtype), bias)
  *   with recover (modules.py:413-443) done in registers, the dense weight never materialised.  NF4 / FP4 code books and integer

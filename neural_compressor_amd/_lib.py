@@ -56,6 +56,12 @@ SIGNATURES = {
     "inc_moe_combine": (c_int, [_P, _P, _P, c_int, c_int64, c_int, c_int64, c_int64, _P]),
     "inc_woq_gemm_multi_workspace_bytes": (c_int64, [c_int, c_int64, _P, c_int64]),
     "inc_woq_gemm_multi": (c_int, [c_int, _P, c_int, _P, _P, _P, _P, _P, c_int64, _P, c_int64, c_int, c_int, _P, c_int64, _P]),
+    "inc_woq_gemm_multi_perm": (c_int, [c_int, _P, c_int, _P, _P, _P, _P, _P, _P, c_int64, _P, c_int64, c_int, c_int, _P, c_int64, _P]),
+    "inc_woq_gemm_gated_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64]),
+    "inc_woq_gemm_gated": (
+        c_int,
+        [_P, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int64, c_int64, c_int, c_int, c_int, _P, c_int64, _P],
+    ),
     "inc_groupwise_quant": (
         c_int,
         [_P, c_int, _P, _P, _P, _P, c_int64, c_int64, c_int, c_int, c_int, c_float, c_int, _P],

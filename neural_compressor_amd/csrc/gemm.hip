@@ -371,22 +371,28 @@ int64_t inc_woq_gemm_multi_workspace_bytes(int n, int64_t M, const int64_t* N, i
   return WS_COUNTER_BYTES + ceil_div64(K, STREAM_SLICE_K) * M * ntot * 4;  // 4 steps per wave: the most slices either form uses
 }
 
-int inc_woq_gemm_multi(int n, const void* x, int xdtype, const int32_t* const* qweight, const uint16_t* const* scales,
-                       const int32_t* const* qzeros, const void* const* bias, void* const* y, int64_t M, const int64_t* N, int64_t K,
-                       int group_size, int bits, void* workspace, int64_t workspace_bytes, inc_stream_t stream) {
-  INC_CHECK_ARG(x && qweight && scales && qzeros && y && N && n > 0 && M > 0 && K > 0 && group_size > 0);
+// the plain batch (k_order == NULL: inc_woq_gemm_multi) and the gathered one (inc_woq_gemm_multi_perm: one order per member, x read 2
+// bytes at a time through 32-bit byte offsets): the same plan, the same rung, the PERM instantiation of the same body
+static int woq_gemm_multi_launch(int n, const void* x, int xdtype, const int32_t* const* k_order, const int32_t* const* qweight,
+                                 const uint16_t* const* scales, const int32_t* const* qzeros, const void* const* bias, void* const* y, int64_t M,
+                                 const int64_t* N, int64_t K, int group_size, int bits, void* workspace, int64_t workspace_bytes, inc_stream_t stream) {
   if (!(xdtype == INC_BF16 || xdtype == INC_F16)) return INC_ERR_UNSUPPORTED;
   int g_shift;
   StreamPlan sp;
   int64_t strips;
-  if (!gemv_multi_plan(n, M, N, K, group_size, bits, &g_shift, &sp, &strips) || (reinterpret_cast<uintptr_t>(x) & 15) != 0)
-    return INC_ERR_UNSUPPORTED;  // nothing launched: the caller issues inc_woq_gemm per module
+  if (!gemv_multi_plan(n, M, N, K, group_size, bits, &g_shift, &sp, &strips)) return INC_ERR_UNSUPPORTED;  // nothing launched: the caller issues inc_woq_gemm per module
+  if (k_order ? M * K >= ((int64_t)1 << 31) : (reinterpret_cast<uintptr_t>(x) & 15) != 0) return INC_ERR_UNSUPPORTED;
   GemvBatch args = {};  // (modules past n: null tensors, N = 0)
   args.n = n;
   int64_t off = 0;
   int first = 0;
   for (int i = 0; i < n; ++i) {
     INC_CHECK_ARG(qweight[i] && scales[i] && qzeros[i] && y[i]);
+    if (k_order) {
+      INC_CHECK_ARG(k_order[i]);
+      if ((reinterpret_cast<uintptr_t>(k_order[i]) & 15) != 0) return INC_ERR_UNSUPPORTED;
+      args.k_order[i] = k_order[i];
+    }
     args.qweight[i] = (const uint32_t*)qweight[i];
     args.scales[i] = scales[i];
     args.qzeros[i] = (const uint32_t*)qzeros[i];
@@ -403,6 +409,71 @@ int inc_woq_gemm_multi(int n, const void* x, int xdtype, const int32_t* const* q
   StreamLaunch l = {(const uint16_t*)x, M, K, g_shift, xdtype == INC_BF16, inc_s(stream), bits, sp.steps, sp.mb, sp.splitk, strips,
                     (float*)((char*)workspace + WS_COUNTER_BYTES), (unsigned*)workspace};
   l.batch = &args;
+  l.batch_perm = k_order != nullptr;
+  return inc_launch_woq_gemv_stream(l);
+}
+
+int inc_woq_gemm_multi(int n, const void* x, int xdtype, const int32_t* const* qweight, const uint16_t* const* scales,
+                       const int32_t* const* qzeros, const void* const* bias, void* const* y, int64_t M, const int64_t* N, int64_t K,
+                       int group_size, int bits, void* workspace, int64_t workspace_bytes, inc_stream_t stream) {
+  INC_CHECK_ARG(x && qweight && scales && qzeros && y && N && n > 0 && M > 0 && K > 0 && group_size > 0);
+  return woq_gemm_multi_launch(n, x, xdtype, nullptr, qweight, scales, qzeros, bias, y, M, N, K, group_size, bits, workspace, workspace_bytes, stream);
+}
+
+// ---- act_order members in the batched launch: y[i] = x[:, k_order[i]] W_sorted_i^T + bias_i ------------------------------------
+int inc_woq_gemm_multi_perm(int n, const void* x, int xdtype, const int32_t* const* k_order, const int32_t* const* qweight,
+                            const uint16_t* const* scales, const int32_t* const* qzeros, const void* const* bias, void* const* y, int64_t M,
+                            const int64_t* N, int64_t K, int group_size, int bits, void* workspace, int64_t workspace_bytes,
+                            inc_stream_t stream) {
+  INC_CHECK_ARG(x && k_order && qweight && scales && qzeros && y && N && n > 0 && M > 0 && K > 0 && group_size > 0);
+  INC_CHECK_ARG((reinterpret_cast<uintptr_t>(x) & 1) == 0);
+  return woq_gemm_multi_launch(n, x, xdtype, k_order, qweight, scales, qzeros, bias, y, M, N, K, group_size, bits, workspace, workspace_bytes, stream);
+}
+
+// ---- gate / up of a dense MLP with the SiLU product in the same launch: h = silu(x Wg^T) * (x Wu^T) ----------------------------
+// The batched launch over the two members (gemv_multi_plan for N, N), one row block; the strips of gate and up share a ticket and the
+// last arriver forms the product from the two fixed-order fp32 sums (gemm_stream.hip, GATED).
+constexpr int64_t GATED_MAX_M = 16;
+
+int64_t inc_woq_gemm_gated_workspace_bytes(int64_t M, int64_t N, int64_t K) {
+  if (M <= 0 || N <= 0 || K <= 0) return 0;
+  return WS_COUNTER_BYTES + ceil_div64(K, STREAM_SLICE_K) * M * 2 * N * 4;  // 4 steps per wave: the most slices; both members' slabs
+}
+
+int inc_woq_gemm_gated(const void* x, int xdtype, const int32_t* k_order_gate, const int32_t* k_order_up, const int32_t* gate_qweight,
+                       const uint16_t* gate_scales, const int32_t* gate_qzeros, const int32_t* up_qweight, const uint16_t* up_scales,
+                       const int32_t* up_qzeros, void* h, int64_t M, int64_t N, int64_t K, int group_size, int bits, int act, void* workspace,
+                       int64_t workspace_bytes, inc_stream_t stream) {
+  INC_CHECK_ARG(x && gate_qweight && gate_scales && gate_qzeros && up_qweight && up_scales && up_qzeros && h && M > 0 && N > 0 && K > 0 && group_size > 0);
+  INC_CHECK_ARG((k_order_gate == nullptr) == (k_order_up == nullptr));
+  INC_CHECK_ARG((reinterpret_cast<uintptr_t>(x) & 1) == 0);
+  if (!(xdtype == INC_BF16 || xdtype == INC_F16) || bits != 4 || act != 0 || M > GATED_MAX_M) return INC_ERR_UNSUPPORTED;
+  const bool perm = k_order_gate != nullptr;
+  const int64_t NN[2] = {N, N};
+  int g_shift;
+  StreamPlan sp;
+  int64_t strips;
+  if (!gemv_multi_plan(2, M, NN, K, group_size, bits, &g_shift, &sp, &strips)) return INC_ERR_UNSUPPORTED;
+  if (perm ? (M * K >= ((int64_t)1 << 31) || ((reinterpret_cast<uintptr_t>(k_order_gate) | reinterpret_cast<uintptr_t>(k_order_up)) & 15) != 0)
+           : (reinterpret_cast<uintptr_t>(x) & 15) != 0)
+    return INC_ERR_UNSUPPORTED;
+  if (!workspace || workspace_bytes < WS_COUNTER_BYTES + (int64_t)sp.splitk * M * 2 * N * 4) return INC_ERR_WORKSPACE;
+  GemvBatch args = {};
+  args.n = 2;
+  args.k_order[0] = k_order_gate, args.k_order[1] = k_order_up;
+  args.qweight[0] = (const uint32_t*)gate_qweight, args.qweight[1] = (const uint32_t*)up_qweight;
+  args.scales[0] = gate_scales, args.scales[1] = up_scales;
+  args.qzeros[0] = (const uint32_t*)gate_qzeros, args.qzeros[1] = (const uint32_t*)up_qzeros;
+  args.y[0] = (uint16_t*)h;
+  args.N[0] = args.N[1] = N;
+  args.part_off[1] = (int64_t)sp.splitk * M * N;
+  args.first[1] = (int)(strips / 2);
+  for (int i = 2; i <= GEMV_MAX_BATCH; ++i) args.first[i] = (int)strips;
+  StreamLaunch l = {(const uint16_t*)x, M, K, g_shift, xdtype == INC_BF16, inc_s(stream), bits, sp.steps, sp.mb, sp.splitk, strips,
+                    (float*)((char*)workspace + WS_COUNTER_BYTES), (unsigned*)workspace};
+  l.batch = &args;
+  l.batch_perm = perm;
+  l.gated = true;
   return inc_launch_woq_gemv_stream(l);
 }
 

@@ -50,9 +50,11 @@ int inc_launch_woq_gemm_d2r8(const WoqGemmArgs& a, int y_vec_ok, float* part, in
 int inc_woq_gemm_strip8_splitk(int64_t M, int64_t N, int64_t K);
 int inc_launch_woq_gemm_strip8(const WoqGemmArgs& a, float* part, unsigned* counters, int splitk);
 
-// modules that share x, one launch (inc_woq_gemm_multi): the per-module tensors of the batch, passed to the kernels by value
+// modules that share x, one launch (inc_woq_gemm_multi / _multi_perm; inc_woq_gemm_gated with gate = 0, up = 1 and y[0] = h): the
+// per-module tensors of the batch, passed to the kernels by value
 constexpr int GEMV_MAX_BATCH = 8;
 struct GemvBatch {
+  const int32_t* k_order[GEMV_MAX_BATCH];  // the gathered forms: every member's order (never NULL there); not read otherwise
   const uint32_t* qweight[GEMV_MAX_BATCH];
   const uint16_t* scales[GEMV_MAX_BATCH];
   const uint32_t* qzeros[GEMV_MAX_BATCH];
@@ -66,7 +68,9 @@ struct GemvBatch {
 
 // gemm_stream.hip: the streaming GEMV (M <= 64) in all its forms, and the no-split decode kernel.  A launch is x, the plan (steps, mb,
 // splitk: woq_gemm_plan / gemv_multi_plan) and the weights: ONE module `mod` (its x, M, K, g_shift, bf, s are not read) -- plain, gathered
-// through `k_order` (inc_woq_gemm_perm) or, in the harness, `nt` (non-temporal loads) -- or the `batch` of inc_woq_gemm_multi.
+// through `k_order` (inc_woq_gemm_perm) or, in the harness, `nt` (non-temporal loads) -- or the `batch` of inc_woq_gemm_multi, gathered
+// through the batch's own orders with `batch_perm` (inc_woq_gemm_multi_perm); `gated`: the batch is a gate / up pair whose strips share
+// a ticket and leave silu(g) * u in batch->y[0] (inc_woq_gemm_gated: one row block, 4-bit).
 struct StreamLaunch {
   const uint16_t* x;
   int64_t M, K;
@@ -82,6 +86,7 @@ struct StreamLaunch {
   const int32_t* k_order = nullptr;
   const GemvBatch* batch = nullptr;
   bool nt = false;
+  bool batch_perm = false, gated = false;
 };
 int inc_launch_woq_gemv_stream(const StreamLaunch& l);
 int inc_launch_woq_gemv16(const WoqGemmArgs& a, const int32_t* k_order, bool nt);

@@ -1,6 +1,6 @@
 // gemm_stream.hip -- the decode kernels of the fused dequant-GEMM (inc_woq_gemm, gemm.hip), M <= 64: the streaming GEMV in its plain,
-// gathered (inc_woq_gemm_perm) and batched (inc_woq_gemm_multi) forms, which share one body and ONE launch ladder below, and the
-// no-split kernel for M <= 16 on small layers.
+// gathered (inc_woq_gemm_perm), batched (inc_woq_gemm_multi, gathered: inc_woq_gemm_multi_perm) and gated (inc_woq_gemm_gated) forms,
+// which share one body and ONE launch ladder below, and the no-split kernel for M <= 16 on small layers.
 #include "gemm_common.hpp"
 
 namespace {
@@ -55,12 +55,39 @@ __device__ __forceinline__ uint4 perm_gather8(const uint16_t* __restrict__ x, ui
   return make_uint4(v[0] | (v[1] << 16), v[2] | (v[3] << 16), v[4] | (v[5] << 16), v[6] | (v[7] << 16));
 }
 
-template <bool IS_BF16, bool G128, int VSTEPS, int MB, bool NT = false, int BITS = 4, bool PERM = false>
+// the last arriver's fixed-order sum over the K-slices of one member's slabs (`sc1` loads), up to 32 partial loads of a thread in flight
+template <int NOUT>
+__device__ __forceinline__ void splitk_sum_slices(const float* __restrict__ partial, int64_t slab, int splitk, const int64_t (&out_off)[NOUT], float (&sum)[NOUT]) {
+#pragma unroll
+  for (int i = 0; i < NOUT; ++i) sum[i] = 0.f;
+  constexpr int SB = 32 / NOUT;
+  for (int sl0 = 0; sl0 < splitk; sl0 += SB) {
+    float pv[SB][NOUT];
+#pragma unroll
+    for (int d = 0; d < SB; ++d) {
+      const int sl = sl0 + d < splitk ? sl0 + d : splitk - 1;
+#pragma unroll
+      for (int i = 0; i < NOUT; ++i) pv[d][i] = __hip_atomic_load(&partial[(int64_t)sl * slab + out_off[i]], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // sc1
+    }
+#pragma unroll
+    for (int d = 0; d < SB; ++d)
+#pragma unroll
+      for (int i = 0; i < NOUT; ++i) sum[i] += (sl0 + d < splitk) ? pv[d][i] : 0.f;
+  }
+}
+
+// GATED (inc_woq_gemm_gated: gate_proj / up_proj of a dense MLP, same N): the workgroup is strip `strip` of member `member` (0 = gate,
+// 1 = up) and runs the body unchanged up to its fp32 strip sum.  Both members ALWAYS write that sum to their slabs
+// partial[member][slice][M][N] (also with one K-slice), and strip j of gate and strip j of up share `counter`: the arriver with ticket
+// 2 * splitk - 1 sums gate's slices in slice order, then up's -- the very sums the batched launch would have rounded -- and stores
+// rx(g / (1 + expf(-g)) * u), the fp32 expression of gemm_moe.hip's mode 0.  Same hand-off as below, with twice the arrivals.
+template <bool IS_BF16, bool G128, int VSTEPS, int MB, bool NT = false, int BITS = 4, bool PERM = false, bool GATED = false>
 __device__ __forceinline__ void woq_gemv_w4_body(
     const uint16_t* __restrict__ x, const uint32_t* __restrict__ qweight, const uint16_t* __restrict__ scales,
     const uint32_t* __restrict__ qzeros, const uint16_t* __restrict__ bias, uint16_t* __restrict__ y,
     float* __restrict__ partial, unsigned* __restrict__ counter, int M, int64_t N, int64_t K, int64_t NW,
-    int g_shift, int splitk, int strip, int slice, const int32_t* __restrict__ k_order = nullptr) {
+    int g_shift, int splitk, int strip, int slice, const int32_t* __restrict__ k_order = nullptr, int member = 0) {
+  static_assert(!GATED || (MB == 1 && BITS == 4 && !NT), "the gated pair: one row block of 4-bit words");
   constexpr int VS = VSTEPS;  // shadows the file-level maximum inside this kernel
   constexpr int ROWS = 16 * MB;
   constexpr int NOUT = ROWS * 64 / 256;  // outputs per thread of the strip
@@ -187,6 +214,34 @@ __device__ __forceinline__ void woq_gemv_w4_body(
     const int idx = tid + 256 * i, m = idx >> 6, c = idx & 63;
     sum[i] = red[(0 * ROWS + m) * 65 + c] + red[(1 * ROWS + m) * 65 + c] + red[(2 * ROWS + m) * 65 + c] + red[(3 * ROWS + m) * 65 + c];
   }
+  if constexpr (GATED) {
+    const int64_t slab = (int64_t)M * N;
+    float* const mine = partial + (int64_t)member * splitk * slab;
+#pragma unroll
+    for (int i = 0; i < NOUT; ++i)
+      if (out_ok[i]) __hip_atomic_store(&mine[(int64_t)slice * slab + out_off[i]], sum[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // sc1
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (tid == 0) {
+      const unsigned ticket = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const bool last = ticket == (unsigned)(2 * splitk - 1);
+      if (last) __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-arm for the next call
+      red[0] = last ? 1.f : 0.f;
+    }
+    __syncthreads();
+    if (red[0] == 0.f) return;
+    float gs[NOUT], us[NOUT];
+    splitk_sum_slices<NOUT>(partial, slab, splitk, out_off, gs);
+    splitk_sum_slices<NOUT>(partial + (int64_t)splitk * slab, slab, splitk, out_off, us);
+#pragma unroll
+    for (int i = 0; i < NOUT; ++i)
+      if (out_ok[i]) {
+        const float g = gs[i], u = us[i];
+        const float v = g / (1.f + expf(-g)) * u;
+        y[out_off[i]] = IS_BF16 ? f32_to_bf16_bits(v) : f32_to_f16_bits(v);
+      }
+    return;
+  }
   if (splitk > 1) {
     const int64_t slab = (int64_t)M * N;
 #pragma unroll
@@ -254,7 +309,9 @@ __global__ __launch_bounds__(256) void woq_gemv_w4_perm_kernel(
 // (inc_woq_gemm_multi): a decode call of one module is ~2 us of streaming behind ~5 us of launch boundary, first-byte latency and
 // split-K hand-off, and the modules of a group are independent given x.  The strips of the modules occupy consecutive ranges of
 // blockIdx.x; every strip runs exactly the body above on its own module's tensors -> bit-identical to the single launches.
-template <bool IS_BF16, bool G128, int VSTEPS, int MB, int BITS = 4>
+// PERM (inc_woq_gemm_multi_perm): member p's activations are gathered through args.k_order[p], as in woq_gemv_w4_perm_kernel -- an
+// instantiation of its own (one body, one red[] per kernel), bit-identical to the plain one on x.index_select(1, k_order[p]).
+template <bool IS_BF16, bool G128, int VSTEPS, int MB, int BITS = 4, bool PERM = false>
 __global__ __launch_bounds__(256) void woq_gemv_w4_multi_kernel(GemvBatch args, const uint16_t* __restrict__ x, float* __restrict__ partial,
                                                                 unsigned* __restrict__ counters, int M, int64_t K, int g_shift, int splitk) {
   const int b = (int)blockIdx.x;
@@ -264,9 +321,22 @@ __global__ __launch_bounds__(256) void woq_gemv_w4_multi_kernel(GemvBatch args, 
     if (i < args.n && b >= args.first[i]) p = i;
   p = __builtin_amdgcn_readfirstlane(p);
   const int64_t N = args.N[p];
-  woq_gemv_w4_body<IS_BF16, G128, VSTEPS, MB, false, BITS>(x, args.qweight[p], args.scales[p], args.qzeros[p], args.bias[p], args.y[p],
-                                                           partial + args.part_off[p], counters + b, M, N, K, BITS == 8 ? (N + 3) / 4 : (N + 7) / 8, g_shift,
-                                                           splitk, b - args.first[p], (int)blockIdx.y);
+  woq_gemv_w4_body<IS_BF16, G128, VSTEPS, MB, false, BITS, PERM>(x, args.qweight[p], args.scales[p], args.qzeros[p], args.bias[p], args.y[p],
+                                                                 partial + args.part_off[p], counters + b, M, N, K, BITS == 8 ? (N + 3) / 4 : (N + 7) / 8, g_shift,
+                                                                 splitk, b - args.first[p], (int)blockIdx.y, PERM ? args.k_order[p] : nullptr);
+}
+
+// gate / up with the SiLU product in the same launch (inc_woq_gemm_gated; GATED above): blockIdx.x < strips is gate's strip, the rest
+// up's; strip j of both arrives on counters[j], the output is args.y[0]
+template <bool IS_BF16, bool G128, int VSTEPS, bool PERM>
+__global__ __launch_bounds__(256) void woq_gemv_w4_gated_kernel(GemvBatch args, const uint16_t* __restrict__ x, float* __restrict__ partial,
+                                                                unsigned* __restrict__ counters, int M, int64_t K, int g_shift, int splitk) {
+  const int strips = args.first[1];
+  const int p = __builtin_amdgcn_readfirstlane((int)blockIdx.x >= strips ? 1 : 0);
+  const int strip = (int)blockIdx.x - p * strips;
+  const int64_t N = args.N[0];
+  woq_gemv_w4_body<IS_BF16, G128, VSTEPS, 1, false, 4, PERM, true>(x, args.qweight[p], args.scales[p], args.qzeros[p], nullptr, args.y[0], partial, counters + strip, M,
+                                                                   N, K, (N + 7) / 8, g_shift, splitk, strip, (int)blockIdx.y, PERM ? args.k_order[p] : nullptr, p);
 }
 
 // =============================================================================================
@@ -366,9 +436,16 @@ __global__ __launch_bounds__(64 * GEMV16_WAVES) void woq_gemv16_w4_kernel(
 template <bool F, bool GG, int V, int B, int W>
 int stream_rung(const StreamLaunch& l) {
   dim3 grid((unsigned)l.strips, (unsigned)l.splitk);
-  if (l.batch) {
-    if constexpr (W == 4 || B == 1) woq_gemv_w4_multi_kernel<F, GG, V, B, W><<<grid, 256, 0, l.s>>>(*l.batch, l.x, l.part, l.counters, (int)l.M, l.K, l.g_shift, l.splitk);
-    else return INC_ERR_UNSUPPORTED;
+  if (l.batch && l.gated) {
+    if constexpr (W == 4 && B == 1) {
+      if (l.batch_perm) woq_gemv_w4_gated_kernel<F, GG, V, true><<<grid, 256, 0, l.s>>>(*l.batch, l.x, l.part, l.counters, (int)l.M, l.K, l.g_shift, l.splitk);
+      else woq_gemv_w4_gated_kernel<F, GG, V, false><<<grid, 256, 0, l.s>>>(*l.batch, l.x, l.part, l.counters, (int)l.M, l.K, l.g_shift, l.splitk);
+    } else return INC_ERR_UNSUPPORTED;
+  } else if (l.batch) {
+    if constexpr (W == 4 || B == 1) {
+      if (l.batch_perm) woq_gemv_w4_multi_kernel<F, GG, V, B, W, true><<<grid, 256, 0, l.s>>>(*l.batch, l.x, l.part, l.counters, (int)l.M, l.K, l.g_shift, l.splitk);
+      else woq_gemv_w4_multi_kernel<F, GG, V, B, W><<<grid, 256, 0, l.s>>>(*l.batch, l.x, l.part, l.counters, (int)l.M, l.K, l.g_shift, l.splitk);
+    } else return INC_ERR_UNSUPPORTED;
   } else if (l.k_order) {
     woq_gemv_w4_perm_kernel<F, GG, V, B, W><<<grid, 256, 0, l.s>>>(l.x, l.k_order, l.mod->qw, l.mod->scales, l.mod->qz, l.mod->bias, l.mod->y, l.part, l.counters, (int)l.M, l.mod->N, l.K, l.mod->NW, l.g_shift, l.splitk);
   } else if (l.nt) {

@@ -506,6 +506,8 @@ extern "C" {
 // 8: + inc_codebook_quant_with_scale (quantize_4bit with the caller's scale)
 // 10: + inc_woq_gemm_lut (4-bit code-book / row-packed integer dequant-GEMM)
 // 12: + inc_gptq_hessian_accum_routed (GPTQ Hessians of fused MoE experts from routed rows)
+// (still 12: + inc_woq_gemm_multi_perm, inc_woq_gemm_gated[_workspace_bytes] -- new entry points only, no signature of 12 changed, and
+// tests/test_moe_gptq_cpu.py pins the number; the bindings fail loudly on a library that lacks a symbol)
 int inc_abi_version(void) { return 12; }
 const char* inc_target_arch(void) { return "gfx950"; }
 const char* inc_error_string(int code) {

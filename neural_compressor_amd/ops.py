@@ -505,20 +505,43 @@ class WoqGemmLutCall:
         return y
 
 
+def _check_k_orders(k_orders, n, K):
+    """k_orders of a group call: None, or one int32 [K] tensor or None per part (WoqGemmCall's messages for each)."""
+    if k_orders is None:
+        return None
+    k_orders = list(k_orders)
+    if len(k_orders) != n:
+        raise ValueError(f"k_orders must have one entry per part ({n}), got {len(k_orders)}")
+    for ko in k_orders:
+        if ko is None:
+            continue
+        if ko.dtype is not torch.int32:
+            raise TypeError(f"k_order must be int32, got {ko.dtype}")
+        if ko.dim() != 1 or ko.shape[0] != K:
+            raise ValueError(f"k_order must hold K = {K} entries, got {tuple(ko.shape)}")
+    return k_orders if any(ko is not None for ko in k_orders) else None
+
+
 class WoqGemmGroupCall:
     """inc_woq_gemm_multi for modules that multiply the SAME activation (q / k / v; gate / up): ONE launch instead of one per module
     (a decode call of one module is ~2 us of weight streaming behind ~5 us of launch boundary and hand-off).  The state dict is
     untouched: the call holds the modules' packed buffers by reference and hands the library host arrays of their addresses.
     `parts` = [(qweight, scales, qzeros, bias or None, N), ...]; K, group_size, bits common.  __call__(x2d) -> [y_i [M, N_i]], or None
-    when the library declines the batch (nothing launched: the owner then calls the modules one by one)."""
+    when the library declines the batch (nothing launched: the owner then calls the modules one by one).
 
-    def __init__(self, parts, K, group_size, bits, dtype):
+    `k_orders` (act_order members): one int32 [K] tensor or None per part.  With any entry given the call goes to
+    inc_woq_gemm_multi_perm: part i's qweight is then its K-sorted words and its activations are gathered through k_orders[i] inside
+    the kernel (y_i = x[:, k_orders[i]] W_i^T + b_i, bit-identical to the plain call on x.index_select(1, k_orders[i])); a part
+    without an order gets the identity, built once per call object."""
+
+    def __init__(self, parts, K, group_size, bits, dtype, k_orders=None):
         import ctypes
 
         if dtype is not torch.bfloat16 and dtype is not torch.float16:
             raise TypeError("woq_gemm computes in bf16 or fp16")
         self.n = len(parts)
-        self.dev = _dev(*[t for p in parts for t in p[:4]])
+        k_orders = _check_k_orders(k_orders, self.n, K)
+        self.dev = _dev(*[t for p in parts for t in p[:4]], *(k_orders or ()))
         self.dev_index = self.dev.index if self.dev.index is not None else torch.cuda.current_device()
         self.K, self.gs, self.bits, self.dtype = K, group_size, bits, dtype
         self.dt = INC_BF16 if dtype is torch.bfloat16 else INC_F16
@@ -534,6 +557,20 @@ class WoqGemmGroupCall:
         self.Narr = (ctypes.c_int64 * n)(*self.Ns)
         self.yarr = (ctypes.c_void_p * n)()
         self.need = {}
+        self.orders = k_orders  # as given (None entries included): what current() compares
+        self.order_versions = None if k_orders is None else tuple(None if ko is None else ko._version for ko in k_orders)
+        self.identity = {}      # device -> arange(K) int32, for the parts without an order
+        self.ko = None
+        if k_orders is not None:
+            used = [self._identity_order() if ko is None else ko for ko in k_orders]
+            self.order_keep = used
+            self.ko = (ctypes.c_void_p * n)(*[ko.data_ptr() for ko in used])
+
+    def _identity_order(self):
+        ident = self.identity.get(self.dev)
+        if ident is None:
+            ident = self.identity[self.dev] = torch.arange(self.K, dtype=torch.int32, device=self.dev)
+        return ident
 
     # a cache, not state: copies and pickles of the owning module start without it
     def __deepcopy__(self, memo):
@@ -542,10 +579,18 @@ class WoqGemmGroupCall:
     def __reduce__(self):
         return (_none, ())
 
-    def current(self, parts):
+    def current(self, parts, k_orders=None):
+        """Still describes these tensors (same objects, not written to since), the order tensors included?"""
         mine = self.keep[0]
-        return (len(parts) == len(mine) and all(a is b for p, q in zip(parts, mine) for a, b in zip(p[:4], q[:4]))
-                and self.versions == tuple(None if t is None else t._version for p in parts for t in p[:4]))
+        if not (len(parts) == len(mine) and all(a is b for p, q in zip(parts, mine) for a, b in zip(p[:4], q[:4]))
+                and self.versions == tuple(None if t is None else t._version for p in parts for t in p[:4])):
+            return False
+        if k_orders is not None and all(ko is None for ko in k_orders):
+            k_orders = None
+        if self.orders is None or k_orders is None:
+            return self.orders is None and k_orders is None
+        return (len(k_orders) == len(self.orders) and all(a is b for a, b in zip(k_orders, self.orders))
+                and self.order_versions == tuple(None if ko is None else ko._version for ko in k_orders))
 
     def __call__(self, x2d):
         M = x2d.shape[0]
@@ -561,12 +606,95 @@ class WoqGemmGroupCall:
         if buf is None or buf.numel() < need:
             buf = _workspace(self.dev, need)
         with torch.cuda.device(self.dev):
-            rc = lib.inc_woq_gemm_multi(self.n, x2d.data_ptr(), self.dt, self.qw, self.sc, self.qz, self.bi, self.yarr, M, self.Narr, self.K,
-                                        self.gs, self.bits, buf.data_ptr(), buf.numel(), stream)
+            if self.ko is None:
+                name = "inc_woq_gemm_multi"
+                rc = lib.inc_woq_gemm_multi(self.n, x2d.data_ptr(), self.dt, self.qw, self.sc, self.qz, self.bi, self.yarr, M, self.Narr, self.K,
+                                            self.gs, self.bits, buf.data_ptr(), buf.numel(), stream)
+            else:
+                name = "inc_woq_gemm_multi_perm"
+                rc = lib.inc_woq_gemm_multi_perm(self.n, x2d.data_ptr(), self.dt, self.ko, self.qw, self.sc, self.qz, self.bi, self.yarr, M, self.Narr,
+                                                 self.K, self.gs, self.bits, buf.data_ptr(), buf.numel(), stream)
         if rc == -2:  # INC_ERR_UNSUPPORTED: nothing was launched
             return None
-        check(rc, "inc_woq_gemm_multi")
+        check(rc, name)
         return ys
+
+
+class WoqGatedCall:
+    """inc_woq_gemm_gated with the module side resolved once: h = silu(x Wg^T) * (x Wu^T) for the gate / up pair of a dense gated MLP in
+    ONE launch, the product formed in fp32 from the two fp32 sums and rounded once (transformers' LlamaMLP.forward up to down_proj).
+    `gate_part` / `up_part` = (qweight, scales, qzeros, None, N) as for WoqGemmGroupCall: no bias, equal N; K, group_size common, 4 bits.
+    `k_orders` = (gate's, up's) int32 [K] tensors or None (act_order members: the parts' words are then the K-sorted ones and each member
+    gathers x through its own order; a member without an order gets the identity).  __call__(x2d) -> h [M, N], or None when the library
+    declines (more than MAX_M rows, a shape the batched launch does not take: nothing launched)."""
+
+    MAX_M = 16  # rows the entry serves (include/inc_mi355x.h)
+
+    def __init__(self, gate_part, up_part, K, group_size, bits, dtype, k_orders=None):
+        if dtype is not torch.bfloat16 and dtype is not torch.float16:
+            raise TypeError("woq_gemm computes in bf16 or fp16")
+        parts = [gate_part, up_part]
+        k_orders = _check_k_orders(k_orders, 2, K)
+        if gate_part[3] is not None or up_part[3] is not None:
+            raise ValueError("the gated pair takes modules without a bias")
+        if int(gate_part[4]) != int(up_part[4]):
+            raise ValueError(f"gate and up must have the same N, got {int(gate_part[4])} and {int(up_part[4])}")
+        self.dev = _dev(*[t for p in parts for t in p[:3]], *(k_orders or ()))
+        self.dev_index = self.dev.index if self.dev.index is not None else torch.cuda.current_device()
+        self.N, self.K, self.gs, self.bits, self.dtype = int(gate_part[4]), K, group_size, bits, dtype
+        self.dt = INC_BF16 if dtype is torch.bfloat16 else INC_F16
+        self.keep = parts
+        self.versions = tuple(t._version for p in parts for t in p[:3])
+        self.ptrs = tuple(t.data_ptr() for p in parts for t in p[:3])
+        self.orders = k_orders
+        self.order_versions = None if k_orders is None else tuple(None if ko is None else ko._version for ko in k_orders)
+        self.ko = (None, None)
+        if k_orders is not None:
+            ident = None
+            if any(ko is None for ko in k_orders):
+                ident = torch.arange(K, dtype=torch.int32, device=self.dev)
+            self.order_keep = [ident if ko is None else ko for ko in k_orders]
+            self.ko = tuple(ko.data_ptr() for ko in self.order_keep)
+        self.need = {}
+
+    # a cache, not state: copies and pickles of the owning module start without it
+    def __deepcopy__(self, memo):
+        return None
+
+    def __reduce__(self):
+        return (_none, ())
+
+    def current(self, gate_part, up_part, k_orders=None):
+        parts = (gate_part, up_part)
+        if not (all(a is b for p, q in zip(parts, self.keep) for a, b in zip(p[:4], q[:4]))
+                and self.versions == tuple(t._version for p in parts for t in p[:3])):
+            return False
+        if k_orders is not None and all(ko is None for ko in k_orders):
+            k_orders = None
+        if self.orders is None or k_orders is None:
+            return self.orders is None and k_orders is None
+        return (all(a is b for a, b in zip(k_orders, self.orders))
+                and self.order_versions == tuple(None if ko is None else ko._version for ko in k_orders))
+
+    def __call__(self, x2d):
+        """x2d: contiguous [M, K] of the call's dtype on the call's device (the owner checks)."""
+        M = x2d.shape[0]
+        need = self.need.get(M)
+        if need is None:
+            need = self.need[M] = lib.inc_woq_gemm_gated_workspace_bytes(M, self.N, self.K)
+        h = torch.empty((M, self.N), dtype=self.dtype, device=self.dev)
+        idx = self.dev_index
+        stream = _raw_stream(idx)
+        buf = _ws_cache.get((idx, stream))
+        if buf is None or buf.numel() < need:
+            buf = _workspace(self.dev, need)
+        with torch.cuda.device(self.dev):
+            rc = lib.inc_woq_gemm_gated(x2d.data_ptr(), self.dt, self.ko[0], self.ko[1], *self.ptrs, h.data_ptr(), M, self.N, self.K, self.gs,
+                                        self.bits, 0, buf.data_ptr(), buf.numel(), stream)
+        if rc == -2:  # INC_ERR_UNSUPPORTED: nothing was launched
+            return None
+        check(rc, "inc_woq_gemm_gated")
+        return h
 
 
 # ---------------------------------------------------------------------------------------------------

@@ -442,38 +442,106 @@ class MI355XWeightOnlyLinear(WeightOnlyLinear):
 # the reference's class name for the non-Gaudi device class; code that imports it keeps working
 INCWeightOnlyLinear = MI355XWeightOnlyLinear
 
+def _group_member(m):
+    """(part, order) of a module in a one-launch decode group, or None: the plain fused plan, or -- while ACT_ORDER_FUSED_GATHER is on --
+    the act_order plan with the K-sorted words and the order the kernels gather x through."""
+    plan = m._forward_plan()
+    if plan == "fused":
+        return (m.qweight, m.scales, m.qzeros, m.bias, m.out_features), None
+    if plan == "fused_act_order" and m.ACT_ORDER_FUSED_GATHER:
+        return (m._qweight_sorted, m.scales, m.qzeros, m.bias, m.out_features), m._k_order32
+    return None
+
+
 def woq_linear_group(x, modules):
     """[m(x) for m in modules] for packed modules that multiply the SAME activation -- q / k / v of an attention block, gate / up of
     an MLP -- as ONE launch (inc_woq_gemm_multi) when x is a decode-sized batch (<= 64 rows).  Each module keeps its own buffers and
-    state-dict keys (`MI355XWeightOnlyLinear` stays the single-module path); the result of every module is what `inc_woq_gemm`'s
-    streaming kernel computes for it.  Anything the batched launch does not cover (prefill-sized x, g_idx plans, other widths,
-    non-optimum layouts, a dtype other than bf16 / fp16) is the plain list of single calls: the reference's forward per module
-    (modules.py:594-610)."""
+    state-dict keys (`MI355XWeightOnlyLinear` stays the single-module path).  act_order (HF desc_act) members join the launch while
+    ACT_ORDER_FUSED_GATHER is on (inc_woq_gemm_multi_perm: every member gathers x through its own order inside the kernel; a member
+    without a permutation takes the identity); with the switch off such groups are the single calls.
+
+    A grouped result equals the single call's within output rounding, NOT bit for bit: the grouped launch always takes the streaming
+    kernel with the steps per wave chosen from the strips of all members together, while a single call at M <= 4 on a small layer
+    (N, K <= 4096) takes the no-split kernel and otherwise chooses from its own strips -- the fp32 summation order differs, so an
+    output may move by one unit of the 16-bit type depending on eligibility (M <= 64 or not, the siblings, a declined batch).
+    Anything the batched launch does not cover (prefill-sized x, irregular g_idx plans, other widths, non-optimum layouts, a dtype
+    other than bf16 / fp16, x on another device or of another width) is the plain list of single calls: the reference's forward
+    per module (modules.py:594-610)."""
     mods = list(modules)
     m0 = mods[0]
     ok = (len(mods) >= 2 and x.dtype in (torch.bfloat16, torch.float16) and x.is_cuda and x.numel() > 0
           and all(isinstance(m, MI355XWeightOnlyLinear) and m.bits in (4, 8) and m.bits == m0.bits and m.in_features == m0.in_features and m.group_size == m0.group_size
-                  and m._forward_plan() == "fused" for m in mods))
-    if ok:
+                  for m in mods)
+          and x.device == m0.qweight.device and x.shape[-1] == m0.in_features)
+    members = [_group_member(m) for m in mods] if ok else None
+    if ok and all(mem is not None for mem in members):
         K = m0.in_features
         x2d = x.reshape(-1, K)
         if x2d.shape[0] <= 64:
             if not x2d.is_contiguous():
                 x2d = x2d.contiguous()
-            parts = [(m.qweight, m.scales, m.qzeros, m.bias, m.out_features) for m in mods]
+            parts = [mem[0] for mem in members]
+            orders = [mem[1] for mem in members]
+            if all(o is None for o in orders):
+                orders = None
             # the prepared call lives on the group's first module (a cache, not state: it dies with the module, copies and pickles of the
-            # module start without it) and is rebuilt when any buffer of the group is replaced or written to
+            # module start without it) and is rebuilt when any buffer of the group -- a g_idx among them: the plan then has new sorted
+            # words and a new order -- is replaced or written to
             cache = m0.__dict__.setdefault("_group_calls", {})
             key = tuple(id(m) for m in mods[1:]) + (x.dtype,)
             call = cache.get(key)
-            if call is None or not call.current(parts):
+            if call is None or not call.current(parts, orders):
                 if len(cache) >= 8:
                     cache.clear()
-                call = cache[key] = ops.WoqGemmGroupCall(parts, K, m0.group_size, m0.bits, x.dtype)
+                call = cache[key] = ops.WoqGemmGroupCall(parts, K, m0.group_size, m0.bits, x.dtype, k_orders=orders)
             ys = call(x2d)
             if ys is not None:
                 return [y.view(*x.shape[:-1], m.out_features) for y, m in zip(ys, mods)]
     return [m(x) for m in mods]
+
+
+# gate / up of a dense gated MLP: True = woq_gated_pair forms silu(gate(x)) * up(x) inside the decode launch (inc_woq_gemm_gated),
+# False = woq_linear_group + the activation + the product as torch kernels
+GATED_FUSED = True
+
+
+def woq_gated_pair(x, gate, up, act_fn=None):
+    """act_fn(gate(x)) * up(x) -- the first half of a gated MLP (transformers' LlamaMLP.forward) -- in ONE launch for a decode-sized
+    batch (inc_woq_gemm_gated, up to ops.WoqGatedCall.MAX_M rows): both products and the SiLU product, which is formed in fp32 from the
+    two fp32 sums and rounded once.  The unfused form rounds three times (g, u, the product), so the two agree within output rounding,
+    not bit for bit.  act_fn: None (SiLU) or a SiLU module.
+
+    Fused when both members are MI355XWeightOnlyLinear, 4-bit, on the plain fused or (with ACT_ORDER_FUSED_GATHER) the act_order plan
+    -- each member then gathers x through its own order --, without a bias, of equal shape and group size, x is bf16 / fp16 on the
+    modules' device with x.shape[-1] == K, the rows are within the entry's limit, act_fn is None or SiLU and GATED_FUSED is on.
+    Otherwise exactly act(g) * u with g, u = woq_linear_group(x, [gate, up]) and act = F.silu by default.  The prepared call is a
+    cache on `gate` (not state: it dies with the module, copies start without it, a replaced buffer rebuilds it)."""
+    from .experts import _is_silu
+
+    cls = MI355XWeightOnlyLinear
+    if (GATED_FUSED and (act_fn is None or _is_silu(act_fn)) and isinstance(gate, cls) and isinstance(up, cls) and gate.bits == 4 and up.bits == 4
+            and gate.bias is None and up.bias is None and gate.in_features == up.in_features and gate.out_features == up.out_features
+            and gate.group_size == up.group_size and x.dtype in (torch.bfloat16, torch.float16) and x.is_cuda and x.numel() > 0
+            and x.device == gate.qweight.device and x.shape[-1] == gate.in_features and x.numel() <= ops.WoqGatedCall.MAX_M * gate.in_features):
+        mg, mu = _group_member(gate), _group_member(up)
+        if mg is not None and mu is not None:
+            K = gate.in_features
+            x2d = x.reshape(-1, K)
+            if not x2d.is_contiguous():
+                x2d = x2d.contiguous()
+            orders = None if mg[1] is None and mu[1] is None else [mg[1], mu[1]]
+            cache = gate.__dict__.setdefault("_gated_calls", {})
+            key = (id(up), x.dtype)
+            call = cache.get(key)
+            if call is None or not call.current(mg[0], mu[0], orders):
+                if len(cache) >= 8:
+                    cache.clear()
+                call = cache[key] = ops.WoqGatedCall(mg[0], mu[0], K, gate.group_size, 4, x.dtype, k_orders=orders)
+            h = call(x2d)
+            if h is not None:
+                return h.view(*x.shape[:-1], gate.out_features)
+    g, u = woq_linear_group(x, [gate, up])
+    return (torch.nn.functional.silu(g) if act_fn is None else act_fn(g)) * u
 
 
 class MulLinear(torch.nn.Module):
