@@ -234,6 +234,27 @@ int inc_woq_gemm_gated(const void* x, int xdtype, const int32_t* k_order_gate, c
                        const int32_t* up_qzeros, void* h, int64_t M, int64_t N, int64_t K, int group_size, int bits, int act,
                        void* workspace, int64_t workspace_bytes, inc_stream_t stream);
 
+/* ---- K4f: decode GEMV of the 1 / 2 / 3 / 5 / 6 / 7-bit optimum-layout modules -------------- *
+ * == INCWeightOnlyLinear.forward (modules.py:594-610) for up to 16 rows of x: y = x . W^T + bias with W[n,k] = rn16(int8(q - zp) * scale)
+ *   rounded once to xdtype (bit-identical to inc_woq_dequant), fp32 accumulation, the dense weight never materialised
+ *   (csrc/gemm_anyw.hip).  inc_woq_gemm keeps INC_WOQ_ROUTE_TILE_ANYW for these widths; this entry is the decode route.
+ *     qweight [ceil(K / n_pack), N] int32, n_pack = 32 / bits: word w of column n holds k = n_pack * w .. in fields of `bits` bits from bit 0
+ *       (fields at k >= K in the last word are padding: they contribute nothing and x is never read at or beyond column K);
+ *     scales [G, N] fp16; qzeros [G, ceil(N / n_pack)] int32 packed along N, stored field = zp - 1 (z = field + 1, above 2^bits - 1 -> 0);
+ *     groups are contiguous, looked up per field (g = k / group_size: a word may straddle two groups); bias [N] of xdtype or NULL.
+ *   INC_ERR_UNSUPPORTED (nothing launched) unless bits is 1, 2, 3, 5, 6 or 7; xdtype INC_BF16 / INC_F16; 1 <= M <= 16; K % 32 == 0;
+ *     N % 4 == 0, N >= 64; group_size a power of two >= 32 or one group per row (-1 or >= K; a ragged last group is allowed:
+ *     G = ceil(K / group_size)); x, y, qweight 16-byte and scales 8-byte aligned.  INC_ERR_BAD_ARG for a G that does not match.
+ *   Split-K over inc_woq_gemv_anyw_slices(M, N, K, bits) K-slices (0 for a shape the entry declines) with a fixed-order sum:
+ *     repeated calls are bit-identical.  `workspace`: inc_woq_gemv_anyw_workspace_bytes bytes (0 where one slice suffices: workspace may
+ *     be NULL then; INC_ERR_WORKSPACE for less than a split needs); its first 16 KiB are arrival counters with the rules of inc_woq_gemm's
+ *     (zero on first use, re-armed by the kernel), so one (device, stream) workspace serves this and the inc_woq_gemm* entries in turn. */
+int inc_woq_gemv_anyw_slices(int64_t M, int64_t N, int64_t K, int bits);
+int64_t inc_woq_gemv_anyw_workspace_bytes(int64_t M, int64_t N, int64_t K, int bits);
+int inc_woq_gemv_anyw(const void* x, int xdtype, const int32_t* qweight, const uint16_t* scales, const int32_t* qzeros, const void* bias,
+                      void* y, int64_t M, int64_t N, int64_t K, int64_t G, int group_size, int bits, void* workspace,
+                      int64_t workspace_bytes, inc_stream_t stream);
+
 /* ---- K4d: fused 4-bit code-book / row-packed integer dequant + GEMM ------------------------ *
  * == INCWeightOnlyLinear.forward (modules.py:594-610) for the layouts that are not the optimum one: F.linear(x, recover(x.dtype), bias)
  *   with recover (modules.py:413-443) done in registers, the dense weight never materialised.  NF4 / FP4 code books and integer

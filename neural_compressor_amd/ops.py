@@ -202,9 +202,16 @@ def _workspace(dev, nbytes):
     if buf is None or buf.numel() < nbytes:
         # zero-filled: the first 16 KiB are the split-K arrival counters of the M <= 16 kernel, which must be zero on
         # first use (the kernel re-arms them); one workspace per (device, stream) so concurrent streams never share them
+        if buf is not None:
+            # the outgrown buffer stays allocated: a captured graph (or a launch in flight) may still hold its address, and a replay
+            # into freed memory is an illegal access.  Growth is rare (sizes are per shape) and the buffers are a few MB.
+            _ws_retired.append(buf)
         buf = torch.zeros(max(nbytes, 1 << 20), dtype=torch.uint8, device=dev)
         _ws_cache[key] = buf
     return buf
+
+
+_ws_retired = []
 
 
 _ws_bytes_cache = {}
@@ -332,6 +339,7 @@ class WoqGemmCall:
     __slots__ = ("dev", "dev_index", "dtype", "dt", "N", "K", "G", "gs", "bits", "qw", "sc", "qz", "gi", "bi", "keep", "need", "fn",
                  "bias_conv", "versions", "tag", "ko", "perm_keep", "perm_versions", "perm_ok")
     lut = False  # (WoqGemmLutCall: True)
+    anyw = False  # (WoqGemvAnywCall: True)
     PERM_ROUTES = (9, 10, 11)  # GEMV16, STREAM_W4, STREAM_W8: the routes inc_woq_gemm_perm launches
 
     def __init__(self, qweight, scales, qzeros, bias, N, K, group_size, bits, dtype, g_idx=None, k_order=None, owner_qweight=None):
@@ -422,6 +430,163 @@ class WoqGemmCall:
         return y
 
 
+GEMV_ANYW_BITS = (1, 2, 3, 5, 6, 7)
+GEMV_ANYW_MAX_M = 16
+
+
+def gemv_anyw_takes(N, K, group_size, bits):
+    """inc_woq_gemv_anyw takes a module of this shape (for 1 .. 16 rows of bf16 / fp16 x)?  Pure arithmetic, no library call."""
+    gs = K if (group_size == -1 or group_size >= K) else group_size
+    return (bits in GEMV_ANYW_BITS and K > 0 and K % 32 == 0 and K <= 1 << 30 and N >= 64 and N % 4 == 0 and N <= 1 << 18
+            and (gs == K or (gs >= 32 and gs & (gs - 1) == 0)))
+
+
+def _gemv_anyw_check_module(qweight, scales, qzeros, bias, N, K, group_size, bits):
+    """The module side of woq_gemv_anyw's argument checks: ValueError before anything touches the device."""
+    if bits not in GEMV_ANYW_BITS:
+        raise ValueError(f"woq_gemv_anyw: bits={bits}; it serves 1, 2, 3, 5, 6 and 7 bits (4 and 8 bits are woq_gemm's)")
+    if K <= 0 or K % 32 != 0 or K > 1 << 30:
+        raise ValueError(f"woq_gemv_anyw: K={K} must be a positive multiple of 32 (at most 2^30)")
+    if N < 64 or N % 4 != 0 or N > 1 << 18:
+        raise ValueError(f"woq_gemv_anyw: N={N} must be a multiple of 4, at least 64 (at most 2^18)")
+    gs = K if (group_size == -1 or group_size >= K) else group_size
+    if gs != K and (gs < 32 or gs & (gs - 1) != 0):
+        raise ValueError(f"woq_gemv_anyw: group_size={group_size} must be a power of two >= 32, or one group per row (-1 / >= K)")
+    n_pack, G = 32 // bits, -(-K // gs)
+    want = {"qweight": ((-(-K // n_pack), N), torch.int32), "scales": ((G, N), torch.float16), "qzeros": ((G, -(-N // n_pack)), torch.int32)}
+    for name, t in (("qweight", qweight), ("scales", scales), ("qzeros", qzeros)):
+        shape, dt = want[name]
+        if tuple(t.shape) != shape or t.dtype is not dt:
+            raise ValueError(f"woq_gemv_anyw: {name} must be {dt} {list(shape)}, got {t.dtype} {list(t.shape)}")
+    if bias is not None and tuple(bias.shape) != (N,):
+        raise ValueError(f"woq_gemv_anyw: bias must be [{N}], got {list(bias.shape)}")
+    for name, t in (("qweight", qweight), ("scales", scales), ("qzeros", qzeros), ("bias", bias)):
+        if t is None:
+            continue
+        if t.device.type != "cuda":
+            raise ValueError(f"woq_gemv_anyw: {name} is on {t.device}; tensors must be resident in HBM (device 'cuda' = HIP)")
+        if t.device != qweight.device:
+            raise ValueError(f"woq_gemv_anyw: tensors on different devices: {qweight.device} vs {t.device}")
+        if not t.is_contiguous():
+            raise ValueError(f"woq_gemv_anyw: {name} must be contiguous")
+    return G
+
+
+def _gemv_anyw_check_x_shape(x2d, K):
+    if x2d.dtype is not torch.bfloat16 and x2d.dtype is not torch.float16:
+        raise ValueError(f"woq_gemv_anyw computes in bf16 or fp16, got {x2d.dtype}")
+    if x2d.dim() != 2 or x2d.shape[1] != K:
+        raise ValueError(f"woq_gemv_anyw: x must be [M, {K}], got {list(x2d.shape)}")
+    if not 1 <= x2d.shape[0] <= GEMV_ANYW_MAX_M:
+        raise ValueError(f"woq_gemv_anyw: M={x2d.shape[0]}; it serves 1 .. {GEMV_ANYW_MAX_M} rows")
+
+
+def _gemv_anyw_check_x(x2d, K, dtype, dev):
+    _gemv_anyw_check_x_shape(x2d, K)
+    if x2d.dtype is not dtype:
+        raise ValueError(f"woq_gemv_anyw: x is {x2d.dtype}, the call computes in {dtype}")
+    if x2d.device != dev:
+        raise ValueError(f"woq_gemv_anyw: x is on {x2d.device}, the weights on {dev}")
+    if not x2d.is_contiguous():
+        raise ValueError("woq_gemv_anyw: x must be contiguous")
+
+
+def woq_gemv_anyw(x2d, qweight, scales, qzeros, bias, N, K, group_size, bits):
+    """y[M,N] = x[M,K] @ recover(x.dtype)^T + bias for 1 <= M <= 16 rows and an optimum-layout module of 1, 2, 3, 5, 6 or 7 bits, in
+    one launch that streams the packed words once (inc_woq_gemv_anyw; == INCWeightOnlyLinear.forward, modules.py:594-610).
+
+    qweight [ceil(K / n_pack), N] int32, scales [G, N] fp16, qzeros [G, ceil(N / n_pack)] int32 (n_pack = 32 // bits), contiguous
+    groups of a power of two >= 32 (or one per row; a ragged last group is fine), K % 32 == 0, N % 4 == 0, N >= 64, x bf16 / fp16.
+    Everything else raises ValueError before any launch."""
+    if bits not in GEMV_ANYW_BITS:
+        raise ValueError(f"woq_gemv_anyw: bits={bits}; it serves 1, 2, 3, 5, 6 and 7 bits (4 and 8 bits are woq_gemm's)")
+    _gemv_anyw_check_x_shape(x2d, K)
+    return WoqGemvAnywCall(qweight, scales, qzeros, bias, N, K, group_size, bits, x2d.dtype)(x2d, checked=False)
+
+
+class WoqGemvAnywCall:
+    """inc_woq_gemv_anyw with the module side resolved once (the decode path of the odd widths, like WoqGemmCall): data pointers, the
+    bias converted to the compute dtype, the K-slices per M.  Per call only x, y, the stream and the workspace are looked up.
+    `current()` has WoqGemmCall's contract (same tensors, version counters unchanged).
+
+    The workspace is the (device, stream) one the other calls use (its counters are zero between launches), asked for 16 rows from the
+    first call on so that a change of M does not move it; when it grows, the outgrown buffer is kept (_workspace), so a captured graph
+    that replays the call never meets a freed workspace."""
+
+    __slots__ = ("dev", "dev_index", "dtype", "dt", "N", "K", "G", "gs", "bits", "qw", "sc", "qz", "bi", "keep", "versions", "bias_conv",
+                 "need", "tag")
+    lut = False
+    anyw = True
+    ko = None
+    MAX_M = GEMV_ANYW_MAX_M
+
+    def __init__(self, qweight, scales, qzeros, bias, N, K, group_size, bits, dtype):
+        if dtype is not torch.bfloat16 and dtype is not torch.float16:
+            raise ValueError(f"woq_gemv_anyw computes in bf16 or fp16, got {dtype}")
+        self.G = _gemv_anyw_check_module(qweight, scales, qzeros, bias, N, K, group_size, bits)
+        if qweight.data_ptr() % 16:
+            raise ValueError("woq_gemv_anyw: qweight must be 16-byte aligned")
+        self.keep = (qweight, scales, qzeros, bias)
+        self.versions = tuple(None if t is None else t._version for t in self.keep)
+        if bias is not None and bias.dtype != dtype:
+            bias = bias.to(dtype)  # converted once (the packed module stores fp16, a bf16 model multiplies in bf16)
+        self.bias_conv = bias
+        dev = qweight.device
+        self.dev, self.dev_index, self.dtype = dev, dev.index if dev.index is not None else torch.cuda.current_device(), dtype
+        self.dt = INC_BF16 if dtype is torch.bfloat16 else INC_F16
+        self.N, self.K, self.gs, self.bits = N, K, group_size, bits
+        self.qw, self.sc, self.qz, self.bi = qweight.data_ptr(), scales.data_ptr(), qzeros.data_ptr(), _ptr(bias)
+        self.need = None
+        self.tag = (None, None)  # (the owner's g_idx buffer, its version) when the owner found the module eligible
+
+    # a cache, not state: copies and pickles of the owning module start without it
+    def __deepcopy__(self, memo):
+        return None
+
+    def __reduce__(self):
+        return (_none, ())
+
+    def current(self, qweight, scales, qzeros, bias, owner_g_idx=None):
+        k, v = self.keep, self.versions
+        return (k[0] is qweight and k[1] is scales and k[2] is qzeros and k[3] is bias and qweight._version == v[0]
+                and scales._version == v[1] and qzeros._version == v[2] and (bias is None or bias._version == v[3])
+                and self.tag[0] is owner_g_idx and (owner_g_idx is None or owner_g_idx._version == self.tag[1]))
+
+    def slices(self, M):
+        """K-slices of the launch for M rows (inc_woq_gemv_anyw_slices: host only)."""
+        return lib.inc_woq_gemv_anyw_slices(M, self.N, self.K, self.bits)
+
+    def __call__(self, x2d, checked=True):
+        """x2d: contiguous [M, K], 1 <= M <= 16, of the call's dtype on the call's device (`checked`: the owner has made sure)."""
+        if not checked:
+            _gemv_anyw_check_x(x2d, self.K, self.dtype, self.dev)
+        M = x2d.shape[0]
+        if x2d.data_ptr() % 16:
+            x2d = x2d.clone()  # the kernel reads x in 16-byte pieces; a fresh allocation is aligned
+        y = torch.empty((M, self.N), dtype=self.dtype, device=self.dev)
+        need = self.need
+        if need is None:
+            need = self.need = lib.inc_woq_gemv_anyw_workspace_bytes(self.MAX_M, self.N, self.K, self.bits)
+        idx = self.dev_index
+        stream = _raw_stream(idx)
+        wp, wn = None, 0
+        if need > 0:
+            buf = _ws_cache.get((idx, stream))
+            if buf is None or buf.numel() < need:
+                buf = _workspace(self.dev, need)
+            wp, wn = buf.data_ptr(), buf.numel()
+        args = (x2d.data_ptr(), self.dt, self.qw, self.sc, self.qz, self.bi, y.data_ptr(), M, self.N, self.K, self.G, self.gs, self.bits,
+                wp, wn, stream)
+        if _cur_device() == idx:
+            rc = lib.inc_woq_gemv_anyw(*args)
+        else:
+            with torch.cuda.device(self.dev):
+                rc = lib.inc_woq_gemv_anyw(*args)
+        if rc != 0:
+            check(rc, "inc_woq_gemv_anyw")
+        return y
+
+
 def woq_gemm_lut(x2d, qweight, table16, scales, qzeros, bias, N, K, group_size, scale_round):
     """y[M,N] = x[M,K] @ recover(x.dtype)^T + bias for 4-bit row-packed modules (NF4 / FP4 code books, integer modules with
     use_optimum_format=False, compression_dim = 1), fused (include/inc_mi355x.h: inc_woq_gemm_lut; reference modules.py:594-610).
@@ -438,6 +603,7 @@ class WoqGemmLutCall:
     `current()` has WoqGemmCall's contract (same tensors, version counters unchanged)."""
 
     lut = True
+    anyw = False
     ko = None  # (WoqGemmCall: the act_order gather)
 
     def __init__(self, qweight, table16, scales, qzeros, bias, N, K, group_size, scale_round, dtype):

@@ -283,7 +283,9 @@ class MI355XWeightOnlyLinear(WeightOnlyLinear):
             bufs = self._buffers
             if (call.current(bufs["qweight"], bufs["scales"], bufs.get("qzeros"), bufs.get("bias", d.get("bias")), bufs.get("g_idx", d.get("g_idx")))
                     and (not call.lut or (self.LUT_FUSED and x.numel() <= self.LUT_MAX_M * call.K))
-                    and (call.ko is None or self.ACT_ORDER_FUSED_GATHER)):
+                    and (call.ko is None or self.ACT_ORDER_FUSED_GATHER)
+                    and (not call.anyw or (self.ODD_WIDTH_DECODE and not self.ODD_WIDTH_FUSED
+                                           and x.numel() <= min(self.ODD_WIDTH_DECODE_MAX_M, call.MAX_M) * call.K))):
                 y = call(x if x.dim() == 2 else x.view(-1, call.K))
                 return y if x.dim() == 2 else y.view(*x.shape[:-1], call.N)
         if x.dtype not in (torch.bfloat16, torch.float16):
@@ -300,7 +302,16 @@ class MI355XWeightOnlyLinear(WeightOnlyLinear):
             plan = "dense"  # (a group size the fast kernels do not take: see _forward_plan)
         if plan == "fused_lut" and x2d.shape[0] > self.LUT_MAX_M:
             plan = "dense"  # (prefill-sized batches: see LUT_MAX_M)
-        if plan == "fused" and self._fused_max_m is not None:
+        if (plan == "dense" and self._decode_anyw and self.ODD_WIDTH_DECODE and not self.ODD_WIDTH_FUSED
+                and x2d.shape[0] <= min(self.ODD_WIDTH_DECODE_MAX_M, ops.GEMV_ANYW_MAX_M)):
+            # 1 / 2 / 3 / 5 / 6 / 7 bits at decode: inc_woq_gemv_anyw streams the packed words once; recover() never runs (larger batches
+            # keep the dense route below, and drop the prepared call again)
+            call = d["_call"] = ops.WoqGemvAnywCall(self.qweight, self.scales, self.qzeros, self.bias, self.out_features, self.in_features,
+                                                    self.group_size, self.bits, x2d.dtype)
+            gi = self.g_idx
+            call.tag = (gi, None if gi is None else gi._version)
+            y = call(x2d)
+        elif plan == "fused" and self._fused_max_m is not None:
             y = ops.woq_gemm(x2d, self.qweight, self.scales, self.qzeros, self.bias, self.out_features, self.in_features, self.group_size, self.bits)
         elif plan == "fused":
             call = d["_call"] = ops.WoqGemmCall(self.qweight, self.scales, self.qzeros, self.bias, self.out_features, self.in_features,
@@ -348,6 +359,16 @@ class MI355XWeightOnlyLinear(WeightOnlyLinear):
     # widths other than 4 / 8 bits: True = multiply through inc_woq_gemm's per-element tile form (no dense weight ever exists; 8-10 x
     # slower), False = HIP recover() into a transient dense weight + the library GEMM (what the reference's forward does on its CPU)
     ODD_WIDTH_FUSED = False
+    # ... and at decode, whatever the above says for larger batches: True = up to ODD_WIDTH_DECODE_MAX_M rows of an eligible module (optimum
+    # layout, contiguous groups of a power of two >= 32 or one per row, K % 32 == 0, N % 4 == 0, N >= 64) go through inc_woq_gemv_anyw,
+    # one launch that reads the packed words once and never builds the dense weight; False = the dense route for every batch.
+    # ODD_WIDTH_FUSED = True takes precedence (its plan is "fused").
+    ODD_WIDTH_DECODE = True
+    # the kernel's own limit.  Measured so far (profiles/anyw_decode/anyw_decode_time.log): 3 bits, 4096^2, M = 1 / 4: 8.3 / 8.5 us against
+    # 41.1 us for the dense route.  M = 16, 2 bits and the two other shapes of scripts/anyw_decode_time.py are NOT measured: 16 rests on
+    # the kernel's work not depending on M (the MFMA takes 16 rows, live or not) while the dense route writes and re-reads a dense weight.
+    # Lower it to 4 or 1 if a row of that script loses.
+    ODD_WIDTH_DECODE_MAX_M = 16
     # 4-bit row-packed modules (compression_dim = 1, dtype int / nf4 / fp4 / fp4_e2m1 / fp4_e2m1_bnb, no g_idx, K % 32 == 0, groups of
     # 32 k multiples): True = inc_woq_gemm_lut, False = HIP recover() into a transient dense weight + the library GEMM
     LUT_FUSED = True
@@ -373,6 +394,7 @@ class MI355XWeightOnlyLinear(WeightOnlyLinear):
         # the library GEMM at 4096^2 for every M from 1 to 4096, profiles/r6/anyw_route_time.log -- so it is opt-in: ODD_WIDTH_FUSED)
         fusable = self.use_optimum_format and (self.group_size % self.n_pack == 0 if self.bits in (4, 8) else self.ODD_WIDTH_FUSED)
         self._k_order = self._k_order32 = self._qweight_sorted = None
+        self._decode_anyw = self._decode_anyw_eligible()
         # group sizes that are neither a power of two >= 32 nor the whole row (e.g. 96) run inc_woq_gemm's general 128 x 128 tile kernel
         # above 16 rows: 190-245 us at 4096 x 4032 against 34-74 us for HIP recover() + the library GEMM (scripts/route_sweep.py) -- such
         # modules keep the fused form for decode-sized batches only
@@ -410,6 +432,18 @@ class MI355XWeightOnlyLinear(WeightOnlyLinear):
             plan = "fused_lut"
         self._plan_key, self._plan = key, plan
         return plan
+
+    def _decode_anyw_eligible(self):
+        """inc_woq_gemv_anyw takes the module at decode (ODD_WIDTH_DECODE)?  Recorded with the plan, once per packed state."""
+        K, gs = self.in_features, self.group_size
+        if (not self.use_optimum_format or not ops.gemv_anyw_takes(self.out_features, K, gs, self.bits)
+                or self.scales.dtype is not torch.float16 or not self.scales.is_contiguous() or not self.qweight.is_contiguous()
+                or not self.qzeros.is_contiguous() or self.qweight.data_ptr() % 16 or self.scales.data_ptr() % 8):
+            return False
+        if self.g_idx is None:
+            return True
+        gs_eff = K if (gs == -1 or gs >= K) else gs
+        return bool(torch.equal(self.g_idx.to(torch.int64), torch.arange(K, device=self.g_idx.device) // gs_eff))  # the contiguous one
 
     def _lut_eligible(self):
         """inc_woq_gemm_lut takes the module (and self._lut_table is its field -> value table)?"""
