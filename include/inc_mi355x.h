@@ -255,6 +255,35 @@ int inc_woq_gemv_anyw(const void* x, int xdtype, const int32_t* qweight, const u
                       void* y, int64_t M, int64_t N, int64_t K, int64_t G, int group_size, int bits, void* workspace,
                       int64_t workspace_bytes, inc_stream_t stream);
 
+/* K4f, gathered: == INCWeightOnlyLinear.forward (modules.py:594-610) of an act_order module of these widths, whose g_idx (modules.py:427-431)
+ *   is a permutation of whole groups: y = x[:, k_order] . W_sorted^T + bias in ONE launch.  `qweight` holds the packed fields with the K
+ *   axis sorted by group (k_order = stable argsort of g_idx; field j of the sorted words is field k_order[j] of the module's), `k_order`
+ *   [K] int32, 16-byte aligned; the kernel gathers the activations itself, entries outside [0, K-1] are clamped.  Bit-identical to
+ *   inc_woq_gemv_anyw on x.index_select(1, k_order): the same MFMAs in the same order.  x needs 2-byte alignment only.
+ *   INC_ERR_UNSUPPORTED (nothing launched): whatever inc_woq_gemv_anyw declines except an unaligned x; M * K >= 2^31 (x is addressed by
+ *   32-bit byte offsets); a misaligned k_order.  Slices, workspace and counters are inc_woq_gemv_anyw's.                              */
+int inc_woq_gemv_anyw_perm(const void* x, int xdtype, const int32_t* k_order, const int32_t* qweight, const uint16_t* scales,
+                           const int32_t* qzeros, const void* bias, void* y, int64_t M, int64_t N, int64_t K, int64_t G,
+                           int group_size, int bits, void* workspace, int64_t workspace_bytes, inc_stream_t stream);
+
+/* K4f, batched: == INCWeightOnlyLinear.forward (modules.py:594-610) of n modules of ONE of these widths that multiply the same x (q / k / v,
+ *   gate / up; act_order members: modules.py:427-431) in ONE launch: y[i] = x . W_i^T + bias[i], or x[:, k_order[i]] . W_sorted_i^T + bias[i].
+ *   2 <= n <= 8; qweight, scales, qzeros, bias, y, k_order and N are arrays of n entries in HOST memory (bias may be NULL, or hold NULL
+ *   entries); K, group_size and bits are common, every member a shape inc_woq_gemv_anyw takes (64 <= N[i] <= 2^18, N[i] % 4 == 0,
+ *   qweight[i] / y[i] 16-byte and scales[i] 8-byte aligned), all members' 64-column strips together within the 16 KiB counter block.
+ *   `k_order`: NULL (no member gathers; x 16-byte aligned) or n non-NULL 16-byte aligned orders (x 2-byte aligned, M * K < 2^31; a
+ *   member without a permutation gets the identity from the caller; a NULL entry is INC_ERR_BAD_ARG).  Everything else the single
+ *   entries decline is INC_ERR_UNSUPPORTED here, nothing launched.
+ *   Output i is bit-identical to inc_woq_gemv_anyw / inc_woq_gemv_anyw_perm on member i: the K-slices depend on K and bits alone.
+ *   `workspace`: inc_woq_gemv_anyw_multi_workspace_bytes = 0 for one slice (or a batch the entry declines), else
+ *   16384 + slices * M * sum(N) * 4 bytes: one arrival counter per strip of the batch, then the members' fp32 slabs [slice][M][N[i]] one
+ *   after the other.  Counter rules as above (zero on first use, re-armed by the kernel, one workspace per (device, stream)).      */
+int64_t inc_woq_gemv_anyw_multi_workspace_bytes(int n, int64_t M, const int64_t* N, int64_t K, int bits);
+int inc_woq_gemv_anyw_multi(int n, const void* x, int xdtype, const int32_t* const* k_order, const int32_t* const* qweight,
+                            const uint16_t* const* scales, const int32_t* const* qzeros, const void* const* bias, void* const* y,
+                            int64_t M, const int64_t* N, int64_t K, int group_size, int bits,
+                            void* workspace, int64_t workspace_bytes, inc_stream_t stream);
+
 /* ---- K4d: fused 4-bit code-book / row-packed integer dequant + GEMM ------------------------ *
  * == INCWeightOnlyLinear.forward (modules.py:594-610) for the layouts that are not the optimum one: F.linear(x, recover(x.dtype), bias)
  *   with recover (modules.py:413-443) done in registers, the dense weight never materialised.  NF4 / FP4 code books and integer

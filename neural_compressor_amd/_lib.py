@@ -65,6 +65,9 @@ SIGNATURES = {
     "inc_woq_gemv_anyw_slices": (c_int, [c_int64, c_int64, c_int64, c_int]),
     "inc_woq_gemv_anyw_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64, c_int]),
     "inc_woq_gemv_anyw": (c_int, [_P, c_int, _P, _P, _P, _P, _P, c_int64, c_int64, c_int64, c_int64, c_int, c_int, _P, c_int64, _P]),
+    "inc_woq_gemv_anyw_perm": (c_int, [_P, c_int, _P, _P, _P, _P, _P, _P, c_int64, c_int64, c_int64, c_int64, c_int, c_int, _P, c_int64, _P]),
+    "inc_woq_gemv_anyw_multi_workspace_bytes": (c_int64, [c_int, c_int64, _P, c_int64, c_int]),
+    "inc_woq_gemv_anyw_multi": (c_int, [c_int, _P, c_int, _P, _P, _P, _P, _P, _P, c_int64, _P, c_int64, c_int, c_int, _P, c_int64, _P]),
     "inc_groupwise_quant": (
         c_int,
         [_P, c_int, _P, _P, _P, _P, c_int64, c_int64, c_int, c_int, c_int, c_float, c_int, _P],

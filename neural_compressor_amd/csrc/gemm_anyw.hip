@@ -38,7 +38,10 @@
 // barrier, ONE relaxed agent-scope ticket per strip; the last arriver re-arms the counter, sums the slices in slice order with `sc1`
 // loads, adds the bias, rounds once and stores.  Bit-identical from call to call.
 //
-// Resources (hipcc --offload-arch=gfx950 -O3, -Rpass-analysis=kernel-resource-usage): see the table above the kernel.
+// Forms: plain (inc_woq_gemv_anyw), gathered for act_order modules (inc_woq_gemv_anyw_perm), and batched over modules that share x, plain
+// or gathered (inc_woq_gemv_anyw_multi) -- one body, described above it.
+//
+// Resources (hipcc --offload-arch=gfx950 -O3, -Rpass-analysis=kernel-resource-usage): see the table above the body.
 #include "gemm_common.hpp"
 
 namespace {
@@ -62,14 +65,37 @@ __device__ __forceinline__ uint32_t anyw_field(const uint4 (&w)[AnywShape<BITS>:
   return (word >> (BITS * (e % NP))) & ((1u << BITS) - 1u);
 }
 
-// Resource report of the cross-compile (VGPRs bf16 / fp16; every instantiation: 16 AGPRs, 40 SGPRs, 16640 bytes of LDS, 0 bytes of scratch):
-//   1 bit 100 / 98     2 bits 112 / 110     3 bits 90 / 90     5 bits 110 / 110     6 bits 112 / 108     7 bits 106 / 104
-// -> 4 waves per SIMD by registers (4 workgroups per CU), no scratch; the 16 AGPRs are the four accumulators.
-template <bool IS_BF16, int BITS>
-__global__ __launch_bounds__(256) void woq_gemv_anyw_kernel(
+// The body of one (64-column strip, K-slice) workgroup: `counter` is the strip's arrival counter, `partial` the module's slabs
+// [slice][M][N].  Three kernels share it, as the forms of gemm_stream.hip share theirs:
+// PERM (inc_woq_gemv_anyw_perm: act_order modules, whose packed fields are sorted along K by group once -- ops.sort_packed_k): the A operand
+// of fragment i is x[row, k_order[k0 + 8 i + t]], t = 0 .. 7, instead of the 16-byte load of x[row, k0 + 8 i ..]: the lane reads its 8
+// entries of k_order (two 16-byte loads: k_order is 16-byte aligned and k0 % 8 == 0), clamps each to [0, K - 1] so that no array can send
+// a read outside x, and packs eight 2-byte loads (perm_load8 / perm_gather8, gemm_common.hpp).  Dead fragments read their entries at
+// K - 8 like x does in the plain form, and their A is zeroed all the same.  Nothing else differs: the same values reach the same MFMAs in
+// the same order, so the result equals the plain form's on x.index_select(1, k_order) bit for bit.  x is addressed by 32-bit byte offsets
+// (M * K < 2^31) and needs 2-byte alignment only.  Order of issue: the entries of k_order of all fragments, then the weights, then the
+// gathers -- vector loads return in order, so the gathers wait for the indices alone while the weights are on their way from HBM; an
+// index register is dead once its gather is issued (up to 64 of them at F = 64: the compiler reuses them for the gathered values).
+// Batched (inc_woq_gemv_anyw_multi): the strips of the members occupy consecutive ranges of blockIdx.x, each runs this body on its own
+// member's tensors with its own counter and its own slabs -- see woq_gemv_anyw_multi_kernel.
+//
+// Resource report of the cross-compile (VGPRs bf16 / fp16; every instantiation: 16 AGPRs, 16640 bytes of LDS, 0 bytes of scratch):
+//   (VGPRs)   plain      gathered   batched    batched + gathered
+//   1 bit     100 / 98   139 / 139  100 / 98   140 / 140
+//   2 bits    112 / 110  150 / 150  112 / 110  146 / 146
+//   3 bits     90 / 90   127 / 127   90 / 90   130 / 130
+//   5 bits    110 / 110  142 / 142  110 / 110  139 / 139
+//   6 bits    112 / 108  132 / 132  112 / 108  136 / 136
+//   7 bits    106 / 104  124 / 124  106 / 104  116 / 116
+// SGPRs: 40 - 42, the gathered 1- and 2-bit forms 98 - 104.  Plain and batched: 4 waves per SIMD by registers (4 workgroups per CU); the
+// gathered forms hold the gathered halves next to the weights in flight and come to 3 -- a decode grid (448 workgroups at 4096^2, 3 bits)
+// puts fewer than that on a CU.  No scratch anywhere; the 16 AGPRs are the four accumulators.
+template <bool IS_BF16, int BITS, bool PERM = false>
+__device__ __forceinline__ void woq_gemv_anyw_body(
     const uint16_t* __restrict__ x, const uint32_t* __restrict__ qweight, const uint16_t* __restrict__ scales,
     const uint32_t* __restrict__ qzeros, const uint16_t* __restrict__ bias, uint16_t* __restrict__ y,
-    float* __restrict__ partial, unsigned* __restrict__ counters, int M, int64_t N, int K, int64_t NW, int G, int g_shift, int splitk) {
+    float* __restrict__ partial, unsigned* __restrict__ counter, int M, int64_t N, int K, int64_t NW, int G, int g_shift, int splitk,
+    int strip, int slice, const int32_t* __restrict__ k_order = nullptr) {
   using S = AnywShape<BITS>;
   constexpr int NP = S::NP, WL = S::WL, F = S::F, NF = S::NF;
   constexpr uint32_t MASK = (1u << BITS) - 1u;
@@ -77,8 +103,6 @@ __global__ __launch_bounds__(256) void woq_gemv_anyw_kernel(
   __shared__ float red[4 * 16 * 65];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int jn = lane & 15, oct = lane >> 4;
-  const int strip = (int)blockIdx.x, slice = (int)blockIdx.y;
-  unsigned* const counter = counters + strip;
   const int64_t n0 = (int64_t)strip * 64;
   int64_t ncol = n0 + 4 * jn;
   if (ncol > N - 4) ncol = N - 4;  // clamped lanes recompute valid columns; their results are not stored
@@ -86,8 +110,18 @@ __global__ __launch_bounds__(256) void woq_gemv_anyw_kernel(
   const int row0 = ((slice * 4 + wave) * 4 + oct) * WL;
   const int k0 = row0 * NP;  // % 8 == 0
 
-  // ---- issue every load of this wave up front: weights first ------------------------------------
+  // ---- issue every load of this wave up front: (PERM: the entries of k_order,) the weights, x -----
   uint4 w[WL], a[NF];
+  PermIdx8 kraw[PERM ? NF : 1];
+  if constexpr (PERM) {
+#pragma unroll
+    for (int i = 0; i < NF; ++i) {
+      int kk = k0 + 8 * i;
+      if (kk > K - 8) kk = K - 8;  // dead fragments: the last 8 entries, never at or beyond entry K
+      kraw[i] = perm_load8(k_order + kk);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
 #pragma unroll
   for (int l = 0; l < WL; ++l) {
     int r = row0 + l;
@@ -99,7 +133,8 @@ __global__ __launch_bounds__(256) void woq_gemv_anyw_kernel(
   for (int i = 0; i < NF; ++i) {
     int kk = k0 + 8 * i;
     if (kk > K - 8) kk = K - 8;  // dead fragments read the row's last 16 bytes: never at or beyond column K
-    a[i] = *reinterpret_cast<const uint4*>(x + (int64_t)am * K + kk);
+    if constexpr (PERM) a[i] = perm_gather8(x, 2u * (uint32_t)am * (uint32_t)K, kraw[i], K - 1);
+    else a[i] = *reinterpret_cast<const uint4*>(x + (int64_t)am * K + kk);
   }
   // the (at most two) groups of this lane's k0 .. k0 + F - 1
   int g_lo = 0, kb = F;  // kb: first stream element of the second group
@@ -225,6 +260,45 @@ __global__ __launch_bounds__(256) void woq_gemv_anyw_kernel(
     }
 }
 
+template <bool IS_BF16, int BITS>
+__global__ __launch_bounds__(256) void woq_gemv_anyw_kernel(
+    const uint16_t* __restrict__ x, const uint32_t* __restrict__ qweight, const uint16_t* __restrict__ scales,
+    const uint32_t* __restrict__ qzeros, const uint16_t* __restrict__ bias, uint16_t* __restrict__ y,
+    float* __restrict__ partial, unsigned* __restrict__ counters, int M, int64_t N, int K, int64_t NW, int G, int g_shift, int splitk) {
+  woq_gemv_anyw_body<IS_BF16, BITS>(x, qweight, scales, qzeros, bias, y, partial, counters + blockIdx.x, M, N, K, NW, G, g_shift, splitk,
+                                    (int)blockIdx.x, (int)blockIdx.y);
+}
+
+// the same workgroup with the activations gathered through k_order (PERM above)
+template <bool IS_BF16, int BITS>
+__global__ __launch_bounds__(256) void woq_gemv_anyw_perm_kernel(
+    const uint16_t* __restrict__ x, const int32_t* __restrict__ k_order, const uint32_t* __restrict__ qweight,
+    const uint16_t* __restrict__ scales, const uint32_t* __restrict__ qzeros, const uint16_t* __restrict__ bias, uint16_t* __restrict__ y,
+    float* __restrict__ partial, unsigned* __restrict__ counters, int M, int64_t N, int K, int64_t NW, int G, int g_shift, int splitk) {
+  woq_gemv_anyw_body<IS_BF16, BITS, true>(x, qweight, scales, qzeros, bias, y, partial, counters + blockIdx.x, M, N, K, NW, G, g_shift, splitk,
+                                          (int)blockIdx.x, (int)blockIdx.y, k_order);
+}
+
+// Several modules of one width that multiply the SAME x (q / k / v; gate / up) in ONE launch (inc_woq_gemv_anyw_multi): grid =
+// (the members' strips together) x K-slices.  The slice count depends on K and the width alone, so a member's strip is computed exactly as
+// its single launch computes it: bit-identical.  Global strip b arrives on counters[b]; member p's slabs [slice][M][N_p] start at
+// args.part_off[p] -- together the [slice][M][sum N] floats of the workspace.  PERM: member p gathers x through args.k_order[p].
+template <bool IS_BF16, int BITS, bool PERM>
+__global__ __launch_bounds__(256) void woq_gemv_anyw_multi_kernel(GemvBatch args, const uint16_t* __restrict__ x, float* __restrict__ partial,
+                                                                  unsigned* __restrict__ counters, int M, int K, int G, int g_shift, int splitk) {
+  const int b = (int)blockIdx.x;
+  int p = 0;
+#pragma unroll
+  for (int i = 1; i < GEMV_MAX_BATCH; ++i)
+    if (i < args.n && b >= args.first[i]) p = i;
+  p = __builtin_amdgcn_readfirstlane(p);
+  const int64_t N = args.N[p];
+  constexpr int NP = AnywShape<BITS>::NP;
+  woq_gemv_anyw_body<IS_BF16, BITS, PERM>(x, args.qweight[p], args.scales[p], args.qzeros[p], args.bias[p], args.y[p], partial + args.part_off[p],
+                                          counters + b, M, N, K, (N + NP - 1) / NP, G, g_shift, splitk, b - args.first[p], (int)blockIdx.y,
+                                          PERM ? args.k_order[p] : nullptr);
+}
+
 // k of one K-slice at this width, 0 for a width that is not this file's
 int anyw_slice_k(int bits) {
   switch (bits) {
@@ -244,13 +318,76 @@ bool anyw_shape_ok(int64_t M, int64_t N, int64_t K, int bits) {
          ceil_div64(N, 64) * 4 <= WS_COUNTER_BYTES && ceil_div64(K, anyw_slice_k(bits)) <= 65535;
 }
 
+// the batch the kernel takes (host only): 2 .. 8 members of the single launch's shapes, all strips' counters in the counter block
+bool anyw_multi_shape_ok(int n, int64_t M, const int64_t* N, int64_t K, int bits, int64_t* strips_out, int64_t* ntot_out) {
+  if (n < 2 || n > GEMV_MAX_BATCH) return false;
+  int64_t strips = 0, ntot = 0;
+  for (int i = 0; i < n; ++i) {
+    if (!anyw_shape_ok(M, N[i], K, bits)) return false;
+    strips += ceil_div64(N[i], 64);
+    ntot += N[i];
+  }
+  if (strips * 4 > WS_COUNTER_BYTES) return false;
+  *strips_out = strips, *ntot_out = ntot;
+  return true;
+}
+
+// group lookup by shift: contiguous groups of a power of two >= 32, or one group (g_shift = -1); G = the number of groups
+bool anyw_groups(int64_t K, int group_size, int* g_shift_out, int64_t* G_out) {
+  const int gs = (group_size == -1 || group_size >= K) ? (int)K : group_size;
+  *g_shift_out = -1;
+  if (gs < K) {
+    if (gs < 32 || (gs & (gs - 1)) != 0) return false;
+    *g_shift_out = __builtin_ctz((unsigned)gs);
+  }
+  *G_out = *g_shift_out < 0 ? 1 : ceil_div64(K, gs);
+  return true;
+}
+
+int anyw_slices(int64_t M, int64_t N, int64_t K, int bits) { return anyw_shape_ok(M, N, K, bits) ? (int)ceil_div64(K, anyw_slice_k(bits)) : 0; }
+
+// inc_woq_gemv_anyw (k_order == NULL: x in 16-byte pieces) and inc_woq_gemv_anyw_perm (x gathered 2 bytes at a time through 32-bit byte
+// offsets): the same checks, the same grid, the PERM instantiation of the same body
+int anyw_single(const void* x, int xdtype, const int32_t* k_order, const int32_t* qweight, const uint16_t* scales, const int32_t* qzeros,
+                const void* bias, void* y, int64_t M, int64_t N, int64_t K, int64_t G, int group_size, int bits, void* workspace,
+                int64_t workspace_bytes, inc_stream_t stream) {
+  if (!(xdtype == INC_BF16 || xdtype == INC_F16) || !anyw_shape_ok(M, N, K, bits)) return INC_ERR_UNSUPPORTED;
+  int g_shift;
+  int64_t G_want;
+  if (!anyw_groups(K, group_size, &g_shift, &G_want)) return INC_ERR_UNSUPPORTED;
+  INC_CHECK_ARG(G == G_want);
+  if (((reinterpret_cast<uintptr_t>(k_order ? (const void*)k_order : x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(qweight)) & 15) != 0 ||
+      (reinterpret_cast<uintptr_t>(scales) & 7) != 0 || (k_order && M * K >= ((int64_t)1 << 31)))
+    return INC_ERR_UNSUPPORTED;
+  const int splitk = anyw_slices(M, N, K, bits);
+  if (splitk > 1 && (!workspace || workspace_bytes < WS_COUNTER_BYTES + (int64_t)splitk * M * N * 4)) return INC_ERR_WORKSPACE;
+  unsigned* const counters = (unsigned*)workspace;
+  float* const part = splitk > 1 ? (float*)((char*)workspace + WS_COUNTER_BYTES) : nullptr;
+  const dim3 grid((unsigned)ceil_div64(N, 64), (unsigned)splitk);
+  const bool bf = xdtype == INC_BF16;
+#define INC_ANYW_ARGS(B) (const uint32_t*)qweight, scales, (const uint32_t*)qzeros, (const uint16_t*)bias, (uint16_t*)y, part, counters, (int)M, N, (int)K, ceil_div64(N, 32 / B), (int)G, g_shift, splitk
+#define INC_ANYW(B)                                                                                                                          \
+  case B:                                                                                                                                    \
+    if (k_order && bf) woq_gemv_anyw_perm_kernel<true, B><<<grid, 256, 0, inc_s(stream)>>>((const uint16_t*)x, k_order, INC_ANYW_ARGS(B));   \
+    else if (k_order) woq_gemv_anyw_perm_kernel<false, B><<<grid, 256, 0, inc_s(stream)>>>((const uint16_t*)x, k_order, INC_ANYW_ARGS(B));   \
+    else if (bf) woq_gemv_anyw_kernel<true, B><<<grid, 256, 0, inc_s(stream)>>>((const uint16_t*)x, INC_ANYW_ARGS(B));                       \
+    else woq_gemv_anyw_kernel<false, B><<<grid, 256, 0, inc_s(stream)>>>((const uint16_t*)x, INC_ANYW_ARGS(B));                              \
+    break;
+  switch (bits) {
+    INC_ANYW(1) INC_ANYW(2) INC_ANYW(3) INC_ANYW(5) INC_ANYW(6) INC_ANYW(7)
+    default: return INC_ERR_UNSUPPORTED;
+  }
+#undef INC_ANYW
+#undef INC_ANYW_ARGS
+  INC_LAUNCH_RETURN();
+}
+
 }  // namespace
 
 extern "C" {
 
 int inc_woq_gemv_anyw_slices(int64_t M, int64_t N, int64_t K, int bits) {
-  if (!anyw_shape_ok(M, N, K, bits)) return 0;
-  return (int)ceil_div64(K, anyw_slice_k(bits));
+  return anyw_slices(M, N, K, bits);
 }
 
 int64_t inc_woq_gemv_anyw_workspace_bytes(int64_t M, int64_t N, int64_t K, int bits) {
@@ -262,35 +399,78 @@ int inc_woq_gemv_anyw(const void* x, int xdtype, const int32_t* qweight, const u
                       void* y, int64_t M, int64_t N, int64_t K, int64_t G, int group_size, int bits, void* workspace,
                       int64_t workspace_bytes, inc_stream_t stream) {
   INC_CHECK_ARG(x && qweight && scales && qzeros && y && N > 0 && K > 0 && G > 0 && (group_size > 0 || group_size == -1));
-  if (!(xdtype == INC_BF16 || xdtype == INC_F16) || !anyw_shape_ok(M, N, K, bits)) return INC_ERR_UNSUPPORTED;
-  const int gs = (group_size == -1 || group_size >= K) ? (int)K : group_size;
-  int g_shift = -1;  // one group
-  if (gs < K) {
-    if (gs < 32 || (gs & (gs - 1)) != 0) return INC_ERR_UNSUPPORTED;
-    g_shift = __builtin_ctz((unsigned)gs);
+  return anyw_single(x, xdtype, nullptr, qweight, scales, qzeros, bias, y, M, N, K, G, group_size, bits, workspace, workspace_bytes, stream);
+}
+
+// ---- act_order decode in one launch: y = x[:, k_order] W_sorted^T + bias (PERM) -------------------------------------------------------
+int inc_woq_gemv_anyw_perm(const void* x, int xdtype, const int32_t* k_order, const int32_t* qweight, const uint16_t* scales,
+                           const int32_t* qzeros, const void* bias, void* y, int64_t M, int64_t N, int64_t K, int64_t G, int group_size,
+                           int bits, void* workspace, int64_t workspace_bytes, inc_stream_t stream) {
+  INC_CHECK_ARG(x && k_order && qweight && scales && qzeros && y && N > 0 && K > 0 && G > 0 && (group_size > 0 || group_size == -1));
+  INC_CHECK_ARG((reinterpret_cast<uintptr_t>(x) & 1) == 0);
+  return anyw_single(x, xdtype, k_order, qweight, scales, qzeros, bias, y, M, N, K, G, group_size, bits, workspace, workspace_bytes, stream);
+}
+
+// ---- modules that share x, one launch --------------------------------------------------------------------------------------------------
+int64_t inc_woq_gemv_anyw_multi_workspace_bytes(int n, int64_t M, const int64_t* N, int64_t K, int bits) {
+  int64_t strips, ntot;
+  if (!N || !anyw_multi_shape_ok(n, M, N, K, bits, &strips, &ntot)) return 0;
+  const int64_t slices = ceil_div64(K, anyw_slice_k(bits));
+  return slices > 1 ? WS_COUNTER_BYTES + slices * M * ntot * 4 : 0;
+}
+
+int inc_woq_gemv_anyw_multi(int n, const void* x, int xdtype, const int32_t* const* k_order, const int32_t* const* qweight,
+                            const uint16_t* const* scales, const int32_t* const* qzeros, const void* const* bias, void* const* y, int64_t M,
+                            const int64_t* N, int64_t K, int group_size, int bits, void* workspace, int64_t workspace_bytes,
+                            inc_stream_t stream) {
+  INC_CHECK_ARG(x && qweight && scales && qzeros && y && N && n > 0 && K > 0 && (group_size > 0 || group_size == -1));
+  INC_CHECK_ARG((reinterpret_cast<uintptr_t>(x) & 1) == 0);
+  int64_t strips, ntot;
+  if (!(xdtype == INC_BF16 || xdtype == INC_F16) || !anyw_multi_shape_ok(n, M, N, K, bits, &strips, &ntot)) return INC_ERR_UNSUPPORTED;
+  int g_shift;
+  int64_t G;
+  if (!anyw_groups(K, group_size, &g_shift, &G)) return INC_ERR_UNSUPPORTED;
+  if (k_order ? M * K >= ((int64_t)1 << 31) : (reinterpret_cast<uintptr_t>(x) & 15) != 0) return INC_ERR_UNSUPPORTED;
+  const int splitk = (int)ceil_div64(K, anyw_slice_k(bits));
+  GemvBatch args = {};  // (members past n: null tensors, N = 0)
+  args.n = n;
+  int64_t off = 0;
+  int first = 0;
+  for (int i = 0; i < n; ++i) {
+    INC_CHECK_ARG(qweight[i] && scales[i] && qzeros[i] && y[i] && (!k_order || k_order[i]));
+    if (((reinterpret_cast<uintptr_t>(y[i]) | reinterpret_cast<uintptr_t>(qweight[i]) | (k_order ? reinterpret_cast<uintptr_t>(k_order[i]) : 0)) & 15) != 0 ||
+        (reinterpret_cast<uintptr_t>(scales[i]) & 7) != 0)
+      return INC_ERR_UNSUPPORTED;
+    args.k_order[i] = k_order ? k_order[i] : nullptr;
+    args.qweight[i] = (const uint32_t*)qweight[i];
+    args.scales[i] = scales[i];
+    args.qzeros[i] = (const uint32_t*)qzeros[i];
+    args.bias[i] = bias ? (const uint16_t*)bias[i] : nullptr;
+    args.y[i] = (uint16_t*)y[i];
+    args.N[i] = N[i];
+    args.part_off[i] = off;
+    args.first[i] = first;
+    off += (int64_t)splitk * M * N[i];
+    first += (int)ceil_div64(N[i], 64);
   }
-  INC_CHECK_ARG(G == (g_shift < 0 ? 1 : ceil_div64(K, gs)));
-  if (((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(qweight)) & 15) != 0 ||
-      (reinterpret_cast<uintptr_t>(scales) & 7) != 0)
-    return INC_ERR_UNSUPPORTED;
-  const int splitk = inc_woq_gemv_anyw_slices(M, N, K, bits);
-  if (splitk > 1 && (!workspace || workspace_bytes < inc_woq_gemv_anyw_workspace_bytes(M, N, K, bits))) return INC_ERR_WORKSPACE;
+  for (int i = n; i <= GEMV_MAX_BATCH; ++i) args.first[i] = first;
+  if (splitk > 1 && (!workspace || workspace_bytes < WS_COUNTER_BYTES + off * 4)) return INC_ERR_WORKSPACE;
   unsigned* const counters = (unsigned*)workspace;
   float* const part = splitk > 1 ? (float*)((char*)workspace + WS_COUNTER_BYTES) : nullptr;
-  const dim3 grid((unsigned)ceil_div64(N, 64), (unsigned)splitk);
-  const bool bf = xdtype == INC_BF16;
-#define INC_ANYW(B)                                                                                                                          \
+  const dim3 grid((unsigned)strips, (unsigned)splitk);
+  const bool bf = xdtype == INC_BF16, perm = k_order != nullptr;
+#define INC_ANYW_MULTI(B)                                                                                                                    \
   case B:                                                                                                                                    \
-    if (bf) woq_gemv_anyw_kernel<true, B><<<grid, 256, 0, inc_s(stream)>>>((const uint16_t*)x, (const uint32_t*)qweight, scales, (const uint32_t*)qzeros, \
-        (const uint16_t*)bias, (uint16_t*)y, part, counters, (int)M, N, (int)K, ceil_div64(N, 32 / B), (int)G, g_shift, splitk);            \
-    else woq_gemv_anyw_kernel<false, B><<<grid, 256, 0, inc_s(stream)>>>((const uint16_t*)x, (const uint32_t*)qweight, scales, (const uint32_t*)qzeros, \
-        (const uint16_t*)bias, (uint16_t*)y, part, counters, (int)M, N, (int)K, ceil_div64(N, 32 / B), (int)G, g_shift, splitk);            \
+    if (bf && perm) woq_gemv_anyw_multi_kernel<true, B, true><<<grid, 256, 0, inc_s(stream)>>>(args, (const uint16_t*)x, part, counters, (int)M, (int)K, (int)G, g_shift, splitk);        \
+    else if (bf) woq_gemv_anyw_multi_kernel<true, B, false><<<grid, 256, 0, inc_s(stream)>>>(args, (const uint16_t*)x, part, counters, (int)M, (int)K, (int)G, g_shift, splitk);          \
+    else if (perm) woq_gemv_anyw_multi_kernel<false, B, true><<<grid, 256, 0, inc_s(stream)>>>(args, (const uint16_t*)x, part, counters, (int)M, (int)K, (int)G, g_shift, splitk);        \
+    else woq_gemv_anyw_multi_kernel<false, B, false><<<grid, 256, 0, inc_s(stream)>>>(args, (const uint16_t*)x, part, counters, (int)M, (int)K, (int)G, g_shift, splitk);                 \
     break;
   switch (bits) {
-    INC_ANYW(1) INC_ANYW(2) INC_ANYW(3) INC_ANYW(5) INC_ANYW(6) INC_ANYW(7)
+    INC_ANYW_MULTI(1) INC_ANYW_MULTI(2) INC_ANYW_MULTI(3) INC_ANYW_MULTI(5) INC_ANYW_MULTI(6) INC_ANYW_MULTI(7)
     default: return INC_ERR_UNSUPPORTED;
   }
-#undef INC_ANYW
+#undef INC_ANYW_MULTI
   INC_LAUNCH_RETURN();
 }
 

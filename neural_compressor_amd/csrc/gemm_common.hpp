@@ -199,6 +199,24 @@ __device__ __forceinline__ f32x4 mfma16(const uint4& a, const uint4& b, f32x4 c)
   }
 }
 
+// the gathered A operand of the decode kernels (PERM: gemm_stream.hip, gemm_anyw.hip): 8 entries of k_order as two 16-byte loads (16-byte
+// aligned, offset a multiple of 8), and the 8 two-byte loads of x[row, k_order[..]] they select, clamped to [0, kmax], packed like the
+// 16-byte load of the plain form; `row_bytes` = the row's byte offset in x (M * K < 2^31)
+struct PermIdx8 { int4 lo, hi; };
+__device__ __forceinline__ PermIdx8 perm_load8(const int32_t* __restrict__ ko) {
+  return PermIdx8{*reinterpret_cast<const int4*>(ko), *reinterpret_cast<const int4*>(ko + 4)};
+}
+__device__ __forceinline__ uint4 perm_gather8(const uint16_t* __restrict__ x, uint32_t row_bytes, const PermIdx8& p, int kmax) {
+  const int raw[8] = {p.lo.x, p.lo.y, p.lo.z, p.lo.w, p.hi.x, p.hi.y, p.hi.z, p.hi.w};
+  uint32_t v[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int k = raw[j] < 0 ? 0 : (raw[j] > kmax ? kmax : raw[j]);
+    v[j] = *reinterpret_cast<const uint16_t*>(reinterpret_cast<const char*>(x) + (row_bytes + 2u * (uint32_t)k));
+  }
+  return make_uint4(v[0] | (v[1] << 16), v[2] | (v[3] << 16), v[4] | (v[5] << 16), v[6] | (v[7] << 16));
+}
+
 // 16-byte write-through store / L2-coherent load of split-K partials (the hand-off of MI355X_MICROARCH.md "Valid forms": sc1 stores ->
 // vmcnt(0) -> barrier -> one relaxed agent-scope ticket -> sc1 loads by the last arriver); the caller waits for the loads (vmcnt) itself
 __device__ __forceinline__ void splitk_store16_sc1(float* p, f32x4 v) {

@@ -39,21 +39,8 @@ constexpr int VS = 8;   // largest VSTEPS (sizes the workspace)
 // most 64 x K 16-bit values and is read by every workgroup: it stays in L2.
 // Order of issue: the entries of k_order for all of a wave's steps first, then the weights, then the gathers -- vector loads
 // return in order, so the gathers wait for the indices alone while the weights are on their way from HBM.  An index register is
-// done once its gather is issued; x is addressed by 32-bit byte offsets (the entry point requires M * K < 2^31).
-struct PermIdx8 { int4 lo, hi; };
-__device__ __forceinline__ PermIdx8 perm_load8(const int32_t* __restrict__ ko) {
-  return PermIdx8{*reinterpret_cast<const int4*>(ko), *reinterpret_cast<const int4*>(ko + 4)};
-}
-__device__ __forceinline__ uint4 perm_gather8(const uint16_t* __restrict__ x, uint32_t row_bytes, const PermIdx8& p, int kmax) {
-  const int raw[8] = {p.lo.x, p.lo.y, p.lo.z, p.lo.w, p.hi.x, p.hi.y, p.hi.z, p.hi.w};
-  uint32_t v[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int k = raw[j] < 0 ? 0 : (raw[j] > kmax ? kmax : raw[j]);
-    v[j] = *reinterpret_cast<const uint16_t*>(reinterpret_cast<const char*>(x) + (row_bytes + 2u * (uint32_t)k));
-  }
-  return make_uint4(v[0] | (v[1] << 16), v[2] | (v[3] << 16), v[4] | (v[5] << 16), v[6] | (v[7] << 16));
-}
+// done once its gather is issued; x is addressed by 32-bit byte offsets (the entry point requires M * K < 2^31).  perm_load8 /
+// perm_gather8 live in gemm_common.hpp: gemm_anyw.hip gathers the same way.
 
 // the last arriver's fixed-order sum over the K-slices of one member's slabs (`sc1` loads), up to 32 partial loads of a thread in flight
 template <int NOUT>

@@ -430,6 +430,33 @@ class WoqGemmCall:
         return y
 
 
+def sort_packed_k(qweight, order, K, bits):
+    """The optimum-layout packed weight with its K axis reordered: field k of the result (k < K) is field order[k] of `qweight`.
+
+    qweight [ceil(K / n_pack), N] int32 with n_pack = 32 // bits fields of `bits` bits per word from bit 0 (any width 1..8, K % n_pack
+    need not be 0: 4096 % 10 = 6 at 3 bits); order [K] integer.  The fields are unpacked, the first K kept, index_select(0, order)
+    applied, the tail padded with zero fields to whole words and packed again.  Pure torch on qweight's device: what
+    MI355XWeightOnlyLinear does once per packed state for an act_order module (order = the stable argsort of g_idx), so that the groups
+    of the sorted words are contiguous and inc_woq_gemv_anyw_perm / inc_woq_gemm_perm only gather the activations."""
+    if not 1 <= bits <= 8:
+        raise ValueError(f"sort_packed_k: bits={bits}; fields of 1 .. 8 bits")
+    npk, mask = 32 // bits, (1 << bits) - 1
+    rows = -(-K // npk)
+    if qweight.dim() != 2 or qweight.shape[0] != rows or qweight.dtype is not torch.int32:
+        raise ValueError(f"sort_packed_k: qweight must be int32 [{rows}, N], got {qweight.dtype} {list(qweight.shape)}")
+    if order.dim() != 1 or order.shape[0] != K:
+        raise ValueError(f"sort_packed_k: order must hold K = {K} entries, got {list(order.shape)}")
+    dev, N = qweight.device, qweight.shape[1]
+    shifts = (torch.arange(npk, device=dev, dtype=torch.int64) * bits).view(1, npk, 1)
+    fields = ((qweight.to(torch.int64).unsqueeze(1) >> shifts) & mask).reshape(rows * npk, N)[:K]
+    fields = fields.index_select(0, order.to(device=dev, dtype=torch.int64))
+    if rows * npk != K:
+        fields = torch.cat([fields, fields.new_zeros((rows * npk - K, N))])
+    words = (fields.reshape(rows, npk, N) << shifts).sum(dim=1)  # disjoint fields, < 2^32
+    words = torch.where(words >= 2**31, words - 2**32, words)
+    return words.to(torch.int32).contiguous()
+
+
 GEMV_ANYW_BITS = (1, 2, 3, 5, 6, 7)
 GEMV_ANYW_MAX_M = 16
 
@@ -511,22 +538,40 @@ class WoqGemvAnywCall:
 
     The workspace is the (device, stream) one the other calls use (its counters are zero between launches), asked for 16 rows from the
     first call on so that a change of M does not move it; when it grows, the outgrown buffer is kept (_workspace), so a captured graph
-    that replays the call never meets a freed workspace."""
+    that replays the call never meets a freed workspace.
+
+    With `k_order` (int32 [K]; act_order modules) `qweight` is the K-sorted packed weight (sort_packed_k) and the call computes
+    x[:, k_order] W^T through inc_woq_gemv_anyw_perm: the gather happens inside the kernel, one launch, and x need not be 16-byte
+    aligned.  `owner_qweight` is the buffer the sorted copy was made from: current() is asked about that one (WoqGemmCall's contract).
+    `gather_max_mn`: with more than that many outputs (M * N) the call gathers with x.index_select(1, k_order) in front of the plain
+    kernel instead (two launches, the same bits: every 64-column strip repeats the in-kernel gather, so its cost grows with rows x
+    columns while the torch gather is paid once; None = always inside the kernel).  See gathers()."""
 
     __slots__ = ("dev", "dev_index", "dtype", "dt", "N", "K", "G", "gs", "bits", "qw", "sc", "qz", "bi", "keep", "versions", "bias_conv",
-                 "need", "tag")
+                 "need", "tag", "ko", "perm_keep", "perm_versions", "gather_max_mn")
     lut = False
     anyw = True
-    ko = None
     MAX_M = GEMV_ANYW_MAX_M
 
-    def __init__(self, qweight, scales, qzeros, bias, N, K, group_size, bits, dtype):
+    def __init__(self, qweight, scales, qzeros, bias, N, K, group_size, bits, dtype, k_order=None, owner_qweight=None,
+                 gather_max_mn=None):
         if dtype is not torch.bfloat16 and dtype is not torch.float16:
             raise ValueError(f"woq_gemv_anyw computes in bf16 or fp16, got {dtype}")
+        self.gather_max_mn = gather_max_mn
         self.G = _gemv_anyw_check_module(qweight, scales, qzeros, bias, N, K, group_size, bits)
         if qweight.data_ptr() % 16:
             raise ValueError("woq_gemv_anyw: qweight must be 16-byte aligned")
-        self.keep = (qweight, scales, qzeros, bias)
+        if k_order is not None:
+            if k_order.dtype is not torch.int32:
+                raise TypeError(f"k_order must be int32, got {k_order.dtype}")
+            if k_order.dim() != 1 or k_order.shape[0] != K:
+                raise ValueError(f"k_order must hold K = {K} entries, got {tuple(k_order.shape)}")
+            if k_order.device != qweight.device or not k_order.is_contiguous() or k_order.data_ptr() % 16:
+                raise ValueError("woq_gemv_anyw: k_order must be contiguous, 16-byte aligned and on the weights' device")
+        self.ko = _ptr(k_order)
+        self.perm_keep = (qweight, k_order)
+        self.perm_versions = (qweight._version, None if k_order is None else k_order._version)
+        self.keep = (qweight if owner_qweight is None else owner_qweight, scales, qzeros, bias)
         self.versions = tuple(None if t is None else t._version for t in self.keep)
         if bias is not None and bias.dtype != dtype:
             bias = bias.to(dtype)  # converted once (the packed module stores fp16, a bf16 model multiplies in bf16)
@@ -550,19 +595,28 @@ class WoqGemvAnywCall:
         k, v = self.keep, self.versions
         return (k[0] is qweight and k[1] is scales and k[2] is qzeros and k[3] is bias and qweight._version == v[0]
                 and scales._version == v[1] and qzeros._version == v[2] and (bias is None or bias._version == v[3])
-                and self.tag[0] is owner_g_idx and (owner_g_idx is None or owner_g_idx._version == self.tag[1]))
+                and self.tag[0] is owner_g_idx and (owner_g_idx is None or owner_g_idx._version == self.tag[1])
+                and (self.ko is None or (self.perm_keep[0]._version, self.perm_keep[1]._version) == self.perm_versions))
 
     def slices(self, M):
         """K-slices of the launch for M rows (inc_woq_gemv_anyw_slices: host only)."""
         return lib.inc_woq_gemv_anyw_slices(M, self.N, self.K, self.bits)
+
+    def gathers(self, M):
+        """M rows go through inc_woq_gemv_anyw_perm (one launch)?  Otherwise x.index_select + inc_woq_gemv_anyw: the same bits."""
+        return (self.ko is not None and (self.gather_max_mn is None or M * self.N <= self.gather_max_mn)
+                and M * self.K < 1 << 31)  # (x by 32-bit byte offsets)
 
     def __call__(self, x2d, checked=True):
         """x2d: contiguous [M, K], 1 <= M <= 16, of the call's dtype on the call's device (`checked`: the owner has made sure)."""
         if not checked:
             _gemv_anyw_check_x(x2d, self.K, self.dtype, self.dev)
         M = x2d.shape[0]
-        if x2d.data_ptr() % 16:
-            x2d = x2d.clone()  # the kernel reads x in 16-byte pieces; a fresh allocation is aligned
+        ko = self.ko
+        if ko is not None and not self.gathers(M):
+            x2d, ko = x2d.index_select(1, self.perm_keep[1]), None
+        if ko is None and x2d.data_ptr() % 16:
+            x2d = x2d.clone()  # the plain kernel reads x in 16-byte pieces; a fresh allocation is aligned
         y = torch.empty((M, self.N), dtype=self.dtype, device=self.dev)
         need = self.need
         if need is None:
@@ -575,15 +629,18 @@ class WoqGemvAnywCall:
             if buf is None or buf.numel() < need:
                 buf = _workspace(self.dev, need)
             wp, wn = buf.data_ptr(), buf.numel()
-        args = (x2d.data_ptr(), self.dt, self.qw, self.sc, self.qz, self.bi, y.data_ptr(), M, self.N, self.K, self.G, self.gs, self.bits,
-                wp, wn, stream)
+        tail = (self.qw, self.sc, self.qz, self.bi, y.data_ptr(), M, self.N, self.K, self.G, self.gs, self.bits, wp, wn, stream)
+        if ko is None:
+            fn, name, args = lib.inc_woq_gemv_anyw, "inc_woq_gemv_anyw", (x2d.data_ptr(), self.dt) + tail
+        else:  # the gather happens in the kernel
+            fn, name, args = lib.inc_woq_gemv_anyw_perm, "inc_woq_gemv_anyw_perm", (x2d.data_ptr(), self.dt, ko) + tail
         if _cur_device() == idx:
-            rc = lib.inc_woq_gemv_anyw(*args)
+            rc = fn(*args)
         else:
             with torch.cuda.device(self.dev):
-                rc = lib.inc_woq_gemv_anyw(*args)
+                rc = fn(*args)
         if rc != 0:
-            check(rc, "inc_woq_gemv_anyw")
+            check(rc, name)
         return y
 
 
@@ -783,6 +840,53 @@ class WoqGemmGroupCall:
         if rc == -2:  # INC_ERR_UNSUPPORTED: nothing was launched
             return None
         check(rc, name)
+        return ys
+
+
+class WoqGemvAnywGroupCall(WoqGemmGroupCall):
+    """inc_woq_gemv_anyw_multi: WoqGemmGroupCall for the members of ONE odd width (1, 2, 3, 5, 6, 7 bits) on up to 16 rows -- q / k / v or
+    gate / up in one launch over the strips of all members.  `parts`, `k_orders`, current() and the return value (a list of outputs, or
+    None where the library declines: nothing launched) are WoqGemmGroupCall's; with orders, part i's qweight is its K-sorted words
+    (sort_packed_k) and a part without an order gets the identity.  Output i equals WoqGemvAnywCall on part i bit for bit.  The workspace
+    is asked for 16 rows from the first call on (0 bytes where K fits one slice)."""
+
+    MAX_M = GEMV_ANYW_MAX_M
+
+    def __init__(self, parts, K, group_size, bits, dtype, k_orders=None):
+        if dtype is not torch.bfloat16 and dtype is not torch.float16:
+            raise ValueError(f"woq_gemv_anyw computes in bf16 or fp16, got {dtype}")
+        for p in parts:
+            _gemv_anyw_check_module(p[0], p[1], p[2], p[3], int(p[4]), K, group_size, bits)
+        super().__init__(parts, K, group_size, bits, dtype, k_orders=k_orders)
+        self.need = None
+
+    def __call__(self, x2d):
+        """x2d: contiguous [M, K] of the call's dtype on the call's device; more than 16 rows -> None."""
+        M = x2d.shape[0]
+        if M > self.MAX_M:
+            return None
+        if self.ko is None and x2d.data_ptr() % 16:
+            x2d = x2d.clone()  # the plain kernel reads x in 16-byte pieces; a fresh allocation is aligned
+        need = self.need
+        if need is None:
+            need = self.need = lib.inc_woq_gemv_anyw_multi_workspace_bytes(self.n, self.MAX_M, self.Narr, self.K, self.bits)
+        ys = [torch.empty((M, N), dtype=self.dtype, device=self.dev) for N in self.Ns]
+        for i, y in enumerate(ys):
+            self.yarr[i] = y.data_ptr()
+        idx = self.dev_index
+        stream = _raw_stream(idx)
+        wp, wn = None, 0
+        if need > 0:
+            buf = _ws_cache.get((idx, stream))
+            if buf is None or buf.numel() < need:
+                buf = _workspace(self.dev, need)
+            wp, wn = buf.data_ptr(), buf.numel()
+        with torch.cuda.device(self.dev):
+            rc = lib.inc_woq_gemv_anyw_multi(self.n, x2d.data_ptr(), self.dt, self.ko, self.qw, self.sc, self.qz, self.bi, self.yarr, M, self.Narr,
+                                             self.K, self.gs, self.bits, wp, wn, stream)
+        if rc == -2:  # INC_ERR_UNSUPPORTED: nothing was launched
+            return None
+        check(rc, "inc_woq_gemv_anyw_multi")
         return ys
 
 

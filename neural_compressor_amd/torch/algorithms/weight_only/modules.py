@@ -285,7 +285,8 @@ class MI355XWeightOnlyLinear(WeightOnlyLinear):
                     and (not call.lut or (self.LUT_FUSED and x.numel() <= self.LUT_MAX_M * call.K))
                     and (call.ko is None or self.ACT_ORDER_FUSED_GATHER)
                     and (not call.anyw or (self.ODD_WIDTH_DECODE and not self.ODD_WIDTH_FUSED
-                                           and x.numel() <= min(self.ODD_WIDTH_DECODE_MAX_M, call.MAX_M) * call.K))):
+                                           and x.numel() <= min(self.ODD_WIDTH_DECODE_MAX_M, call.MAX_M) * call.K
+                                           and (call.ko is None or call.gather_max_mn == self.ODD_WIDTH_GATHER_MAX_MN)))):
                 y = call(x if x.dim() == 2 else x.view(-1, call.K))
                 return y if x.dim() == 2 else y.view(*x.shape[:-1], call.N)
         if x.dtype not in (torch.bfloat16, torch.float16):
@@ -302,12 +303,20 @@ class MI355XWeightOnlyLinear(WeightOnlyLinear):
             plan = "dense"  # (a group size the fast kernels do not take: see _forward_plan)
         if plan == "fused_lut" and x2d.shape[0] > self.LUT_MAX_M:
             plan = "dense"  # (prefill-sized batches: see LUT_MAX_M)
-        if (plan == "dense" and self._decode_anyw and self.ODD_WIDTH_DECODE and not self.ODD_WIDTH_FUSED
+        if (plan == "dense" and self.ODD_WIDTH_DECODE and not self.ODD_WIDTH_FUSED
+                and (self._decode_anyw or (self._decode_anyw_perm and self.ACT_ORDER_FUSED_GATHER))
                 and x2d.shape[0] <= min(self.ODD_WIDTH_DECODE_MAX_M, ops.GEMV_ANYW_MAX_M)):
             # 1 / 2 / 3 / 5 / 6 / 7 bits at decode: inc_woq_gemv_anyw streams the packed words once; recover() never runs (larger batches
-            # keep the dense route below, and drop the prepared call again)
-            call = d["_call"] = ops.WoqGemvAnywCall(self.qweight, self.scales, self.qzeros, self.bias, self.out_features, self.in_features,
-                                                    self.group_size, self.bits, x2d.dtype)
+            # keep the dense route below, and drop the prepared call again).  act_order modules: the K-sorted words and the gather inside
+            # the kernel (inc_woq_gemv_anyw_perm), still one launch
+            if self._decode_anyw:
+                call = ops.WoqGemvAnywCall(self.qweight, self.scales, self.qzeros, self.bias, self.out_features, self.in_features,
+                                           self.group_size, self.bits, x2d.dtype)
+            else:
+                call = ops.WoqGemvAnywCall(self._qweight_sorted, self.scales, self.qzeros, self.bias, self.out_features, self.in_features,
+                                           self.group_size, self.bits, x2d.dtype, k_order=self._k_order32, owner_qweight=self.qweight,
+                                           gather_max_mn=self.ODD_WIDTH_GATHER_MAX_MN)
+            d["_call"] = call
             gi = self.g_idx
             call.tag = (gi, None if gi is None else gi._version)
             y = call(x2d)
@@ -363,12 +372,25 @@ class MI355XWeightOnlyLinear(WeightOnlyLinear):
     # layout, contiguous groups of a power of two >= 32 or one per row, K % 32 == 0, N % 4 == 0, N >= 64) go through inc_woq_gemv_anyw,
     # one launch that reads the packed words once and never builds the dense weight; False = the dense route for every batch.
     # ODD_WIDTH_FUSED = True takes precedence (its plan is "fused").
+    # An act_order module of these widths (eligible in everything but its g_idx, which permutes whole groups) takes the same route
+    # through inc_woq_gemv_anyw_perm while ACT_ORDER_FUSED_GATHER is on too: the packed fields are sorted along K by group once per packed
+    # state (ops.sort_packed_k) and the kernel gathers the activations.  The K-sorted copy doubles such a module's packed-weight memory,
+    # as it does at 4 bits; with either switch off the module runs the dense route exactly as before (the copy stays until re-packing).
     ODD_WIDTH_DECODE = True
     # the kernel's own limit.  Measured so far (profiles/anyw_decode/anyw_decode_time.log): 3 bits, 4096^2, M = 1 / 4: 8.3 / 8.5 us against
     # 41.1 us for the dense route.  M = 16, 2 bits and the two other shapes of scripts/anyw_decode_time.py are NOT measured: 16 rests on
     # the kernel's work not depending on M (the MFMA takes 16 rows, live or not) while the dense route writes and re-reads a dense weight.
     # Lower it to 4 or 1 if a row of that script loses.
     ODD_WIDTH_DECODE_MAX_M = 16
+    # act_order modules of these widths: outputs (rows of x times out_features) up to which the activations are gathered INSIDE the kernel
+    # (inc_woq_gemv_anyw_perm, one launch).  Above it, up to ODD_WIDTH_DECODE_MAX_M rows, the prepared call runs x.index_select(1, k_order)
+    # + inc_woq_gemv_anyw on the K-sorted words: two launches, the same bits.  Every 64-column strip repeats the in-kernel gather and its
+    # 2-byte loads touch one cache line per (row, k), so its cost grows with rows x columns while the torch gather is paid once.  Measured
+    # (profiles/anyw_decode/anyw_group_time.log, 3 bits g128, us gathered | index_select form): 4096^2 M = 1 / 4 / 8 / 16: 9.3 | 12.7, 11.5 | 12.8,
+    # 14.5 | 13.0, 18.5 | 13.7; 11008 x 4096 (per module of the pair) M = 1 / 4: 16.7 | 17.6, 22.6 | 17.8.  The kernel wins up to 4 x 4096
+    # outputs and loses from 8 x 4096 and 4 x 11008 on; nothing in between is measured, so the limit is the largest product that won.
+    # woq_linear_group applies it to a group with act_order members through the widest member (beyond it: the single calls).
+    ODD_WIDTH_GATHER_MAX_MN = 4 * 4096
     # 4-bit row-packed modules (compression_dim = 1, dtype int / nf4 / fp4 / fp4_e2m1 / fp4_e2m1_bnb, no g_idx, K % 32 == 0, groups of
     # 32 k multiples): True = inc_woq_gemm_lut, False = HIP recover() into a transient dense weight + the library GEMM
     LUT_FUSED = True
@@ -395,6 +417,7 @@ class MI355XWeightOnlyLinear(WeightOnlyLinear):
         fusable = self.use_optimum_format and (self.group_size % self.n_pack == 0 if self.bits in (4, 8) else self.ODD_WIDTH_FUSED)
         self._k_order = self._k_order32 = self._qweight_sorted = None
         self._decode_anyw = self._decode_anyw_eligible()
+        self._decode_anyw_perm = False
         # group sizes that are neither a power of two >= 32 nor the whole row (e.g. 96) run inc_woq_gemm's general 128 x 128 tile kernel
         # above 16 rows: 190-245 us at 4096 x 4032 against 34-74 us for HIP recover() + the library GEMM (scripts/route_sweep.py) -- such
         # modules keep the fused form for decode-sized batches only
@@ -428,19 +451,31 @@ class MI355XWeightOnlyLinear(WeightOnlyLinear):
                         plan = "fused_g_idx"  # groups of uneven size: the library's general kernel looks the group up per k
                 else:
                     plan = "fused_g_idx"
+        if plan == "dense" and not self._decode_anyw and self.g_idx is not None and self._decode_anyw_eligible(any_g_idx=True):
+            # an odd width whose g_idx permutes whole groups: the plan stays "dense" (larger batches), decode gathers through the order
+            K = self.in_features
+            g = self.g_idx.to(torch.int64)
+            gs_eff = K if (self.group_size == -1 or self.group_size >= K) else self.group_size
+            order = torch.argsort(g, stable=True)
+            if torch.equal(g[order], torch.arange(K, device=g.device) // gs_eff):
+                self._qweight_sorted = ops.sort_packed_k(self.qweight, order, K, self.bits)
+                self._k_order = order
+                self._k_order32 = order.to(torch.int32)  # what inc_woq_gemv_anyw_perm reads
+                self._decode_anyw_perm = True
         if not self.use_optimum_format and self.LUT_FUSED and self._lut_eligible():
             plan = "fused_lut"
         self._plan_key, self._plan = key, plan
         return plan
 
-    def _decode_anyw_eligible(self):
-        """inc_woq_gemv_anyw takes the module at decode (ODD_WIDTH_DECODE)?  Recorded with the plan, once per packed state."""
+    def _decode_anyw_eligible(self, any_g_idx=False):
+        """inc_woq_gemv_anyw takes the module at decode (ODD_WIDTH_DECODE)?  Recorded with the plan, once per packed state.
+        `any_g_idx`: everything but the g_idx test (the gathered form's precondition)."""
         K, gs = self.in_features, self.group_size
         if (not self.use_optimum_format or not ops.gemv_anyw_takes(self.out_features, K, gs, self.bits)
                 or self.scales.dtype is not torch.float16 or not self.scales.is_contiguous() or not self.qweight.is_contiguous()
                 or not self.qzeros.is_contiguous() or self.qweight.data_ptr() % 16 or self.scales.data_ptr() % 8):
             return False
-        if self.g_idx is None:
+        if self.g_idx is None or any_g_idx:
             return True
         gs_eff = K if (gs == -1 or gs >= K) else gs
         return bool(torch.equal(self.g_idx.to(torch.int64), torch.arange(K, device=self.g_idx.device) // gs_eff))  # the contiguous one
@@ -487,6 +522,18 @@ def _group_member(m):
     return None
 
 
+def _anyw_group_member(m):
+    """(part, order) of a 1 / 2 / 3 / 5 / 6 / 7-bit module in a one-launch decode group (inc_woq_gemv_anyw_multi), or None: a module that
+    decodes through inc_woq_gemv_anyw, or -- while ACT_ORDER_FUSED_GATHER is on -- through inc_woq_gemv_anyw_perm."""
+    if m._forward_plan() != "dense" or not m.ODD_WIDTH_DECODE or m.ODD_WIDTH_FUSED:
+        return None
+    if m._decode_anyw:
+        return (m.qweight, m.scales, m.qzeros, m.bias, m.out_features), None
+    if m._decode_anyw_perm and m.ACT_ORDER_FUSED_GATHER:
+        return (m._qweight_sorted, m.scales, m.qzeros, m.bias, m.out_features), m._k_order32
+    return None
+
+
 def woq_linear_group(x, modules):
     """[m(x) for m in modules] for packed modules that multiply the SAME activation -- q / k / v of an attention block, gate / up of
     an MLP -- as ONE launch (inc_woq_gemm_multi) when x is a decode-sized batch (<= 64 rows).  Each module keeps its own buffers and
@@ -498,20 +545,28 @@ def woq_linear_group(x, modules):
     kernel with the steps per wave chosen from the strips of all members together, while a single call at M <= 4 on a small layer
     (N, K <= 4096) takes the no-split kernel and otherwise chooses from its own strips -- the fp32 summation order differs, so an
     output may move by one unit of the 16-bit type depending on eligibility (M <= 64 or not, the siblings, a declined batch).
+    Members of one odd width (1, 2, 3, 5, 6, 7 bits) that all decode through inc_woq_gemv_anyw or its gathered form go out as ONE
+    inc_woq_gemv_anyw_multi launch up to min(ODD_WIDTH_DECODE_MAX_M, 16) rows -- with act_order members up to ODD_WIDTH_GATHER_MAX_MN
+    outputs of the widest member; there every output IS the single call's bit for bit (the K-slices depend on K and the width alone).
     Anything the batched launch does not cover (prefill-sized x, irregular g_idx plans, other widths, non-optimum layouts, a dtype
     other than bf16 / fp16, x on another device or of another width) is the plain list of single calls: the reference's forward
     per module (modules.py:594-610)."""
     mods = list(modules)
     m0 = mods[0]
     ok = (len(mods) >= 2 and x.dtype in (torch.bfloat16, torch.float16) and x.is_cuda and x.numel() > 0
-          and all(isinstance(m, MI355XWeightOnlyLinear) and m.bits in (4, 8) and m.bits == m0.bits and m.in_features == m0.in_features and m.group_size == m0.group_size
+          and all(isinstance(m, MI355XWeightOnlyLinear) and m.bits == m0.bits and m.in_features == m0.in_features and m.group_size == m0.group_size
                   for m in mods)
           and x.device == m0.qweight.device and x.shape[-1] == m0.in_features)
-    members = [_group_member(m) for m in mods] if ok else None
+    anyw = ok and m0.bits in ops.GEMV_ANYW_BITS
+    ok = ok and (anyw or m0.bits in (4, 8))
+    members = [(_anyw_group_member if anyw else _group_member)(m) for m in mods] if ok else None
     if ok and all(mem is not None for mem in members):
         K = m0.in_features
         x2d = x.reshape(-1, K)
-        if x2d.shape[0] <= 64:
+        max_m = min([ops.GEMV_ANYW_MAX_M] + [m.ODD_WIDTH_DECODE_MAX_M for m in mods]) if anyw else 64
+        if anyw and any(mem[1] is not None for mem in members):  # (the gather inside the kernel: see the attribute)
+            max_m = min(max_m, min(m.ODD_WIDTH_GATHER_MAX_MN for m in mods) // max(m.out_features for m in mods))
+        if x2d.shape[0] <= max_m:
             if not x2d.is_contiguous():
                 x2d = x2d.contiguous()
             parts = [mem[0] for mem in members]
@@ -527,7 +582,8 @@ def woq_linear_group(x, modules):
             if call is None or not call.current(parts, orders):
                 if len(cache) >= 8:
                     cache.clear()
-                call = cache[key] = ops.WoqGemmGroupCall(parts, K, m0.group_size, m0.bits, x.dtype, k_orders=orders)
+                cls = ops.WoqGemvAnywGroupCall if anyw else ops.WoqGemmGroupCall
+                call = cache[key] = cls(parts, K, m0.group_size, m0.bits, x.dtype, k_orders=orders)
             ys = call(x2d)
             if ys is not None:
                 return [y.view(*x.shape[:-1], m.out_features) for y, m in zip(ys, mods)]
