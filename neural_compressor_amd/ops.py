@@ -216,6 +216,42 @@ _ws_retired = []
 
 _ws_bytes_cache = {}
 
+_raw_stream = torch._C._cuda_getCurrentRawStream  # (device index) -> hipStream_t of torch's current stream, no Stream object
+_cur_device = torch._C._cuda_getDevice
+
+
+def _ws_lookup(dev, idx, need):
+    """(address, bytes, stream) for a launch on torch's current stream of device `dev` (index `idx`) that needs `need` workspace
+    bytes: the (device, stream) workspace, grown when it is too small; (None, 0, stream) when the launch needs none."""
+    stream = _raw_stream(idx)
+    if need <= 0:
+        return None, 0, stream
+    buf = _ws_cache.get((idx, stream))
+    if buf is None or buf.numel() < need:
+        buf = _workspace(dev, need)
+    return buf.data_ptr(), buf.numel(), stream
+
+
+def _launch(dev, idx, fn, name, args, may_decline=False):
+    """rc = fn(*args), under the device guard only when `dev` (index `idx`) is not the current device; a non-zero rc raises through
+    check(rc, name) -- except INC_ERR_UNSUPPORTED (-2: nothing was launched) with `may_decline`, which the caller turns into None."""
+    if _cur_device() == idx:
+        rc = fn(*args)
+    else:
+        with torch.cuda.device(dev):
+            rc = fn(*args)
+    if rc != 0 and not (may_decline and rc == -2):
+        check(rc, name)
+    return rc
+
+
+def _check_k_order(k_order, K):
+    """An act_order gather order: int32 [K]."""
+    if k_order.dtype is not torch.int32:
+        raise TypeError(f"k_order must be int32, got {k_order.dtype}")
+    if k_order.dim() != 1 or k_order.shape[0] != K:
+        raise ValueError(f"k_order must hold K = {K} entries, got {tuple(k_order.shape)}")
+
 
 def woq_gemm(x2d, qweight, scales, qzeros, bias, N, K, group_size, bits, g_idx=None):
     """y[M,N] = x[M,K] @ dequant(qweight)^T + bias, fused (== INCWeightOnlyLinear.forward, modules.py:594-610).
@@ -231,28 +267,16 @@ def woq_gemm(x2d, qweight, scales, qzeros, bias, N, K, group_size, bits, g_idx=N
     if bias is not None and bias.dtype != x2d.dtype:
         bias = bias.to(x2d.dtype)
     M = x2d.shape[0]
-    G = scales.shape[0]
     y = torch.empty((M, N), dtype=x2d.dtype, device=dev)
-    ws = None
     key = (M, N, K)
     nbytes = _ws_bytes_cache.get(key)
     if nbytes is None:
         nbytes = _ws_bytes_cache[key] = lib.inc_woq_gemm_workspace_bytes(M, N, K)
-    if nbytes > 0:  # M <= 16: arrival counters + split-K partials; medium M: split-K slabs of the 256x256 kernel
-        ws = _workspace(dev, nbytes)
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    args = (
+    # (M <= 16: arrival counters + split-K partials; medium M: split-K slabs of the 256x256 kernel)
+    wp, wn, stream = _ws_lookup(dev, dev.index, nbytes)
+    _launch(dev, dev.index, lib.inc_woq_gemm, "inc_woq_gemm", (
         x2d.data_ptr(), INC_BF16 if x2d.dtype is torch.bfloat16 else INC_F16, qweight.data_ptr(), scales.data_ptr(),
-        qzeros.data_ptr(), _ptr(g_idx), _ptr(bias), y.data_ptr(), M, N, K, G, group_size, bits, _ptr(ws),
-        0 if ws is None else ws.numel(), stream,
-    )
-    if torch.cuda.current_device() == dev.index:
-        rc = lib.inc_woq_gemm(*args)
-    else:
-        with torch.cuda.device(dev):
-            rc = lib.inc_woq_gemm(*args)
-    if rc != 0:
-        check(rc, "inc_woq_gemm")
+        qzeros.data_ptr(), _ptr(g_idx), _ptr(bias), y.data_ptr(), M, N, K, scales.shape[0], group_size, bits, wp, wn, stream))
     return y
 
 
@@ -267,7 +291,7 @@ def woq_gemm_perm(x2d, k_order, qweight_sorted, scales, qzeros, bias, N, K, grou
     anything else raises -- gather x and call woq_gemm there, which WoqGemmCall(k_order=...) does by itself."""
     if k_order.dtype is not torch.int32:
         raise TypeError(f"k_order must be int32, got {k_order.dtype}")
-    if k_order.dim() != 1 or k_order.shape[0] != K or x2d.dim() != 2 or x2d.shape[1] != K:
+    if k_order.dim() != 1 or k_order.shape[0] != K or x2d.dim() != 2 or x2d.shape[1] != K:  # (one message for both shapes)
         raise ValueError(f"k_order must hold K = {K} entries and x2d be [M, {K}]; got {tuple(k_order.shape)} and {tuple(x2d.shape)}")
     dev = x2d.device
     if k_order.device != dev:
@@ -283,14 +307,10 @@ def woq_gemm_perm(x2d, k_order, qweight_sorted, scales, qzeros, bias, N, K, grou
     nbytes = _ws_bytes_cache.get((M, N, K))
     if nbytes is None:
         nbytes = _ws_bytes_cache[(M, N, K)] = lib.inc_woq_gemm_workspace_bytes(M, N, K)
-    with torch.cuda.device(dev):
-        ws = _workspace(dev, nbytes) if nbytes > 0 else None
-        rc = lib.inc_woq_gemm_perm(
-            x2d.data_ptr(), INC_BF16 if x2d.dtype is torch.bfloat16 else INC_F16, k_order.data_ptr(), qweight_sorted.data_ptr(),
-            scales.data_ptr(), qzeros.data_ptr(), _ptr(bias), y.data_ptr(), M, N, K, scales.shape[0], group_size, bits, _ptr(ws),
-            0 if ws is None else ws.numel(), torch.cuda.current_stream(dev).cuda_stream)
-    if rc != 0:
-        check(rc, "inc_woq_gemm_perm")
+    wp, wn, stream = _ws_lookup(dev, dev.index, nbytes)
+    _launch(dev, dev.index, lib.inc_woq_gemm_perm, "inc_woq_gemm_perm", (
+        x2d.data_ptr(), INC_BF16 if x2d.dtype is torch.bfloat16 else INC_F16, k_order.data_ptr(), qweight_sorted.data_ptr(),
+        scales.data_ptr(), qzeros.data_ptr(), _ptr(bias), y.data_ptr(), M, N, K, scales.shape[0], group_size, bits, wp, wn, stream))
     return y
 
 
@@ -317,58 +337,37 @@ def woq_gemm_route(M, N, K, group_size, bits, dtype, has_g_idx=False, x_ptr=0, y
                 x_vec_ok=o[4].value, need=need.value)
 
 
-_raw_stream = torch._C._cuda_getCurrentRawStream  # (device index) -> hipStream_t of torch's current stream, no Stream object
-_cur_device = torch._C._cuda_getDevice
-
-
 def _none():
     return None
 
 
-class WoqGemmCall:
-    """inc_woq_gemm with everything that does not change between calls resolved once (the decode path: the kernel is ~6 us,
-    so the host side counts).  Built by MI355XWeightOnlyLinear for its packed buffers; per call only the activation pointer,
-    the output, the stream and the (device, stream) workspace are looked up.  Holds references to the tensors whose addresses
-    it caches; the owner rebuilds it when a buffer is replaced.
+def _versions(tensors):
+    return tuple(None if t is None else t._version for t in tensors)
 
-    With `k_order` (int32 [K]; act_order modules) `qweight` is the K-sorted packed weight and the call computes x[:, k_order] W^T:
-    up to 64 rows through inc_woq_gemm_perm wherever the shape takes a streaming decode route (the gather happens inside the
-    kernel: one launch), otherwise x2d.index_select(1, k_order) and the ordinary launch.  `owner_qweight` is the buffer the sorted
-    copy was made from: current() is asked about that one."""
 
-    __slots__ = ("dev", "dev_index", "dtype", "dt", "N", "K", "G", "gs", "bits", "qw", "sc", "qz", "gi", "bi", "keep", "need", "fn",
-                 "bias_conv", "versions", "tag", "ko", "perm_keep", "perm_versions", "perm_ok")
+def _unchanged(kept, versions, tensors):
+    """`tensors` are the very objects of `kept` (None entries included), none written to since `versions` = _versions(kept)?"""
+    if len(kept) != len(tensors):
+        return False
+    for a, v, b in zip(kept, versions, tensors):
+        if a is not b or (a is not None and a._version != v):
+            return False
+    return True
+
+
+class _PreparedCall:
+    """What the prepared calls below share.  Each resolves once whatever does not change between the calls of one packed module (or
+    group of modules): the device, the compute dtype and its code, the bias in the compute dtype, the addresses.  Each holds the
+    tensors whose addresses it caches and remembers their version counters, so that current() can tell the owner whether it still
+    describes the owner's buffers (same objects, not written to since); the owner rebuilds it otherwise.  Per call a subclass looks up
+    the workspace (_ws_lookup) and launches (_launch); argument layout, entry point and row limits are the subclass's."""
+
+    __slots__ = ("dev", "dev_index", "dtype", "dt", "bias_conv", "bi", "keep", "versions", "hold")
     lut = False  # (WoqGemmLutCall: True)
     anyw = False  # (WoqGemvAnywCall: True)
-    PERM_ROUTES = (9, 10, 11)  # GEMV16, STREAM_W4, STREAM_W8: the routes inc_woq_gemm_perm launches
-
-    def __init__(self, qweight, scales, qzeros, bias, N, K, group_size, bits, dtype, g_idx=None, k_order=None, owner_qweight=None):
-        if dtype is not torch.bfloat16 and dtype is not torch.float16:
-            raise TypeError("woq_gemm computes in bf16 or fp16")
-        if k_order is not None:
-            if k_order.dtype is not torch.int32:
-                raise TypeError(f"k_order must be int32, got {k_order.dtype}")
-            if k_order.dim() != 1 or k_order.shape[0] != K:
-                raise ValueError(f"k_order must hold K = {K} entries, got {tuple(k_order.shape)}")
-            if g_idx is not None:
-                raise ValueError("k_order goes with the K-sorted weight, whose groups are contiguous: no g_idx")
-        dev = _dev(qweight, scales, qzeros, bias, g_idx, k_order, owner_qweight)
-        self.ko = _ptr(k_order)
-        self.perm_keep = (qweight, k_order)
-        self.perm_versions = (qweight._version, None if k_order is None else k_order._version)
-        self.perm_ok = {}  # M -> inc_woq_gemm_perm takes it
-        self.keep = (qweight if owner_qweight is None else owner_qweight, scales, qzeros, bias, g_idx)
-        self.versions = tuple(None if t is None else t._version for t in self.keep)
-        if bias is not None and bias.dtype != dtype:
-            bias = bias.to(dtype)  # converted once (the packed module stores fp16, a bf16 model multiplies in bf16)
-        self.bias_conv = bias
-        self.dev, self.dev_index, self.dtype = dev, dev.index if dev.index is not None else torch.cuda.current_device(), dtype
-        self.dt = INC_BF16 if dtype is torch.bfloat16 else INC_F16
-        self.N, self.K, self.G, self.gs, self.bits = N, K, scales.shape[0], group_size, bits
-        self.qw, self.sc, self.qz, self.gi, self.bi = qweight.data_ptr(), scales.data_ptr(), qzeros.data_ptr(), _ptr(g_idx), _ptr(bias)
-        self.need = {}
-        self.tag = (None, None)  # (the owner's g_idx buffer, its version) when the owner's plan was chosen
-        self.fn = lib.inc_woq_gemm
+    ko = None  # (the act_order gather of WoqGemmCall / WoqGemvAnywCall; the batched calls: their members' orders)
+    gather_max_mn = None  # (WoqGemvAnywCall with a gather: the limit it was built for)
+    COMPUTES = (TypeError, "woq_gemm computes in bf16 or fp16")  # what a compute dtype other than bf16 / fp16 raises
 
     # a cache, not state: copies and pickles of the owning module start without it
     def __deepcopy__(self, memo):
@@ -377,14 +376,73 @@ class WoqGemmCall:
     def __reduce__(self):
         return (_none, ())
 
+    def _compute_dt(self, dtype):
+        if dtype is torch.bfloat16:
+            return INC_BF16
+        if dtype is torch.float16:
+            return INC_F16
+        exc, msg = self.COMPUTES
+        raise exc(msg.format(dtype))
+
+    def _bind(self, dev, dtype=None, dt=None, bias=None):
+        """The device side of the constructor; the bias is converted once (the packed module stores fp16, a bf16 model multiplies in
+        bf16)."""
+        self.dev, self.dev_index = dev, dev.index if dev.index is not None else torch.cuda.current_device()
+        self.dtype, self.dt = dtype, dt
+        if bias is not None and bias.dtype != dtype:
+            bias = bias.to(dtype)
+        self.bias_conv, self.bi = bias, _ptr(bias)
+
+    def _track(self, tensors):
+        """The tensors (entries may be None) current() is asked about."""
+        self.keep = tuple(tensors)
+        self.versions = _versions(self.keep)
+
     def current(self, qweight, scales, qzeros, bias, owner_g_idx=None):
         """Still describes these tensors (same objects, not written to since)?  `owner_g_idx`: the owner's g_idx buffer as it is now --
-        the call was built for the owner's plan at that time (`tag`), which a new or rewritten g_idx invalidates."""
+        the call was built for the owner's plan at that time, which a new or rewritten g_idx invalidates.  (The form of the
+        single-module calls; the batched ones have their own arguments.)"""
+        # _unchanged over the five, written out: this runs in front of every decode forward, and the loop is host time there
+        # (profiles/decode_host/)
         k, v = self.keep, self.versions
-        return (k[0] is qweight and k[1] is scales and k[2] is qzeros and k[3] is bias and qweight._version == v[0]
-                and scales._version == v[1] and qzeros._version == v[2] and (bias is None or bias._version == v[3])
-                and self.tag[0] is owner_g_idx and (owner_g_idx is None or owner_g_idx._version == self.tag[1])
+        return (k[0] is qweight and k[1] is scales and k[2] is qzeros and k[3] is bias and k[4] is owner_g_idx
+                and qweight._version == v[0] and scales._version == v[1] and (qzeros is None or qzeros._version == v[2])
+                and (bias is None or bias._version == v[3]) and (owner_g_idx is None or owner_g_idx._version == v[4])
                 and (self.ko is None or (self.perm_keep[0]._version, self.perm_keep[1]._version) == self.perm_versions))
+
+
+class WoqGemmCall(_PreparedCall):
+    """inc_woq_gemm with everything that does not change between calls resolved once (the decode path: the kernel is ~6 us,
+    so the host side counts).  Built by MI355XWeightOnlyLinear for its packed buffers; per call only the activation pointer,
+    the output, the stream and the (device, stream) workspace are looked up.  Holds references to the tensors whose addresses
+    it caches; the owner rebuilds it when a buffer is replaced.
+
+    With `k_order` (int32 [K]; act_order modules) `qweight` is the K-sorted packed weight and the call computes x[:, k_order] W^T:
+    up to 64 rows through inc_woq_gemm_perm wherever the shape takes a streaming decode route (the gather happens inside the
+    kernel: one launch), otherwise x2d.index_select(1, k_order) and the ordinary launch.  `owner_qweight` is the buffer the sorted
+    copy was made from: current() is asked about that one.  `owner_g_idx`: the owner's g_idx buffer when its plan was chosen."""
+
+    __slots__ = ("N", "K", "G", "gs", "bits", "qw", "sc", "qz", "gi", "need", "ko", "perm_keep", "perm_versions", "perm_ok")
+    PERM_ROUTES = (9, 10, 11)  # GEMV16, STREAM_W4, STREAM_W8: the routes inc_woq_gemm_perm launches
+
+    def __init__(self, qweight, scales, qzeros, bias, N, K, group_size, bits, dtype, g_idx=None, k_order=None, owner_qweight=None,
+                 owner_g_idx=None):
+        dt = self._compute_dt(dtype)
+        if k_order is not None:
+            _check_k_order(k_order, K)
+            if g_idx is not None:
+                raise ValueError("k_order goes with the K-sorted weight, whose groups are contiguous: no g_idx")
+        dev = _dev(qweight, scales, qzeros, bias, g_idx, k_order, owner_qweight)
+        self.ko = _ptr(k_order)
+        self.perm_keep = (qweight, k_order)
+        self.perm_versions = _versions(self.perm_keep)
+        self.perm_ok = {}  # M -> inc_woq_gemm_perm takes it
+        self._track((qweight if owner_qweight is None else owner_qweight, scales, qzeros, bias, owner_g_idx))
+        self.hold = g_idx
+        self._bind(dev, dtype, dt, bias)
+        self.N, self.K, self.G, self.gs, self.bits = N, K, scales.shape[0], group_size, bits
+        self.qw, self.sc, self.qz, self.gi = qweight.data_ptr(), scales.data_ptr(), qzeros.data_ptr(), _ptr(g_idx)
+        self.need = {}
 
     def _perm_takes(self, M):
         """inc_woq_gemm_perm launches for M rows: the dispatcher's own plan for the shape (host only; y comes from torch.empty and
@@ -397,7 +455,7 @@ class WoqGemmCall:
         """x2d: contiguous [M, K] of the call's dtype on the call's device (the owner checks)."""
         M = x2d.shape[0]
         # the pointers between dtype and bias: (qweight, scales, qzeros, g_idx), or (k_order, qweight, scales, qzeros) for inc_woq_gemm_perm
-        fn, name, a2, a3, a4, a5 = self.fn, "inc_woq_gemm", self.qw, self.sc, self.qz, self.gi
+        fn, name, a2, a3, a4, a5 = lib.inc_woq_gemm, "inc_woq_gemm", self.qw, self.sc, self.qz, self.gi
         if self.ko is not None:
             ok = self.perm_ok.get(M)
             if ok is None:
@@ -410,6 +468,8 @@ class WoqGemmCall:
         need = self.need.get(M)
         if need is None:
             need = self.need[M] = lib.inc_woq_gemm_workspace_bytes(M, self.N, self.K)
+        # _ws_lookup and _launch, written out: of all prepared routes these two (4 / 8 bits, plain and act_order) are the ones whose host
+        # enqueue time the two extra Python frames moved by more than its spread between processes (profiles/decode_host/)
         idx = self.dev_index
         stream = _raw_stream(idx)
         wp, wn = None, 0
@@ -531,7 +591,7 @@ def woq_gemv_anyw(x2d, qweight, scales, qzeros, bias, N, K, group_size, bits):
     return WoqGemvAnywCall(qweight, scales, qzeros, bias, N, K, group_size, bits, x2d.dtype)(x2d, checked=False)
 
 
-class WoqGemvAnywCall:
+class WoqGemvAnywCall(_PreparedCall):
     """inc_woq_gemv_anyw with the module side resolved once (the decode path of the odd widths, like WoqGemmCall): data pointers, the
     bias converted to the compute dtype, the K-slices per M.  Per call only x, y, the stream and the workspace are looked up.
     `current()` has WoqGemmCall's contract (same tensors, version counters unchanged).
@@ -547,56 +607,30 @@ class WoqGemvAnywCall:
     kernel instead (two launches, the same bits: every 64-column strip repeats the in-kernel gather, so its cost grows with rows x
     columns while the torch gather is paid once; None = always inside the kernel).  See gathers()."""
 
-    __slots__ = ("dev", "dev_index", "dtype", "dt", "N", "K", "G", "gs", "bits", "qw", "sc", "qz", "bi", "keep", "versions", "bias_conv",
-                 "need", "tag", "ko", "perm_keep", "perm_versions", "gather_max_mn")
-    lut = False
+    __slots__ = ("N", "K", "G", "gs", "bits", "qw", "sc", "qz", "need", "ko", "perm_keep", "perm_versions", "gather_max_mn")
     anyw = True
     MAX_M = GEMV_ANYW_MAX_M
+    COMPUTES = (ValueError, "woq_gemv_anyw computes in bf16 or fp16, got {}")
 
     def __init__(self, qweight, scales, qzeros, bias, N, K, group_size, bits, dtype, k_order=None, owner_qweight=None,
-                 gather_max_mn=None):
-        if dtype is not torch.bfloat16 and dtype is not torch.float16:
-            raise ValueError(f"woq_gemv_anyw computes in bf16 or fp16, got {dtype}")
+                 gather_max_mn=None, owner_g_idx=None):
+        dt = self._compute_dt(dtype)
         self.gather_max_mn = gather_max_mn
         self.G = _gemv_anyw_check_module(qweight, scales, qzeros, bias, N, K, group_size, bits)
         if qweight.data_ptr() % 16:
             raise ValueError("woq_gemv_anyw: qweight must be 16-byte aligned")
         if k_order is not None:
-            if k_order.dtype is not torch.int32:
-                raise TypeError(f"k_order must be int32, got {k_order.dtype}")
-            if k_order.dim() != 1 or k_order.shape[0] != K:
-                raise ValueError(f"k_order must hold K = {K} entries, got {tuple(k_order.shape)}")
+            _check_k_order(k_order, K)
             if k_order.device != qweight.device or not k_order.is_contiguous() or k_order.data_ptr() % 16:
                 raise ValueError("woq_gemv_anyw: k_order must be contiguous, 16-byte aligned and on the weights' device")
         self.ko = _ptr(k_order)
         self.perm_keep = (qweight, k_order)
-        self.perm_versions = (qweight._version, None if k_order is None else k_order._version)
-        self.keep = (qweight if owner_qweight is None else owner_qweight, scales, qzeros, bias)
-        self.versions = tuple(None if t is None else t._version for t in self.keep)
-        if bias is not None and bias.dtype != dtype:
-            bias = bias.to(dtype)  # converted once (the packed module stores fp16, a bf16 model multiplies in bf16)
-        self.bias_conv = bias
-        dev = qweight.device
-        self.dev, self.dev_index, self.dtype = dev, dev.index if dev.index is not None else torch.cuda.current_device(), dtype
-        self.dt = INC_BF16 if dtype is torch.bfloat16 else INC_F16
+        self.perm_versions = _versions(self.perm_keep)
+        self._track((qweight if owner_qweight is None else owner_qweight, scales, qzeros, bias, owner_g_idx))
+        self._bind(qweight.device, dtype, dt, bias)
         self.N, self.K, self.gs, self.bits = N, K, group_size, bits
-        self.qw, self.sc, self.qz, self.bi = qweight.data_ptr(), scales.data_ptr(), qzeros.data_ptr(), _ptr(bias)
+        self.qw, self.sc, self.qz = qweight.data_ptr(), scales.data_ptr(), qzeros.data_ptr()
         self.need = None
-        self.tag = (None, None)  # (the owner's g_idx buffer, its version) when the owner found the module eligible
-
-    # a cache, not state: copies and pickles of the owning module start without it
-    def __deepcopy__(self, memo):
-        return None
-
-    def __reduce__(self):
-        return (_none, ())
-
-    def current(self, qweight, scales, qzeros, bias, owner_g_idx=None):
-        k, v = self.keep, self.versions
-        return (k[0] is qweight and k[1] is scales and k[2] is qzeros and k[3] is bias and qweight._version == v[0]
-                and scales._version == v[1] and qzeros._version == v[2] and (bias is None or bias._version == v[3])
-                and self.tag[0] is owner_g_idx and (owner_g_idx is None or owner_g_idx._version == self.tag[1])
-                and (self.ko is None or (self.perm_keep[0]._version, self.perm_keep[1]._version) == self.perm_versions))
 
     def slices(self, M):
         """K-slices of the launch for M rows (inc_woq_gemv_anyw_slices: host only)."""
@@ -621,26 +655,12 @@ class WoqGemvAnywCall:
         need = self.need
         if need is None:
             need = self.need = lib.inc_woq_gemv_anyw_workspace_bytes(self.MAX_M, self.N, self.K, self.bits)
-        idx = self.dev_index
-        stream = _raw_stream(idx)
-        wp, wn = None, 0
-        if need > 0:
-            buf = _ws_cache.get((idx, stream))
-            if buf is None or buf.numel() < need:
-                buf = _workspace(self.dev, need)
-            wp, wn = buf.data_ptr(), buf.numel()
+        wp, wn, stream = _ws_lookup(self.dev, self.dev_index, need)
         tail = (self.qw, self.sc, self.qz, self.bi, y.data_ptr(), M, self.N, self.K, self.G, self.gs, self.bits, wp, wn, stream)
         if ko is None:
-            fn, name, args = lib.inc_woq_gemv_anyw, "inc_woq_gemv_anyw", (x2d.data_ptr(), self.dt) + tail
+            _launch(self.dev, self.dev_index, lib.inc_woq_gemv_anyw, "inc_woq_gemv_anyw", (x2d.data_ptr(), self.dt) + tail)
         else:  # the gather happens in the kernel
-            fn, name, args = lib.inc_woq_gemv_anyw_perm, "inc_woq_gemv_anyw_perm", (x2d.data_ptr(), self.dt, ko) + tail
-        if _cur_device() == idx:
-            rc = fn(*args)
-        else:
-            with torch.cuda.device(self.dev):
-                rc = fn(*args)
-        if rc != 0:
-            check(rc, name)
+            _launch(self.dev, self.dev_index, lib.inc_woq_gemv_anyw_perm, "inc_woq_gemv_anyw_perm", (x2d.data_ptr(), self.dt, ko) + tail)
         return y
 
 
@@ -654,50 +674,30 @@ def woq_gemm_lut(x2d, qweight, table16, scales, qzeros, bias, N, K, group_size, 
     return WoqGemmLutCall(qweight, table16, scales, qzeros, bias, N, K, group_size, scale_round, x2d.dtype)(x2d)
 
 
-class WoqGemmLutCall:
+class WoqGemmLutCall(_PreparedCall):
     """inc_woq_gemm_lut with the module side resolved once (the decode path, like WoqGemmCall): the bias converted to the compute
     dtype, the table as a host array, the row sizes in bytes; per call only x, y, the stream and the (device, stream) workspace.
-    `current()` has WoqGemmCall's contract (same tensors, version counters unchanged)."""
+    `current()` has WoqGemmCall's contract (same tensors, version counters unchanged; these modules have no g_idx)."""
 
     lut = True
-    anyw = False
-    ko = None  # (WoqGemmCall: the act_order gather)
+    COMPUTES = (TypeError, "woq_gemm_lut computes in bf16 or fp16")
 
     def __init__(self, qweight, table16, scales, qzeros, bias, N, K, group_size, scale_round, dtype):
         import ctypes
 
         dev = _dev(qweight, scales, qzeros, bias)
-        if dtype is not torch.bfloat16 and dtype is not torch.float16:
-            raise TypeError("woq_gemm_lut computes in bf16 or fp16")
+        dt = self._compute_dt(dtype)
         if len(table16) != 16:
             raise ValueError("table16 holds the 16 values of a 4-bit field")
-        self.keep = (qweight, scales, qzeros, bias)
-        self.versions = tuple(None if t is None else t._version for t in self.keep)
-        if bias is not None and bias.dtype != dtype:
-            bias = bias.to(dtype)  # converted once
-        self.bias_conv = bias
-        self.dev, self.dev_index, self.dtype = dev, dev.index if dev.index is not None else torch.cuda.current_device(), dtype
-        self.dt = INC_BF16 if dtype is torch.bfloat16 else INC_F16
+        self._track((qweight, scales, qzeros, bias, None))
+        self._bind(dev, dtype, dt, bias)
         self.N, self.K, self.G, self.gs = N, K, scales.shape[1], group_size
         self.table = (ctypes.c_float * 16)(*[float(v) for v in table16])
         self.sdt, self.rnd = dtype_code(scales.dtype), int(bool(scale_round))
         self.qw, self.row_bytes = qweight.data_ptr(), qweight.shape[1] * qweight.element_size()
         self.qz, self.zrow_bytes = (None, 0) if qzeros is None else (qzeros.data_ptr(), qzeros.shape[1] * qzeros.element_size())
-        self.sc, self.bi = scales.data_ptr(), _ptr(bias)
+        self.sc = scales.data_ptr()
         self.need = {}
-
-    # a cache, not state: copies and pickles of the owning module start without it
-    def __deepcopy__(self, memo):
-        return None
-
-    def __reduce__(self):
-        return (_none, ())
-
-    def current(self, qweight, scales, qzeros, bias, owner_g_idx=None):
-        k, v = self.keep, self.versions
-        return (k[0] is qweight and k[1] is scales and k[2] is qzeros and k[3] is bias and owner_g_idx is None
-                and qweight._version == v[0] and scales._version == v[1] and (qzeros is None or qzeros._version == v[2])
-                and (bias is None or bias._version == v[3]))
 
     def __call__(self, x2d):
         """x2d: contiguous [M, K] of the call's dtype on the call's device."""
@@ -708,44 +708,58 @@ class WoqGemmLutCall:
         need = self.need.get(M)
         if need is None:
             need = self.need[M] = lib.inc_woq_gemm_lut_workspace_bytes(M, self.N, self.K)
-        idx = self.dev_index
-        stream = _raw_stream(idx)
-        wp, wn = None, 0
-        if need > 0:
-            buf = _ws_cache.get((idx, stream))
-            if buf is None or buf.numel() < need:
-                buf = _workspace(self.dev, need)
-            wp, wn = buf.data_ptr(), buf.numel()
-        args = (x2d.data_ptr(), self.dt, self.qw, self.row_bytes, self.table, self.sc, self.sdt, self.rnd, self.qz, self.zrow_bytes,
-                self.bi, y.data_ptr(), M, self.N, self.K, self.G, self.gs, wp, wn, stream)
-        if _cur_device() == idx:
-            rc = lib.inc_woq_gemm_lut(*args)
-        else:
-            with torch.cuda.device(self.dev):
-                rc = lib.inc_woq_gemm_lut(*args)
-        if rc != 0:
-            check(rc, "inc_woq_gemm_lut")
+        wp, wn, stream = _ws_lookup(self.dev, self.dev_index, need)
+        _launch(self.dev, self.dev_index, lib.inc_woq_gemm_lut, "inc_woq_gemm_lut", (
+            x2d.data_ptr(), self.dt, self.qw, self.row_bytes, self.table, self.sc, self.sdt, self.rnd, self.qz, self.zrow_bytes,
+            self.bi, y.data_ptr(), M, self.N, self.K, self.G, self.gs, wp, wn, stream))
         return y
 
 
 def _check_k_orders(k_orders, n, K):
-    """k_orders of a group call: None, or one int32 [K] tensor or None per part (WoqGemmCall's messages for each)."""
+    """k_orders of a batched call: None, or one int32 [K] tensor or None per part (WoqGemmCall's messages for each)."""
     if k_orders is None:
         return None
     k_orders = list(k_orders)
     if len(k_orders) != n:
         raise ValueError(f"k_orders must have one entry per part ({n}), got {len(k_orders)}")
     for ko in k_orders:
-        if ko is None:
-            continue
-        if ko.dtype is not torch.int32:
-            raise TypeError(f"k_order must be int32, got {ko.dtype}")
-        if ko.dim() != 1 or ko.shape[0] != K:
-            raise ValueError(f"k_order must hold K = {K} entries, got {tuple(ko.shape)}")
+        if ko is not None:
+            _check_k_order(ko, K)
     return k_orders if any(ko is not None for ko in k_orders) else None
 
 
-class WoqGemmGroupCall:
+class _BatchedCall(_PreparedCall):
+    """The batched calls: `parts` = [(qweight, scales, qzeros, bias or None, N), ...] multiply the SAME activation.  `k_orders`
+    (act_order members): one int32 [K] tensor or None per part; with any entry given, part i's qweight is its K-sorted words and its
+    activations are gathered through k_orders[i] inside the kernel; a part without an order gets the identity, built once per call
+    object."""
+
+    def _bind_parts(self, parts, K, dtype, dt, k_orders):
+        """-> the order tensor of every part (the identity where it has none), or None when no part has one."""
+        dev = _dev(*[t for p in parts for t in p[:4]], *(k_orders or ()))
+        self._bind(dev, dtype, dt)
+        self._track(t for p in parts for t in p[:4])
+        self.orders = k_orders  # as given (None entries included): what current() compares
+        self.order_versions = None if k_orders is None else _versions(k_orders)
+        used = None
+        if k_orders is not None:
+            ident = torch.arange(K, dtype=torch.int32, device=dev) if any(ko is None for ko in k_orders) else None
+            used = [ident if ko is None else ko for ko in k_orders]
+        self.hold = (parts, used)
+        return used
+
+    def _parts_current(self, parts, k_orders):
+        """Still describes these parts (same tensors, not written to since), the order tensors included?"""
+        if not _unchanged(self.keep, self.versions, [t for p in parts for t in p[:4]]):
+            return False
+        if k_orders is not None and all(ko is None for ko in k_orders):
+            k_orders = None
+        if self.orders is None or k_orders is None:
+            return self.orders is None and k_orders is None
+        return _unchanged(self.orders, self.order_versions, k_orders)
+
+
+class WoqGemmGroupCall(_BatchedCall):
     """inc_woq_gemm_multi for modules that multiply the SAME activation (q / k / v; gate / up): ONE launch instead of one per module
     (a decode call of one module is ~2 us of weight streaming behind ~5 us of launch boundary and hand-off).  The state dict is
     untouched: the call holds the modules' packed buffers by reference and hands the library host arrays of their addresses.
@@ -760,19 +774,13 @@ class WoqGemmGroupCall:
     def __init__(self, parts, K, group_size, bits, dtype, k_orders=None):
         import ctypes
 
-        if dtype is not torch.bfloat16 and dtype is not torch.float16:
-            raise TypeError("woq_gemm computes in bf16 or fp16")
-        self.n = len(parts)
-        k_orders = _check_k_orders(k_orders, self.n, K)
-        self.dev = _dev(*[t for p in parts for t in p[:4]], *(k_orders or ()))
-        self.dev_index = self.dev.index if self.dev.index is not None else torch.cuda.current_device()
-        self.K, self.gs, self.bits, self.dtype = K, group_size, bits, dtype
-        self.dt = INC_BF16 if dtype is torch.bfloat16 else INC_F16
+        dt = self._compute_dt(dtype)
+        n = self.n = len(parts)
+        used = self._bind_parts(parts, K, dtype, dt, _check_k_orders(k_orders, n, K))
+        self.K, self.gs, self.bits = K, group_size, bits
         bias = [None if p[3] is None else (p[3] if p[3].dtype == dtype else p[3].to(dtype)) for p in parts]
-        self.keep = (parts, bias)
-        self.versions = tuple(None if t is None else t._version for p in parts for t in p[:4])
+        self.bias_conv = bias
         self.Ns = [int(p[4]) for p in parts]
-        n = self.n
         self.qw = (ctypes.c_void_p * n)(*[p[0].data_ptr() for p in parts])
         self.sc = (ctypes.c_void_p * n)(*[p[1].data_ptr() for p in parts])
         self.qz = (ctypes.c_void_p * n)(*[p[2].data_ptr() for p in parts])
@@ -780,67 +788,31 @@ class WoqGemmGroupCall:
         self.Narr = (ctypes.c_int64 * n)(*self.Ns)
         self.yarr = (ctypes.c_void_p * n)()
         self.need = {}
-        self.orders = k_orders  # as given (None entries included): what current() compares
-        self.order_versions = None if k_orders is None else tuple(None if ko is None else ko._version for ko in k_orders)
-        self.identity = {}      # device -> arange(K) int32, for the parts without an order
-        self.ko = None
-        if k_orders is not None:
-            used = [self._identity_order() if ko is None else ko for ko in k_orders]
-            self.order_keep = used
-            self.ko = (ctypes.c_void_p * n)(*[ko.data_ptr() for ko in used])
-
-    def _identity_order(self):
-        ident = self.identity.get(self.dev)
-        if ident is None:
-            ident = self.identity[self.dev] = torch.arange(self.K, dtype=torch.int32, device=self.dev)
-        return ident
-
-    # a cache, not state: copies and pickles of the owning module start without it
-    def __deepcopy__(self, memo):
-        return None
-
-    def __reduce__(self):
-        return (_none, ())
+        self.ko = None if used is None else (ctypes.c_void_p * n)(*[ko.data_ptr() for ko in used])
 
     def current(self, parts, k_orders=None):
-        """Still describes these tensors (same objects, not written to since), the order tensors included?"""
-        mine = self.keep[0]
-        if not (len(parts) == len(mine) and all(a is b for p, q in zip(parts, mine) for a, b in zip(p[:4], q[:4]))
-                and self.versions == tuple(None if t is None else t._version for p in parts for t in p[:4])):
-            return False
-        if k_orders is not None and all(ko is None for ko in k_orders):
-            k_orders = None
-        if self.orders is None or k_orders is None:
-            return self.orders is None and k_orders is None
-        return (len(k_orders) == len(self.orders) and all(a is b for a, b in zip(k_orders, self.orders))
-                and self.order_versions == tuple(None if ko is None else ko._version for ko in k_orders))
+        return self._parts_current(parts, k_orders)
+
+    def _outputs(self, M):
+        ys = [torch.empty((M, N), dtype=self.dtype, device=self.dev) for N in self.Ns]
+        for i, y in enumerate(ys):
+            self.yarr[i] = y.data_ptr()
+        return ys
 
     def __call__(self, x2d):
         M = x2d.shape[0]
         need = self.need.get(M)
         if need is None:
             need = self.need[M] = lib.inc_woq_gemm_multi_workspace_bytes(self.n, M, self.Narr, self.K)
-        ys = [torch.empty((M, N), dtype=self.dtype, device=self.dev) for N in self.Ns]
-        for i, y in enumerate(ys):
-            self.yarr[i] = y.data_ptr()
-        idx = self.dev_index
-        stream = _raw_stream(idx)
-        buf = _ws_cache.get((idx, stream))
-        if buf is None or buf.numel() < need:
-            buf = _workspace(self.dev, need)
-        with torch.cuda.device(self.dev):
-            if self.ko is None:
-                name = "inc_woq_gemm_multi"
-                rc = lib.inc_woq_gemm_multi(self.n, x2d.data_ptr(), self.dt, self.qw, self.sc, self.qz, self.bi, self.yarr, M, self.Narr, self.K,
-                                            self.gs, self.bits, buf.data_ptr(), buf.numel(), stream)
-            else:
-                name = "inc_woq_gemm_multi_perm"
-                rc = lib.inc_woq_gemm_multi_perm(self.n, x2d.data_ptr(), self.dt, self.ko, self.qw, self.sc, self.qz, self.bi, self.yarr, M, self.Narr,
-                                                 self.K, self.gs, self.bits, buf.data_ptr(), buf.numel(), stream)
-        if rc == -2:  # INC_ERR_UNSUPPORTED: nothing was launched
-            return None
-        check(rc, name)
-        return ys
+        ys = self._outputs(M)
+        wp, wn, stream = _ws_lookup(self.dev, self.dev_index, need)
+        tail = (self.qw, self.sc, self.qz, self.bi, self.yarr, M, self.Narr, self.K, self.gs, self.bits, wp, wn, stream)
+        if self.ko is None:
+            rc = _launch(self.dev, self.dev_index, lib.inc_woq_gemm_multi, "inc_woq_gemm_multi", (self.n, x2d.data_ptr(), self.dt) + tail, True)
+        else:
+            rc = _launch(self.dev, self.dev_index, lib.inc_woq_gemm_multi_perm, "inc_woq_gemm_multi_perm",
+                         (self.n, x2d.data_ptr(), self.dt, self.ko) + tail, True)
+        return None if rc == -2 else ys  # (INC_ERR_UNSUPPORTED: nothing was launched)
 
 
 class WoqGemvAnywGroupCall(WoqGemmGroupCall):
@@ -851,10 +823,10 @@ class WoqGemvAnywGroupCall(WoqGemmGroupCall):
     is asked for 16 rows from the first call on (0 bytes where K fits one slice)."""
 
     MAX_M = GEMV_ANYW_MAX_M
+    COMPUTES = WoqGemvAnywCall.COMPUTES
 
     def __init__(self, parts, K, group_size, bits, dtype, k_orders=None):
-        if dtype is not torch.bfloat16 and dtype is not torch.float16:
-            raise ValueError(f"woq_gemv_anyw computes in bf16 or fp16, got {dtype}")
+        self._compute_dt(dtype)
         for p in parts:
             _gemv_anyw_check_module(p[0], p[1], p[2], p[3], int(p[4]), K, group_size, bits)
         super().__init__(parts, K, group_size, bits, dtype, k_orders=k_orders)
@@ -870,27 +842,15 @@ class WoqGemvAnywGroupCall(WoqGemmGroupCall):
         need = self.need
         if need is None:
             need = self.need = lib.inc_woq_gemv_anyw_multi_workspace_bytes(self.n, self.MAX_M, self.Narr, self.K, self.bits)
-        ys = [torch.empty((M, N), dtype=self.dtype, device=self.dev) for N in self.Ns]
-        for i, y in enumerate(ys):
-            self.yarr[i] = y.data_ptr()
-        idx = self.dev_index
-        stream = _raw_stream(idx)
-        wp, wn = None, 0
-        if need > 0:
-            buf = _ws_cache.get((idx, stream))
-            if buf is None or buf.numel() < need:
-                buf = _workspace(self.dev, need)
-            wp, wn = buf.data_ptr(), buf.numel()
-        with torch.cuda.device(self.dev):
-            rc = lib.inc_woq_gemv_anyw_multi(self.n, x2d.data_ptr(), self.dt, self.ko, self.qw, self.sc, self.qz, self.bi, self.yarr, M, self.Narr,
-                                             self.K, self.gs, self.bits, wp, wn, stream)
-        if rc == -2:  # INC_ERR_UNSUPPORTED: nothing was launched
-            return None
-        check(rc, "inc_woq_gemv_anyw_multi")
-        return ys
+        ys = self._outputs(M)
+        wp, wn, stream = _ws_lookup(self.dev, self.dev_index, need)
+        rc = _launch(self.dev, self.dev_index, lib.inc_woq_gemv_anyw_multi, "inc_woq_gemv_anyw_multi", (
+            self.n, x2d.data_ptr(), self.dt, self.ko, self.qw, self.sc, self.qz, self.bi, self.yarr, M, self.Narr, self.K, self.gs,
+            self.bits, wp, wn, stream), True)
+        return None if rc == -2 else ys  # (INC_ERR_UNSUPPORTED: nothing was launched)
 
 
-class WoqGatedCall:
+class WoqGatedCall(_BatchedCall):
     """inc_woq_gemm_gated with the module side resolved once: h = silu(x Wg^T) * (x Wu^T) for the gate / up pair of a dense gated MLP in
     ONE launch, the product formed in fp32 from the two fp32 sums and rounded once (transformers' LlamaMLP.forward up to down_proj).
     `gate_part` / `up_part` = (qweight, scales, qzeros, None, N) as for WoqGemmGroupCall: no bias, equal N; K, group_size common, 4 bits.
@@ -901,50 +861,21 @@ class WoqGatedCall:
     MAX_M = 16  # rows the entry serves (include/inc_mi355x.h)
 
     def __init__(self, gate_part, up_part, K, group_size, bits, dtype, k_orders=None):
-        if dtype is not torch.bfloat16 and dtype is not torch.float16:
-            raise TypeError("woq_gemm computes in bf16 or fp16")
+        dt = self._compute_dt(dtype)
         parts = [gate_part, up_part]
         k_orders = _check_k_orders(k_orders, 2, K)
         if gate_part[3] is not None or up_part[3] is not None:
             raise ValueError("the gated pair takes modules without a bias")
         if int(gate_part[4]) != int(up_part[4]):
             raise ValueError(f"gate and up must have the same N, got {int(gate_part[4])} and {int(up_part[4])}")
-        self.dev = _dev(*[t for p in parts for t in p[:3]], *(k_orders or ()))
-        self.dev_index = self.dev.index if self.dev.index is not None else torch.cuda.current_device()
-        self.N, self.K, self.gs, self.bits, self.dtype = int(gate_part[4]), K, group_size, bits, dtype
-        self.dt = INC_BF16 if dtype is torch.bfloat16 else INC_F16
-        self.keep = parts
-        self.versions = tuple(t._version for p in parts for t in p[:3])
+        used = self._bind_parts(parts, K, dtype, dt, k_orders)
+        self.N, self.K, self.gs, self.bits = int(gate_part[4]), K, group_size, bits
         self.ptrs = tuple(t.data_ptr() for p in parts for t in p[:3])
-        self.orders = k_orders
-        self.order_versions = None if k_orders is None else tuple(None if ko is None else ko._version for ko in k_orders)
-        self.ko = (None, None)
-        if k_orders is not None:
-            ident = None
-            if any(ko is None for ko in k_orders):
-                ident = torch.arange(K, dtype=torch.int32, device=self.dev)
-            self.order_keep = [ident if ko is None else ko for ko in k_orders]
-            self.ko = tuple(ko.data_ptr() for ko in self.order_keep)
+        self.ko = (None, None) if used is None else tuple(ko.data_ptr() for ko in used)
         self.need = {}
 
-    # a cache, not state: copies and pickles of the owning module start without it
-    def __deepcopy__(self, memo):
-        return None
-
-    def __reduce__(self):
-        return (_none, ())
-
     def current(self, gate_part, up_part, k_orders=None):
-        parts = (gate_part, up_part)
-        if not (all(a is b for p, q in zip(parts, self.keep) for a, b in zip(p[:4], q[:4]))
-                and self.versions == tuple(t._version for p in parts for t in p[:3])):
-            return False
-        if k_orders is not None and all(ko is None for ko in k_orders):
-            k_orders = None
-        if self.orders is None or k_orders is None:
-            return self.orders is None and k_orders is None
-        return (all(a is b for a, b in zip(k_orders, self.orders))
-                and self.order_versions == tuple(None if ko is None else ko._version for ko in k_orders))
+        return self._parts_current((gate_part, up_part), k_orders)
 
     def __call__(self, x2d):
         """x2d: contiguous [M, K] of the call's dtype on the call's device (the owner checks)."""
@@ -953,18 +884,11 @@ class WoqGatedCall:
         if need is None:
             need = self.need[M] = lib.inc_woq_gemm_gated_workspace_bytes(M, self.N, self.K)
         h = torch.empty((M, self.N), dtype=self.dtype, device=self.dev)
-        idx = self.dev_index
-        stream = _raw_stream(idx)
-        buf = _ws_cache.get((idx, stream))
-        if buf is None or buf.numel() < need:
-            buf = _workspace(self.dev, need)
-        with torch.cuda.device(self.dev):
-            rc = lib.inc_woq_gemm_gated(x2d.data_ptr(), self.dt, self.ko[0], self.ko[1], *self.ptrs, h.data_ptr(), M, self.N, self.K, self.gs,
-                                        self.bits, 0, buf.data_ptr(), buf.numel(), stream)
-        if rc == -2:  # INC_ERR_UNSUPPORTED: nothing was launched
-            return None
-        check(rc, "inc_woq_gemm_gated")
-        return h
+        wp, wn, stream = _ws_lookup(self.dev, self.dev_index, need)
+        rc = _launch(self.dev, self.dev_index, lib.inc_woq_gemm_gated, "inc_woq_gemm_gated", (
+            x2d.data_ptr(), self.dt, self.ko[0], self.ko[1], *self.ptrs, h.data_ptr(), M, self.N, self.K, self.gs, self.bits, 0, wp, wn,
+            stream), True)
+        return None if rc == -2 else h  # (INC_ERR_UNSUPPORTED: nothing was launched)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -1055,7 +979,7 @@ def moe_combine(y, route, T, top_k, num_experts, dtype, out=None):
     return out
 
 
-class WoqMoeCall:
+class WoqMoeCall(_PreparedCall):
     """One fused experts forward (route -> gate_up -> down -> combine, four launches, no host wait) with the module side resolved once.
     The route buffer and the two intermediates are allocated per call (the caching allocator makes that free of device allocations, and
     inside a graph capture they come from the graph's pool).  Only the split-K workspace is kept: one zero-initialised buffer per call
@@ -1066,26 +990,16 @@ class WoqMoeCall:
     packed buffers."""
 
     def __init__(self, gate_up, down, E, H, I, group_size):
-        self.keep = tuple(gate_up) + tuple(down)
-        self.versions = tuple(t._version for t in self.keep)
-        self.dev = _dev(*self.keep)
-        self.dev_index = self.dev.index if self.dev.index is not None else torch.cuda.current_device()
+        self._track(tuple(gate_up) + tuple(down))
+        self._bind(_dev(*self.keep))
         self.gu, self.dn = [t.data_ptr() for t in gate_up], [t.data_ptr() for t in down]
         self.E, self.H, self.I, self.gs = E, H, I, group_size
         self.Gh, self.Gi = gate_up[1].shape[1], down[1].shape[1]
         self.workspace = None
         self.retired = []  # grown-out workspaces, kept alive for graphs that captured them
 
-    # a cache, not state: copies and pickles of the owning module start without it
-    def __deepcopy__(self, memo):
-        return None
-
-    def __reduce__(self):
-        return (_none, ())
-
     def current(self, gate_up, down):
-        tensors = tuple(gate_up) + tuple(down)
-        return all(a is b for a, b in zip(tensors, self.keep)) and tuple(t._version for t in tensors) == self.versions
+        return _unchanged(self.keep, self.versions, tuple(gate_up) + tuple(down))
 
     def held_bytes(self):
         """Device memory this call keeps between calls (the workspace and the retired ones)."""

@@ -162,17 +162,8 @@ class MI355XWeightOnlyLinear(WeightOnlyLinear):
         adds the sym shift / subtracts 1 from zp in place)."""
         dev = self.qweight.device
         N, K = self.out_features, self.in_features
-        self._plan_key = None  # the kernels write the buffers through raw pointers: drop the cached forward plan
-        self.__dict__["_call"] = None  # ... and the prepared call (its converted bias / plan belong to the old contents)
-        if bias is not None:
-            assert hasattr(self, "bias"), "bias is not set when initializing."
-            self.bias = bias.detach().to(dev).type(self.float_type)
-        if g_idx is not None:
-            assert hasattr(self, "g_idx"), "g_idx is not set when initializing."
-            g = g_idx.to(dev).type(torch.int32)
-            if self.use_optimum_format:
-                g = (torch.argsort(g) // self.group_size).type(torch.int32)  # modules.py:341-344 (index plumbing)
-            self.g_idx = g.contiguous()
+        assert bias is None or hasattr(self, "bias"), "bias is not set when initializing."
+        self._begin_pack(bias, g_idx, self.use_optimum_format)
         if scale_bf16_to_fp8 is not None:
             self.scale_bf16_to_fp8 = scale_bf16_to_fp8.to(dev).type(self.float_type)
         int_weight = int_weight.to(dev)
@@ -206,20 +197,27 @@ class MI355XWeightOnlyLinear(WeightOnlyLinear):
                 pz = pz.T.contiguous()
             self.qzeros.copy_(pz)
 
-    def pack_codes(self, codes, scales, zp, bias, g_idx=None):
-        """MI355X-native fast path (optimum format only): pack already-offset codes 0..2^bits-1 (uint8 [N,K], what
-        the GPTQ column-loop kernel emits) instead of int32 signed ints.  Produces bit-identical buffers to
-        `pack(codes - 2^(bits-1), scales, None, ...)` for sym and `pack(codes, scales, zp, ...)` for asym."""
-        assert self.use_optimum_format, "pack_codes writes the optimum layout"
+    def _begin_pack(self, bias, g_idx, sort_g_idx):
+        """What pack() and pack_codes() do before they write the packed buffers: drop what was derived from the old contents, store
+        the bias and the g_idx (`sort_g_idx`: in the optimum format's argsort // group_size form, reference modules.py:341-344)."""
         dev = self.qweight.device
-        self._plan_key = None
-        self.__dict__["_call"] = None
+        self._plan_key = None  # the kernels write the buffers through raw pointers: drop the cached forward plan
+        self.__dict__["_call"] = None  # ... and the prepared call (its converted bias / plan belong to the old contents)
         if bias is not None:
             self.bias = bias.detach().to(dev).type(self.float_type)
         if g_idx is not None:
             assert hasattr(self, "g_idx"), "g_idx is not set when initializing."
             g = g_idx.to(dev).type(torch.int32)
-            self.g_idx = (torch.argsort(g) // self.group_size).type(torch.int32).contiguous()
+            if sort_g_idx:
+                g = (torch.argsort(g) // self.group_size).type(torch.int32)  # (index plumbing)
+            self.g_idx = g.contiguous()
+
+    def pack_codes(self, codes, scales, zp, bias, g_idx=None):
+        """MI355X-native fast path (optimum format only): pack already-offset codes 0..2^bits-1 (uint8 [N,K], what
+        the GPTQ column-loop kernel emits) instead of int32 signed ints.  Produces bit-identical buffers to
+        `pack(codes - 2^(bits-1), scales, None, ...)` for sym and `pack(codes, scales, zp, ...)` for asym."""
+        assert self.use_optimum_format, "pack_codes writes the optimum layout"
+        self._begin_pack(bias, g_idx, True)
         ops.woq_pack(codes, scales, zp, self.bits, 0, qweight=self.qweight, qzeros=self.qzeros, scales_out=self.scales)
 
     def unpack(self):
@@ -276,11 +274,12 @@ class MI355XWeightOnlyLinear(WeightOnlyLinear):
         running after some of its layers are packed (true_sequential re-runs the block mid-way).
         """
         x = input
-        # decode path: a prepared call for the plain fused plan (ops.WoqGemmCall); the 6-us kernel makes the host side count
+        # decode path: a prepared call for the plan (ops.WoqGemmCall and its kin); the 6-us kernels make the host side count
         d = self.__dict__
         call = d.get("_call")
         if call is not None and x.dtype is call.dtype and x.device == call.dev and x.is_contiguous() and x.numel() > 0 and x.shape[-1] == call.K:
             bufs = self._buffers
+            # (_prepared_serves for the call held, written out: the method call is host time on the plain 4-bit route, profiles/decode_host/)
             if (call.current(bufs["qweight"], bufs["scales"], bufs.get("qzeros"), bufs.get("bias", d.get("bias")), bufs.get("g_idx", d.get("g_idx")))
                     and (not call.lut or (self.LUT_FUSED and x.numel() <= self.LUT_MAX_M * call.K))
                     and (call.ko is None or self.ACT_ORDER_FUSED_GATHER)
@@ -301,60 +300,26 @@ class MI355XWeightOnlyLinear(WeightOnlyLinear):
         d["_call"] = None
         if plan == "fused" and self._fused_max_m is not None and x2d.shape[0] > self._fused_max_m:
             plan = "dense"  # (a group size the fast kernels do not take: see _forward_plan)
-        if plan == "fused_lut" and x2d.shape[0] > self.LUT_MAX_M:
-            plan = "dense"  # (prefill-sized batches: see LUT_MAX_M)
-        if (plan == "dense" and self.ODD_WIDTH_DECODE and not self.ODD_WIDTH_FUSED
-                and (self._decode_anyw or (self._decode_anyw_perm and self.ACT_ORDER_FUSED_GATHER))
-                and x2d.shape[0] <= min(self.ODD_WIDTH_DECODE_MAX_M, ops.GEMV_ANYW_MAX_M)):
-            # 1 / 2 / 3 / 5 / 6 / 7 bits at decode: inc_woq_gemv_anyw streams the packed words once; recover() never runs (larger batches
-            # keep the dense route below, and drop the prepared call again).  act_order modules: the K-sorted words and the gather inside
-            # the kernel (inc_woq_gemv_anyw_perm), still one launch
-            if self._decode_anyw:
-                call = ops.WoqGemvAnywCall(self.qweight, self.scales, self.qzeros, self.bias, self.out_features, self.in_features,
-                                           self.group_size, self.bits, x2d.dtype)
-            else:
-                call = ops.WoqGemvAnywCall(self._qweight_sorted, self.scales, self.qzeros, self.bias, self.out_features, self.in_features,
-                                           self.group_size, self.bits, x2d.dtype, k_order=self._k_order32, owner_qweight=self.qweight,
-                                           gather_max_mn=self.ODD_WIDTH_GATHER_MAX_MN)
-            d["_call"] = call
-            gi = self.g_idx
-            call.tag = (gi, None if gi is None else gi._version)
+        # the prepared call serves the module from now on -- or, where this batch takes another route, none does
+        call = d["_call"] = self._prepare_call(plan, x2d.dtype, x2d.shape[0])
+        if call is not None:
             y = call(x2d)
-        elif plan == "fused" and self._fused_max_m is not None:
+        elif plan == "fused":  # (_fused_max_m: decode-sized batches of such a module)
             y = ops.woq_gemm(x2d, self.qweight, self.scales, self.qzeros, self.bias, self.out_features, self.in_features, self.group_size, self.bits)
-        elif plan == "fused":
-            call = d["_call"] = ops.WoqGemmCall(self.qweight, self.scales, self.qzeros, self.bias, self.out_features, self.in_features,
-                                                self.group_size, self.bits, x2d.dtype)
-            gi = self.g_idx
-            call.tag = (gi, None if gi is None else gi._version)
-            y = call(x2d)
-        elif plan == "fused_act_order" and self.ACT_ORDER_FUSED_GATHER:
-            # act_order: the K axis is sorted by group once (below); per call only the activations are gathered -- inside the decode
-            # kernels up to 64 rows (inc_woq_gemm_perm: one launch, and the prepared call serves the module from now on)
-            call = d["_call"] = ops.WoqGemmCall(self._qweight_sorted, self.scales, self.qzeros, self.bias, self.out_features, self.in_features,
-                                                self.group_size, self.bits, x2d.dtype, k_order=self._k_order32, owner_qweight=self.qweight)
-            gi = self.g_idx
-            call.tag = (gi, gi._version)
-            y = call(x2d)
         elif plan == "fused_act_order":
-            # ... or by a torch kernel in front of the ordinary launch (ACT_ORDER_FUSED_GATHER = False)
+            # ACT_ORDER_FUSED_GATHER = False: the activations are gathered by a torch kernel in front of the ordinary launch
             y = ops.woq_gemm(
                 x2d.index_select(1, self._k_order), self._qweight_sorted, self.scales, self.qzeros, self.bias,
                 self.out_features, self.in_features, self.group_size, self.bits,
             )
-        elif plan == "fused_lut":
-            # 4-bit row-packed modules (NF4 / FP4 code books, non-optimum integers): inc_woq_gemm_lut decodes the fields through a
-            # 16-entry table per (row, group) in registers; recover() never runs
-            call = d["_call"] = ops.WoqGemmLutCall(self.qweight, self._lut_table, self.scales, getattr(self, "qzeros", None), self.bias,
-                                                   self.out_features, self.in_features, self.group_size, self._lut is None, x2d.dtype)
-            y = call(x2d)
         elif plan == "fused_g_idx":
             # an irregular g_idx (not a permutation of whole groups): inc_woq_gemm's general tile kernel reads scale / zero of
             # group g_idx[k] per element (reference modules.py:427-431 semantics), still without a dense weight
             y = ops.woq_gemm(x2d, self.qweight, self.scales, self.qzeros, self.bias, self.out_features, self.in_features,
                              self.group_size, self.bits, g_idx=self.g_idx)
         else:
-            # non-optimum layouts (compression_dim / int8-16-64 containers, NF4 / FP4 code books): HIP dequant + dense library GEMM
+            # non-optimum layouts (compression_dim / int8-16-64 containers, NF4 / FP4 code books beyond LUT_MAX_M rows), odd widths beyond
+            # their decode limit: HIP dequant + dense library GEMM
             w = self.recover(dtype=x2d.dtype)
             b = None if self.bias is None else self.bias.to(x2d.dtype)
             y = torch.nn.functional.linear(x2d, w, b)
@@ -415,91 +380,123 @@ class MI355XWeightOnlyLinear(WeightOnlyLinear):
         # (the per-element form is the memory-saving route, not the fast one: measured 376-480 us against 40-100 us for HIP recover() +
         # the library GEMM at 4096^2 for every M from 1 to 4096, profiles/r6/anyw_route_time.log -- so it is opt-in: ODD_WIDTH_FUSED)
         fusable = self.use_optimum_format and (self.group_size % self.n_pack == 0 if self.bits in (4, 8) else self.ODD_WIDTH_FUSED)
-        self._k_order = self._k_order32 = self._qweight_sorted = None
-        self._decode_anyw = self._decode_anyw_eligible()
-        self._decode_anyw_perm = False
         # group sizes that are neither a power of two >= 32 nor the whole row (e.g. 96) run inc_woq_gemm's general 128 x 128 tile kernel
         # above 16 rows: 190-245 us at 4096 x 4032 against 34-74 us for HIP recover() + the library GEMM (scripts/route_sweep.py) -- such
         # modules keep the fused form for decode-sized batches only
-        gs_eff = self.in_features if (self.group_size == -1 or self.group_size >= self.in_features) else self.group_size
-        fast_groups = gs_eff == self.in_features or (gs_eff >= 32 and (gs_eff & (gs_eff - 1)) == 0)
+        K = self.in_features
+        gs_eff = K if (self.group_size == -1 or self.group_size >= K) else self.group_size
+        fast_groups = gs_eff == K or (gs_eff >= 32 and (gs_eff & (gs_eff - 1)) == 0)
         self._fused_max_m = None if (fast_groups or self.bits not in (4, 8)) else 16
+        anyw = self._decode_anyw_eligible()
+        kind, order = "contiguous", None
+        if self.g_idx is not None and (fusable or anyw):  # (a device sync: once per packed state)
+            kind, order = _classify_g_idx(self.g_idx, K, self.group_size)
+        self._decode_anyw = anyw and kind == "contiguous"
+        self._decode_anyw_perm = False
         if fusable:
-            K, gs = self.in_features, self.group_size
-            if self.g_idx is None:
+            if kind == "contiguous":
                 plan = "fused"
+            elif kind == "permuted" and K % self.n_pack == 0:
+                plan = "fused_act_order"
             else:
-                g = self.g_idx.to(torch.int64)
-                contiguous = torch.arange(K, device=g.device) // gs
-                if torch.equal(g, contiguous):
-                    plan = "fused"
-                elif K % self.n_pack == 0:
-                    order = torch.argsort(g, stable=True)
-                    if torch.equal(g[order], contiguous):
-                        bits, npk = self.bits, self.n_pack
-                        shifts = (torch.arange(npk, device=g.device, dtype=torch.int32) * bits).view(1, npk, 1)
-                        mask = (1 << bits) - 1
-                        codes = ((self.qweight.unsqueeze(1) >> shifts) & mask).reshape(K, -1)  # [K, N] fields
-                        codes = codes.index_select(0, order).reshape(K // npk, npk, -1)
-                        words = (codes.to(torch.int64) << shifts.to(torch.int64)).sum(dim=1)  # disjoint fields, < 2^32
-                        words = torch.where(words >= 2**31, words - 2**32, words)
-                        self._qweight_sorted = words.to(torch.int32).contiguous()
-                        self._k_order = order
-                        self._k_order32 = order.to(torch.int32)  # what inc_woq_gemm_perm reads
-                        plan = "fused_act_order"
-                    else:
-                        plan = "fused_g_idx"  # groups of uneven size: the library's general kernel looks the group up per k
-                else:
-                    plan = "fused_g_idx"
-        if plan == "dense" and not self._decode_anyw and self.g_idx is not None and self._decode_anyw_eligible(any_g_idx=True):
+                plan = "fused_g_idx"  # groups of uneven size, or ragged words: the library's general kernel looks the group up per k
+        elif anyw and kind == "permuted":
             # an odd width whose g_idx permutes whole groups: the plan stays "dense" (larger batches), decode gathers through the order
-            K = self.in_features
-            g = self.g_idx.to(torch.int64)
-            gs_eff = K if (self.group_size == -1 or self.group_size >= K) else self.group_size
-            order = torch.argsort(g, stable=True)
-            if torch.equal(g[order], torch.arange(K, device=g.device) // gs_eff):
-                self._qweight_sorted = ops.sort_packed_k(self.qweight, order, K, self.bits)
-                self._k_order = order
-                self._k_order32 = order.to(torch.int32)  # what inc_woq_gemv_anyw_perm reads
-                self._decode_anyw_perm = True
-        if not self.use_optimum_format and self.LUT_FUSED and self._lut_eligible():
+            self._decode_anyw_perm = True
+        self._k_order = self._k_order32 = self._qweight_sorted = None
+        if plan == "fused_act_order" or self._decode_anyw_perm:
+            self._qweight_sorted = ops.sort_packed_k(self.qweight, order, K, self.bits)
+            self._k_order = order
+            self._k_order32 = order.to(torch.int32)  # what inc_woq_gemm_perm / inc_woq_gemv_anyw_perm read
+        self._lut_table = self._lut_eligible() if (not self.use_optimum_format and self.LUT_FUSED) else None
+        if self._lut_table is not None:
             plan = "fused_lut"
         self._plan_key, self._plan = key, plan
         return plan
 
-    def _decode_anyw_eligible(self, any_g_idx=False):
-        """inc_woq_gemv_anyw takes the module at decode (ODD_WIDTH_DECODE)?  Recorded with the plan, once per packed state.
-        `any_g_idx`: everything but the g_idx test (the gathered form's precondition)."""
-        K, gs = self.in_features, self.group_size
-        if (not self.use_optimum_format or not ops.gemv_anyw_takes(self.out_features, K, gs, self.bits)
-                or self.scales.dtype is not torch.float16 or not self.scales.is_contiguous() or not self.qweight.is_contiguous()
-                or not self.qzeros.is_contiguous() or self.qweight.data_ptr() % 16 or self.scales.data_ptr() % 8):
+    def _prepared_serves(self, M, lut, anyw, perm, gather_max_mn):
+        """A prepared call of this kind -- `lut`: inc_woq_gemm_lut, `anyw`: the odd-width GEMV, `perm`: with the act_order gather, built
+        for `gather_max_mn` -- may serve M rows now (M = None: by the switches alone, the caller has its own row limit)?  The one place
+        where the switches and limits above decide that, at call time (they may change between two forwards): _prepare_call and
+        _group_member ask here, and forward's guard repeats it inline for the call it holds (the flipping tests hold the two together)."""
+        if lut:
+            return self.LUT_FUSED and M <= self.LUT_MAX_M
+        if perm and not self.ACT_ORDER_FUSED_GATHER:
             return False
-        if self.g_idx is None or any_g_idx:
-            return True
-        gs_eff = K if (gs == -1 or gs >= K) else gs
-        return bool(torch.equal(self.g_idx.to(torch.int64), torch.arange(K, device=self.g_idx.device) // gs_eff))  # the contiguous one
+        if anyw:
+            return (self.ODD_WIDTH_DECODE and not self.ODD_WIDTH_FUSED
+                    and (M is None or M <= min(self.ODD_WIDTH_DECODE_MAX_M, ops.GEMV_ANYW_MAX_M))
+                    and (not perm or gather_max_mn == self.ODD_WIDTH_GATHER_MAX_MN))
+        return True
+
+    def _prepare_call(self, plan, dtype, M):
+        """The prepared call that serves M rows of `dtype` under `plan` (and every later batch its guard admits), or None where the
+        batch takes an un-prepared route: _fused_max_m modules, act_order with ACT_ORDER_FUSED_GATHER off, "fused_g_idx", dense."""
+        lut = plan == "fused_lut"
+        # 1 / 2 / 3 / 5 / 6 / 7 bits at decode: inc_woq_gemv_anyw streams the packed words once; recover() never runs.  act_order modules:
+        # the K-sorted words and the gather inside the kernel (inc_woq_gemv_anyw_perm / inc_woq_gemm_perm), still one launch
+        anyw = plan == "dense" and (self._decode_anyw or self._decode_anyw_perm)
+        perm = plan == "fused_act_order" or (anyw and not self._decode_anyw)
+        if not (lut or anyw or perm or (plan == "fused" and self._fused_max_m is None)):
+            return None
+        if not self._prepared_serves(M, lut, anyw, perm, self.ODD_WIDTH_GATHER_MAX_MN):
+            return None
+        if lut:
+            # 4-bit row-packed modules (NF4 / FP4 code books, non-optimum integers): inc_woq_gemm_lut decodes the fields through a
+            # 16-entry table per (row, group) in registers; recover() never runs
+            return ops.WoqGemmLutCall(self.qweight, self._lut_table, self.scales, getattr(self, "qzeros", None), self.bias,
+                                      self.out_features, self.in_features, self.group_size, self._lut is None, dtype)
+        kw = dict(owner_g_idx=self.g_idx)
+        if perm:
+            kw.update(k_order=self._k_order32, owner_qweight=self.qweight)
+            if anyw:
+                kw["gather_max_mn"] = self.ODD_WIDTH_GATHER_MAX_MN
+        return (ops.WoqGemvAnywCall if anyw else ops.WoqGemmCall)(
+            self._qweight_sorted if perm else self.qweight, self.scales, self.qzeros, self.bias, self.out_features, self.in_features,
+            self.group_size, self.bits, dtype, **kw)
+
+    def _group_member(self):
+        """(part, order) of the module in a one-launch decode group (woq_linear_group, woq_gated_pair), or None.  4 / 8 bits: the plain
+        fused plan, or -- while ACT_ORDER_FUSED_GATHER is on -- the act_order plan with the K-sorted words and the order the kernels
+        gather x through.  1 / 2 / 3 / 5 / 6 / 7 bits: a module that decodes through inc_woq_gemv_anyw or, likewise, its gathered form."""
+        plan = self._forward_plan()
+        anyw = self.bits not in (4, 8)
+        if anyw:
+            perm = self._decode_anyw_perm
+            ok = plan == "dense" and (self._decode_anyw or perm)
+        else:
+            perm = plan == "fused_act_order"
+            ok = plan == "fused" or perm
+        if not ok or not self._prepared_serves(None, False, anyw, perm, self.ODD_WIDTH_GATHER_MAX_MN):
+            return None
+        return ((self._qweight_sorted if perm else self.qweight, self.scales, self.qzeros, self.bias, self.out_features),
+                self._k_order32 if perm else None)
+
+    def _decode_anyw_eligible(self):
+        """inc_woq_gemv_anyw takes the module's layout at decode (ODD_WIDTH_DECODE)?  Everything but the g_idx, which _forward_plan
+        classifies: contiguous -> the plain kernel, a permutation of whole groups -> the gathered form."""
+        return bool(self.use_optimum_format and ops.gemv_anyw_takes(self.out_features, self.in_features, self.group_size, self.bits)
+                    and self.scales.dtype is torch.float16 and self.scales.is_contiguous() and self.qweight.is_contiguous()
+                    and self.qzeros.is_contiguous() and not self.qweight.data_ptr() % 16 and not self.scales.data_ptr() % 8)
 
     def _lut_eligible(self):
-        """inc_woq_gemm_lut takes the module (and self._lut_table is its field -> value table)?"""
+        """The field -> value table of the module where inc_woq_gemm_lut takes it, else None."""
         K, gs = self.in_features, self.group_size
         gs_eff = K if (gs == -1 or gs >= K) else gs
         has_zp = hasattr(self, "qzeros")
         if (self.compression_dim != 1 or self.bits != 4 or self.g_idx is not None or K % 32 != 0 or (gs_eff != K and gs_eff % 32 != 0)
                 or self.scales.dtype not in (torch.float32, torch.float16, torch.bfloat16) or not self.scales.is_contiguous()
                 or not self.qweight.is_contiguous() or self.qweight.data_ptr() % 16 or (has_zp and not self.qzeros.is_contiguous())):
-            return False
+            return None
         f = list(range(16))
         if self._lut is not None:  # code book: the stored code is sign-extended, then +8 (unpack)
             if has_zp:
-                return False  # (recover() of a code book has no zero point)
+                return None  # (recover() of a code book has no zero point)
             lut = self._lut.cpu().tolist()
-            self._lut_table = [lut[(v + 8) & 15] for v in f]
-        elif "int" in self.dtype:
-            self._lut_table = [float(v) for v in f] if has_zp else [float(v - 16 if v >= 8 else v) for v in f]
-        else:
-            return False
-        return True
+            return [lut[(v + 8) & 15] for v in f]
+        if "int" in self.dtype:
+            return [float(v) for v in f] if has_zp else [float(v - 16 if v >= 8 else v) for v in f]
+        return None
 
     def extra_repr(self):
         s = super().extra_repr()
@@ -511,27 +508,33 @@ class MI355XWeightOnlyLinear(WeightOnlyLinear):
 # the reference's class name for the non-Gaudi device class; code that imports it keeps working
 INCWeightOnlyLinear = MI355XWeightOnlyLinear
 
-def _group_member(m):
-    """(part, order) of a module in a one-launch decode group, or None: the plain fused plan, or -- while ACT_ORDER_FUSED_GATHER is on --
-    the act_order plan with the K-sorted words and the order the kernels gather x through."""
-    plan = m._forward_plan()
-    if plan == "fused":
-        return (m.qweight, m.scales, m.qzeros, m.bias, m.out_features), None
-    if plan == "fused_act_order" and m.ACT_ORDER_FUSED_GATHER:
-        return (m._qweight_sorted, m.scales, m.qzeros, m.bias, m.out_features), m._k_order32
-    return None
+
+def _classify_g_idx(g_idx, K, group_size):
+    """(kind, order) of a per-element group index [K]: "contiguous" (arange(K) // gs_eff, gs_eff = K for group_size -1 or >= K: what a
+    module without g_idx has), "permuted" (a permutation of whole groups: the stable argsort `order`, int64, restores the contiguous
+    one) or "irregular" (anything else); order is None unless "permuted".  Pure torch on g_idx's device; each comparison is a sync."""
+    gs_eff = K if (group_size == -1 or group_size >= K) else group_size
+    g = g_idx.to(torch.int64)
+    contiguous = torch.arange(K, device=g.device) // gs_eff
+    if torch.equal(g, contiguous):
+        return "contiguous", None
+    order = torch.argsort(g, stable=True)
+    if torch.equal(g[order], contiguous):
+        return "permuted", order
+    return "irregular", None
 
 
-def _anyw_group_member(m):
-    """(part, order) of a 1 / 2 / 3 / 5 / 6 / 7-bit module in a one-launch decode group (inc_woq_gemv_anyw_multi), or None: a module that
-    decodes through inc_woq_gemv_anyw, or -- while ACT_ORDER_FUSED_GATHER is on -- through inc_woq_gemv_anyw_perm."""
-    if m._forward_plan() != "dense" or not m.ODD_WIDTH_DECODE or m.ODD_WIDTH_FUSED:
-        return None
-    if m._decode_anyw:
-        return (m.qweight, m.scales, m.qzeros, m.bias, m.out_features), None
-    if m._decode_anyw_perm and m.ACT_ORDER_FUSED_GATHER:
-        return (m._qweight_sorted, m.scales, m.qzeros, m.bias, m.out_features), m._k_order32
-    return None
+def _owner_call(owner, name, key, tensors, build):
+    """The prepared call `key` of the per-owner cache `name` (a cache, not state: it dies with the owner module, copies and pickles of
+    the module start without it), rebuilt through build() when any buffer it describes -- a g_idx among them: the plan then has new
+    sorted words and a new order -- was replaced or written to."""
+    cache = owner.__dict__.setdefault(name, {})
+    call = cache.get(key)
+    if call is None or not call.current(*tensors):
+        if len(cache) >= 8:
+            cache.clear()
+        call = cache[key] = build()
+    return call
 
 
 def woq_linear_group(x, modules):
@@ -559,7 +562,7 @@ def woq_linear_group(x, modules):
           and x.device == m0.qweight.device and x.shape[-1] == m0.in_features)
     anyw = ok and m0.bits in ops.GEMV_ANYW_BITS
     ok = ok and (anyw or m0.bits in (4, 8))
-    members = [(_anyw_group_member if anyw else _group_member)(m) for m in mods] if ok else None
+    members = [m._group_member() for m in mods] if ok else None
     if ok and all(mem is not None for mem in members):
         K = m0.in_features
         x2d = x.reshape(-1, K)
@@ -573,17 +576,10 @@ def woq_linear_group(x, modules):
             orders = [mem[1] for mem in members]
             if all(o is None for o in orders):
                 orders = None
-            # the prepared call lives on the group's first module (a cache, not state: it dies with the module, copies and pickles of the
-            # module start without it) and is rebuilt when any buffer of the group -- a g_idx among them: the plan then has new sorted
-            # words and a new order -- is replaced or written to
-            cache = m0.__dict__.setdefault("_group_calls", {})
-            key = tuple(id(m) for m in mods[1:]) + (x.dtype,)
-            call = cache.get(key)
-            if call is None or not call.current(parts, orders):
-                if len(cache) >= 8:
-                    cache.clear()
-                cls = ops.WoqGemvAnywGroupCall if anyw else ops.WoqGemmGroupCall
-                call = cache[key] = cls(parts, K, m0.group_size, m0.bits, x.dtype, k_orders=orders)
+            # the prepared call lives on the group's first module
+            cls = ops.WoqGemvAnywGroupCall if anyw else ops.WoqGemmGroupCall
+            call = _owner_call(m0, "_group_calls", tuple(id(m) for m in mods[1:]) + (x.dtype,), (parts, orders),
+                               lambda: cls(parts, K, m0.group_size, m0.bits, x.dtype, k_orders=orders))
             ys = call(x2d)
             if ys is not None:
                 return [y.view(*x.shape[:-1], m.out_features) for y, m in zip(ys, mods)]
@@ -613,20 +609,15 @@ def woq_gated_pair(x, gate, up, act_fn=None):
             and gate.bias is None and up.bias is None and gate.in_features == up.in_features and gate.out_features == up.out_features
             and gate.group_size == up.group_size and x.dtype in (torch.bfloat16, torch.float16) and x.is_cuda and x.numel() > 0
             and x.device == gate.qweight.device and x.shape[-1] == gate.in_features and x.numel() <= ops.WoqGatedCall.MAX_M * gate.in_features):
-        mg, mu = _group_member(gate), _group_member(up)
+        mg, mu = gate._group_member(), up._group_member()
         if mg is not None and mu is not None:
             K = gate.in_features
             x2d = x.reshape(-1, K)
             if not x2d.is_contiguous():
                 x2d = x2d.contiguous()
             orders = None if mg[1] is None and mu[1] is None else [mg[1], mu[1]]
-            cache = gate.__dict__.setdefault("_gated_calls", {})
-            key = (id(up), x.dtype)
-            call = cache.get(key)
-            if call is None or not call.current(mg[0], mu[0], orders):
-                if len(cache) >= 8:
-                    cache.clear()
-                call = cache[key] = ops.WoqGatedCall(mg[0], mu[0], K, gate.group_size, 4, x.dtype, k_orders=orders)
+            call = _owner_call(gate, "_gated_calls", (id(up), x.dtype), (mg[0], mu[0], orders),
+                               lambda: ops.WoqGatedCall(mg[0], mu[0], K, gate.group_size, 4, x.dtype, k_orders=orders))
             h = call(x2d)
             if h is not None:
                 return h.view(*x.shape[:-1], gate.out_features)

@@ -2,6 +2,7 @@
 call) and a self-test of the cases of tests/act_order_cases.py: the comparator must tell a missing or wrong gather from a correct
 one.  No GPU call anywhere in this file."""
 
+import numpy as np
 import pytest
 import torch
 
@@ -62,6 +63,46 @@ def test_prepared_call_rejects_a_bad_k_order():
                         k_order=torch.empty(K, dtype=torch.int32, **meta))
     with pytest.raises(RuntimeError, match="HBM"):  # ... and then the usual residency check
         ops.WoqGemmCall(qw, sc, qz, None, N, K, 128, 4, torch.bfloat16, k_order=torch.empty(K, dtype=torch.int32, **meta))
+
+
+def _classify_oracle(g, K, gs):
+    """numpy: (kind, order) as modules._classify_g_idx defines them."""
+    gs_eff = K if (gs == -1 or gs >= K) else gs
+    contiguous = np.arange(K) // gs_eff
+    if np.array_equal(g, contiguous):
+        return "contiguous", None
+    order = np.argsort(g, kind="stable")
+    return ("permuted", order) if np.array_equal(g[order], contiguous) else ("irregular", None)
+
+
+def _g_idx_inputs():
+    K, gs = 96, 32
+    contiguous = np.arange(K) // gs
+    yield "contiguous", K, gs, contiguous, "contiguous"
+    for kind in A.PERM_KINDS:  # whole elements permuted (the identity leaves the contiguous index)
+        yield kind, K, gs, contiguous[A.perm(K, kind)], "contiguous" if kind == "identity" else "permuted"
+    moved = contiguous.copy()
+    moved[gs - 1] = 1  # 31 elements in group 0, 33 in group 1
+    yield "moved", K, gs, moved, "irregular"
+    yield "ragged", 80, 32, (np.arange(80) // 32)[A.perm(80, "random")], "permuted"  # last group of 16
+    for one in (128, -1):  # one group per row
+        yield f"one_group_{one}", K, one, np.zeros(K, dtype=np.int64), "contiguous"
+        yield f"one_group_{one}_plus", K, one, (np.arange(K) == 5).astype(np.int64), "irregular"
+
+
+@pytest.mark.parametrize("name,K,gs,g,want", list(_g_idx_inputs()), ids=[t[0] for t in _g_idx_inputs()])
+@pytest.mark.parametrize("dtype", [torch.int64, torch.int32], ids=["i64", "i32"])
+def test_classify_g_idx(name, K, gs, g, want, dtype):
+    """One classification serves every plan: contiguous / a permutation of whole groups (with the stable argsort) / irregular."""
+    from neural_compressor_amd.torch.algorithms.weight_only.modules import _classify_g_idx
+
+    kind, order = _classify_g_idx(torch.from_numpy(g).to(dtype), K, gs)
+    okind, oorder = _classify_oracle(g, K, gs)
+    assert kind == okind == want
+    if kind == "permuted":
+        assert order.dtype is torch.int64 and np.array_equal(order.numpy(), oorder)
+    else:
+        assert order is None and oorder is None
 
 
 def test_entry_point_rejects_on_the_host():

@@ -110,7 +110,7 @@ def test_multi_workspace_formula():
 
 
 @pytest.mark.parametrize("K", [96, 2080])
-@pytest.mark.parametrize("bits", A.BITS)
+@pytest.mark.parametrize("bits", A.BITS + (4, 8))  # (4 / 8 bits: the act_order plan of the whole-word widths sorts through it too)
 def test_sort_packed_k(bits, K):
     from neural_compressor_amd import ops
 

@@ -299,13 +299,15 @@ def test_accelerator_registry_selection_order(monkeypatch):
 
 
 def test_prepared_gemm_call_is_a_cache_not_state():
-    """ops.WoqGemmCall (the decode path's prepared inc_woq_gemm call kept in the module's __dict__) must not travel with copies or
-    pickles of the module."""
+    """The prepared calls (ops.WoqGemmCall and its kin, kept in the owning module's __dict__ for the decode path) must not travel with
+    copies or pickles of the module."""
     import copy
     import pickle
 
-    from neural_compressor_amd.ops import WoqGemmCall
+    from neural_compressor_amd import ops
 
-    obj = WoqGemmCall.__new__(WoqGemmCall)
-    assert copy.deepcopy({"_call": obj})["_call"] is None
-    assert pickle.loads(pickle.dumps({"_call": obj}))["_call"] is None
+    for cls in (ops.WoqGemmCall, ops.WoqGemvAnywCall, ops.WoqGemmLutCall, ops.WoqGemmGroupCall, ops.WoqGemvAnywGroupCall, ops.WoqGatedCall,
+                ops.WoqMoeCall):
+        obj = cls.__new__(cls)
+        assert copy.deepcopy({"_call": obj})["_call"] is None, cls.__name__
+        assert pickle.loads(pickle.dumps({"_call": obj}))["_call"] is None, cls.__name__

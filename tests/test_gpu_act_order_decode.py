@@ -232,7 +232,32 @@ def test_module_above_64_rows_gathers_with_index_select(hip, monkeypatch):
     assert torch.equal(m(x), want)          # builds the prepared call
     assert torch.equal(m(x), want)          # ... and goes through it
     assert calls == [x.shape, x.shape]
-    assert m.__dict__["_call"] is not None
+    call = m.__dict__["_call"]
+    assert call is not None
+    assert torch.equal(_two_launch(m, x), want)  # the switch off: the call is dropped (asserted there), the same bits
+    assert torch.equal(m(x), want) and m.__dict__["_call"] not in (None, call)  # ... and on again: rebuilt
+
+
+@pytest.mark.parametrize("M", [1, 5])
+@pytest.mark.parametrize("bits", [4, 8])
+def test_plan_sorts_the_words_as_sort_packed_k_does(hip, bits, M):
+    """The K-sorted words of the 4 / 8-bit act_order plan are ops.sort_packed_k's, and the forward is inc_woq_gemm on them and the
+    gathered x, bit for bit."""
+    from neural_compressor_amd import ops
+    from neural_compressor_amd.torch.algorithms.weight_only.modules import MI355XWeightOnlyLinear
+
+    N, K, gs = 64, 256, 32
+    g = torch.Generator().manual_seed(900 + bits)
+    iw = torch.randint(0, 1 << bits, (N, K), generator=g, dtype=torch.int32)
+    sc = torch.rand(N, K // gs, generator=g) * 0.02 + 0.002
+    zp = torch.randint(1, 1 << bits, (N, K // gs), generator=g, dtype=torch.int32)
+    m = MI355XWeightOnlyLinear(K, N, bits=bits, group_size=gs, zp=True, bias=True, g_idx=True, device=hip)
+    m.pack(iw.to(hip), sc.to(hip), zp.to(hip), torch.randn(N, generator=g).to(hip), g_idx=torch.randperm(K, generator=g).to(hip))
+    x = (torch.randn(M, K, generator=g) * 0.5).to(torch.bfloat16).to(hip)
+    y = m(x)
+    assert m._plan == "fused_act_order"
+    assert torch.equal(m._qweight_sorted, ops.sort_packed_k(m.qweight, m._k_order, K, bits))
+    assert torch.equal(y, ops.woq_gemm(x.index_select(1, m._k_order), m._qweight_sorted, m.scales, m.qzeros, m.bias, N, K, gs, bits))
 
 
 def test_module_rebuilds_plan_and_call_after_g_idx_is_rewritten(hip, monkeypatch):

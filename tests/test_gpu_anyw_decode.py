@@ -237,7 +237,10 @@ def test_module_keeps_the_parent_route_elsewhere(hip):
     # a batch one row over the limit, right after a decode call (the fast path must not hand it over)
     xb = A.make_x(m.ODD_WIDTH_DECODE_MAX_M + 1, c.K, dtype).to(hip)
     assert torch.equal(m(xb), _parent_route(m, xb))
+    assert m.__dict__.get("_call") is None
     # the switch off
+    m(x1)
+    assert isinstance(m.__dict__["_call"], ops.WoqGemvAnywCall)
     m.ODD_WIDTH_DECODE = False
     assert torch.equal(m(x1), _parent_route(m, x1))
     m(x1)
@@ -249,9 +252,12 @@ def test_module_keeps_the_parent_route_elsewhere(hip):
     assert y32.dtype is torch.float32 and torch.equal(y32, m(x1.half()).float())
     assert m(x1[:0]).shape == (0, c.N)
     # the fused form keeps its meaning and takes precedence
-    m.ODD_WIDTH_FUSED = True
     m(x1)
-    assert m._plan == "fused" and not isinstance(m.__dict__.get("_call"), ops.WoqGemvAnywCall)
+    assert isinstance(m.__dict__["_call"], ops.WoqGemvAnywCall)
+    m.ODD_WIDTH_FUSED = True
+    y_fused = m(x1)
+    assert m._plan == "fused" and type(m.__dict__.get("_call")) is ops.WoqGemmCall
+    assert torch.equal(y_fused, ops.woq_gemm(x1, m.qweight, m.scales, m.qzeros, m.bias, c.N, c.K, m.group_size, m.bits))
 
 
 def test_ineligible_module_takes_the_parent_route(hip):

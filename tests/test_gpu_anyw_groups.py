@@ -270,6 +270,7 @@ def test_act_order_module_keeps_the_parent_route_elsewhere(hip):
     assert isinstance(m.__dict__["_call"], ops.WoqGemvAnywCall)
     xb = R.make_x(17, MK, dtype).to(hip)  # one row over the limit, right after a decode call
     assert torch.equal(m(xb), _parent_route(m, xb))
+    assert m.__dict__.get("_call") is None
     for switch in ("ODD_WIDTH_DECODE", "ACT_ORDER_FUSED_GATHER"):
         m(x1)
         assert m.__dict__["_call"] is not None
@@ -287,12 +288,14 @@ def test_gather_row_limit_changes_the_launches_not_the_bits(hip, dtype):
     m = _module(hip, 264, 75)
     assert m.ODD_WIDTH_GATHER_MAX_MN >= 4096  # one row of a 4096-column module at the least
     x = R.make_x(5, MK, dtype).to(hip)
-    outs = []
+    outs, calls = [], [None]
     for limit in (5 * 264, 5 * 264 - 1, 5 * 264):
         m.ODD_WIDTH_GATHER_MAX_MN = limit
-        for _ in range(2):  # the building call, then the fast path
+        for again in (False, True):  # the building call, then the fast path
             outs.append(m(x))
             call = m.__dict__["_call"]
+            assert (call is calls[-1]) == again, "a new limit rebuilds the prepared call, the same limit keeps it"
+            calls.append(call)
             assert call.ko is not None and call.gather_max_mn == limit and call.gathers(5) == (limit == 5 * 264) and call.gathers(4)
     assert all(torch.equal(o, outs[0]) for o in outs)
     ref, S = _module_oracle(m, x.cpu(), dtype)

@@ -107,14 +107,20 @@ def test_prefill_batches_take_the_dense_route(hip, monkeypatch):
     cap = MI355XWeightOnlyLinear.LUT_MAX_M
     x = torch.randn(cap + 1, 512, device=hip).to(torch.bfloat16)
     m(x[:1])  # a prepared call exists; it must not take the larger batch
+    call = m.__dict__["_call"]
+    assert call is not None and call.lut
+    y_cap = m(x[:cap])
+    assert m.__dict__["_call"] is call, "LUT_MAX_M rows rebuilt the prepared call"
     assert torch.equal(m(x), F.linear(x, m.recover(dtype=torch.bfloat16)))
+    assert m.__dict__["_call"] is None, "a batch on the dense route kept the prepared call"
     calls = []
     real = m.recover
     monkeypatch.setattr(m, "recover", lambda *a, **k: calls.append(1) or real(*a, **k))
-    m(x[:cap])
+    assert torch.equal(m(x[:cap]), y_cap)
     assert not calls
+    assert m.__dict__["_call"] is not None and m.__dict__["_call"] is not call  # rebuilt
     m(x)
-    assert calls
+    assert calls and m.__dict__["_call"] is None
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -152,13 +158,17 @@ def test_prepared_call_follows_repack_and_switch(hip):
     m.pack(_ints_of(m2), m2.scales, None, None)
     y1 = m(x)
     assert torch.equal(y1, m2(x)) and not torch.equal(y0, y1)
+    call = m.__dict__["_call"]
+    assert call is not None and call.lut
     try:
         MI355XWeightOnlyLinear.LUT_FUSED = False
-        assert _plan(m) == "dense"
-        yd = m(x)
+        yd = m(x)  # (the forward itself must notice the switch: its guard stands in front of the plan)
+        assert m.__dict__["_call"] is None and _plan(m) == "dense"
+        assert torch.equal(yd, F.linear(x, m.recover(dtype=torch.float16)))
     finally:
         MI355XWeightOnlyLinear.LUT_FUSED = True
     assert _plan(m) == "fused_lut"
+    assert torch.equal(m(x), y1) and m.__dict__["_call"] not in (None, call)  # rebuilt
     w = m.recover(dtype=torch.float16).float()
     ref = F.linear(x.float(), w)
     assert float((yd.float() - ref).abs().max()) <= 2.0**-9 * float(ref.abs().max()) + 1e-6
