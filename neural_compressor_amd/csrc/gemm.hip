@@ -60,13 +60,6 @@ constexpr int64_t GEMV8_MAX_M = 64, GEMV8_WIDE_MAX_M = 32, GEMV8_WIDE_ELEMS = (i
 // harness-build routes (tools/kbench flags; never returned by libinc_mi355x.so)
 constexpr int WOQ_ROUTE_DBG_PC = 100, WOQ_ROUTE_DBG_GEMV16_NT = 103, WOQ_ROUTE_DBG_STREAM_NT = 104;
 
-// group lookup by shift: log2(group_size) for a power of two >= 32, -1 = one group (group_size >= K), -2 = neither
-static int g_shift_of(int group_size, int64_t K) {
-  if (group_size >= K) return -1;
-  if (group_size < 32 || (group_size & (group_size - 1)) != 0) return -2;
-  return __builtin_ctz((unsigned)group_size);
-}
-
 // above 32 rows a layer of more than this many weights is the strip kernel's, not the streaming kernel's (M = 64, 11008 x 4096: 21 vs 29 us)
 constexpr int64_t STRIP_PREF_ELEMS = (int64_t)24 << 20;
 static bool strip_m(int64_t M, int64_t N, int64_t K) { return M > GEMV_MAX_M || (M > 32 && N * K > STRIP_PREF_ELEMS); }
@@ -276,8 +269,7 @@ int inc_woq_gemm(const void* x, int xdtype, const int32_t* qweight, const uint16
   const bool streams = route == INC_WOQ_ROUTE_STREAM_W4 || route == INC_WOQ_ROUTE_STREAM_W8 || route == WOQ_ROUTE_DBG_STREAM_NT;
   if ((streams || route == INC_WOQ_ROUTE_SMALL) && (!workspace || workspace_bytes < plan.need)) return INC_ERR_WORKSPACE;
   // the fp32 partials sit behind the counter block; the strip / 256-row kernels get them only when the plan has K-slices
-  unsigned* const counters = (unsigned*)workspace;
-  float* const part = workspace ? (float*)((char*)workspace + WS_COUNTER_BYTES) : nullptr;
+  const auto [counters, part] = ws_parts(workspace);
   float* const slabs = plan.splitk > 1 ? part : nullptr;
   switch (route) {
     case INC_WOQ_ROUTE_TILE_ANYW:
@@ -304,7 +296,7 @@ int inc_woq_gemm(const void* x, int xdtype, const int32_t* qweight, const uint16
     case INC_WOQ_ROUTE_STREAM_W4:
     case INC_WOQ_ROUTE_STREAM_W8:
     case WOQ_ROUTE_DBG_STREAM_NT: {  // (the last: harness, non-temporal weight loads)
-      StreamLaunch l = {a.x, M, K, a.g_shift, a.bf, a.s, bits, plan.steps, plan.mb, plan.splitk, ceil_div64(N, 64), part, counters, &a, G};
+      StreamLaunch l = {a.x, M, K, a.g_shift, a.bf, a.s, bits, plan.steps, plan.mb, plan.splitk, ceil_div64(N, 64), part, counters, &a};
       l.nt = route == WOQ_ROUTE_DBG_STREAM_NT;
       return inc_launch_woq_gemv_stream(l);
     }
@@ -335,8 +327,8 @@ int inc_woq_gemm_perm(const void* x, int xdtype, const int32_t* k_order, const i
   const WoqGemmArgs a = {(const uint16_t*)x, (const uint32_t*)qweight, scales, (const uint32_t*)qzeros, (const uint16_t*)bias, (uint16_t*)y,
                          M, N, K, ceil_div64(N, 32 / bits), plan.g_shift, xdtype == INC_BF16, inc_s(stream)};
   if (route == INC_WOQ_ROUTE_GEMV16) return inc_launch_woq_gemv16(a, k_order, false);
-  StreamLaunch l = {a.x, M, K, a.g_shift, a.bf, a.s, bits, plan.steps, plan.mb, plan.splitk, ceil_div64(N, 64), (float*)((char*)workspace + WS_COUNTER_BYTES), (unsigned*)workspace,
-                    &a, G};
+  const auto [counters, part] = ws_parts(workspace);
+  StreamLaunch l = {a.x, M, K, a.g_shift, a.bf, a.s, bits, plan.steps, plan.mb, plan.splitk, ceil_div64(N, 64), part, counters, &a};
   l.k_order = k_order;
   return inc_launch_woq_gemv_stream(l);
 }
@@ -382,32 +374,18 @@ static int woq_gemm_multi_launch(int n, const void* x, int xdtype, const int32_t
   int64_t strips;
   if (!gemv_multi_plan(n, M, N, K, group_size, bits, &g_shift, &sp, &strips)) return INC_ERR_UNSUPPORTED;  // nothing launched: the caller issues inc_woq_gemm per module
   if (k_order ? M * K >= ((int64_t)1 << 31) : (reinterpret_cast<uintptr_t>(x) & 15) != 0) return INC_ERR_UNSUPPORTED;
-  GemvBatch args = {};  // (modules past n: null tensors, N = 0)
-  args.n = n;
-  int64_t off = 0;
-  int first = 0;
   for (int i = 0; i < n; ++i) {
     INC_CHECK_ARG(qweight[i] && scales[i] && qzeros[i] && y[i]);
     if (k_order) {
       INC_CHECK_ARG(k_order[i]);
       if ((reinterpret_cast<uintptr_t>(k_order[i]) & 15) != 0) return INC_ERR_UNSUPPORTED;
-      args.k_order[i] = k_order[i];
     }
-    args.qweight[i] = (const uint32_t*)qweight[i];
-    args.scales[i] = scales[i];
-    args.qzeros[i] = (const uint32_t*)qzeros[i];
-    args.bias[i] = bias ? (const uint16_t*)bias[i] : nullptr;
-    args.y[i] = (uint16_t*)y[i];
-    args.N[i] = N[i];
-    args.part_off[i] = off;
-    args.first[i] = first;
-    off += (int64_t)sp.splitk * M * N[i];
-    first += (int)ceil_div64(N[i], 64);
   }
-  for (int i = n; i <= GEMV_MAX_BATCH; ++i) args.first[i] = first;
-  if (!workspace || workspace_bytes < WS_COUNTER_BYTES + off * 4) return INC_ERR_WORKSPACE;
-  StreamLaunch l = {(const uint16_t*)x, M, K, g_shift, xdtype == INC_BF16, inc_s(stream), bits, sp.steps, sp.mb, sp.splitk, strips,
-                    (float*)((char*)workspace + WS_COUNTER_BYTES), (unsigned*)workspace};
+  GemvBatch args;
+  const int64_t floats = gemv_batch_fill(&args, n, k_order, qweight, scales, qzeros, bias, y, sp.splitk, M, N).floats;
+  if (!workspace || workspace_bytes < WS_COUNTER_BYTES + floats * 4) return INC_ERR_WORKSPACE;
+  const auto [counters, part] = ws_parts(workspace);
+  StreamLaunch l = {(const uint16_t*)x, M, K, g_shift, xdtype == INC_BF16, inc_s(stream), bits, sp.steps, sp.mb, sp.splitk, strips, part, counters};
   l.batch = &args;
   l.batch_perm = k_order != nullptr;
   return inc_launch_woq_gemv_stream(l);
@@ -469,8 +447,8 @@ int inc_woq_gemm_gated(const void* x, int xdtype, const int32_t* k_order_gate, c
   args.part_off[1] = (int64_t)sp.splitk * M * N;
   args.first[1] = (int)(strips / 2);
   for (int i = 2; i <= GEMV_MAX_BATCH; ++i) args.first[i] = (int)strips;
-  StreamLaunch l = {(const uint16_t*)x, M, K, g_shift, xdtype == INC_BF16, inc_s(stream), bits, sp.steps, sp.mb, sp.splitk, strips,
-                    (float*)((char*)workspace + WS_COUNTER_BYTES), (unsigned*)workspace};
+  const auto [counters, part] = ws_parts(workspace);
+  StreamLaunch l = {(const uint16_t*)x, M, K, g_shift, xdtype == INC_BF16, inc_s(stream), bits, sp.steps, sp.mb, sp.splitk, strips, part, counters};
   l.batch = &args;
   l.batch_perm = perm;
   l.gated = true;

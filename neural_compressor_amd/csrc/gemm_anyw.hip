@@ -34,9 +34,10 @@
 // The multiply is on the matrix cores, not the vector ALUs: at M <= 16 neither is the limit, but the MFMA form costs the same for 1
 // and for 16 rows (F / 8 x 4 instructions per wave) where fp32 FMAs grow to 16 x 4 x F per lane -- ~7 us of VALU time at 4096^2, M = 16.
 //
-// Split-K: the sibling's hand-off, unchanged -- fp32 slabs stored write-through (`sc1`), every wave drains (`s_waitcnt vmcnt(0)`),
-// barrier, ONE relaxed agent-scope ticket per strip; the last arriver re-arms the counter, sums the slices in slice order with `sc1`
-// loads, adds the bias, rounds once and stores.  Bit-identical from call to call.
+// The way out of the workgroup is the sibling's, the same code: strip_finish (gemm_common.hpp) -- the four waves add in fixed order
+// through LDS; with K-slices the fp32 strip goes to the slice's slab write-through (`sc1`), splitk_arrive hands off (drain, barrier, ONE
+// relaxed agent-scope ticket per strip; the last arriver re-arms the counter), and the last arriver sums the slices in slice order with
+// `sc1` loads; then the bias, one rounding, the store.  Bit-identical from call to call.
 //
 // Forms: plain (inc_woq_gemv_anyw), gathered for act_order modules (inc_woq_gemv_anyw_perm), and batched over modules that share x, plain
 // or gathered (inc_woq_gemv_anyw_multi) -- one body, described above it.
@@ -87,7 +88,7 @@ __device__ __forceinline__ uint32_t anyw_field(const uint4 (&w)[AnywShape<BITS>:
 //   5 bits    110 / 110  142 / 142  110 / 110  139 / 139
 //   6 bits    112 / 108  132 / 132  112 / 108  136 / 136
 //   7 bits    106 / 104  124 / 124  106 / 104  116 / 116
-// SGPRs: 40 - 42, the gathered 1- and 2-bit forms 98 - 104.  Plain and batched: 4 waves per SIMD by registers (4 workgroups per CU); the
+// SGPRs: 37 - 42, the gathered 1- and 2-bit forms 98 - 104 (profiles/strip_epilogue/resources.txt holds every instantiation).  Plain and batched: 4 waves per SIMD by registers (4 workgroups per CU); the
 // gathered forms hold the gathered halves next to the weights in flight and come to 3 -- a decode grid (448 workgroups at 4096^2, 3 bits)
 // puts fewer than that on a CU.  No scratch anywhere; the 16 AGPRs are the four accumulators.
 template <bool IS_BF16, int BITS, bool PERM = false>
@@ -99,7 +100,6 @@ __device__ __forceinline__ void woq_gemv_anyw_body(
   using S = AnywShape<BITS>;
   constexpr int NP = S::NP, WL = S::WL, F = S::F, NF = S::NF;
   constexpr uint32_t MASK = (1u << BITS) - 1u;
-  constexpr int NOUT = 16 * 64 / 256;  // outputs per thread of the strip
   __shared__ float red[4 * 16 * 65];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int jn = lane & 15, oct = lane >> 4;
@@ -154,18 +154,12 @@ __device__ __forceinline__ void woq_gemv_anyw_body(
     zraw[t][0] = qzeros[(int64_t)gsel[t] * NW + zw0];
     zraw[t][1] = qzeros[(int64_t)gsel[t] * NW + zw1];
   }
-  // this thread's outputs of the strip: idx = tid + 256*i -> row idx>>6, column idx&63; bias fetched now
-  uint16_t braw[NOUT];
-  const uint16_t* const bsrc = bias ? bias : scales;  // always a valid address: the loads stay unconditional
-  bool out_ok[NOUT];
-  int64_t out_off[NOUT];
+  // this thread's outputs of the strip and their bias, fetched now (scales: a valid address where there is no bias).  The loop is
+  // written here, not taken from strip_out_prefetch: unrolled with the loops above it, the plain 5-bit kernels keep their 110 VGPRs
+  // (112 with the helper's loop)
+  StripOut<16> out;
 #pragma unroll
-  for (int i = 0; i < NOUT; ++i) {
-    const int idx = tid + 256 * i, m = idx >> 6, c = idx & 63;
-    out_ok[i] = m < M && n0 + c < N;
-    out_off[i] = out_ok[i] ? (int64_t)m * N + n0 + c : 0;
-    braw[i] = bsrc[out_ok[i] ? n0 + c : 0];
-  }
+  for (int i = 0; i < out.NOUT; ++i) strip_out_prefetch_one(out, i, tid, M, N, n0, bias, scales);
   __builtin_amdgcn_sched_barrier(0);  // everything above is in flight before the first use below
 
   // scale and -z * scale of (group t, column c)
@@ -211,53 +205,7 @@ __device__ __forceinline__ void woq_gemv_anyw_body(
   for (int c = 0; c < 4; ++c)
 #pragma unroll
     for (int r = 0; r < 4; ++r) red[(wave * 16 + 4 * oct + r) * 65 + 4 * jn + c] = acc[c][r];
-  __syncthreads();
-  float sum[NOUT];
-#pragma unroll
-  for (int i = 0; i < NOUT; ++i) {
-    const int idx = tid + 256 * i, m = idx >> 6, c = idx & 63;
-    sum[i] = red[(0 * 16 + m) * 65 + c] + red[(1 * 16 + m) * 65 + c] + red[(2 * 16 + m) * 65 + c] + red[(3 * 16 + m) * 65 + c];
-  }
-  if (splitk > 1) {
-    const int64_t slab = (int64_t)M * N;
-#pragma unroll
-    for (int i = 0; i < NOUT; ++i)
-      if (out_ok[i]) __hip_atomic_store(&partial[(int64_t)slice * slab + out_off[i]], sum[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // sc1
-    // publish: every wave drains its write-through stores, then one relaxed agent-scope ticket from lane 0
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-      const unsigned ticket = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const bool last = ticket == (unsigned)(splitk - 1);
-      if (last) __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-arm for the next call
-      red[0] = last ? 1.f : 0.f;
-    }
-    __syncthreads();
-    if (red[0] == 0.f) return;
-    // last arriver: fixed-order sum over the slices, up to 32 partial loads of this thread in flight at a time
-#pragma unroll
-    for (int i = 0; i < NOUT; ++i) sum[i] = 0.f;
-    constexpr int SB = 32 / NOUT;
-    for (int sl0 = 0; sl0 < splitk; sl0 += SB) {
-      float pv[SB][NOUT];
-#pragma unroll
-      for (int d = 0; d < SB; ++d) {
-        const int sl = sl0 + d < splitk ? sl0 + d : splitk - 1;
-#pragma unroll
-        for (int i = 0; i < NOUT; ++i) pv[d][i] = __hip_atomic_load(&partial[(int64_t)sl * slab + out_off[i]], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // sc1
-      }
-#pragma unroll
-      for (int d = 0; d < SB; ++d)
-#pragma unroll
-        for (int i = 0; i < NOUT; ++i) sum[i] += (sl0 + d < splitk) ? pv[d][i] : 0.f;
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < NOUT; ++i)
-    if (out_ok[i]) {
-      const float v = sum[i] + (bias ? cvt16<IS_BF16>(braw[i]) : 0.f);
-      y[out_off[i]] = IS_BF16 ? f32_to_bf16_bits(v) : f32_to_f16_bits(v);
-    }
+  strip_finish<IS_BF16, 16>(red, tid, out, bias, y, partial, counter, M, N, splitk, slice);
 }
 
 template <bool IS_BF16, int BITS>
@@ -332,14 +280,11 @@ bool anyw_multi_shape_ok(int n, int64_t M, const int64_t* N, int64_t K, int bits
   return true;
 }
 
-// group lookup by shift: contiguous groups of a power of two >= 32, or one group (g_shift = -1); G = the number of groups
+// group lookup by shift (g_shift_of): contiguous groups of a power of two >= 32, or one group (g_shift = -1); G = the number of groups
 bool anyw_groups(int64_t K, int group_size, int* g_shift_out, int64_t* G_out) {
   const int gs = (group_size == -1 || group_size >= K) ? (int)K : group_size;
-  *g_shift_out = -1;
-  if (gs < K) {
-    if (gs < 32 || (gs & (gs - 1)) != 0) return false;
-    *g_shift_out = __builtin_ctz((unsigned)gs);
-  }
+  *g_shift_out = g_shift_of(gs, K);
+  if (*g_shift_out == -2) return false;
   *G_out = *g_shift_out < 0 ? 1 : ceil_div64(K, gs);
   return true;
 }
@@ -361,8 +306,7 @@ int anyw_single(const void* x, int xdtype, const int32_t* k_order, const int32_t
     return INC_ERR_UNSUPPORTED;
   const int splitk = anyw_slices(M, N, K, bits);
   if (splitk > 1 && (!workspace || workspace_bytes < WS_COUNTER_BYTES + (int64_t)splitk * M * N * 4)) return INC_ERR_WORKSPACE;
-  unsigned* const counters = (unsigned*)workspace;
-  float* const part = splitk > 1 ? (float*)((char*)workspace + WS_COUNTER_BYTES) : nullptr;
+  const auto [counters, part] = ws_parts(workspace, splitk > 1);
   const dim3 grid((unsigned)ceil_div64(N, 64), (unsigned)splitk);
   const bool bf = xdtype == INC_BF16;
 #define INC_ANYW_ARGS(B) (const uint32_t*)qweight, scales, (const uint32_t*)qzeros, (const uint16_t*)bias, (uint16_t*)y, part, counters, (int)M, N, (int)K, ceil_div64(N, 32 / B), (int)G, g_shift, splitk
@@ -432,31 +376,16 @@ int inc_woq_gemv_anyw_multi(int n, const void* x, int xdtype, const int32_t* con
   if (!anyw_groups(K, group_size, &g_shift, &G)) return INC_ERR_UNSUPPORTED;
   if (k_order ? M * K >= ((int64_t)1 << 31) : (reinterpret_cast<uintptr_t>(x) & 15) != 0) return INC_ERR_UNSUPPORTED;
   const int splitk = (int)ceil_div64(K, anyw_slice_k(bits));
-  GemvBatch args = {};  // (members past n: null tensors, N = 0)
-  args.n = n;
-  int64_t off = 0;
-  int first = 0;
   for (int i = 0; i < n; ++i) {
     INC_CHECK_ARG(qweight[i] && scales[i] && qzeros[i] && y[i] && (!k_order || k_order[i]));
     if (((reinterpret_cast<uintptr_t>(y[i]) | reinterpret_cast<uintptr_t>(qweight[i]) | (k_order ? reinterpret_cast<uintptr_t>(k_order[i]) : 0)) & 15) != 0 ||
         (reinterpret_cast<uintptr_t>(scales[i]) & 7) != 0)
       return INC_ERR_UNSUPPORTED;
-    args.k_order[i] = k_order ? k_order[i] : nullptr;
-    args.qweight[i] = (const uint32_t*)qweight[i];
-    args.scales[i] = scales[i];
-    args.qzeros[i] = (const uint32_t*)qzeros[i];
-    args.bias[i] = bias ? (const uint16_t*)bias[i] : nullptr;
-    args.y[i] = (uint16_t*)y[i];
-    args.N[i] = N[i];
-    args.part_off[i] = off;
-    args.first[i] = first;
-    off += (int64_t)splitk * M * N[i];
-    first += (int)ceil_div64(N[i], 64);
   }
-  for (int i = n; i <= GEMV_MAX_BATCH; ++i) args.first[i] = first;
-  if (splitk > 1 && (!workspace || workspace_bytes < WS_COUNTER_BYTES + off * 4)) return INC_ERR_WORKSPACE;
-  unsigned* const counters = (unsigned*)workspace;
-  float* const part = splitk > 1 ? (float*)((char*)workspace + WS_COUNTER_BYTES) : nullptr;
+  GemvBatch args;
+  const int64_t floats = gemv_batch_fill(&args, n, k_order, qweight, scales, qzeros, bias, y, splitk, M, N).floats;
+  if (splitk > 1 && (!workspace || workspace_bytes < WS_COUNTER_BYTES + floats * 4)) return INC_ERR_WORKSPACE;
+  const auto [counters, part] = ws_parts(workspace, splitk > 1);
   const dim3 grid((unsigned)strips, (unsigned)splitk);
   const bool bf = xdtype == INC_BF16, perm = k_order != nullptr;
 #define INC_ANYW_MULTI(B)                                                                                                                    \

@@ -65,6 +65,45 @@ struct GemvBatch {
   int first[GEMV_MAX_BATCH + 1];     // first strip of every module, then the number of strips
   int n;
 };
+// fills the batch from the entry points' pointer arrays (k_order / bias may be NULL: no orders / no biases; members past n stay null with
+// N = 0): member i's strips start at first[i], its slabs [splitk][M][N[i]] at float part_off[i].  Returns the totals.  No checks: each
+// entry point makes its own before it calls this.
+struct GemvBatchTotals { int64_t floats, strips; };
+inline GemvBatchTotals gemv_batch_fill(GemvBatch* b, int n, const int32_t* const* k_order, const int32_t* const* qweight, const uint16_t* const* scales,
+                                       const int32_t* const* qzeros, const void* const* bias, void* const* y, int splitk, int64_t M, const int64_t* N) {
+  *b = GemvBatch{};
+  b->n = n;
+  int64_t off = 0;
+  int first = 0;
+  for (int i = 0; i < n; ++i) {
+    b->k_order[i] = k_order ? k_order[i] : nullptr;
+    b->qweight[i] = (const uint32_t*)qweight[i];
+    b->scales[i] = scales[i];
+    b->qzeros[i] = (const uint32_t*)qzeros[i];
+    b->bias[i] = bias ? (const uint16_t*)bias[i] : nullptr;
+    b->y[i] = (uint16_t*)y[i];
+    b->N[i] = N[i];
+    b->part_off[i] = off;
+    b->first[i] = first;
+    off += (int64_t)splitk * M * N[i];
+    first += (int)((N[i] + 63) / 64);
+  }
+  for (int i = n; i <= GEMV_MAX_BATCH; ++i) b->first[i] = first;
+  return {off, first};
+}
+
+// the two parts of the workspace (layout above); `slabs` = false: a launch without K-slices gets no partials
+struct WsParts { unsigned* counters; float* part; };
+inline WsParts ws_parts(void* workspace, bool slabs = true) {
+  return {(unsigned*)workspace, workspace && slabs ? (float*)((char*)workspace + WS_COUNTER_BYTES) : nullptr};
+}
+
+// group lookup by shift: log2(group_size) for a power of two >= 32, -1 = one group (group_size >= K), -2 = neither
+inline int g_shift_of(int group_size, int64_t K) {
+  if (group_size >= K) return -1;
+  if (group_size < 32 || (group_size & (group_size - 1)) != 0) return -2;
+  return __builtin_ctz((unsigned)group_size);
+}
 
 // gemm_stream.hip: the streaming GEMV (M <= 64) in all its forms, and the no-split decode kernel.  A launch is x, the plan (steps, mb,
 // splitk: woq_gemm_plan / gemv_multi_plan) and the weights: ONE module `mod` (its x, M, K, g_shift, bf, s are not read) -- plain, gathered
@@ -82,7 +121,6 @@ struct StreamLaunch {
   float* part;
   unsigned* counters;
   const WoqGemmArgs* mod = nullptr;
-  int64_t G = 0;       // (an argument the plain kernel takes and does not use)
   const int32_t* k_order = nullptr;
   const GemvBatch* batch = nullptr;
   bool nt = false;
@@ -241,6 +279,113 @@ __device__ __forceinline__ void splitk_load16x16_sc1(f32x4 (&pv)[4][4], const fl
       : "v"(o0), "v"(o1), "v"(o2), "v"(o3), "s"(b0), "s"(b1), "s"(b2), "s"(b3)
       : "memory");
 }
+
+// ---- the way out of a split-K workgroup -----------------------------------------------------------------------------------------------
+// The hand-off after a workgroup's write-through (`sc1`) partial stores: every wave drains them (`s_waitcnt vmcnt(0)`), barrier, ONE
+// relaxed agent-scope ticket from thread 0; the arriver with ticket `arrivals` - 1 re-arms the counter for the next call and is told so
+// through `lds_word`, an LDS word of the caller's that nothing else reads until the next barrier.  Returns whether this workgroup is that
+// last arriver; it then reads the slabs with `sc1` loads (L2-coherent), so neither side needs an agent-scope fence.  The order of these
+// steps IS the protocol (MI355X_MICROARCH.md, "Valid forms besides R1/R2"): the stores go before the call, the loads after it.
+template <typename T>
+__device__ __forceinline__ bool splitk_arrive(unsigned* counter, int arrivals, T* lds_word) {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned ticket = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const bool last = ticket == (unsigned)(arrivals - 1);
+    if (last) __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-arm for the next call
+    *lds_word = last ? T(1) : T(0);
+  }
+  __syncthreads();
+  return *lds_word != T(0);
+}
+
+// The (64-column strip, K-slice) workgroups of the decode GEMVs (gemm_stream.hip, gemm_anyw.hip): 256 threads, ROWS rows of x, the four
+// waves' fp32 strips in red[wave][ROWS][65].  Thread tid owns outputs idx = tid + 256 i -> row idx >> 6, column idx & 63 of the strip.
+template <int ROWS>
+struct StripOut {
+  static constexpr int NOUT = ROWS * 64 / 256;  // outputs per thread
+  bool ok[NOUT];                                // inside [M, N]
+  int64_t off[NOUT];                            // m * N + n (0 where !ok)
+  uint16_t braw[NOUT];                          // the bias of the column, fetched up front
+};
+// output i of the thread; `fallback`: any valid address (read instead of a NULL bias, so that the loads stay unconditional)
+template <int ROWS>
+__device__ __forceinline__ void strip_out_prefetch_one(StripOut<ROWS>& o, int i, int tid, int M, int64_t N, int64_t n0, const uint16_t* __restrict__ bias,
+                                                       const uint16_t* __restrict__ fallback) {
+  const uint16_t* const bsrc = bias ? bias : fallback;
+  const int idx = tid + 256 * i, m = idx >> 6, c = idx & 63;
+  o.ok[i] = m < M && n0 + c < N;
+  o.off[i] = o.ok[i] ? (int64_t)m * N + n0 + c : 0;
+  o.braw[i] = bsrc[o.ok[i] ? n0 + c : 0];
+}
+// all of them, issued with the body's other loads before its sched_barrier: the bias is in flight with the weights
+template <int ROWS>
+__device__ __forceinline__ void strip_out_prefetch(StripOut<ROWS>& o, int tid, int M, int64_t N, int64_t n0, const uint16_t* __restrict__ bias,
+                                                   const uint16_t* __restrict__ fallback) {
+#pragma unroll
+  for (int i = 0; i < StripOut<ROWS>::NOUT; ++i) strip_out_prefetch_one(o, i, tid, M, N, n0, bias, fallback);
+}
+// barrier, then the sum of the four waves in wave order
+template <int ROWS>
+__device__ __forceinline__ void strip_sum_waves(const float* red, int tid, float (&sum)[StripOut<ROWS>::NOUT]) {
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < StripOut<ROWS>::NOUT; ++i) {
+    const int idx = tid + 256 * i, m = idx >> 6, c = idx & 63;
+    sum[i] = red[(0 * ROWS + m) * 65 + c] + red[(1 * ROWS + m) * 65 + c] + red[(2 * ROWS + m) * 65 + c] + red[(3 * ROWS + m) * 65 + c];
+  }
+}
+// the strip sum of one slice into its slab [M][N], write-through
+template <int ROWS>
+__device__ __forceinline__ void strip_store_partial(float* __restrict__ slab, const StripOut<ROWS>& o, const float (&sum)[StripOut<ROWS>::NOUT]) {
+#pragma unroll
+  for (int i = 0; i < StripOut<ROWS>::NOUT; ++i)
+    if (o.ok[i]) __hip_atomic_store(&slab[o.off[i]], sum[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // sc1
+}
+// the last arriver's fixed-order sum over the K-slices of one module's slabs (`sc1` loads), slice 0 first; up to 32 partial loads of a
+// thread in flight (8 slices for M <= 16: one L2 round trip)
+template <int NOUT>
+__device__ __forceinline__ void splitk_sum_slices(const float* __restrict__ partial, int64_t slab, int splitk, const int64_t (&out_off)[NOUT], float (&sum)[NOUT]) {
+#pragma unroll
+  for (int i = 0; i < NOUT; ++i) sum[i] = 0.f;
+  constexpr int SB = 32 / NOUT;
+  for (int sl0 = 0; sl0 < splitk; sl0 += SB) {
+    float pv[SB][NOUT];
+#pragma unroll
+    for (int d = 0; d < SB; ++d) {
+      const int sl = sl0 + d < splitk ? sl0 + d : splitk - 1;
+#pragma unroll
+      for (int i = 0; i < NOUT; ++i) pv[d][i] = __hip_atomic_load(&partial[(int64_t)sl * slab + out_off[i]], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // sc1
+    }
+#pragma unroll
+    for (int d = 0; d < SB; ++d)
+#pragma unroll
+      for (int i = 0; i < NOUT; ++i) sum[i] += (sl0 + d < splitk) ? pv[d][i] : 0.f;
+  }
+}
+// everything after the waves have written red[]: waves 0 + 1 + 2 + 3; with K-slices the partial store, the hand-off on the strip's
+// `counter` and, in the last arriver, the slices in slice order; then + bias, ONE rounding, store.  `partial`: the module's slabs [slice][M][N]
+template <bool IS_BF16, int ROWS>
+__device__ __forceinline__ void strip_finish(float* red, int tid, const StripOut<ROWS>& o, const uint16_t* __restrict__ bias, uint16_t* __restrict__ y,
+                                             float* __restrict__ partial, unsigned* __restrict__ counter, int M, int64_t N, int splitk, int slice) {
+  constexpr int NOUT = StripOut<ROWS>::NOUT;
+  float sum[NOUT];
+  strip_sum_waves<ROWS>(red, tid, sum);
+  if (splitk > 1) {
+    const int64_t slab = (int64_t)M * N;
+    strip_store_partial<ROWS>(partial + (int64_t)slice * slab, o, sum);
+    if (!splitk_arrive(counter, splitk, red)) return;
+    splitk_sum_slices<NOUT>(partial, slab, splitk, o.off, sum);
+  }
+#pragma unroll
+  for (int i = 0; i < NOUT; ++i)
+    if (o.ok[i]) {
+      const float v = sum[i] + (bias ? cvt16<IS_BF16>(o.braw[i]) : 0.f);
+      y[o.off[i]] = IS_BF16 ? f32_to_bf16_bits(v) : f32_to_f16_bits(v);
+    }
+}
+
 // four adjacent outputs of one row: + bias, one rounding to the 16-bit type, one 8-byte store (y + n with n % 4 == 0 and N % 4 == 0)
 template <bool IS_BF16>
 __device__ __forceinline__ void store_out4(uint16_t* dst, float4 v, const uint16_t* bias4) {

@@ -189,18 +189,8 @@ __global__ __launch_bounds__(256) void woq_gemm_lut_kernel(
         const int64_t m = m0 + 16 * b + 4 * oct + r;
         if (n_ok && m < M) __hip_atomic_store(&partial[(int64_t)slice * slab + m * N + n], acc[b][r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // sc1
       }
-    // publish: every wave drains its write-through stores, then one relaxed agent-scope ticket from thread 0
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-      unsigned* counter = counters + (int64_t)mt * gridDim.x + strip;
-      const unsigned ticket = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const bool last = ticket == (unsigned)(splitk - 1);
-      if (last) __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-arm for the next call
-      last_flag = last ? 1 : 0;
-    }
-    __syncthreads();
-    if (!last_flag) return;
+    // publish: drain, barrier, one ticket (splitk_arrive, gemm_common.hpp)
+    if (!splitk_arrive(counters + (int64_t)mt * gridDim.x + strip, splitk, &last_flag)) return;
     // last arriver: fixed-order sum over the slices (its own slab included)
 #pragma unroll
     for (int b = 0; b < MB; ++b) acc[b] = f32x4{0.f, 0.f, 0.f, 0.f};

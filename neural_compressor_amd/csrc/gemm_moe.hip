@@ -253,18 +253,8 @@ __global__ __launch_bounds__(256) void woq_moe_gemm_kernel(
             for (int c = 0; c < 4; ++c) __hip_atomic_store(dst + c, acc[s][b][c][r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // sc1
           }
         }
-    // publish: every wave drains its write-through stores, then one relaxed agent-scope ticket from thread 0
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-      unsigned* counter = counters + (int64_t)tile * gridDim.x + strip;
-      const unsigned ticket = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const bool last = ticket == (unsigned)(splitk - 1);
-      if (last) __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-arm for the next call
-      last_flag = last ? 1 : 0;
-    }
-    __syncthreads();
-    if (!last_flag) return;
+    // publish: drain, barrier, one ticket (splitk_arrive, gemm_common.hpp)
+    if (!splitk_arrive(counters + (int64_t)tile * gridDim.x + strip, splitk, &last_flag)) return;
     // last arriver: fixed-order sum over the slices (its own slab included)
 #pragma unroll
     for (int s = 0; s < NS; ++s)

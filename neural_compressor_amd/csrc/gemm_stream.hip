@@ -13,13 +13,14 @@ namespace {
 // (256 at 4096^2: one per CU).  x is the 16-row A operand of v_mfma_f32_16x16x32 (rows >= M zeroed), each
 // lane's 16-byte weight load is 4 adjacent columns = 4 B operands (output column 4*(lane&15)+c).
 // Reduction: the 4 waves add through LDS; across workgroups each writes its fp32 partial strip, then the
-// LAST workgroup to arrive on the strip's counter (agent-scope release / acquire, cdna_hip_programming.md
-// Guideline 16) sums the partials in a fixed order, adds the bias, converts and stores -> one launch,
-// deterministic.  The counters live in the caller's workspace, must be zero on entry and are returned to
-// zero by the last arriver.
-// Hand-off of the split-K partials (MI355X_MICROARCH.md, "Valid forms besides R1/R2"): write-through (`sc1`) partial stores ->
-// every wave drains them (`s_waitcnt vmcnt(0)`) -> barrier -> ONE relaxed agent-scope ticket; the last arriver reads the slabs
-// with `sc1` loads (L1-bypassing), so neither side needs an agent-scope fence (the release / acquire pair this replaces cost
+// LAST workgroup to arrive on the strip's counter sums the partials in a fixed order, adds the bias, converts
+// and stores -> one launch, deterministic.  The counters live in the caller's workspace, must be zero on entry
+// and are returned to zero by the last arriver.  All of that -- the output map and bias prefetch (StripOut), the
+// four-wave sum, the partial store, the hand-off (splitk_arrive) and the slice sum -- is strip_finish and its
+// pieces in gemm_common.hpp, shared with gemm_anyw.hip; the body below ends in it, the gated pair in a tail of its
+// own built from the same pieces.  The hand-off in one line: write-through (`sc1`) partial stores -> every wave
+// drains them -> barrier -> ONE relaxed agent-scope ticket; the last arriver reads the slabs with `sc1` loads, so
+// neither side needs an agent-scope fence (the release / acquire pair this replaced cost
 // ~3.4 us of an 8.4 us kernel).  VSTEPS = MFMA K=32 steps per wave: 8 (a wave streams 8 KiB of weights) for large matrices,
 // 4 when that would leave CUs without a workgroup or SIMDs with a single wave (the dequantisation arithmetic of a wave is a
 // serial ~60-instruction chain per step).
@@ -42,32 +43,11 @@ constexpr int VS = 8;   // largest VSTEPS (sizes the workspace)
 // done once its gather is issued; x is addressed by 32-bit byte offsets (the entry point requires M * K < 2^31).  perm_load8 /
 // perm_gather8 live in gemm_common.hpp: gemm_anyw.hip gathers the same way.
 
-// the last arriver's fixed-order sum over the K-slices of one member's slabs (`sc1` loads), up to 32 partial loads of a thread in flight
-template <int NOUT>
-__device__ __forceinline__ void splitk_sum_slices(const float* __restrict__ partial, int64_t slab, int splitk, const int64_t (&out_off)[NOUT], float (&sum)[NOUT]) {
-#pragma unroll
-  for (int i = 0; i < NOUT; ++i) sum[i] = 0.f;
-  constexpr int SB = 32 / NOUT;
-  for (int sl0 = 0; sl0 < splitk; sl0 += SB) {
-    float pv[SB][NOUT];
-#pragma unroll
-    for (int d = 0; d < SB; ++d) {
-      const int sl = sl0 + d < splitk ? sl0 + d : splitk - 1;
-#pragma unroll
-      for (int i = 0; i < NOUT; ++i) pv[d][i] = __hip_atomic_load(&partial[(int64_t)sl * slab + out_off[i]], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // sc1
-    }
-#pragma unroll
-    for (int d = 0; d < SB; ++d)
-#pragma unroll
-      for (int i = 0; i < NOUT; ++i) sum[i] += (sl0 + d < splitk) ? pv[d][i] : 0.f;
-  }
-}
-
 // GATED (inc_woq_gemm_gated: gate_proj / up_proj of a dense MLP, same N): the workgroup is strip `strip` of member `member` (0 = gate,
 // 1 = up) and runs the body unchanged up to its fp32 strip sum.  Both members ALWAYS write that sum to their slabs
 // partial[member][slice][M][N] (also with one K-slice), and strip j of gate and strip j of up share `counter`: the arriver with ticket
 // 2 * splitk - 1 sums gate's slices in slice order, then up's -- the very sums the batched launch would have rounded -- and stores
-// rx(g / (1 + expf(-g)) * u), the fp32 expression of gemm_moe.hip's mode 0.  Same hand-off as below, with twice the arrivals.
+// rx(g / (1 + expf(-g)) * u), the fp32 expression of gemm_moe.hip's mode 0.  The same hand-off (splitk_arrive), with twice the arrivals.
 template <bool IS_BF16, bool G128, int VSTEPS, int MB, bool NT = false, int BITS = 4, bool PERM = false, bool GATED = false>
 __device__ __forceinline__ void woq_gemv_w4_body(
     const uint16_t* __restrict__ x, const uint32_t* __restrict__ qweight, const uint16_t* __restrict__ scales,
@@ -136,18 +116,9 @@ __device__ __forceinline__ void woq_gemv_w4_body(
     zraw[i] = qzeros[g * NW + (BITS == 8 ? (ncol >> 2) : (ncol >> 3))];
   }
   const int zsh = 4 * (int)(ncol & 7);  // ncol % 4 == 0: the 4 zero nibbles sit at bits zsh .. zsh+15
-  // this thread's outputs of the strip: idx = tid + 256*i -> row idx>>6, column idx&63; bias fetched now
-  uint16_t braw[NOUT];
-  const uint16_t* const bsrc = bias ? bias : scales;  // always a valid address: the loads stay unconditional
-  bool out_ok[NOUT];
-  int64_t out_off[NOUT];
-#pragma unroll
-  for (int i = 0; i < NOUT; ++i) {
-    const int idx = tid + 256 * i, m = idx >> 6, c = idx & 63;
-    out_ok[i] = m < M && n0 + c < N;
-    out_off[i] = out_ok[i] ? (int64_t)m * N + n0 + c : 0;
-    braw[i] = bsrc[out_ok[i] ? n0 + c : 0];
-  }
+  // this thread's outputs of the strip and their bias, fetched now (scales: a valid address where there is no bias)
+  StripOut<ROWS> out;
+  strip_out_prefetch(out, tid, M, N, n0, bias, scales);
   __builtin_amdgcn_sched_barrier(0);  // everything above is in flight before the first use below
 
   f32x4 acc[MB][4];
@@ -194,81 +165,24 @@ __device__ __forceinline__ void woq_gemv_w4_body(
     for (int c = 0; c < 4; ++c)
 #pragma unroll
       for (int r = 0; r < 4; ++r) red[(wave * ROWS + 16 * b + 4 * oct + r) * 65 + 4 * jn + c] = acc[b][c][r];
-  __syncthreads();
-  float sum[NOUT];
-#pragma unroll
-  for (int i = 0; i < NOUT; ++i) {
-    const int idx = tid + 256 * i, m = idx >> 6, c = idx & 63;
-    sum[i] = red[(0 * ROWS + m) * 65 + c] + red[(1 * ROWS + m) * 65 + c] + red[(2 * ROWS + m) * 65 + c] + red[(3 * ROWS + m) * 65 + c];
-  }
-  if constexpr (GATED) {
+  if constexpr (GATED) {  // both members always write their slabs; the last of the 2 * splitk arrivers forms the product
+    float sum[NOUT], gs[NOUT], us[NOUT];
+    strip_sum_waves<ROWS>(red, tid, sum);
     const int64_t slab = (int64_t)M * N;
-    float* const mine = partial + (int64_t)member * splitk * slab;
+    strip_store_partial<ROWS>(partial + ((int64_t)member * splitk + slice) * slab, out, sum);
+    if (!splitk_arrive(counter, 2 * splitk, red)) return;
+    splitk_sum_slices<NOUT>(partial, slab, splitk, out.off, gs);
+    splitk_sum_slices<NOUT>(partial + (int64_t)splitk * slab, slab, splitk, out.off, us);
 #pragma unroll
     for (int i = 0; i < NOUT; ++i)
-      if (out_ok[i]) __hip_atomic_store(&mine[(int64_t)slice * slab + out_off[i]], sum[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // sc1
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-      const unsigned ticket = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const bool last = ticket == (unsigned)(2 * splitk - 1);
-      if (last) __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-arm for the next call
-      red[0] = last ? 1.f : 0.f;
-    }
-    __syncthreads();
-    if (red[0] == 0.f) return;
-    float gs[NOUT], us[NOUT];
-    splitk_sum_slices<NOUT>(partial, slab, splitk, out_off, gs);
-    splitk_sum_slices<NOUT>(partial + (int64_t)splitk * slab, slab, splitk, out_off, us);
-#pragma unroll
-    for (int i = 0; i < NOUT; ++i)
-      if (out_ok[i]) {
+      if (out.ok[i]) {
         const float g = gs[i], u = us[i];
         const float v = g / (1.f + expf(-g)) * u;
-        y[out_off[i]] = IS_BF16 ? f32_to_bf16_bits(v) : f32_to_f16_bits(v);
+        y[out.off[i]] = IS_BF16 ? f32_to_bf16_bits(v) : f32_to_f16_bits(v);
       }
-    return;
+  } else {
+    strip_finish<IS_BF16, ROWS>(red, tid, out, bias, y, partial, counter, M, N, splitk, slice);
   }
-  if (splitk > 1) {
-    const int64_t slab = (int64_t)M * N;
-#pragma unroll
-    for (int i = 0; i < NOUT; ++i)
-      if (out_ok[i]) __hip_atomic_store(&partial[(int64_t)slice * slab + out_off[i]], sum[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // sc1
-    // publish: every wave drains its write-through stores, then one relaxed agent-scope ticket from lane 0
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-      const unsigned ticket = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const bool last = ticket == (unsigned)(splitk - 1);
-      if (last) __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-arm for the next call
-      red[0] = last ? 1.f : 0.f;
-    }
-    __syncthreads();
-    if (red[0] == 0.f) return;
-    // last arriver: fixed-order sum over the slices, up to 32 partial loads of this thread in flight at a time
-#pragma unroll
-    for (int i = 0; i < NOUT; ++i) sum[i] = 0.f;
-    constexpr int SB = 32 / NOUT;  // slices per batch (8 for M <= 16: one L2 round trip for up to 8 slices)
-    for (int sl0 = 0; sl0 < splitk; sl0 += SB) {
-      float pv[SB][NOUT];
-#pragma unroll
-      for (int d = 0; d < SB; ++d) {
-        const int sl = sl0 + d < splitk ? sl0 + d : splitk - 1;
-#pragma unroll
-        for (int i = 0; i < NOUT; ++i) pv[d][i] = __hip_atomic_load(&partial[(int64_t)sl * slab + out_off[i]], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // sc1
-      }
-#pragma unroll
-      for (int d = 0; d < SB; ++d)
-#pragma unroll
-        for (int i = 0; i < NOUT; ++i) sum[i] += (sl0 + d < splitk) ? pv[d][i] : 0.f;
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < NOUT; ++i)
-    if (out_ok[i]) {
-      const float v = sum[i] + (bias ? cvt16<IS_BF16>(braw[i]) : 0.f);
-      y[out_off[i]] = IS_BF16 ? f32_to_bf16_bits(v) : f32_to_f16_bits(v);
-    }
 }
 
 template <bool IS_BF16, bool G128, int VSTEPS, int MB, bool NT = false, int BITS = 4>
@@ -276,7 +190,7 @@ __global__ __launch_bounds__(256) void woq_gemv_w4_kernel(
     const uint16_t* __restrict__ x, const uint32_t* __restrict__ qweight, const uint16_t* __restrict__ scales,
     const uint32_t* __restrict__ qzeros, const uint16_t* __restrict__ bias, uint16_t* __restrict__ y,
     float* __restrict__ partial, unsigned* __restrict__ counters, int M, int64_t N, int64_t K, int64_t NW,
-    int64_t G, int g_shift, int splitk) {
+    int g_shift, int splitk) {
   woq_gemv_w4_body<IS_BF16, G128, VSTEPS, MB, NT, BITS>(x, qweight, scales, qzeros, bias, y, partial, counters + blockIdx.x, M, N, K, NW, g_shift, splitk,
                                                  (int)blockIdx.x, (int)blockIdx.y);
 }
@@ -437,12 +351,12 @@ int stream_rung(const StreamLaunch& l) {
     woq_gemv_w4_perm_kernel<F, GG, V, B, W><<<grid, 256, 0, l.s>>>(l.x, l.k_order, l.mod->qw, l.mod->scales, l.mod->qz, l.mod->bias, l.mod->y, l.part, l.counters, (int)l.M, l.mod->N, l.K, l.mod->NW, l.g_shift, l.splitk);
   } else if (l.nt) {
 #ifdef INC_KBENCH
-    if constexpr (F && GG && B == 1 && W == 4) woq_gemv_w4_kernel<F, GG, V, B, true><<<grid, 256, 0, l.s>>>(l.x, l.mod->qw, l.mod->scales, l.mod->qz, l.mod->bias, l.mod->y, l.part, l.counters, (int)l.M, l.mod->N, l.K, l.mod->NW, l.G, l.g_shift, l.splitk);
+    if constexpr (F && GG && B == 1 && W == 4) woq_gemv_w4_kernel<F, GG, V, B, true><<<grid, 256, 0, l.s>>>(l.x, l.mod->qw, l.mod->scales, l.mod->qz, l.mod->bias, l.mod->y, l.part, l.counters, (int)l.M, l.mod->N, l.K, l.mod->NW, l.g_shift, l.splitk);
     else
 #endif
       return INC_ERR_UNSUPPORTED;
   } else {
-    woq_gemv_w4_kernel<F, GG, V, B, false, W><<<grid, 256, 0, l.s>>>(l.x, l.mod->qw, l.mod->scales, l.mod->qz, l.mod->bias, l.mod->y, l.part, l.counters, (int)l.M, l.mod->N, l.K, l.mod->NW, l.G, l.g_shift, l.splitk);
+    woq_gemv_w4_kernel<F, GG, V, B, false, W><<<grid, 256, 0, l.s>>>(l.x, l.mod->qw, l.mod->scales, l.mod->qz, l.mod->bias, l.mod->y, l.part, l.counters, (int)l.M, l.mod->N, l.K, l.mod->NW, l.g_shift, l.splitk);
   }
   INC_LAUNCH_RETURN();
 }

@@ -298,18 +298,8 @@ __global__ __launch_bounds__(64 * WAVES) void woq_gemm_w4_strip_kernel(
     }
   }
   if (splitk <= 1) return;
-  // publish: every wave drains its write-through stores, then one relaxed agent-scope ticket from thread 0
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  unsigned* const counter = counters + (by * gridDim.x + bx);
-  if (tid == 0) {
-    const unsigned ticket = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const bool last = ticket == (unsigned)(splitk - 1);
-    if (last) __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-arm for the next call
-    red[0] = last ? 1.f : 0.f;
-  }
-  __syncthreads();
-  if (red[0] == 0.f) return;
+  // publish: drain, barrier, one ticket (splitk_arrive, gemm_common.hpp)
+  if (!splitk_arrive(counters + (by * gridDim.x + bx), splitk, red)) return;
   // last arriver: fixed-order sum over the slices (sc1 16-byte loads: the partials were written through); 4 column quads x up to 4
   // slices of a thread are in flight together
   constexpr int QUADS = ROWS * COLS / 4 / NT;
