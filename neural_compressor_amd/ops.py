@@ -1550,8 +1550,9 @@ _ws_i8_cache = {}
 
 
 def _workspace_i8(dev, nbytes):
-    """Zero-filled on creation (arrival tickets), one per (device, stream); separate from the 4-bit GEMM's workspace
-    because both kernels keep their tickets in the first 16 KiB."""
+    """The int32 slabs of the W8A8 GEMM's K-split tail tiles, one buffer per (device, stream).  The kernels keep no state in it
+    (every slab element that is read was written by the same call), so its contents never matter; separate from the 4-bit
+    GEMM's workspace, whose first 16 KiB hold arrival counters that must stay zero between calls."""
     key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
     buf = _ws_i8_cache.get(key)
     if buf is None or buf.numel() < nbytes:
