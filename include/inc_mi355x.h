@@ -621,6 +621,25 @@ int inc_probe_mfma_bf16(const void* src, float* sink, int blocks, int iters, dou
  *   `rocprofv3 --kernel-trace` timeline shows as inc_trace_marker_kernel with Grid_Size_X = 64 * id (scripts/step_timeline.py). */
 int inc_trace_marker(int id, inc_stream_t stream);
 
+/* ---- forward elementwise chains of a Llama block (csrc/fwd_elementwise.hip) -------------------------------------------------- *
+ * One streaming kernel each for the three elementwise chains of a block forward, BIT-IDENTICAL to eager PyTorch-ROCm (every
+ * intermediate rounds to the tensor dtype where a torch kernel would).  dtype INC_BF16 / INC_F16.  All three return
+ * INC_ERR_BAD_ARG for a NULL pointer or a non-positive size before any HIP call, and INC_ERR_UNSUPPORTED (nothing launched) for
+ * anything they do not take -- the caller then runs the eager ops.  Every pointer must be 16-byte aligned.
+ * inc_fwd_silu_mul: out[i] = DT(float(DT(g / (1 + expf(-g)))) * float(up[i])), g = float(gate[i]); n contiguous elements, any n.
+ * inc_fwd_rope: q [B, Hq, T, D], k [B, Hk, T, D] (Hk may differ: GQA), cos / sin contiguous [cs_batch, T, D] with cs_batch 1 or B;
+ *   out[.., d] = DT(DT(x[d] * cos[d]) + DT(r[d] * sin[d])), r[d] = -x[d + D/2] for d < D/2, else x[d - D/2].  `strides`: HOST array
+ *   of 12 element strides, (b, h, t) of q, k, q_out, k_out in that order (the d stride is 1); each a non-negative multiple of 8.
+ *   INC_ERR_UNSUPPORTED unless D % 16 == 0 and B * T * (Hq + Hk) * D / 16 < 2^31.
+ * inc_fwd_rmsnorm: LlamaRMSNorm.forward on row-major contiguous x [rows, cols], weight [cols]:
+ *   out = DT(float(w) * float(DT(float(x) * rsqrt(mean(float(x)^2) + eps)))), the mean summed in the order of torch's reduction
+ *   kernel for this shape (fwd_elementwise.hip).  INC_ERR_UNSUPPORTED unless rows >= 8, cols % 8 == 0 and 256 <= cols <= 16384:
+ *   torch reduces other shapes in another order.                                                                             */
+int inc_fwd_silu_mul(const void* gate, const void* up, void* out, int64_t n, int dtype, inc_stream_t stream);
+int inc_fwd_rope(const void* q, const void* k, const void* cos, const void* sin, void* q_out, void* k_out, int64_t B, int64_t Hq,
+                 int64_t Hk, int64_t T, int64_t D, const int64_t* strides, int64_t cs_batch, int dtype, inc_stream_t stream);
+int inc_fwd_rmsnorm(const void* x, const void* w, void* out, int64_t rows, int64_t cols, float eps, int dtype, inc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

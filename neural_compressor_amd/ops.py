@@ -1333,6 +1333,69 @@ def probe_mfma_bf16(src, sink, blocks, iters):
     return flops.value
 
 
+# ---------------------------------------------------------------------------------------------------
+# forward elementwise chains of a Llama block (csrc/fwd_elementwise.hip): bit-identical to eager, or declined
+# ---------------------------------------------------------------------------------------------------
+def _fwd_call(fn, name, args):
+    """check(rc) -- except INC_ERR_UNSUPPORTED (-2: nothing was launched), which is False: the caller runs the eager ops."""
+    rc = fn(*args)
+    if rc == -2:
+        return False
+    check(rc, name)
+    return True
+
+
+def fwd_silu_mul(gate, up):
+    """`silu(gate) * up` with eager's two roundings in one pass (inc_fwd_silu_mul); None where the library declines."""
+    dev = _dev(gate, up)
+    if gate.shape != up.shape or gate.dtype != up.dtype or gate.numel() == 0:
+        return None
+    out = torch.empty_like(gate)
+    with torch.cuda.device(dev):
+        ok = _fwd_call(lib.inc_fwd_silu_mul, "inc_fwd_silu_mul", (_ptr(gate), _ptr(up), _ptr(out), gate.numel(), dtype_code(gate.dtype), _stream()))
+    return out if ok else None
+
+
+def fwd_rmsnorm(x, weight, eps):
+    """LlamaRMSNorm.forward on contiguous x [..., cols] in one pass (inc_fwd_rmsnorm); None where the library declines (shapes whose
+    mean torch sums in an order the kernel does not reproduce)."""
+    dev = _dev(x, weight)
+    cols = x.shape[-1]
+    if x.dtype != weight.dtype or weight.shape != (cols,) or x.numel() == 0:
+        return None
+    out = torch.empty_like(x)
+    with torch.cuda.device(dev):
+        ok = _fwd_call(lib.inc_fwd_rmsnorm, "inc_fwd_rmsnorm",
+                       (_ptr(x), _ptr(weight), _ptr(out), x.numel() // cols, cols, float(eps), dtype_code(x.dtype), _stream()))
+    return out if ok else None
+
+
+def fwd_rope(q, k, cos, sin, q_out_strides, k_out_strides):
+    """apply_rotary_pos_emb(q, k, cos, sin) for q [B, Hq, T, D], k [B, Hk, T, D] addressed by their strides (last stride 1) and contiguous
+    cos / sin [1 or B, T, D], in one launch (inc_fwd_rope).  The outputs get the given strides (the ones eager's results have); None where
+    the library declines."""
+    import ctypes
+
+    for t in (q, k, cos, sin):
+        if t.device.type != "cuda" or t.device != q.device or t.dtype != q.dtype:
+            return None
+    if q.dim() != 4 or k.dim() != 4 or cos.dim() != 3 or cos.shape != sin.shape or not cos.is_contiguous() or not sin.is_contiguous():
+        return None
+    B, Hq, T, D = q.shape
+    if k.shape[0] != B or k.shape[2] != T or k.shape[3] != D or cos.shape[1:] != (T, D) or cos.shape[0] not in (1, B):
+        return None
+    if q.numel() == 0 or k.numel() == 0 or q.stride(3) != 1 or k.stride(3) != 1 or q_out_strides[3] != 1 or k_out_strides[3] != 1:
+        return None
+    q_out = torch.empty_strided(q.shape, q_out_strides, dtype=q.dtype, device=q.device)
+    k_out = torch.empty_strided(k.shape, k_out_strides, dtype=k.dtype, device=k.device)
+    strides = (ctypes.c_int64 * 12)(*q.stride()[:3], *k.stride()[:3], *q_out_strides[:3], *k_out_strides[:3])
+    with torch.cuda.device(q.device):
+        ok = _fwd_call(lib.inc_fwd_rope, "inc_fwd_rope",
+                       (_ptr(q), _ptr(k), _ptr(cos), _ptr(sin), _ptr(q_out), _ptr(k_out), B, Hq, k.shape[1], T, D, strides, cos.shape[0],
+                        dtype_code(q.dtype), _stream()))
+    return (q_out, k_out) if ok else None
+
+
 _HIP_RT = None
 
 

@@ -33,6 +33,7 @@ from .... import ops
 from ....common.utils import logger
 from ...utils.utility import batch_broadcastable, get_accelerator, get_model_device, set_module
 from ..base_algorithm import Quantizer as INCQuantizer
+from .fused_forward import FusedForward
 from .modules import MI355XWeightOnlyLinear
 
 try:
@@ -691,6 +692,7 @@ class RAWGPTQuantizer(object):
         self._fstreams = []
         self._late_stream = None  # stream of the block's last solve (LATE_SOLVE)
         self._block_writes_input = None  # decided by the first block forward (see _run_block)
+        self._fused = FusedForward()  # per-run state of the fused elementwise chains inside _run_block's forwards
         self._stacks = {}  # first batch index of a forward group -> (stacked hidden states, the list entries that are its slices)
         self.block_callback = kwargs.get("block_callback", None)  # used by the multi-GPU driver
         # sample-sharded multi-GPU calibration: every rank feeds ITS calibration samples through prepare()/run_fn and the
@@ -883,7 +885,8 @@ class RAWGPTQuantizer(object):
             else:
                 probe_in = None
             try:
-                out = self.track_hidden_states(block(*pos, **kw))
+                with self._fused.around(block):  # fused_forward.py: bit-identical elementwise chains, checked on these very tensors
+                    out = self.track_hidden_states(block(*pos, **kw))
             except _CaptureDone:
                 if not capture:
                     raise

@@ -29,6 +29,8 @@ def classify(name):
         return "factorisation (own)"
     if "gptq_quant_block" in n or "gptq_lazy_update" in n or "gptq_find_params" in n or "gptq_prepare" in n or "gptq_hessian_finalize" in n:
         return "column loop (own)"
+    if "fwd_silu_mul" in n or "fwd_rope" in n or "fwd_rmsnorm" in n:
+        return "forward elementwise (own)"
     if "woq_pack" in n or "pack_" in n or "woq_" in n:
         return "pack / woq (own)"
     if "Cijk_" in n:
