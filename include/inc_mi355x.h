@@ -593,7 +593,16 @@ int inc_awq_repack(const int32_t* awq_qweight, const int32_t* awq_qzeros, int64_
  *   y bf16 / fp16 [M,N]; K % 128 == 0 (pad with zero weight codes), xq / wq 16-byte aligned.
  *   workspace (inc_w8a8_gemm_workspace_bytes, may be NULL): when the last round of 256x256 tiles would leave most
  *   CUs idle its tiles are split along K into int32 slabs there and a second small kernel finishes them (no
- *   initialisation needed).  Integer sums: the result is bit-identical with or without the workspace.               */
+ *   initialisation needed).  Integer sums: the result is bit-identical with or without the workspace.
+ *
+ * The dynamic per-token symmetric int8 activation cell.  The reference has no text for it (its IPEX path picks the activation
+ * observer out of tree); it stands in for inc_sq_quant_act + inc_w8a8_gemm where a frozen per-tensor range is too coarse, and its
+ * specification is DESIGN.md section 8, in fp32 with true division and round-half-even:
+ * inc_sq_quant_act_token: t = x[m,k] * in_scale[k] (in_scale may be NULL), row_scale[m] = max(max_k |t| / 127, FLT_EPSILON),
+ *   xq[m,k] = clamp(rint(t / row_scale[m]), -127, 127) as int8 [M, Kp], 0 for k >= K; no zero point.  Kp % 16 == 0, xq 16-byte
+ *   aligned, row_scale fp32 [M].  x bf16 / fp16 / fp32 [M,K] contiguous, read from HBM once for Kp <= 16384.
+ * inc_w8a8_gemm_rowscale: y[m,n] = (row_scale[m] * alpha[n]) * (sum_k xq[m,k] * wq[n,k]) + bias[n] with alpha = w_scale: the
+ *   kernels, plan and workspace (inc_w8a8_gemm_workspace_bytes) of inc_w8a8_gemm with a row factor in the epilogues, no corr. */
 int64_t inc_w8a8_gemm_workspace_bytes(int64_t M, int64_t N, int64_t K);
 int inc_sq_channel_minmax(const void* x, int xdtype, int64_t T, int64_t K, int64_t ld, float* mn, float* mx,
                           inc_stream_t stream);
@@ -607,6 +616,11 @@ int inc_sq_quant_act(const void* x, int xdtype, int64_t M, int64_t K, int64_t Kp
 int inc_w8a8_gemm(const int8_t* xq, const int8_t* wq, const float* alpha, const int32_t* corr, const void* bias, void* y,
                   int ydtype, int64_t M, int64_t N, int64_t K, void* workspace, int64_t workspace_bytes,
                   inc_stream_t stream);
+int inc_sq_quant_act_token(const void* x, int xdtype, int64_t M, int64_t K, int64_t Kp, const float* in_scale, int8_t* xq,
+                           float* row_scale, inc_stream_t stream);
+int inc_w8a8_gemm_rowscale(const int8_t* xq, const int8_t* wq, const float* row_scale, const float* alpha, const void* bias,
+                           void* y, int ydtype, int64_t M, int64_t N, int64_t K, void* workspace, int64_t workspace_bytes,
+                           inc_stream_t stream);
 
 /* ---- measured ceilings (bench.py `ceilings`) -- measurement helpers, not on the hot path ------------- *
  * inc_probe_hbm_triad: a <- b + s*c over n fp32 (n % 4 == 0): 12 n bytes of HBM traffic per call.

@@ -21,6 +21,10 @@
 // was measured 1.5x SLOWER than not splitting at all: every release writes back the XCD's whole dirty L2, which at that
 // moment holds the other workgroups' output tiles.)  Integer addition is associative: bit-identical to the unsplit kernel.
 // Algorithmic work per launch: 2*M*N*K int8 op; bytes M*K + N*K + 2*M*N (+ 8*N).
+//
+// inc_w8a8_gemm_rowscale (the dynamic per-token activation cell; xq and row_scale from inc_sq_quant_act_token):
+//   y[m, n] = (row_scale[m] * alpha[n]) * sum_k xq[m,k] * wq[n,k] + bias[n],   alpha = w_scale, no corr
+// the same kernels, plan and workspace with the row factor in the three epilogues (template parameter ROWS).
 #include "common.hpp"
 
 namespace {
@@ -75,13 +79,20 @@ __device__ __forceinline__ i32x16 mfma_i8(const uint4& a, const uint4& b, i32x16
   return __builtin_amdgcn_mfma_i32_32x32x32_i8(av, bv, c, 0, 0, 0);
 }
 
-template <bool IS_BF16>
+// ROWS (the per-token cell, inc_w8a8_gemm_rowscale): y = (row_scale[m] * alpha[n]) * acc + bias[n].  `aux` is corr (int32 [N], may
+// be NULL) in the static instantiations and row_scale (fp32 [M]) in the ROWS ones: the kernels keep one argument list, and the
+// static instantiations the code they had before ROWS existed.
+template <bool ROWS>
+__device__ __forceinline__ const int32_t* aux_corr(const void* aux) { return ROWS ? nullptr : static_cast<const int32_t*>(aux); }
+
+template <bool IS_BF16, bool ROWS>
 __global__ __launch_bounds__(512) void w8a8_gemm_kernel(const int8_t* __restrict__ xq, const int8_t* __restrict__ wq,
-                                                        const float* __restrict__ alpha, const int32_t* __restrict__ corr,
+                                                        const float* __restrict__ alpha, const void* __restrict__ aux,
                                                         const uint16_t* __restrict__ bias, uint16_t* __restrict__ y,
                                                         int64_t M, int64_t N, int64_t K, int y_vec_ok, int full_tiles,
                                                         int split, int* __restrict__ slabs) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int32_t* const corr = aux_corr<ROWS>(aux);
   const int tiles_n = (int)((N + IN - 1) / IN);
   const int tiles_m = (int)((M + IM - 1) / IM);
   int wg = blockIdx.x, ks = 0, tail_id = -1;
@@ -217,8 +228,14 @@ __global__ __launch_bounds__(512) void w8a8_gemm_kernel(const int8_t* __restrict
         const int64_t m = m0 + wm * 128 + mf * 32 + (lane & 31);
         if (m >= M) continue;
         float v[4];
+        if constexpr (ROWS) {
+          const float rs = static_cast<const float*>(aux)[m];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = al[e] * (float)(acc[nf][mf][4 * rq + e] + cr[e]) + bv[e];
+          for (int e = 0; e < 4; ++e) v[e] = (rs * al[e]) * (float)acc[nf][mf][4 * rq + e] + bv[e];
+        } else {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[e] = al[e] * (float)(acc[nf][mf][4 * rq + e] + cr[e]) + bv[e];
+        }
         uint16_t* dst = y + m * N + nb;
         if (y_vec_ok && nb + 4 <= N) {
           *reinterpret_cast<uint2*>(dst) = make_uint2(cvt_pair16<IS_BF16>(v[0], v[1]), cvt_pair16<IS_BF16>(v[2], v[3]));
@@ -241,11 +258,12 @@ constexpr int GV_ROWS = 4;     // weight rows per wave
 constexpr int GV_KC = 4096;    // bytes of K staged in LDS per chunk
 constexpr int GV_MAXM = 16;
 
-template <bool IS_BF16, int MT>
+template <bool IS_BF16, int MT, bool ROWS>
 __global__ __launch_bounds__(256) void w8a8_gemv_kernel(const int8_t* __restrict__ xq, const int8_t* __restrict__ wq,
-                                                        const float* __restrict__ alpha, const int32_t* __restrict__ corr,
+                                                        const float* __restrict__ alpha, const void* __restrict__ aux,
                                                         const uint16_t* __restrict__ bias, uint16_t* __restrict__ y, int M,
                                                         int64_t N, int64_t K) {
+  const int32_t* const corr = aux_corr<ROWS>(aux);
   __shared__ __attribute__((aligned(16))) int8_t xs[MT * GV_KC];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int64_t n0 = ((int64_t)blockIdx.x * 4 + wave) * GV_ROWS;
@@ -309,7 +327,9 @@ __global__ __launch_bounds__(256) void w8a8_gemv_kernel(const int8_t* __restrict
     const int r = lane / MT, m = lane - r * MT;
     const int64_t n = n0 + r;
     if (n < N && m < M) {
-      float v = alpha[n] * (float)(mine + (corr ? corr[n] : 0));
+      float v;
+      if constexpr (ROWS) v = (static_cast<const float*>(aux)[m] * alpha[n]) * (float)mine;
+      else v = alpha[n] * (float)(mine + (corr ? corr[n] : 0));
       if (bias) v += IS_BF16 ? bf16_bits_to_f32(bias[n]) : f16_bits_to_f32(bias[n]);
       y[(int64_t)m * N + n] = IS_BF16 ? f32_to_bf16_bits(v) : f32_to_f16_bits(v);
     }
@@ -318,11 +338,12 @@ __global__ __launch_bounds__(256) void w8a8_gemv_kernel(const int8_t* __restrict
 
 // tail tiles: sum the `split` slabs of a tile (same register-order layout: thread tid of the tile's workgroup owns element
 // ((nf*4+mf)*16 + r)*512 + tid) and run the GEMM's epilogue.  One workgroup of 512 threads per tail tile.
-template <bool IS_BF16>
+template <bool IS_BF16, bool ROWS>
 __global__ __launch_bounds__(512) void w8a8_tail_finish_kernel(const int* __restrict__ slabs, const float* __restrict__ alpha,
-                                                               const int32_t* __restrict__ corr, const uint16_t* __restrict__ bias,
+                                                               const void* __restrict__ aux, const uint16_t* __restrict__ bias,
                                                                uint16_t* __restrict__ y, int64_t M, int64_t N, int y_vec_ok,
                                                                int full_tiles, int split) {
+  const int32_t* const corr = aux_corr<ROWS>(aux);
   const int tiles_n = (int)((N + IN - 1) / IN);
   const int tiles_m = (int)((M + IM - 1) / IM);
   const int tail_id = blockIdx.x, wg = full_tiles + tail_id;
@@ -364,8 +385,14 @@ __global__ __launch_bounds__(512) void w8a8_tail_finish_kernel(const int* __rest
           for (int e = 0; e < 4; ++e) a4[e] += part[o][e];
         if (m >= M) continue;
         float v[4];
+        if constexpr (ROWS) {
+          const float rs = static_cast<const float*>(aux)[m];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = al[e] * (float)(a4[e] + cr[e]) + bv[e];
+          for (int e = 0; e < 4; ++e) v[e] = (rs * al[e]) * (float)a4[e] + bv[e];
+        } else {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[e] = al[e] * (float)(a4[e] + cr[e]) + bv[e];
+        }
         uint16_t* dst = y + m * N + nb;
         if (y_vec_ok && nb + 4 <= N) {
           *reinterpret_cast<uint2*>(dst) = make_uint2(cvt_pair16<IS_BF16>(v[0], v[1]), cvt_pair16<IS_BF16>(v[2], v[3]));
@@ -381,9 +408,7 @@ __global__ __launch_bounds__(512) void w8a8_tail_finish_kernel(const int* __rest
 
 }  // namespace
 
-extern "C" {
-
-int64_t inc_w8a8_gemm_workspace_bytes(int64_t M, int64_t N, int64_t K) {
+extern "C" int64_t inc_w8a8_gemm_workspace_bytes(int64_t M, int64_t N, int64_t K) {
   if (M <= GV_MAXM || N <= 0 || K <= 0 || (K % IK) != 0) return 0;
   const int64_t tiles = ceil_div64(M, IM) * ceil_div64(N, IN);
   int64_t full;
@@ -392,9 +417,12 @@ int64_t inc_w8a8_gemm_workspace_bytes(int64_t M, int64_t N, int64_t K) {
   return I_COUNTER_BYTES + (tiles - full) * split * I_SLAB_BYTES;
 }
 
-int inc_w8a8_gemm(const int8_t* xq, const int8_t* wq, const float* alpha, const int32_t* corr, const void* bias, void* y,
-                  int ydtype, int64_t M, int64_t N, int64_t K, void* workspace, int64_t workspace_bytes,
-                  inc_stream_t stream) {
+namespace {
+
+// one plan, one workspace and one launch sequence for both cells; `aux` as in the kernels
+template <bool ROWS>
+int w8a8_launch(const int8_t* xq, const int8_t* wq, const float* alpha, const void* aux, const void* bias, void* y, int ydtype,
+                int64_t M, int64_t N, int64_t K, void* workspace, int64_t workspace_bytes, inc_stream_t stream) {
   INC_CHECK_ARG(xq && wq && alpha && y && M > 0 && N > 0 && K > 0);
   if (ydtype != INC_BF16 && ydtype != INC_F16) return INC_ERR_UNSUPPORTED;
   if ((K % IK) != 0) return INC_ERR_UNSUPPORTED;  // the module pads K to a multiple of 128 with zero weight codes
@@ -403,15 +431,15 @@ int inc_w8a8_gemm(const int8_t* xq, const int8_t* wq, const float* alpha, const 
   const size_t smem = (size_t)2 * I_STAGE;  // 128 KiB
   static std::atomic<uint64_t> attr_set{0};
   if (inc_attr_needed(attr_set)) {
-    (void)hipFuncSetAttribute((const void*)w8a8_gemm_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    (void)hipFuncSetAttribute((const void*)w8a8_gemm_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    (void)hipFuncSetAttribute((const void*)w8a8_gemm_kernel<true, ROWS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    (void)hipFuncSetAttribute((const void*)w8a8_gemm_kernel<false, ROWS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     inc_attr_done(attr_set);
   }
   if (M <= GV_MAXM) {  // decode: stream the weights once, dot products on the vector ALUs
     const unsigned g = (unsigned)ceil_div64(N, 4 * GV_ROWS);
     hipStream_t sv = inc_s(stream);
     const bool bf = ydtype == INC_BF16;
-#define INC_GV(B, MT) w8a8_gemv_kernel<B, MT><<<g, 256, 0, sv>>>(xq, wq, alpha, corr, (const uint16_t*)bias, (uint16_t*)y, (int)M, N, K)
+#define INC_GV(B, MT) w8a8_gemv_kernel<B, MT, ROWS><<<g, 256, 0, sv>>>(xq, wq, alpha, aux, (const uint16_t*)bias, (uint16_t*)y, (int)M, N, K)
     if (M == 1) { if (bf) INC_GV(true, 1); else INC_GV(false, 1); }
     else if (M <= 4) { if (bf) INC_GV(true, 4); else INC_GV(false, 4); }
     else if (M <= 8) { if (bf) INC_GV(true, 8); else INC_GV(false, 8); }
@@ -433,17 +461,34 @@ int inc_w8a8_gemm(const int8_t* xq, const int8_t* wq, const float* alpha, const 
   hipStream_t s = inc_s(stream);
   const unsigned tail = (unsigned)(tiles - full);
   if (ydtype == INC_BF16) {
-    w8a8_gemm_kernel<true><<<grid, 512, smem, s>>>(xq, wq, alpha, corr, (const uint16_t*)bias, (uint16_t*)y, M, N, K, y_vec_ok,
+    w8a8_gemm_kernel<true, ROWS><<<grid, 512, smem, s>>>(xq, wq, alpha, aux, (const uint16_t*)bias, (uint16_t*)y, M, N, K, y_vec_ok,
                                                    (int)full, split, slabs);
     if (split > 1)
-      w8a8_tail_finish_kernel<true><<<tail, 512, 0, s>>>(slabs, alpha, corr, (const uint16_t*)bias, (uint16_t*)y, M, N, y_vec_ok, (int)full, split);
+      w8a8_tail_finish_kernel<true, ROWS><<<tail, 512, 0, s>>>(slabs, alpha, aux, (const uint16_t*)bias, (uint16_t*)y, M, N, y_vec_ok, (int)full, split);
   } else {
-    w8a8_gemm_kernel<false><<<grid, 512, smem, s>>>(xq, wq, alpha, corr, (const uint16_t*)bias, (uint16_t*)y, M, N, K, y_vec_ok,
+    w8a8_gemm_kernel<false, ROWS><<<grid, 512, smem, s>>>(xq, wq, alpha, aux, (const uint16_t*)bias, (uint16_t*)y, M, N, K, y_vec_ok,
                                                     (int)full, split, slabs);
     if (split > 1)
-      w8a8_tail_finish_kernel<false><<<tail, 512, 0, s>>>(slabs, alpha, corr, (const uint16_t*)bias, (uint16_t*)y, M, N, y_vec_ok, (int)full, split);
+      w8a8_tail_finish_kernel<false, ROWS><<<tail, 512, 0, s>>>(slabs, alpha, aux, (const uint16_t*)bias, (uint16_t*)y, M, N, y_vec_ok, (int)full, split);
   }
   INC_LAUNCH_RETURN();
+}
+
+}  // namespace
+
+extern "C" {
+
+int inc_w8a8_gemm(const int8_t* xq, const int8_t* wq, const float* alpha, const int32_t* corr, const void* bias, void* y,
+                  int ydtype, int64_t M, int64_t N, int64_t K, void* workspace, int64_t workspace_bytes,
+                  inc_stream_t stream) {
+  return w8a8_launch<false>(xq, wq, alpha, corr, bias, y, ydtype, M, N, K, workspace, workspace_bytes, stream);
+}
+
+int inc_w8a8_gemm_rowscale(const int8_t* xq, const int8_t* wq, const float* row_scale, const float* alpha, const void* bias,
+                           void* y, int ydtype, int64_t M, int64_t N, int64_t K, void* workspace, int64_t workspace_bytes,
+                           inc_stream_t stream) {
+  INC_CHECK_ARG(row_scale);
+  return w8a8_launch<true>(xq, wq, alpha, row_scale, bias, y, ydtype, M, N, K, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

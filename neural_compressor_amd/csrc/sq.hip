@@ -6,6 +6,7 @@
 //                                             -> inc_sq_weight_col_absmax + inc_sq_cal_scale
 //   quant_dequant_w_v1 (Linear)     :652-695  per-output-channel int8 of the weight               -> inc_sq_quant_weight
 //   SQLinearWrapper.forward         :2591-2605 X * input_scale, then quant_dequant_x_v1 :726-755   -> inc_sq_quant_act
+//   (no reference text)             dynamic per-token symmetric int8 of X * input_scale            -> inc_sq_quant_act_token
 // The INT8 GEMM that consumes these lives in gemm_i8.hip.  (The reference hands W8A8 execution to
 // intel_extension_for_pytorch, which is not in /root/reference: the in-tree fake-quant functions above are the spec.)
 #include <float.h>
@@ -227,6 +228,113 @@ __global__ __launch_bounds__(256) void quant_act_kernel(const void* __restrict__
   *reinterpret_cast<uint4*>(out + m * Kp + k0) = make_uint4(packed[0], packed[1], packed[2], packed[3]);
 }
 
+// ---- K13b: dynamic per-token symmetric int8: s[m] = max(max_k |x * in_scale| / 127, eps), q = clamp(rint(x * in_scale / s), +-127) ----
+// No reference text: the specification is DESIGN section 8.  One workgroup per row.  A lane owns 16-value chunks tid, tid + 256,
+// ... (two 16-byte loads of a 16-bit input or four of fp32, one 16-byte store each).  Rows of up to QT_HELD * 4096 = 16384 padded
+// values (HELD) are read from HBM once: the smoothed fp32 values stay in registers between the abs-max and the quantise pass.
+// Longer rows are read twice (the second time from L2).  max is order-free, so q and s have one right answer, bit for bit.
+constexpr int QT_HELD = 4;
+
+// the 16 values at k0 .. k0 + 15 of a row that starts at element `row`, times in_scale; 0 from K on
+template <int DT>
+__device__ __forceinline__ void token_load16(const void* __restrict__ x, int64_t row, int64_t k0, int64_t K, bool vec,
+                                             const float* __restrict__ in_scale, float (&t)[16]) {
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int64_t kb = k0 + 8 * h;
+    float* v = t + 8 * h;
+    if (vec && kb < K) {  // K % 8 == 0: the half is whole
+      if constexpr (DT == INC_F32) {
+        const float4 a = *reinterpret_cast<const float4*>(static_cast<const float*>(x) + row + kb);
+        const float4 b = *reinterpret_cast<const float4*>(static_cast<const float*>(x) + row + kb + 4);
+        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+      } else {
+        const uint4 u = *reinterpret_cast<const uint4*>(static_cast<const uint16_t*>(x) + row + kb);
+        const uint32_t r[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          if constexpr (DT == INC_BF16) {
+            v[2 * j] = __uint_as_float(r[j] << 16);
+            v[2 * j + 1] = __uint_as_float(r[j] & 0xffff0000u);
+          } else {
+            v[2 * j] = f16_bits_to_f32((uint16_t)(r[j] & 0xffffu));
+            v[2 * j + 1] = f16_bits_to_f32((uint16_t)(r[j] >> 16));
+          }
+        }
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[j] = (kb + j < K) ? load_as_f32<DT>(x, row + kb + j) : 0.f;
+    }
+    if (in_scale) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        if (kb + j < K) v[j] = v[j] * in_scale[kb + j];
+    }
+  }
+}
+
+__device__ __forceinline__ float token_absmax16(const float (&t)[16], float amax) {
+#pragma unroll
+  for (int j = 0; j < 16; ++j) amax = fmaxf(amax, fabsf(t[j]));
+  return amax;
+}
+
+__device__ __forceinline__ uint4 token_pack16(const float (&t)[16], float s) {
+  uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+  for (int j = 0; j < 16; ++j) {
+    float r = rintf(t[j] / s);
+    r = fminf(fmaxf(r, -127.f), 127.f);
+    w[j >> 2] |= ((uint32_t)(int)r & 0xffu) << (8 * (j & 3));
+  }
+  return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+template <int DT, bool HELD>
+__global__ __launch_bounds__(256) void quant_act_token_kernel(const void* __restrict__ x, int64_t K, int64_t Kp,
+                                                              const float* __restrict__ in_scale, int8_t* __restrict__ xq,
+                                                              float* __restrict__ row_scale) {
+  __shared__ float red[4];
+  const int64_t m = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int chunks = (int)(Kp / 16);
+  const int64_t row = m * K;
+  const bool vec = (K % 8) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
+  float t[HELD ? QT_HELD : 1][16];
+  float amax = 0.f;
+  if constexpr (HELD) {
+#pragma unroll
+    for (int j = 0; j < QT_HELD; ++j)
+      if (tid + 256 * j < chunks) {
+        token_load16<DT>(x, row, (int64_t)(tid + 256 * j) * 16, K, vec, in_scale, t[j]);
+        amax = token_absmax16(t[j], amax);
+      }
+  } else {
+    for (int c = tid; c < chunks; c += 256) {
+      token_load16<DT>(x, row, (int64_t)c * 16, K, vec, in_scale, t[0]);
+      amax = token_absmax16(t[0], amax);
+    }
+  }
+  amax = wave_max(amax);
+  if (lane == 0) red[wave] = amax;
+  __syncthreads();
+  amax = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  const float s = fmaxf(amax / 127.0f, FLT_EPSILON);
+  int8_t* const out = xq + m * Kp;
+  if constexpr (HELD) {
+#pragma unroll
+    for (int j = 0; j < QT_HELD; ++j)
+      if (tid + 256 * j < chunks) *reinterpret_cast<uint4*>(out + (int64_t)(tid + 256 * j) * 16) = token_pack16(t[j], s);
+  } else {
+    for (int c = tid; c < chunks; c += 256) {
+      token_load16<DT>(x, row, (int64_t)c * 16, K, vec, in_scale, t[0]);
+      *reinterpret_cast<uint4*>(out + (int64_t)c * 16) = token_pack16(t[0], s);
+    }
+  }
+  if (tid == 0) row_scale[m] = s;
+}
+
 }  // namespace
 
 extern "C" {
@@ -269,6 +377,19 @@ int inc_sq_quant_act(const void* x, int xdtype, int64_t M, int64_t K, int64_t Kp
   const int64_t total = M * (Kp / 16);
   INC_DISPATCH_DTYPE(xdtype, DT, {
     quant_act_kernel<DT><<<(unsigned)ceil_div64(total, 256), 256, 0, inc_s(stream)>>>(x, M, K, Kp, in_scale, sx, zp, out);
+  })
+  INC_LAUNCH_RETURN();
+}
+
+int inc_sq_quant_act_token(const void* x, int xdtype, int64_t M, int64_t K, int64_t Kp, const float* in_scale, int8_t* xq,
+                           float* row_scale, inc_stream_t stream) {
+  INC_CHECK_ARG(x && xq && row_scale && M > 0 && K > 0 && Kp >= K && (Kp % 16) == 0);
+  INC_CHECK_ARG(M <= 0x7fffffff && Kp <= 0x7fffffff);
+  INC_CHECK_ARG((reinterpret_cast<uintptr_t>(xq) & 15) == 0);
+  const bool held = Kp <= (int64_t)QT_HELD * 256 * 16;
+  INC_DISPATCH_DTYPE(xdtype, DT, {
+    if (held) quant_act_token_kernel<DT, true><<<(unsigned)M, 256, 0, inc_s(stream)>>>(x, K, Kp, in_scale, xq, row_scale);
+    else quant_act_token_kernel<DT, false><<<(unsigned)M, 256, 0, inc_s(stream)>>>(x, K, Kp, in_scale, xq, row_scale);
   })
   INC_LAUNCH_RETURN();
 }

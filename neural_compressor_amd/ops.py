@@ -1592,9 +1592,26 @@ def sq_quant_act(x2d, in_scale, sx, zp, Kp=None):
     return out
 
 
-def w8a8_gemm(xq, wq, alpha, corr, bias, out_dtype):
-    """y = alpha[n] * (xq @ wq^T + corr[n]) + bias[n], int32 accumulate on the matrix cores (K14)."""
-    dev = _dev(xq, wq, alpha, corr, bias)
+def sq_quant_act_token(x2d, in_scale, Kp=None):
+    """Dynamic per-token symmetric int8: s[m] = max(max_k |x * in_scale| / 127, eps), q = clamp(rint(x * in_scale / s),
+    -127, 127) -> (xq int8 [M, Kp], row_scale fp32 [M])."""
+    x2d = x2d.contiguous()
+    in_scale = None if in_scale is None else in_scale.to(torch.float32).contiguous()
+    dev = _dev(x2d, in_scale)
+    M, K = x2d.shape
+    Kp = K if Kp is None else int(Kp)
+    xq = torch.empty((M, Kp), dtype=torch.int8, device=dev)
+    row_scale = torch.empty(M, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.inc_sq_quant_act_token(_ptr(x2d), dtype_code(x2d.dtype), M, K, Kp, _ptr(in_scale), _ptr(xq), _ptr(row_scale), _stream()),
+              "inc_sq_quant_act_token")
+    return xq, row_scale
+
+
+def w8a8_gemm(xq, wq, alpha, corr, bias, out_dtype, row_scale=None):
+    """y = alpha[n] * (xq @ wq^T + corr[n]) + bias[n], int32 accumulate on the matrix cores (K14).  With `row_scale` (fp32 [M], the
+    per-token cell): y = (row_scale[m] * alpha[n]) * (xq @ wq^T) + bias[n], alpha = w_scale and no corr."""
+    dev = _dev(xq, wq, alpha, corr, bias, row_scale)
     M, K = xq.shape
     N = wq.shape[0]
     assert wq.shape[1] == K and xq.dtype == torch.int8 and wq.dtype == torch.int8
@@ -1603,6 +1620,12 @@ def w8a8_gemm(xq, wq, alpha, corr, bias, out_dtype):
     y = torch.empty((M, N), dtype=out_dtype, device=dev)
     nbytes = lib.inc_w8a8_gemm_workspace_bytes(M, N, K)
     ws = _workspace_i8(dev, nbytes) if nbytes > 0 else None
+    if row_scale is not None:
+        assert corr is None and row_scale.dtype == torch.float32 and row_scale.numel() == M and row_scale.is_contiguous()
+        with torch.cuda.device(dev):
+            check(lib.inc_w8a8_gemm_rowscale(_ptr(xq), _ptr(wq), _ptr(row_scale), _ptr(alpha), _ptr(bias), _ptr(y), dtype_code(out_dtype),
+                                             M, N, K, _ptr(ws), 0 if ws is None else ws.numel(), _stream()), "inc_w8a8_gemm_rowscale")
+        return y
     with torch.cuda.device(dev):
         check(lib.inc_w8a8_gemm(_ptr(xq), _ptr(wq), _ptr(alpha), _ptr(corr), _ptr(bias), _ptr(y), dtype_code(out_dtype), M, N, K,
                                 _ptr(ws), 0 if ws is None else ws.numel(), _stream()), "inc_w8a8_gemm")

@@ -4,7 +4,8 @@ save / load: `model.save(output_dir)`, `load(output_dir, original_model)`).
 The reference stores a TorchScript of the IPEX model (`quantized_model.pt`) plus the IPEX qconfig JSON; neither exists here.
 The files keep the reference's names where they mean the same thing:
   quantized_weight.pt   state_dict: int8 `qweight`, `w_scale`, `alpha`, `corr`, `act_scale`, `act_zp`, `input_scale`, bias of every
-                        W8A8Linear, the (possibly folded) float parameters of everything else
+                        W8A8Linear (a per-token module has no `alpha`, `corr`, `act_scale`, `act_zp`: that is how load tells the two
+                        activation cells apart), the (possibly folded) float parameters of everything else
   qconfig.json          {"smooth_quant": {alpha, folding, absorb_to_layer}, "w8a8_modules": [names]}
 """
 
@@ -44,7 +45,8 @@ def load(output_dir, original_model, device="cuda"):
         ft = state[name + ".bias"].dtype if (name + ".bias") in state else (
             lin.weight.dtype if lin.weight.dtype in (torch.float16, torch.bfloat16) else torch.float16)
         new = W8A8Linear(lin.in_features, lin.out_features, bias=(name + ".bias") in state,
-                         has_input_scale=(name + ".input_scale") in state, device=dev, float_type=ft)
+                         has_input_scale=(name + ".input_scale") in state, device=dev, float_type=ft,
+                         act_quant="static" if (name + ".act_scale") in state else "per_token")
         own = {k[len(name) + 1:]: v for k, v in state.items() if k.startswith(name + ".")}
         new.load_state_dict({k: v.to(dev) for k, v in own.items()}, strict=True)
         for k in own:

@@ -3,8 +3,8 @@
 prepare()  installs the per-channel min / max observers on every nn.Linear (HIP kernel, statistics stay in HBM);
            the user then runs calibration data through the model;
 convert()  removes the observers, computes and applies the smoothing scales (`TorchSmoothQuant.transform`) and replaces
-           every selected Linear by `W8A8Linear` (per-channel int8 weights, static per-tensor uint8 activations from the
-           same calibration statistics).
+           every selected Linear by `W8A8Linear` (per-channel int8 weights; static per-tensor uint8 activations from the
+           same calibration statistics, or, for a layer whose config asks for it, dynamic per-token int8 activations).
 The reference's prepare / convert hand the model to `ipex.quantization.prepare / convert`; nothing of that is needed
 here, so `example_inputs` is accepted for signature compatibility and otherwise unused.
 """
@@ -20,6 +20,10 @@ from .utility import Calibration, SQLinearWrapper, TorchSmoothQuant, W8A8Linear
 class SmoothQuantQuantizer(Quantizer):
     def __init__(self, quant_config=None):
         super().__init__(quant_config)
+
+    def _act_quant(self, name):
+        """The activation cell of W8A8Linear the layer's config selects."""
+        return "per_token" if self.quant_config[name].get("act_granularity") == "per_token" else "static"
 
     def _selected(self, model):
         """Names of the nn.Linear layers the per-op config selects (dtype fp32 = leave in floating point)."""
@@ -67,14 +71,15 @@ class SmoothQuantQuantizer(Quantizer):
         sq.calibration = calib                # alpha="auto" replays the first calibration forwards (calib.captured_calls)
         sq.transform(alpha=first.get("alpha", 0.5), folding=first.get("folding", False), op_types=(torch.nn.Linear,),
                      scale_sharing=first.get("scale_sharing", False), absorb_to_layer=first.get("absorb_to_layer"),
-                     auto_alpha_args=first.get("auto_alpha_args"))
+                     auto_alpha_args=first.get("auto_alpha_args"), act_quant={n: self._act_quant(n) for n in names})
         dev = next(model.parameters()).device
         for name in names:
             mod = get_module(model, name)
             assert isinstance(mod, (torch.nn.Linear, SQLinearWrapper)), type(mod)
             folded = not isinstance(mod, SQLinearWrapper) and name in sq.weight_scale_info
             stat_scale = (1.0 / sq.weight_scale_info[name]) if folded else None  # the producer now emits x / s
-            new = W8A8Linear.from_float(mod, calib.input_mins[name], calib.input_maxes[name], device=dev, stat_scale=stat_scale)
+            new = W8A8Linear.from_float(mod, calib.input_mins[name], calib.input_maxes[name], device=dev, stat_scale=stat_scale,
+                                        act_quant=self._act_quant(name))
             set_module(model, name, new)
         model.sq_info = {"alpha": sq.alpha if isinstance(sq.alpha, dict) else first.get("alpha", 0.5), "folding": first.get("folding", False),
                          "absorb_to_layer": sq.absorb_to_layer}

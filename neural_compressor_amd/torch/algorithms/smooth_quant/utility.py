@@ -160,57 +160,70 @@ class SQLinearWrapper(torch.nn.Module):
 
 
 class W8A8Linear(torch.nn.Module):
-    """INT8 x INT8 Linear: per-output-channel symmetric int8 weights, static per-tensor asymmetric uint8 activations.
+    """INT8 x INT8 Linear: per-output-channel symmetric int8 weights and one of two activation cells (`act_quant`).
 
+    "static" (the default): per-tensor asymmetric uint8 activations, range frozen at calibration.
     forward = inc_sq_quant_act (mul by input_scale, quantise, shift to signed) + inc_w8a8_gemm (int32 accumulate,
     fp32 epilogue).  Buffers: qweight int8 [N, Kp] (K padded to a multiple of 128 with zeros), w_scale fp32 [N],
     alpha fp32 [N] = act_scale * w_scale, corr int32 [N] = (128 - act_zp) * rowsum(qweight), input_scale fp32 [K]
     (absent when the smoothing was folded into the producer), act_scale / act_zp, bias.
+
+    "per_token": dynamic per-token symmetric int8 activations, nothing calibrated.
+    forward = inc_sq_quant_act_token (mul by input_scale, row abs-max, quantise) + inc_w8a8_gemm_rowscale (the same GEMM with
+    row_scale[m] * w_scale[n] in the epilogue); no host read.  Buffers: qweight, w_scale, input_scale, bias only.
     """
 
     K_ALIGN = 128
+    ACT_QUANT = ("static", "per_token")
 
-    def __init__(self, in_features, out_features, bias=False, has_input_scale=False, device="cuda", float_type=torch.float16):
+    def __init__(self, in_features, out_features, bias=False, has_input_scale=False, device="cuda", float_type=torch.float16,
+                 act_quant="static"):
         super().__init__()
         dev = torch.device(device)
         if dev.type != "cuda":
             raise RuntimeError(f"W8A8Linear needs a HIP device ('cuda[:N]'), got '{device}'. There is no CPU implementation.")
+        if act_quant not in self.ACT_QUANT:
+            raise ValueError(f"act_quant must be one of {self.ACT_QUANT}, got {act_quant!r}")
+        self.act_quant = act_quant
         self.in_features, self.out_features = in_features, out_features
         self.kp = -(-in_features // self.K_ALIGN) * self.K_ALIGN
         self.float_type = float_type
         self.register_buffer("qweight", torch.zeros((out_features, self.kp), dtype=torch.int8, device=dev))
         self.register_buffer("w_scale", torch.zeros(out_features, dtype=torch.float32, device=dev))
-        self.register_buffer("alpha", torch.zeros(out_features, dtype=torch.float32, device=dev))
-        self.register_buffer("corr", torch.zeros(out_features, dtype=torch.int32, device=dev))
-        self.register_buffer("act_scale", torch.ones(1, dtype=torch.float32, device=dev))
-        self.register_buffer("act_zp", torch.zeros(1, dtype=torch.int32, device=dev))
+        if act_quant == "static":
+            self.register_buffer("alpha", torch.zeros(out_features, dtype=torch.float32, device=dev))
+            self.register_buffer("corr", torch.zeros(out_features, dtype=torch.int32, device=dev))
+            self.register_buffer("act_scale", torch.ones(1, dtype=torch.float32, device=dev))
+            self.register_buffer("act_zp", torch.zeros(1, dtype=torch.int32, device=dev))
         self.register_buffer("input_scale", torch.ones(in_features, dtype=torch.float32, device=dev) if has_input_scale else None)
         self.register_buffer("bias", torch.zeros(out_features, dtype=float_type, device=dev) if bias else None)
         self._sx = self._zp = self._ver = None
 
     @classmethod
     @torch.no_grad()
-    def from_float(cls, module, input_min, input_max, device="cuda", stat_scale=None):
+    def from_float(cls, module, input_min=None, input_max=None, device="cuda", stat_scale=None, act_quant="static"):
         """`module`: nn.Linear (smoothing folded or absent) or SQLinearWrapper; input_min / input_max: the calibrated
         per-channel statistics of the layer's ORIGINAL input; `stat_scale`: the per-channel factor the producer now
-        applies to that input when the smoothing was folded (1/s) -- a wrapper brings its own (`input_scale`)."""
+        applies to that input when the smoothing was folded (1/s) -- a wrapper brings its own (`input_scale`).
+        The "per_token" cell calibrates nothing and needs neither statistics nor `stat_scale`."""
         wrapper = module if isinstance(module, SQLinearWrapper) else None
         lin = wrapper.sq_linear if wrapper is not None else module
         in_scale = wrapper.input_scale.float() if wrapper is not None else None
         ft = lin.weight.dtype if lin.weight.dtype in (torch.float16, torch.bfloat16) else torch.float16
         new = cls(lin.in_features, lin.out_features, bias=lin.bias is not None, has_input_scale=in_scale is not None,
-                  device=device, float_type=ft)
+                  device=device, float_type=ft, act_quant=act_quant)
         dev = new.qweight.device
         w = lin.weight.detach().to(dev)
         qw, w_scale, rowsum = ops.sq_quant_weight(w, None, new.kp)
-        stat = in_scale if in_scale is not None else stat_scale
-        sx, zp = SQLinearWrapper._calculate_qparams(None if stat is None else stat.to(dev), [input_min.to(dev), input_max.to(dev)])
         new.qweight.copy_(qw)
         new.w_scale.copy_(w_scale)
-        new.act_scale.copy_(sx)
-        new.act_zp.copy_(zp)
-        new.alpha.copy_(w_scale * sx)
-        new.corr.copy_(((128 - zp.to(torch.int64)) * rowsum.to(torch.int64)).to(torch.int32))
+        if act_quant == "static":
+            stat = in_scale if in_scale is not None else stat_scale
+            sx, zp = SQLinearWrapper._calculate_qparams(None if stat is None else stat.to(dev), [input_min.to(dev), input_max.to(dev)])
+            new.act_scale.copy_(sx)
+            new.act_zp.copy_(zp)
+            new.alpha.copy_(w_scale * sx)
+            new.corr.copy_(((128 - zp.to(torch.int64)) * rowsum.to(torch.int64)).to(torch.int32))
         if in_scale is not None:
             new.input_scale.copy_(in_scale)
         if lin.bias is not None:
@@ -221,14 +234,18 @@ class W8A8Linear(torch.nn.Module):
         x = input
         lead = x.shape[:-1]
         x2d = x.reshape(-1, self.in_features)
-        ver = (self.act_scale.data_ptr(), self.act_scale._version, self.act_zp._version)
-        if self._sx is None or self._ver != ver:  # one host read per (re)load: the static activation parameters are launch arguments
-            self._sx, self._zp, self._ver = float(self.act_scale.item()), float(self.act_zp.item()), ver
         out_dtype = x.dtype if x.dtype in (torch.float16, torch.bfloat16) else self.float_type
         if x2d.shape[0] == 0:
             return torch.empty((*lead, self.out_features), dtype=torch.float32 if x.dtype == torch.float32 else out_dtype, device=x.device)
-        xq = ops.sq_quant_act(x2d, self.input_scale, self._sx, self._zp, self.kp)
-        y = ops.w8a8_gemm(xq, self.qweight, self.alpha, self.corr, self.bias, out_dtype)
+        if self.act_quant == "per_token":
+            xq, row_scale = ops.sq_quant_act_token(x2d, self.input_scale, self.kp)
+            y = ops.w8a8_gemm(xq, self.qweight, self.w_scale, None, self.bias, out_dtype, row_scale=row_scale)
+        else:
+            ver = (self.act_scale.data_ptr(), self.act_scale._version, self.act_zp._version)
+            if self._sx is None or self._ver != ver:  # one host read per (re)load: the static activation parameters are launch arguments
+                self._sx, self._zp, self._ver = float(self.act_scale.item()), float(self.act_zp.item()), ver
+            xq = ops.sq_quant_act(x2d, self.input_scale, self._sx, self._zp, self.kp)
+            y = ops.w8a8_gemm(xq, self.qweight, self.alpha, self.corr, self.bias, out_dtype)
         if x.dtype == torch.float32:  # an fp32 model keeps seeing fp32 activations (the kernel's epilogue emits 16-bit)
             y = y.float()
         return y.reshape(*lead, self.out_features)
@@ -238,7 +255,8 @@ class W8A8Linear(torch.nn.Module):
         return self.qweight[:, : self.in_features].float() * self.w_scale.view(-1, 1)
 
     def extra_repr(self):
-        return f"in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}, w8a8"
+        cell = "w8a8" if self.act_quant == "static" else "w8a8, act=int8 per_token dynamic"
+        return f"in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}, {cell}"
 
 
 def quant_dequant_w_v1(m, num_bits=8, scheme="sym"):
@@ -276,12 +294,24 @@ def quant_dequant_x_v1(x, min_x=None, max_x=None, num_bits=8):
     return scale * (q_x - bias)
 
 
+def quant_dequant_x_token(x):
+    """Dynamic per-token symmetric int8 fake quantisation of an activation (no reference text): for every row of
+    the last dimension s = max(max|x| / 127, eps), q = clamp(round(x / s), -127, 127), result q * s.  fp32, true division (the
+    divisors are tensors: torch may turn a division by a host scalar into a multiplication by its reciprocal)."""
+    x = x.float()
+    amax = x.abs().amax(dim=-1, keepdim=True)
+    s = torch.clamp(amax / torch.full_like(amax, 127.0), min=torch.finfo(torch.float32).eps)
+    return torch.round(x / s).clamp_(-127.0, 127.0) * s
+
+
 class WrapperLayer(torch.nn.Module):
     """Fake-quant stand-in of a Linear during alpha tuning (reference :2665-2771): records its (quantised-model) input and its
-    output; `q_dq_forward` evaluates the layer for a candidate (input_scale, weight_scale) pair."""
+    output; `q_dq_forward` evaluates the layer for a candidate (input_scale, weight_scale) pair.  `act_quant` names the activation
+    cell the layer will get ("static": the reference's per-tensor range from the calibrated min / max; "per_token")."""
 
-    def __init__(self, layer, input_min, input_max, save_q_input=False):
+    def __init__(self, layer, input_min, input_max, save_q_input=False, act_quant="static"):
         super().__init__()
+        self.act_quant = act_quant
         self.add_module("orig_layer", layer)
         self.quant = False
         self.q_input = None
@@ -309,24 +339,22 @@ class WrapperLayer(torch.nn.Module):
         tmp = torch.nn.Linear(w.shape[1], w.shape[0], bias=False, device=w.device)
         tmp.weight.data = w
         w_qdq = quant_dequant_w_v1(tmp)
-        x = x.float()
-        if input_scale is None:
-            x = quant_dequant_x_v1(x, self.input_min, self.input_max)
-        else:
-            x = input_scale * x
-            x = quant_dequant_x_v1(x, self.input_min * input_scale, self.input_max * input_scale)
+        x = self._q_dq_input(x.float(), input_scale)
         bias = None if lin.bias is None else lin.bias.float()
         return torch.nn.functional.linear(x, w_qdq, bias)
+
+    def _q_dq_input(self, x, input_scale):
+        if self.act_quant == "per_token":
+            return quant_dequant_x_token(x if input_scale is None else input_scale * x)
+        if input_scale is None:
+            return quant_dequant_x_v1(x, self.input_min, self.input_max)
+        x = input_scale * x
+        return quant_dequant_x_v1(x, self.input_min * input_scale, self.input_max * input_scale)
 
     def q_dq_forward_blockwise(self, x, input_scale):
         """Reference :2731-2748: the input is fake-quantised as in q_dq_forward, the weight was prepared by the tuner."""
         lin = self.orig_layer
-        x = x.float()
-        if input_scale is None:
-            x = quant_dequant_x_v1(x, self.input_min, self.input_max)
-        else:
-            x = input_scale * x
-            x = quant_dequant_x_v1(x, self.input_min * input_scale, self.input_max * input_scale)
+        x = self._q_dq_input(x.float(), input_scale)
         bias = None if lin.bias is None else lin.bias.float()
         return torch.nn.functional.linear(x, self._bw_weight, bias)
 
@@ -368,7 +396,7 @@ class AutoAlpha:
 
     def __init__(self, model, dataloader, absorb_to_layer, op_types, device, q_func, example_inputs, weight_clip=True,
                  alpha_min=0.3, alpha_max=0.7, alpha_step=0.1, shared_criterion="mean", init_alpha=0.5, folding=False,
-                 do_blockwise=False, n_samples=32, calibration=None):
+                 do_blockwise=False, n_samples=32, calibration=None, act_quant=None):
         self.model = model
         self.model.eval()
         self.dataloader = dataloader
@@ -387,6 +415,7 @@ class AutoAlpha:
         self.device = device
         self.calibration = calibration  # statistics + captured forwards of an earlier calibration pass (prepare/convert flow)
         self.last_loss_alphas = None    # {layer: {str(alpha): loss}} of the final decision (diagnostics / parity tests)
+        self.act_quant = act_quant or {}  # {layer name: activation cell}; a layer that is not named gets the static cell
 
     # -- entry (:1278-1324) ---------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -450,7 +479,8 @@ class AutoAlpha:
             if name not in self.input_mins:
                 continue
             module = get_module(self.model, name)
-            set_module(self.model, name, WrapperLayer(module, self.input_mins[name], self.input_maxes[name], save_q_input=save_q_input))
+            set_module(self.model, name, WrapperLayer(module, self.input_mins[name], self.input_maxes[name], save_q_input=save_q_input,
+                                                      act_quant=self.act_quant.get(name, "static")))
 
     def _qdq_model_unwrapper_for_auto(self):
         for name in self.to_unwrap_module_names:
@@ -889,7 +919,7 @@ class TorchSmoothQuant:
             args = dict(kwargs.get("auto_alpha_args") or {})
             tuner = AutoAlpha(self.model, self.dataloader, self.absorb_to_layer, op_types=op_types, device=next(self.model.parameters()).device,
                               q_func=self.q_func, folding=folding, example_inputs=self.example_inputs,
-                              calibration=getattr(self, "calibration", None), **args)
+                              calibration=getattr(self, "calibration", None), act_quant=kwargs.get("act_quant"), **args)
             alpha = tuner.tune()
             self.auto_alpha_tuner = tuner
         self.alpha = alpha

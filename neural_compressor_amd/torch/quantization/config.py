@@ -231,9 +231,11 @@ def get_default_awq_config() -> AWQConfig:
 
 @register_config(framework_name=FRAMEWORK_NAME, algo_name=SMOOTH_QUANT, priority=PRIORITY_SMOOTH_QUANT)
 class SmoothQuantConfig(TorchBaseConfig):
-    """SmoothQuant W8A8 (reference config.py:1485-1612): same fields and defaults.  On MI355X the supported cell is
-    the default one -- int8 per-channel symmetric weights, uint8 per-tensor asymmetric min/max activations; `alpha` is a
-    number or "auto" (reference smooth_quant/utility.py:1232 AutoAlpha: the layer-wise tuner, or the block-wise one with `do_blockwise=True`)."""
+    """SmoothQuant W8A8 (reference config.py:1485-1612): same fields and defaults.  On MI355X the weights are int8 per-channel
+    symmetric and the activations one of two cells: the default, uint8 per-tensor asymmetric min/max (static: the range is frozen at
+    calibration), or `act_dtype="int8", act_sym=True, act_granularity="per_token"` (dynamic: every token gets its own symmetric scale
+    at run time).  A model may mix them per layer through `set_local`.  `alpha` is a number or "auto" (reference
+    smooth_quant/utility.py:1232 AutoAlpha: the layer-wise tuner, or the block-wise one with `do_blockwise=True`)."""
 
     name = SMOOTH_QUANT
     supported_configs: List = []
@@ -277,7 +279,9 @@ class SmoothQuantConfig(TorchBaseConfig):
             unsupported = []
             if w_dtype != "int8" or not w_sym or w_granularity != "per_channel" or w_algo != "minmax":
                 unsupported.append("weights must be int8 / symmetric / per_channel / minmax")
-            if act_dtype != "uint8" or act_sym or act_granularity != "per_tensor" or act_algo != "minmax":
+            static_cell = act_dtype == "uint8" and not act_sym and act_granularity == "per_tensor"
+            token_cell = act_dtype == "int8" and act_sym is True and act_granularity == "per_token"
+            if not (static_cell or token_cell) or act_algo != "minmax":
                 unsupported.append("activations must be uint8 / asymmetric / per_tensor / minmax")
             if unsupported:
                 raise NotImplementedError("SmoothQuant on MI355X: " + "; ".join(unsupported))
