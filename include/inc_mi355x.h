@@ -622,6 +622,40 @@ int inc_w8a8_gemm_rowscale(const int8_t* xq, const int8_t* wq, const float* row_
                            void* y, int ydtype, int64_t M, int64_t N, int64_t K, void* workspace, int64_t workspace_bytes,
                            inc_stream_t stream);
 
+/* ---- OCP microscaling (MX): MXFP8 / MXFP4 linears on v_mfma_scale_f32_32x32x64_f8f6f4 (csrc/mx.hip, csrc/gemm_mx.hip) ---------- *
+ * The reference's MXQuantConfig / MXLinear (torch/algorithms/mx_quant/) emulate the formats with fake quantisation in float; these
+ * two entry points execute them.  This text is the specification.  Inputs are finite.
+ *   A block is 32 consecutive elements along K (= in_features, for activation rows and weight rows alike).
+ *   Scale:    amax = max |x| of the block as fp32;  byte = clamp(expfield(amax) - emax, 0, 254), expfield the biased 8-bit exponent
+ *             field of amax (0 for zero and subnormals), emax = 8 for e4m3 and 2 for e2m1.  The block scale is 2^(byte - 127)
+ *             (E8M0; byte 255 is never written).
+ *   Elements: v = x * 2^(127 - byte), exact; v rounded to nearest, ties to even, onto the element format, saturating to +-448 for
+ *             e4m3 (OCP e4m3fn, subnormals down to 2^-9 kept, no NaN code emitted) and to +-6 for e2m1 (grid 0, 0.5, 1, 1.5, 2, 3,
+ *             4, 6).  The sign bit of a code is the sign bit of x, for zeros too.
+ *   Padding:  columns K .. Kp-1 count as zeros: code 0, and a block that is all padding gets byte 0.  Kp is a multiple of
+ *             INC_MX_KTILE = 128 elements for both formats (the GEMM's K-tile; fp4 needs no larger one).
+ *   Storage:  fp8 codes [rows, Kp] uint8; fp4 codes [rows, Kp/2] uint8, element 2i in the low nibble and 2i+1 in the high nibble
+ *             (the instruction's own order: no permutation in the kernel); scales [rows, Kp/32] uint8.
+ *   Product:  y[m,n] = sum_blocks 2^(sx + sw - 254) * sum_{k in block} a_k * b_k  +  bias[n], accumulated in fp32 inside the
+ *             matrix pipe (its summation order is not documented), fp32 bias add, one rounding to bf16 / fp16.
+ * `fmt` values are the instruction's own format codes.
+ * inc_mx_quant: the row quantiser above.  x bf16 / fp16 / fp32 [M,K] contiguous, of any alignment (16-byte loads when K is a
+ *   multiple of 8 (fp32: 4) and x is 16-byte aligned); codes 16-byte aligned.  One lane per block: each row is read from HBM once.
+ *   Writes every code byte and scale byte, the padding included, and nothing else.  Serves activations at run time and weights at
+ *   convert time.  INC_ERR_UNSUPPORTED (nothing launched) for an unknown fmt / dtype or Kp % 128 != 0.
+ * inc_mx_gemm: the product above for (xfmt, wfmt) = (fp8, fp8), (fp8, fp4), (fp4, fp4); any other pair is INC_ERR_UNSUPPORTED.
+ *   xq [M, Kp or Kp/2], xs [M, Kp/32], wq [N, Kp or Kp/2], ws [N, Kp/32] as stored by inc_mx_quant, xq / wq 16-byte and xs / ws
+ *   4-byte aligned; bias [N] in ydtype or NULL; y [M,N] bf16 / fp16, any M >= 1 and N >= 1 (8-byte stores when N % 4 == 0 and y is
+ *   8-byte aligned, 2-byte stores otherwise).  256 x 256 x 128 tiles, one workgroup per tile: no decode GEMV and no split-K tail.
+ * Both validate their arguments before any HIP call.                                                                            */
+#define INC_MX_FP8_E4M3 0
+#define INC_MX_FP4_E2M1 4
+#define INC_MX_KTILE 128
+int inc_mx_quant(const void* x, int xdtype, int64_t M, int64_t K, int64_t Kp, int fmt, uint8_t* codes, uint8_t* scales,
+                 inc_stream_t stream);
+int inc_mx_gemm(const uint8_t* xq, const uint8_t* xs, int xfmt, const uint8_t* wq, const uint8_t* ws, int wfmt, const void* bias,
+                void* y, int ydtype, int64_t M, int64_t N, int64_t Kp, inc_stream_t stream);
+
 /* ---- measured ceilings (bench.py `ceilings`) -- measurement helpers, not on the hot path ------------- *
  * inc_probe_hbm_triad: a <- b + s*c over n fp32 (n % 4 == 0): 12 n bytes of HBM traffic per call.
  * inc_probe_mfma_bf16: `blocks` workgroups x 4 waves x `iters` x 8 v_mfma_f32_32x32x16_bf16 on operands read from `src`

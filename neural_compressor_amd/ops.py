@@ -1645,3 +1645,45 @@ def _workspace_i8(dev, nbytes):
         buf = torch.zeros(max(nbytes, 1 << 20), dtype=torch.uint8, device=dev)
         _ws_i8_cache[key] = buf
     return buf
+
+
+# ---------------------------------------------------------------------------------------------------
+# K15/K16 OCP microscaling: MXFP8 / MXFP4 on the block-scaled matrix instruction (include/inc_mi355x.h has the specification)
+# ---------------------------------------------------------------------------------------------------
+MX_FP8_E4M3, MX_FP4_E2M1 = 0, 4  # the instruction's own format codes
+MX_KTILE = 128
+
+
+def mx_padded_k(K):
+    """K rounded up to the MX GEMM's K-tile."""
+    return (int(K) + MX_KTILE - 1) // MX_KTILE * MX_KTILE
+
+
+def mx_quant(x2d, fmt, Kp=None):
+    """The MX row quantiser: x [M,K] bf16 / fp16 / fp32 -> (codes uint8 [M,Kp] (fp8) or [M,Kp/2] (fp4), scales uint8 [M,Kp/32])."""
+    x2d = x2d.contiguous()
+    dev = _dev(x2d)
+    M, K = x2d.shape
+    Kp = mx_padded_k(K) if Kp is None else int(Kp)
+    codes = torch.empty((M, Kp if fmt == MX_FP8_E4M3 else Kp // 2), dtype=torch.uint8, device=dev)
+    scales = torch.empty((M, Kp // 32), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.inc_mx_quant(_ptr(x2d), dtype_code(x2d.dtype), M, K, Kp, int(fmt), _ptr(codes), _ptr(scales), _stream()), "inc_mx_quant")
+    return codes, scales
+
+
+def mx_gemm(xq, xs, xfmt, wq, ws, wfmt, bias, out_dtype):
+    """y[m,n] = sum_blocks 2^(xs + ws - 254) * sum_{k in block} x_k * w_k + bias[n] on v_mfma_scale_f32_32x32x64_f8f6f4 (K16)."""
+    dev = _dev(xq, xs, wq, ws, bias)
+    M, N = xq.shape[0], wq.shape[0]
+    Kp = xs.shape[1] * 32
+    assert ws.shape[1] * 32 == Kp and xq.dtype == torch.uint8 and wq.dtype == torch.uint8
+    assert xq.shape[1] == (Kp if xfmt == MX_FP8_E4M3 else Kp // 2) and wq.shape[1] == (Kp if wfmt == MX_FP8_E4M3 else Kp // 2)
+    assert xq.is_contiguous() and xs.is_contiguous() and wq.is_contiguous() and ws.is_contiguous()
+    if bias is not None and bias.dtype != out_dtype:
+        bias = bias.to(out_dtype)
+    y = torch.empty((M, N), dtype=out_dtype, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.inc_mx_gemm(_ptr(xq), _ptr(xs), int(xfmt), _ptr(wq), _ptr(ws), int(wfmt), _ptr(bias), _ptr(y), dtype_code(out_dtype),
+                              M, N, Kp, _stream()), "inc_mx_gemm")
+    return y

@@ -9,7 +9,7 @@ from types import MethodType
 
 import torch
 
-from ...common.utils import AWQ, GPTQ, RTN, SMOOTH_QUANT, Mode, logger
+from ...common.utils import AWQ, GPTQ, MX_QUANT, RTN, SMOOTH_QUANT, Mode, logger
 from ..utils.utility import get_quantizer, postprocess_model, register_algo
 
 
@@ -175,5 +175,33 @@ def smooth_quant_entry(model, configs_mapping, mode=Mode.QUANTIZE, *args, **kwar
     quantizer = get_quantizer(model, quantizer_cls=SmoothQuantQuantizer, quant_config=quant_config)
     model = quantizer.execute(model, mode=mode, run_fn=run_fn, example_inputs=example_inputs)
     model.qconfig = configs_mapping
+    postprocess_model(model, mode, quantizer)
+    return model
+
+
+def _mx_save(self, output_dir="./saved_results", **kwargs):
+    from ..algorithms.mx_quant import save
+
+    return save(self, output_dir)
+
+
+@register_algo(MX_QUANT)
+@torch.no_grad()
+def mx_quant_entry(model, configs_mapping, mode=Mode.QUANTIZE, *args, **kwargs):
+    """Reference algorithm_entry.py mx_quant_entry: the plain dict per Linear goes to MXQuantizer; the result carries MXLinear
+    modules.  Data-free: prepare changes nothing."""
+    from ..algorithms.mx_quant import MXQuantizer
+
+    quant_config = {}
+    for (op_name, op_type), cfg in configs_mapping.items():
+        if cfg.name != MX_QUANT:
+            continue
+        quant_config[op_name] = {"w_dtype": cfg.w_dtype, "act_dtype": cfg.act_dtype, "blocksize": cfg.blocksize,
+                                 "round_method": cfg.round_method}
+    quantizer = get_quantizer(model, quantizer_cls=MXQuantizer, quant_config=quant_config)
+    model = quantizer.execute(model, mode=mode)
+    model.qconfig = configs_mapping
+    if mode != Mode.PREPARE:
+        model.save = MethodType(_mx_save, model)
     postprocess_model(model, mode, quantizer)
     return model

@@ -12,16 +12,16 @@ from typing import List, Optional
 import torch
 
 from ...common.base_config import BaseConfig, register_config
-from ...common.utils import AWQ, DEFAULT_WHITE_LIST, GPTQ, RTN, SMOOTH_QUANT
+from ...common.utils import AWQ, DEFAULT_WHITE_LIST, GPTQ, MX_QUANT, RTN, SMOOTH_QUANT
 from ..utils.utility import (
-    LM_HEAD_NAMES, PRIORITY_AWQ, PRIORITY_GPTQ, PRIORITY_RTN, PRIORITY_SMOOTH_QUANT, WOQ_WHITE_LIST, is_fused_experts,
+    LM_HEAD_NAMES, PRIORITY_AWQ, PRIORITY_GPTQ, PRIORITY_MX_QUANT, PRIORITY_RTN, PRIORITY_SMOOTH_QUANT, WOQ_WHITE_LIST, is_fused_experts,
 )
 
 FRAMEWORK_NAME = "torch"
 
 __all__ = [
     "RTNConfig", "GPTQConfig", "AWQConfig", "get_default_rtn_config", "get_default_gptq_config",
-    "get_default_awq_config", "SmoothQuantConfig", "get_default_sq_config", "FRAMEWORK_NAME",
+    "get_default_awq_config", "SmoothQuantConfig", "get_default_sq_config", "MXQuantConfig", "get_default_mx_config", "FRAMEWORK_NAME",
 ]
 
 
@@ -298,3 +298,62 @@ class SmoothQuantConfig(TorchBaseConfig):
 
 def get_default_sq_config() -> SmoothQuantConfig:
     return SmoothQuantConfig()
+
+
+@register_config(framework_name=FRAMEWORK_NAME, algo_name=MX_QUANT, priority=PRIORITY_MX_QUANT)
+class MXQuantConfig(TorchBaseConfig):
+    """OCP microscaling linears (reference config.py MXQuantConfig: same fields).  The reference emulates the formats in float and
+    defaults to MX-INT8 (`w_dtype="int8", act_dtype="int8"`); the block-scaled matrix instruction of the MI355X has no INT8 operand,
+    so the defaults here are `w_dtype="fp8_e4m3", act_dtype="fp8_e4m3"` -- a deliberate deviation.  Supported (w_dtype, act_dtype):
+    ("fp8_e4m3", "fp8_e4m3"), ("fp4", "fp8_e4m3"), ("fp4", "fp4"), "fp4" being e2m1; `blocksize=32`, `round_method="nearest"`,
+    `weight_only=False`; `out_dtype` is accepted and unused (the output has the activation's type).  `w_dtype="fp32"` (through
+    `set_local`) leaves a layer float; lm_head stays float unless `quant_lm_head=True`."""
+
+    name = MX_QUANT
+    supported_configs: List = []
+    PAIRS = (("fp8_e4m3", "fp8_e4m3"), ("fp4", "fp8_e4m3"), ("fp4", "fp4"))
+
+    def __init__(
+        self,
+        w_dtype: str = "fp8_e4m3",
+        act_dtype: str = "fp8_e4m3",
+        out_dtype: str = "bfloat16",
+        blocksize: int = 32,
+        round_method: str = "nearest",
+        weight_only: bool = False,
+        quant_lm_head: bool = False,
+        white_list: Optional[List] = DEFAULT_WHITE_LIST,
+        **kwargs,
+    ):
+        super().__init__(white_list=white_list)
+        _assign(self, locals(), ["w_dtype", "act_dtype", "out_dtype", "blocksize", "round_method", "weight_only", "quant_lm_head"])
+        if w_dtype != "fp32":
+            unsupported = []
+            if (w_dtype, act_dtype) not in self.PAIRS:
+                unsupported.append(f"(w_dtype, act_dtype) must be one of {self.PAIRS}, got {(w_dtype, act_dtype)}")
+            if blocksize != 32:
+                unsupported.append("blocksize must be 32 (the block of the matrix instruction)")
+            if round_method != "nearest":
+                unsupported.append('round_method must be "nearest"')
+            if weight_only:
+                unsupported.append("weight_only=True is not built (the instruction takes MX operands on both sides)")
+            if unsupported:
+                raise NotImplementedError("MXQuant on MI355X: " + "; ".join(unsupported))
+        self._post_init()
+
+    def to_config_mapping(self, config_list=None, model_info=None):
+        if not self.quant_lm_head:
+            self.set_local(LM_HEAD_NAMES, self.__class__(w_dtype="fp32"))
+        return super().to_config_mapping(config_list, model_info)
+
+    @staticmethod
+    def get_model_info(model: torch.nn.Module, example_inputs=None):
+        return [(name, type(m).__name__) for name, m in model.named_modules() if isinstance(m, torch.nn.Linear)]
+
+    @classmethod
+    def register_supported_configs(cls):
+        cls.supported_configs = []
+
+
+def get_default_mx_config() -> MXQuantConfig:
+    return MXQuantConfig()

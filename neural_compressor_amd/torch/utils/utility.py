@@ -38,6 +38,7 @@ def is_fused_experts(module):
 LM_HEAD_NAMES = [".*lm_head", ".*output_layer", ".*embed_out"]  # reference torch/utils/constants.py:69
 PRIORITY_GPTQ, PRIORITY_RTN, PRIORITY_AWQ = 90, 80, 70  # reference torch/utils/constants.py:45-48
 PRIORITY_SMOOTH_QUANT = 60
+PRIORITY_MX_QUANT = 50
 
 algos_mapping = {}
 
