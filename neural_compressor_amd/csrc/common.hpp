@@ -64,6 +64,24 @@ __device__ __forceinline__ uint16_t f32_to_f16_bits(float f) {
   return b;
 }
 
+// two fp32 -> one dword of bf16 / f16 (low half = a), round-to-nearest-even
+typedef __attribute__((ext_vector_type(2))) float f32x2;
+typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
+typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
+template <bool IS_BF16>
+__device__ __forceinline__ uint32_t cvt_pair(float a, float b) {
+  f32x2 f = {a, b};
+  uint32_t r;
+  if constexpr (IS_BF16) {
+    bf16x2 h = __builtin_convertvector(f, bf16x2);  // v_cvt_pk_bf16_f32 (RNE)
+    __builtin_memcpy(&r, &h, 4);
+  } else {
+    f16x2 h = __builtin_convertvector(f, f16x2);
+    __builtin_memcpy(&r, &h, 4);
+  }
+  return r;
+}
+
 // load/store one element of a dtype-coded tensor as fp32
 template <int DT>
 __device__ __forceinline__ float load_as_f32(const void* p, int64_t i) {
@@ -202,6 +220,13 @@ __device__ __forceinline__ void banded_tile_decode(int idx, int tiles_m, int til
   const int r = idx - band * per_band;
   tm = first + r % rows;
   tn = r / rows;
+}
+
+// the first step of that: block `wg` of `n` runs on XCD wg % 8; its logical index, such that XCD c owns the contiguous range that
+// starts at c * (n / 8) + min(c, n % 8) (bijective on [0, n) for every n)
+__device__ __forceinline__ int xcd_remap(int wg, int n) {
+  const int q = n / 8, r = n % 8, xcd = wg % 8, idx = wg / 8;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
 }
 
 // dispatch a runtime dtype code to a template parameter

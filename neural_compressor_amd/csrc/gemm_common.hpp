@@ -404,24 +404,6 @@ constexpr int TM = 256, TN = 256, TK = 64;
 constexpr int T_ASTAGE = TM * TK * 2;  // bytes
 constexpr int T_BSTAGE = TN * TK * 2;
 
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
-
-template <bool IS_BF16>
-__device__ __forceinline__ uint32_t cvt_pair(float a, float b) {
-  f32x2 f = {a, b};
-  uint32_t r;
-  if constexpr (IS_BF16) {
-    bf16x2 h = __builtin_convertvector(f, bf16x2);  // v_cvt_pk_bf16_f32 (RNE)
-    __builtin_memcpy(&r, &h, 4);
-  } else {
-    f16x2 h = __builtin_convertvector(f, f16x2);
-    __builtin_memcpy(&r, &h, 4);
-  }
-  return r;
-}
-
 // 8 nibbles of `w` -> 8 x rn16((q - z) * s), k-ordered, as 4 dwords.
 // int -> float goes through the fp8 converter: an e4m3 byte with value q in 0..15 decodes to q * u (u = 2^-9 for the
 // OCP format of gfx950: codes 0..7 are subnormals m * 2^-9, codes 8..15 are (1 + m/8) * 2^-6 = (8 + m) * 2^-9), so ONE

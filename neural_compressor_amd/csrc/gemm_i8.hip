@@ -8,12 +8,8 @@
 // in tree (smooth_quant/utility.py:652-755); the reference itself executes W8A8 through intel_extension_for_pytorch
 // (smooth_quant/smooth_quant.py:105-125), which is not part of /root/reference, so this formula is the specification.
 //
-// Tile 256 (M) x 256 (N) x 128 (K bytes) per workgroup, 512 threads = 8 waves as 2 (M) x 4 (N), a wave owns 128 x 64 = 4 x 2
-// MFMA tiles (128 int32 accumulators).  Both operands are K-contiguous int8, so both tiles are 256 rows x 128 B and use the
-// SAME path as the x tile of the 4-bit kernels (gemm_tile256.hip): LDS-DMA, 8 full 128-byte rows per instruction, 16-byte chunk
-// index XOR-ed with (row >> 1) & 7 on the source address and again on the ds_read_b128 side (no bank conflicts).  Two 64 KiB
-// stages: the DMA of tile t+1 is issued at the top of step t.  W is the A operand and x the B operand, as in gemm_tile256.hip, so a
-// lane owns 4 consecutive output columns and the epilogue stores 8 bytes.
+// The wave frame of tile256_frame.hpp (wave grid, operand roles, swizzled LDS image, C/D map) with a K-tile of 128 bytes: both operands
+// are K-contiguous int8, so both tiles are 256 rows x 128 B.  Two 64 KiB stages: the DMA of tile t+1 is issued at the top of step t.
 // Tile quantisation: the tiles of the last, partly filled round of workgroups (or all of them when there are fewer tiles
 // than CUs) are split along K into `split` workgroups each; every split stores its int32 tile into its own slab of the
 // caller's workspace and a second, small kernel adds the slabs and runs the epilogue for those tiles.  (A single-kernel
@@ -25,18 +21,16 @@
 // inc_w8a8_gemm_rowscale (the dynamic per-token activation cell; xq and row_scale from inc_sq_quant_act_token):
 //   y[m, n] = (row_scale[m] * alpha[n]) * sum_k xq[m,k] * wq[n,k] + bias[n],   alpha = w_scale, no corr
 // the same kernels, plan and workspace with the row factor in the three epilogues (template parameter ROWS).
-#include "common.hpp"
+#include "tile256_frame.hpp"
 
 namespace {
 
 typedef __attribute__((ext_vector_type(4))) int i32x4;
 typedef __attribute__((ext_vector_type(16))) int i32x16;
-typedef __attribute__((ext_vector_type(2))) float f32x2_;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_;
-typedef __attribute__((ext_vector_type(2))) _Float16 f16x2_;
 
 constexpr int IM = 256, IN = 256, IK = 128;
-constexpr int I_TILE = 256 * IK;        // 32 KiB: one operand tile
+using IStage = RowStage<IK>;            // either operand's tile
+constexpr int I_TILE = IStage::TILE;    // 32 KiB
 constexpr int I_STAGE = 2 * I_TILE;     // x tile + w tile
 constexpr int I_CUS = 256;              // workgroups per round (one per CU: 128 KiB of LDS each)
 constexpr int64_t I_COUNTER_BYTES = 0;              // (no tickets: the tail tiles are finished by a second kernel)
@@ -58,20 +52,6 @@ static inline int i8_tail_plan(int64_t tiles, int nk, int64_t* full_tiles) {
   return split;
 }
 
-template <bool IS_BF16>
-__device__ __forceinline__ uint32_t cvt_pair16(float a, float b) {
-  f32x2_ f = {a, b};
-  uint32_t r;
-  if constexpr (IS_BF16) {
-    bf16x2_ h = __builtin_convertvector(f, bf16x2_);
-    __builtin_memcpy(&r, &h, 4);
-  } else {
-    f16x2_ h = __builtin_convertvector(f, f16x2_);
-    __builtin_memcpy(&r, &h, 4);
-  }
-  return r;
-}
-
 __device__ __forceinline__ i32x16 mfma_i8(const uint4& a, const uint4& b, i32x16 c) {
   i32x4 av, bv;
   __builtin_memcpy(&av, &a, 16);
@@ -85,6 +65,32 @@ __device__ __forceinline__ i32x16 mfma_i8(const uint4& a, const uint4& b, i32x16
 template <bool ROWS>
 __device__ __forceinline__ const int32_t* aux_corr(const void* aux) { return ROWS ? nullptr : static_cast<const int32_t*>(aux); }
 
+// what an output depends on through its column only, and the outputs of one accumulator quad `a` of row m from it
+struct W8A8Cols { float al[4], bv[4]; int cr[4]; };
+template <bool IS_BF16>
+__device__ __forceinline__ W8A8Cols w8a8_cols(const float* alpha, const int32_t* corr, const uint16_t* bias, int64_t nb, int64_t N) {
+  W8A8Cols c = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0, 0, 0, 0}};
+#pragma unroll
+  for (int e = 0; e < 4; ++e)
+    if (nb + e < N) {
+      c.al[e] = alpha[nb + e];
+      if (corr) c.cr[e] = corr[nb + e];
+      if (bias) c.bv[e] = IS_BF16 ? bf16_bits_to_f32(bias[nb + e]) : f16_bits_to_f32(bias[nb + e]);
+    }
+  return c;
+}
+template <bool ROWS>
+__device__ __forceinline__ void w8a8_values(const W8A8Cols& c, const void* aux, int64_t m, const int (&a)[4], float (&v)[4]) {
+  if constexpr (ROWS) {
+    const float rs = static_cast<const float*>(aux)[m];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = (rs * c.al[e]) * (float)a[e] + c.bv[e];
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = c.al[e] * (float)(a[e] + c.cr[e]) + c.bv[e];
+  }
+}
+
 template <bool IS_BF16, bool ROWS>
 __global__ __launch_bounds__(512) void w8a8_gemm_kernel(const int8_t* __restrict__ xq, const int8_t* __restrict__ wq,
                                                         const float* __restrict__ alpha, const void* __restrict__ aux,
@@ -97,9 +103,7 @@ __global__ __launch_bounds__(512) void w8a8_gemm_kernel(const int8_t* __restrict
   const int tiles_m = (int)((M + IM - 1) / IM);
   int wg = blockIdx.x, ks = 0, tail_id = -1;
   if (wg < full_tiles) {
-    const int q = full_tiles / 8, xcd = wg % 8, idx = wg / 8;  // full_tiles is a multiple of 256 (or all tiles when no split)
-    const int r = full_tiles % 8;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;  // bijective XCD remap (block b runs on XCD b % 8)
+    wg = xcd_remap(wg, full_tiles);  // full_tiles is a multiple of 256 (or all tiles when no split)
   } else {
     const int j = wg - full_tiles;
     tail_id = j / split;
@@ -114,18 +118,9 @@ __global__ __launch_bounds__(512) void w8a8_gemm_kernel(const int8_t* __restrict
   const int wm = wave >> 2, wn = wave & 3;
   const uint32_t lds0 = (uint32_t)(uintptr_t)smem;
 
-  // DMA source offsets: instruction i of this wave brings rows (wave*4+i)*8 .. +7; a lane brings chunk (lane&7)^sw of row lane>>3
   uint32_t xoff[4], woff[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int R = (wave * 4 + i) * 8 + (lane >> 3);
-    const int c = (lane & 7) ^ ((R >> 1) & 7);
-    int64_t xr = m0 + R, wr = n0 + R;
-    if (xr > M - 1) xr = M - 1;
-    if (wr > N - 1) wr = N - 1;
-    xoff[i] = (uint32_t)((xr - m0) * K + 16 * c);
-    woff[i] = (uint32_t)((wr - n0) * K + 16 * c);
-  }
+  IStage::offsets(wave, lane, m0, M, K, xoff);
+  IStage::offsets(wave, lane, n0, N, K, woff);
   const int8_t* const xtile = xq + m0 * K;
   const int8_t* const wtile = wq + n0 * K;
   const int nk_all = (int)(K / IK);
@@ -147,11 +142,11 @@ __global__ __launch_bounds__(512) void w8a8_gemm_kernel(const int8_t* __restrict
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[a][b][r] = 0;
 
-  const int sw = ((lane & 31) >> 1) & 7, hi = lane >> 5;
+  const int sw = IStage::swz(lane & 31), hi = lane >> 5;
   const int x_row = wm * 128 + (lane & 31);
   const int w_row = wn * 64 + (lane & 31);
   auto read_frags = [&](const char* S, int kk, uint4 (&xa)[4], uint4 (&wa)[2]) {
-    const int chunk = ((2 * kk + hi) ^ sw) << 4;
+    const int chunk = IStage::chunk_off(2 * kk + hi, sw);
 #pragma unroll
     for (int mf = 0; mf < 4; ++mf) xa[mf] = *reinterpret_cast<const uint4*>(S + (x_row + 32 * mf) * 128 + chunk);
 #pragma unroll
@@ -208,37 +203,24 @@ __global__ __launch_bounds__(512) void w8a8_gemm_kernel(const int8_t* __restrict
     return;
   }
 
-  // epilogue: D row i = n-offset (r&3) + 8*(r>>2) + 4*(lane>>5), col j = m-offset lane&31
+  // the frame's C/D walk and its 8-byte store, written out: through tile256_walk and store_quad16 the row-scale launch measured 1.6 %
+  // slower at K = 13824 (the epilogue was 135 - 163 instructions longer; now 3)
 #pragma unroll
   for (int nf = 0; nf < 2; ++nf) {
 #pragma unroll
     for (int rq = 0; rq < 4; ++rq) {
       const int64_t nb = n0 + wn * 64 + nf * 32 + 8 * rq + 4 * (lane >> 5);
-      float al[4] = {0.f, 0.f, 0.f, 0.f}, bv[4] = {0.f, 0.f, 0.f, 0.f};
-      int cr[4] = {0, 0, 0, 0};
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        if (nb + e < N) {
-          al[e] = alpha[nb + e];
-          if (corr) cr[e] = corr[nb + e];
-          if (bias) bv[e] = IS_BF16 ? bf16_bits_to_f32(bias[nb + e]) : f16_bits_to_f32(bias[nb + e]);
-        }
+      const W8A8Cols c = w8a8_cols<IS_BF16>(alpha, corr, bias, nb, N);
 #pragma unroll
       for (int mf = 0; mf < 4; ++mf) {
         const int64_t m = m0 + wm * 128 + mf * 32 + (lane & 31);
         if (m >= M) continue;
+        const int a4[4] = {acc[nf][mf][4 * rq], acc[nf][mf][4 * rq + 1], acc[nf][mf][4 * rq + 2], acc[nf][mf][4 * rq + 3]};
         float v[4];
-        if constexpr (ROWS) {
-          const float rs = static_cast<const float*>(aux)[m];
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = (rs * al[e]) * (float)acc[nf][mf][4 * rq + e] + bv[e];
-        } else {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = al[e] * (float)(acc[nf][mf][4 * rq + e] + cr[e]) + bv[e];
-        }
+        w8a8_values<ROWS>(c, aux, m, a4, v);
         uint16_t* dst = y + m * N + nb;
         if (y_vec_ok && nb + 4 <= N) {
-          *reinterpret_cast<uint2*>(dst) = make_uint2(cvt_pair16<IS_BF16>(v[0], v[1]), cvt_pair16<IS_BF16>(v[2], v[3]));
+          *reinterpret_cast<uint2*>(dst) = make_uint2(cvt_pair<IS_BF16>(v[0], v[1]), cvt_pair<IS_BF16>(v[2], v[3]));
         } else {
 #pragma unroll
           for (int e = 0; e < 4; ++e)
@@ -353,20 +335,14 @@ __global__ __launch_bounds__(512) void w8a8_tail_finish_kernel(const int* __rest
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 2, wn = wave & 3;
   const int* base = slabs + (int64_t)tail_id * split * (IM * IN);
+  // the frame's walk written out (tile256_walk moved this kernel's register counts): a 32-row block without a real row was not parked and is
+  // skipped before its slab loads are issued; rows past M are dropped only after the loads
 #pragma unroll
   for (int nf = 0; nf < 2; ++nf) {
 #pragma unroll
     for (int rq = 0; rq < 4; ++rq) {
       const int64_t nb = n0 + wn * 64 + nf * 32 + 8 * rq + 4 * (lane >> 5);
-      float al[4] = {0.f, 0.f, 0.f, 0.f}, bv[4] = {0.f, 0.f, 0.f, 0.f};
-      int cr[4] = {0, 0, 0, 0};
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-        if (nb + e < N) {
-          al[e] = alpha[nb + e];
-          if (corr) cr[e] = corr[nb + e];
-          if (bias) bv[e] = IS_BF16 ? bf16_bits_to_f32(bias[nb + e]) : f16_bits_to_f32(bias[nb + e]);
-        }
+      const W8A8Cols c = w8a8_cols<IS_BF16>(alpha, corr, bias, nb, N);
 #pragma unroll
       for (int mf = 0; mf < 4; ++mf) {
         if (m0 + wm * 128 + mf * 32 >= M) continue;
@@ -385,22 +361,8 @@ __global__ __launch_bounds__(512) void w8a8_tail_finish_kernel(const int* __rest
           for (int e = 0; e < 4; ++e) a4[e] += part[o][e];
         if (m >= M) continue;
         float v[4];
-        if constexpr (ROWS) {
-          const float rs = static_cast<const float*>(aux)[m];
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = (rs * al[e]) * (float)a4[e] + bv[e];
-        } else {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = al[e] * (float)(a4[e] + cr[e]) + bv[e];
-        }
-        uint16_t* dst = y + m * N + nb;
-        if (y_vec_ok && nb + 4 <= N) {
-          *reinterpret_cast<uint2*>(dst) = make_uint2(cvt_pair16<IS_BF16>(v[0], v[1]), cvt_pair16<IS_BF16>(v[2], v[3]));
-        } else {
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            if (nb + e < N) dst[e] = IS_BF16 ? f32_to_bf16_bits(v[e]) : f32_to_f16_bits(v[e]);
-        }
+        w8a8_values<ROWS>(c, aux, m, a4, v);
+        store_quad16<IS_BF16>(y, m, nb, N, y_vec_ok, v);
       }
     }
   }

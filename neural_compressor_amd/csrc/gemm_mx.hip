@@ -9,66 +9,33 @@
 //   the first 4 dwords (element 2i in the low nibble of byte i -- the stored order; dwords 4 .. 7 are not read).  fp8: dwords 0 .. 3
 //   are bytes 16 h .. 16 h + 15 and dwords 4 .. 7 bytes 32 + 16 h .. of the step (two back-to-back 8-bit MFMAs of K = 32), so a
 //   block is spread over both lane halves.  For either format lane half h supplies the scale of block h of its row, in the byte of
-//   the scale register that opsel names; C/D is the 32 x 32 map of every other 32x32 MFMA (gemm_i8.hip's epilogue).
+//   the scale register that opsel names; C/D is the 32 x 32 map of every other 32x32 MFMA (tile256_frame.hpp).
 //
-// The kernel is gemm_i8.hip's main kernel with the scaled instruction: tile 256 (M) x 256 (N) x 128 (K elements) per workgroup, 512
-// threads = 8 waves as 2 (M) x 4 (N), a wave owns 128 x 64 = 4 x 2 MFMA tiles (128 fp32 accumulators).  Both operands are
-// K-contiguous, so a tile is 256 rows of 128 bytes (fp8) or 64 bytes (fp4), staged by LDS-DMA in 1 KiB pieces (8 or 16 whole rows)
-// with the 16-byte chunk index XOR-ed with (row >> 1) & 7 (128-byte rows) or (row >> 2) & 3 (64-byte rows) on the source address and
-// again on the ds_read_b128 side: 16 consecutive rows then read 16 different 16-byte slots of a 256-byte bank window.  Two stages,
-// the DMA of tile t+1 issued at the top of step t.  W is the A operand and x the B operand, so a lane owns 4 consecutive output
-// columns and the epilogue stores 8 bytes.
+// The kernel stands on the wave frame of tile256_frame.hpp (wave grid, operand roles, swizzled LDS image, C/D map) with a K-tile of 128
+// elements: both operands are K-contiguous, so a tile is 256 rows of 128 bytes (fp8) or 64 bytes (fp4).  Two stages, the DMA of tile
+// t+1 issued at the top of step t.
 // Scales: a row has 4 scale bytes per K-tile, one dword.  Each lane loads the dwords of its 2 W rows and 4 x rows one step ahead
 // (before that step's DMA is issued; they are first touched behind the barrier that ends the step, so no wait for them is placed in
 // front of an MFMA), shifts them right by 8 * (l >> 5) once -- the two lane halves supply different blocks -- and the two 64-wide
 // steps of a tile take bytes 0 and 2 of the result through opsel.
 // One workgroup per tile: no decode GEMV (M <= 16 runs this kernel with clamped source rows) and no split-K tail.
 // Algorithmic work per launch: 2*M*N*Kp flop; bytes (M + N) * Kp * (1 or 1/2) + (M + N) * Kp / 32 + 2*M*N.
-#include "common.hpp"
+#include "tile256_frame.hpp"
 
 namespace {
 
 typedef __attribute__((ext_vector_type(8))) int i32x8;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(2))) float f32x2_;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_;
-typedef __attribute__((ext_vector_type(2))) _Float16 f16x2_;
 
 constexpr int XM = 256, XN = 256, XK = INC_MX_KTILE;
 
 __host__ __device__ constexpr int mx_row_bytes(int fmt) { return fmt == INC_MX_FP8_E4M3 ? XK : XK / 2; }  // of one K-tile
 
-template <bool IS_BF16>
-__device__ __forceinline__ uint32_t cvt_pair16(float a, float b) {
-  f32x2_ f = {a, b};
-  uint32_t r;
-  if constexpr (IS_BF16) {
-    bf16x2_ h = __builtin_convertvector(f, bf16x2_);
-    __builtin_memcpy(&r, &h, 4);
-  } else {
-    f16x2_ h = __builtin_convertvector(f, f16x2_);
-    __builtin_memcpy(&r, &h, 4);
-  }
-  return r;
-}
-
-// stage one operand tile: 256 rows of RB bytes = RB / 32 LDS-DMA instructions per wave, each 1024 / RB whole rows
+// the row stage of the frame, issued as single 1 KiB pieces, and the operand of the scaled MFMA read from it
 template <int RB>
-struct MxStage {
-  static constexpr int NI = RB / 32, RPI = 1024 / RB, CPR = RB / 16;
-  static constexpr int TILE = 256 * RB;
-  __device__ static __forceinline__ int swz(int row) { return RB == 128 ? (row >> 1) & 7 : (row >> 2) & 3; }
-  // per-lane source offsets (bytes from the tile's first row at K-tile 0); rows past the last real row re-read it
-  __device__ static __forceinline__ void offsets(int wave, int lane, int64_t r0, int64_t rows, int64_t ld, uint32_t (&off)[NI]) {
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-      const int R = (wave * NI + i) * RPI + lane / CPR;
-      const int c = (lane % CPR) ^ swz(R);
-      int64_t r = r0 + R;
-      if (r > rows - 1) r = rows - 1;
-      off[i] = (uint32_t)((r - r0) * ld + 16 * c);
-    }
-  }
+struct MxStage : RowStage<RB> {
+  using RowStage<RB>::NI;
+  using RowStage<RB>::chunk_off;
   __device__ static __forceinline__ void issue(const uint8_t* src, uint32_t lds_tile, int wave, const uint32_t (&off)[NI]) {
 #pragma unroll
     for (int i = 0; i < NI; ++i) lds_dma_1k(src, __builtin_amdgcn_readfirstlane(lds_tile + (wave * NI + i) * 1024), off[i]);
@@ -77,13 +44,13 @@ struct MxStage {
   __device__ static __forceinline__ i32x8 frag(const char* tile, int row, int kk, int h, int sw) {
     i32x8 f;
     if constexpr (RB == 128) {
-      const int slot = (4 * kk + h) ^ sw;  // 16-byte chunks h and 2 + h of the step's four
-      const uint4 lo = *reinterpret_cast<const uint4*>(tile + row * 128 + (slot << 4));
-      const uint4 hi = *reinterpret_cast<const uint4*>(tile + row * 128 + ((slot ^ 2) << 4));
+      const int slot = chunk_off(4 * kk + h, sw);  // 16-byte chunks h and 2 + h of the step's four
+      const uint4 lo = *reinterpret_cast<const uint4*>(tile + row * 128 + slot);
+      const uint4 hi = *reinterpret_cast<const uint4*>(tile + row * 128 + (slot ^ 32));
       f[0] = (int)lo.x; f[1] = (int)lo.y; f[2] = (int)lo.z; f[3] = (int)lo.w;
       f[4] = (int)hi.x; f[5] = (int)hi.y; f[6] = (int)hi.z; f[7] = (int)hi.w;
     } else {
-      const uint4 lo = *reinterpret_cast<const uint4*>(tile + row * 64 + (((2 * kk + h) ^ sw) << 4));  // block 2 kk + h
+      const uint4 lo = *reinterpret_cast<const uint4*>(tile + row * 64 + chunk_off(2 * kk + h, sw));  // block 2 kk + h
       f[0] = (int)lo.x; f[1] = (int)lo.y; f[2] = (int)lo.z; f[3] = (int)lo.w;
       f[4] = 0; f[5] = 0; f[6] = 0; f[7] = 0;  // fp4 occupies the first four registers; the instruction reads no more
     }
@@ -103,11 +70,7 @@ __global__ __launch_bounds__(512) void mx_gemm_kernel(const uint8_t* __restrict_
   const int tiles_n = (int)((N + XN - 1) / XN);
   const int tiles_m = (int)((M + XM - 1) / XM);
   const int tiles = tiles_m * tiles_n;
-  int wg = blockIdx.x;
-  {
-    const int q = tiles / 8, r = tiles % 8, xcd = wg % 8, idx = wg / 8;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;  // bijective XCD remap (block b runs on XCD b % 8)
-  }
+  const int wg = xcd_remap(blockIdx.x, tiles);
   int tm, tn;
   banded_tile_decode(wg, tiles_m, tiles_n, tm, tn);
   const int64_t m0 = (int64_t)tm * XM, n0 = (int64_t)tn * XN;
@@ -213,18 +176,15 @@ __global__ __launch_bounds__(512) void mx_gemm_kernel(const uint8_t* __restrict_
   }
 #undef MX_SB
 
-  // epilogue: D row i = n-offset (r&3) + 8*(r>>2) + 4*(lane>>5), col j = m-offset lane&31
+  // the frame's C/D walk and its 8-byte store, written out: with this text the kernel's machine code is the parent's, byte for byte;
+  // through tile256_walk or store_quad16 the epilogue grew by 160 instructions and every launch measured 0.1 - 1 % slower
 #pragma unroll
   for (int nf = 0; nf < 2; ++nf) {
 #pragma unroll
     for (int rq = 0; rq < 4; ++rq) {
       const int64_t nb = n0 + wn * 64 + nf * 32 + 8 * rq + 4 * (lane >> 5);
-      float bv[4] = {0.f, 0.f, 0.f, 0.f};
-      if (bias) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          if (nb + e < N) bv[e] = IS_BF16 ? bf16_bits_to_f32(bias[nb + e]) : f16_bits_to_f32(bias[nb + e]);
-      }
+      const BiasQuad bq = load_bias_quad<IS_BF16>(bias, nb, N);
+      const float (&bv)[4] = bq.b;
 #pragma unroll
       for (int mf = 0; mf < 4; ++mf) {
         const int64_t m = m0 + wm * 128 + mf * 32 + (lane & 31);
@@ -234,7 +194,7 @@ __global__ __launch_bounds__(512) void mx_gemm_kernel(const uint8_t* __restrict_
         for (int e = 0; e < 4; ++e) v[e] = acc[nf][mf][4 * rq + e] + bv[e];
         uint16_t* dst = y + m * N + nb;
         if (y_vec_ok && nb + 4 <= N) {
-          *reinterpret_cast<uint2*>(dst) = make_uint2(cvt_pair16<IS_BF16>(v[0], v[1]), cvt_pair16<IS_BF16>(v[2], v[3]));
+          *reinterpret_cast<uint2*>(dst) = make_uint2(cvt_pair<IS_BF16>(v[0], v[1]), cvt_pair<IS_BF16>(v[2], v[3]));
         } else {
 #pragma unroll
           for (int e = 0; e < 4; ++e)

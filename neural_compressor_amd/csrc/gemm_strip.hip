@@ -38,8 +38,7 @@ __global__ __launch_bounds__(64 * WAVES) void woq_gemm_w4_strip_kernel(
   int bx = (int)blockIdx.x, by = (int)blockIdx.y;
   {
     const int nx = (int)gridDim.x, nt = nx * (int)gridDim.y, L = by * nx + bx;
-    const int q = nt / 8, r = nt % 8, xcd = L % 8, idx = L / 8;
-    const int t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;  // bijective (same form as the d2r kernel's)
+    const int t = xcd_remap(L, nt);
     by = t / nx;
     bx = t - by * nx;
   }

@@ -39,11 +39,7 @@ __global__ __launch_bounds__(256) void woq_gemm_tile_kernel(
   const int tiles_n = (int)((N + GN - 1) / GN);
   const int tiles_m = (int)((M + GM - 1) / GM);
   const int nwg = tiles_m * tiles_n;
-  int wg = blockIdx.x;
-  {
-    const int q = nwg / 8, r = nwg % 8, xcd = wg % 8, idx = wg / 8;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;  // bijective remap
-  }
+  const int wg = xcd_remap(blockIdx.x, nwg);
   const int tm = wg / tiles_n, tn = wg - tm * tiles_n;
   const int64_t m0 = (int64_t)tm * GM, n0 = (int64_t)tn * GN;
 

@@ -2,25 +2,20 @@
 // "big" kernel, "3A2B" (three x stages + two W stages, 4- and 8-bit) and, in the harness build, the producer / consumer kernel -- and the
 // slab reduce that ends every split-K launch of a 256-row kernel.  (gemm_d2r.hip took over the large-M 4-bit path from them.)
 #include "gemm_common.hpp"
+#include "tile256_frame.hpp"
 
 namespace {
 
 // =============================================================================================
 // large-M fast path (4-bit, K % 64 == 0, group_size % 32 == 0): 256x256x64 workgroup tile
 // =============================================================================================
-// 512 threads = 8 waves as 2 (M) x 4 (N); a wave owns 128 (m) x 64 (n) = 4 x 2 MFMA 32x32x16 tiles
-// (128 fp32 accumulators).  One workgroup per CU (128 KiB LDS, two stages):
-//   x tile      256 rows x 128 B, brought in by LDS-DMA (global_load_lds_dwordx4): every DMA
-//               instruction moves 8 full 128-byte rows.  The LDS image is row-major with the 16-byte
-//               chunk index XOR-ed by ((row >> 1) & 7); the DMA destination is lane-linear, so the
-//               permutation is applied to the per-lane SOURCE address and again on the ds_read_b128
-//               side -> conflict-free fragment reads and full-line global reads.
+// The wave frame of tile256_frame.hpp with 32x32x16 MFMAs and a K-tile of 64 elements; one workgroup per CU (128 KiB LDS, two stages):
+//   x tile      the frame's swizzled row stage (XStage: 256 rows x 128 B by LDS-DMA).
 //   W tile      each thread fetches 4 packed words (4 packed rows of ONE column: the wave reads 256
 //               contiguous bytes per row), dequantises them once for the whole workgroup and writes
 //               the 4 x 16 B in MFMA-fragment order [n-frag][k16][lane] -> both the ds_write_b128 and
 //               the ds_read_b128 are lane-linear (conflict-free).
-// The MFMA is issued with W as the A operand and x as the B operand: a lane then owns 4 consecutive
-// output columns per accumulator quad -> 8-byte stores in the epilogue (4x fewer store instructions).
+using XStage = RowStage<TK * 2>;  // the x tile of every kernel of this file
 
 // ABL != 0: timing-only ablations for tools/kbench (results are WRONG): 1 = no dequant arithmetic, 2 = x fragments read
 // once per K-step, 3 = no global traffic inside the K-loop, 4 = no MFMA
@@ -37,11 +32,7 @@ __global__ __launch_bounds__(512) void woq_gemm_w4_big_kernel(
   const int tiles_n = (int)((N + TN - 1) / TN);
   const int tiles_m = (int)((M + TM - 1) / TM);
   const int nwg = tiles_m * tiles_n;
-  int wg = blockIdx.x;
-  {
-    const int q = nwg / 8, r = nwg % 8, xcd = wg % 8, idx = wg / 8;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;  // bijective XCD remap
-  }
+  const int wg = xcd_remap(blockIdx.x, nwg);
   const int tm = wg / tiles_n, tn = wg - tm * tiles_n;
   const int64_t m0 = (int64_t)tm * TM, n0 = (int64_t)tn * TN;
 
@@ -50,16 +41,9 @@ __global__ __launch_bounds__(512) void woq_gemm_w4_big_kernel(
   const float inv_u = fp8_unit_inverse();
   const int wm = wave >> 2, wn = wave & 3;
 
-  // ---- x staging (LDS-DMA): instruction i of this wave fills LDS rows (wave*4+i)*8 .. +7 -------
+  // ---- x staging (LDS-DMA) ----------------------------------------------------------------------
   uint32_t avoff[4];  // byte offset of this lane's 16-byte chunk from x + m0*K + kt*TK
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int R = (wave * 4 + i) * 8 + (lane >> 3);
-    const int c = (lane & 7) ^ ((R >> 1) & 7);
-    int64_t row = m0 + R;
-    if (row > M - 1) row = M - 1;  // rows past M are computed from a valid row and never stored
-    avoff[i] = (uint32_t)(((row - m0) * K + 8 * c) * 2);
-  }
+  XStage::offsets(wave, lane, m0, M, 2 * K, avoff);
   const uint16_t* const xtile = x + m0 * K;
   const uint32_t lds0 = (uint32_t)(uintptr_t)smem;  // LDS byte address of the dynamic segment (low half of the flat address)
   // ---- W staging: this thread's column and packed-row half ---------------------------------------
@@ -127,14 +111,14 @@ __global__ __launch_bounds__(512) void woq_gemm_w4_big_kernel(
 
   // fragment read offsets
   const int a_row = wm * 128 + (lane & 31);         // + 32*mf
-  const int a_sw = ((lane & 31) >> 1) & 7;           // (row >> 1) & 7 (tile bases are multiples of 32)
+  const int a_sw = XStage::swz(lane & 31);
   const int a_hi = lane >> 5;                        // chunk = 2*kk + a_hi
   const int b_off = (wn * 2 * 4 * 64 + lane) * 16;   // + (nf*4 + kk) * 1024
 
   uint4 xa_keep[4];
   auto mma_step = [&](const char* As, const char* Bs, int kk) {
     uint4 xa[4], wb[2];
-    const int chunk = ((2 * kk + a_hi) ^ a_sw) << 4;
+    const int chunk = XStage::chunk_off(2 * kk + a_hi, a_sw);
 #pragma unroll
     for (int mf = 0; mf < 4; ++mf) {
       if (ABL == 2 && kk != 0) xa[mf] = xa_keep[mf];
@@ -218,36 +202,14 @@ __global__ __launch_bounds__(512) void woq_gemm_w4_big_kernel(
     for (int kk = 0; kk < 4; ++kk) mma_step(As, Bs, kk);
   }
 
-  // epilogue: D row i = n-offset (r&3) + 8*(r>>2) + 4*(lane>>5), col j = m-offset lane&31
-#pragma unroll
-  for (int nf = 0; nf < 2; ++nf) {
-#pragma unroll
-    for (int rq = 0; rq < 4; ++rq) {
-      const int64_t nb = n0 + wn * 64 + nf * 32 + 8 * rq + 4 * (lane >> 5);
-      float bv[4] = {0.f, 0.f, 0.f, 0.f};
-      if (bias) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          if (nb + e < N) bv[e] = cvt16<IS_BF16>(bias[nb + e]);
-      }
-#pragma unroll
-      for (int mf = 0; mf < 4; ++mf) {
-        const int64_t m = m0 + wm * 128 + mf * 32 + (lane & 31);
-        if (m >= M) continue;
-        const float v0 = acc[nf][mf][4 * rq + 0] + bv[0], v1 = acc[nf][mf][4 * rq + 1] + bv[1];
-        const float v2 = acc[nf][mf][4 * rq + 2] + bv[2], v3 = acc[nf][mf][4 * rq + 3] + bv[3];
-        uint16_t* dst = y + m * N + nb;
-        if (y_vec_ok && nb + 4 <= N) {
-          *reinterpret_cast<uint2*>(dst) = make_uint2(cvt_pair<IS_BF16>(v0, v1), cvt_pair<IS_BF16>(v2, v3));
-        } else {
-          const float vv[4] = {v0, v1, v2, v3};
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            if (nb + e < N) dst[e] = IS_BF16 ? f32_to_bf16_bits(vv[e]) : f32_to_f16_bits(vv[e]);
-        }
-      }
-    }
-  }
+  tile256_walk(
+      m0, n0, wm, wn, lane, [&](int64_t nb) { return load_bias_quad<IS_BF16>(bias, nb, N); },
+      [&](int nf, int mf, int rq, int64_t m, int64_t nb, const BiasQuad& bq) {
+        if (m >= M) return;
+        const float v[4] = {acc[nf][mf][4 * rq + 0] + bq.b[0], acc[nf][mf][4 * rq + 1] + bq.b[1], acc[nf][mf][4 * rq + 2] + bq.b[2],
+                            acc[nf][mf][4 * rq + 3] + bq.b[3]};
+        store_quad16<IS_BF16>(y, m, nb, N, y_vec_ok, v);
+      });
 }
 
 // =============================================================================================
@@ -287,11 +249,7 @@ __global__ __launch_bounds__(512) void woq_gemm_w4_3a2b_kernel(
   const int tiles_n = (int)((N + TN - 1) / TN);
   const int tiles_m = (int)((M + TM - 1) / TM);
   const int nwg = tiles_m * tiles_n;
-  int wg = blockIdx.x;
-  {
-    const int q = nwg / 8, r = nwg % 8, xcd = wg % 8, idx = wg / 8;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;  // bijective XCD remap
-  }
+  const int wg = xcd_remap(blockIdx.x, nwg);
   // row-major inside an XCD's range: a 2 x 16 strip shares the 32 KiB x tiles 16 ways and the 8 KiB W tiles 2 ways -- 192 KiB of
   // unique operand bytes per K-step for 32 tiles; the 8 x 4 patch of banded_tile_decode needs 288 KiB and measured 15 % slower
   const int tm = wg / tiles_n, tn = wg - tm * tiles_n;
@@ -316,14 +274,7 @@ __global__ __launch_bounds__(512) void woq_gemm_w4_3a2b_kernel(
   const uint32_t lds0 = (uint32_t)(uintptr_t)smem;
 
   uint32_t avoff[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int R = (wave * 4 + i) * 8 + (lane >> 3);
-    const int c = (lane & 7) ^ ((R >> 1) & 7);
-    int64_t row = m0 + R;
-    if (row > M - 1) row = M - 1;
-    avoff[i] = (uint32_t)(((row - m0) * K + 8 * c) * 2);
-  }
+  XStage::offsets(wave, lane, m0, M, 2 * K, avoff);
   const uint16_t* const xtile = x + m0 * K;
   const int bcol = tid & 255, kwh = tid >> 8;
   int64_t ncol = n0 + bcol;
@@ -390,11 +341,11 @@ __global__ __launch_bounds__(512) void woq_gemm_w4_3a2b_kernel(
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
   const int a_row = wm * 128 + (lane & 31);
-  const int a_sw = ((lane & 31) >> 1) & 7;
+  const int a_sw = XStage::swz(lane & 31);
   const int a_hi = lane >> 5;
   const int b_off = (wn * 2 * 4 * 64 + lane) * 16;
   auto read_frags = [&](const char* As, const char* Bs, int kk, uint4 (&xa)[4], uint4 (&wbv)[2]) {
-    const int chunk = ((2 * kk + a_hi) ^ a_sw) << 4;
+    const int chunk = XStage::chunk_off(2 * kk + a_hi, a_sw);
 #pragma unroll
     for (int mf = 0; mf < 4; ++mf) xa[mf] = *reinterpret_cast<const uint4*>(As + (a_row + 32 * mf) * 128 + chunk);
 #pragma unroll
@@ -589,8 +540,8 @@ __global__ __launch_bounds__(512) void woq_gemm_w4_3a2b_kernel(
 #undef INC_SB
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 
-  // epilogue: D row i = n-offset (r&3) + 8*(r>>2) + 4*(lane>>5), col j = m-offset lane&31
-  if (partial) {  // split-K: raw fp32 tile into this split's slab (bias and conversion happen in the finalize kernel)
+  if (partial) {  // split-K: raw fp32 tile into this split's slab (bias and conversion happen in the finalize kernel).  The frame's walk
+    // written out: through tile256_walk the compiler split the 16-byte store into 12 + 4 bytes and the slab launches lost 10-16 %
     float* slab = partial + (int64_t)blockIdx.y * M * N;
 #pragma unroll
     for (int nf = 0; nf < 2; ++nf)
@@ -613,32 +564,20 @@ __global__ __launch_bounds__(512) void woq_gemm_w4_3a2b_kernel(
       }
     return;
   }
+  // (written out like the slab store above: with tile256_walk here the 4-bit kernel took one more VGPR than it had)
 #pragma unroll
   for (int nf = 0; nf < 2; ++nf) {
 #pragma unroll
     for (int rq = 0; rq < 4; ++rq) {
       const int64_t nb = n0 + wn * 64 + nf * 32 + 8 * rq + 4 * (lane >> 5);
-      float bv[4] = {0.f, 0.f, 0.f, 0.f};
-      if (bias) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          if (nb + e < N) bv[e] = cvt16<IS_BF16>(bias[nb + e]);
-      }
+      const BiasQuad bq = load_bias_quad<IS_BF16>(bias, nb, N);
 #pragma unroll
       for (int mf = 0; mf < 4; ++mf) {
         const int64_t m = m0 + wm * 128 + mf * 32 + (lane & 31);
         if (m >= M) continue;
-        const float v0 = acc[nf][mf][4 * rq + 0] + bv[0], v1 = acc[nf][mf][4 * rq + 1] + bv[1];
-        const float v2 = acc[nf][mf][4 * rq + 2] + bv[2], v3 = acc[nf][mf][4 * rq + 3] + bv[3];
-        uint16_t* dst = y + m * N + nb;
-        if (y_vec_ok && nb + 4 <= N) {
-          *reinterpret_cast<uint2*>(dst) = make_uint2(cvt_pair<IS_BF16>(v0, v1), cvt_pair<IS_BF16>(v2, v3));
-        } else {
-          const float vv[4] = {v0, v1, v2, v3};
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            if (nb + e < N) dst[e] = IS_BF16 ? f32_to_bf16_bits(vv[e]) : f32_to_f16_bits(vv[e]);
-        }
+        const float v[4] = {acc[nf][mf][4 * rq + 0] + bq.b[0], acc[nf][mf][4 * rq + 1] + bq.b[1], acc[nf][mf][4 * rq + 2] + bq.b[2],
+                            acc[nf][mf][4 * rq + 3] + bq.b[3]};
+        store_quad16<IS_BF16>(y, m, nb, N, y_vec_ok, v);
       }
     }
   }

@@ -53,8 +53,7 @@ __device__ __forceinline__ void tri_decode(int idx, int nt, int& ti, int& tj) {
 // touching ~40 different ones: the panels are then re-read from that XCD's L2, not from HBM / Infinity Cache
 // (profiles/r1_pmc: 0.5-1 GB fetched per launch for 45 MB of X with the plain row-major order).
 __device__ __forceinline__ void xcd_supertile_decode(int b, int n, int nt, int& ti, int& tj) {
-  const int q = n / 8, r = n % 8, xcd = b % 8, t = b / 8;
-  int rem = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + t;  // logical index
+  int rem = xcd_remap(b, n);  // logical index
   constexpr int S = 8;
   const int ns = (nt + S - 1) / S;
   for (int si = 0; si < ns; ++si) {

@@ -17,6 +17,7 @@
 #include <type_traits>
 
 #include "gemm_common.hpp"
+#include "tile256_frame.hpp"
 
 namespace {
 
@@ -56,11 +57,7 @@ __global__ __launch_bounds__(D8_THREADS) void woq_gemm_w4_d2r8_kernel(
   const int tiles_n = (int)((N + TN - 1) / TN);
   const int tiles_m = (int)((M + TM - 1) / TM);
   const int nwg = tiles_m * tiles_n;
-  int wg = blockIdx.x;
-  {
-    const int q = nwg / 8, r = nwg % 8, xcd = wg % 8, idx = wg / 8;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;  // bijective XCD remap
-  }
+  const int wg = xcd_remap(blockIdx.x, nwg);
   const int tm = wg / tiles_n, tn = wg - tm * tiles_n;
   const int64_t m0 = (int64_t)tm * TM, n0 = (int64_t)tn * TN;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -73,16 +70,10 @@ __global__ __launch_bounds__(D8_THREADS) void woq_gemm_w4_d2r8_kernel(
   const bool lds_epilogue = !partial && (y_vec_ok & 2) && m0 + TM <= M && n0 + TN <= N;
   const float inv_u = fp8_unit_inverse();
 
-  // ---- x tile by LDS-DMA: piece i of this wave = LDS rows (wave * 4 + i) * 8 .. + 7, 16-byte chunk XOR-ed by (row >> 1) & 7 ----
+  // ---- x tile by LDS-DMA: the swizzled row stage of tile256_frame.hpp ----
+  using XStage = RowStage<TK * 2>;
   uint32_t avoff[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int R = (wave * 4 + i) * 8 + (lane >> 3);
-    const int c = (lane & 7) ^ ((R >> 1) & 7);
-    int64_t row = m0 + R;
-    if (row > M - 1) row = M - 1;  // rows past M are computed from a valid row and never stored
-    avoff[i] = (uint32_t)(((row - m0) * K + 8 * c) * 2);
-  }
+  XStage::offsets(wave, lane, m0, M, 2 * K, avoff);
   const uint16_t* xptr = x + m0 * K + (int64_t)kbase * TK;
   int xt = 0;
   uint32_t dma_off = 0;
@@ -150,11 +141,11 @@ __global__ __launch_bounds__(D8_THREADS) void woq_gemm_w4_d2r8_kernel(
 #define INC_D8_WAIT(SET) \
   asm volatile("s_waitcnt vmcnt(14)" : "+v"(W[SET][0]), "+v"(W[SET][1]), "+v"(W[SET][2]), "+v"(W[SET][3]), "+v"(SC[SET]), "+v"(ZW[SET]) : : "memory");
 
-  // ---- x fragments (B operands): rows 128 wm + 32 mf + (lane & 31), 16-byte chunk (2 kk + (lane >> 5)) ^ ((row >> 1) & 7) ----
-  const int a_sw = ((lane & 31) >> 1) & 7, a_hi = lane >> 5;
+  // ---- x fragments (B operands): rows 128 wm + 32 mf + (lane & 31), 16-byte chunk 2 kk + (lane >> 5) of the swizzled row ----
+  const int a_sw = XStage::swz(lane & 31), a_hi = lane >> 5;
   uint32_t xaddr[4];
 #pragma unroll
-  for (int kk = 0; kk < 4; ++kk) xaddr[kk] = lds0 + (uint32_t)(wm * 16384 + (lane & 31) * 128) + (uint32_t)(((2 * kk + a_hi) ^ a_sw) << 4);
+  for (int kk = 0; kk < 4; ++kk) xaddr[kk] = lds0 + (uint32_t)(wm * 16384 + (lane & 31) * 128) + (uint32_t)XStage::chunk_off(2 * kk + a_hi, a_sw);
   uint32_t rd_off = 0, rd_nxt = 0;
   u32x4 X[2][4];
   uint32_t xa_;

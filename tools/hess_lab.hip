@@ -21,8 +21,7 @@ constexpr int H2 = 256;
 
 // (same order as gptq.hip's xcd_supertile_decode)
 __device__ __forceinline__ void xcd_supertile_decode(int b, int n, int nt, int& ti, int& tj) {
-  const int q = n / 8, r = n % 8, xcd = b % 8, t = b / 8;
-  int rem = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + t;
+  int rem = xcd_remap(b, n);
   constexpr int S = 8;
   const int ns = (nt + S - 1) / S;
   for (int si = 0; si < ns; ++si) {

@@ -77,11 +77,7 @@ __global__ __launch_bounds__(PC_THREADS) void woq_gemm_w4_pc_kernel(
   const int tiles_n = (int)((N + TN - 1) / TN);
   const int tiles_m = (int)((M + TM - 1) / TM);
   const int nwg = tiles_m * tiles_n;
-  int wg = blockIdx.x;
-  {
-    const int q = nwg / 8, r = nwg % 8, xcd = wg % 8, idx = wg / 8;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;  // bijective XCD remap
-  }
+  const int wg = xcd_remap(blockIdx.x, nwg);
   const int tm = wg / tiles_n, tn = wg - tm * tiles_n;
   const int64_t m0 = (int64_t)tm * TM, n0 = (int64_t)tn * TN;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -201,15 +197,8 @@ __global__ __launch_bounds__(PC_THREADS) void woq_gemm_w4_pc_kernel(
   // =========================================== CONSUMER (x DMA + MFMA) ===========================================
   if constexpr ((ABL & 256) != 0) __builtin_amdgcn_s_setprio(2);
   const int wm = wave >> 2, wn = wave & 3;
-  uint32_t avoff[4];  // this wave's share of the x tile: LDS rows (wave*4+i)*8 .. +7, 16-byte chunk XOR-ed by (row >> 1) & 7
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int R = (wave * 4 + i) * 8 + (lane >> 3);
-    const int c = (lane & 7) ^ ((R >> 1) & 7);
-    int64_t row = m0 + R;
-    if (row > M - 1) row = M - 1;  // rows past M are computed from a valid row and never stored
-    avoff[i] = (uint32_t)(((row - m0) * K + 8 * c) * 2);
-  }
+  uint32_t avoff[4];  // this wave's share of the x tile (consumer waves 0..7 = the frame's eight)
+  XStage::offsets(wave, lane, m0, M, 2 * K, avoff);
   const uint16_t* const xtile = x + m0 * K;
   auto dma_piece = [&](int kt, int astage, int i) {
     if constexpr ((ABL & 4) != 0) return;
@@ -225,7 +214,7 @@ __global__ __launch_bounds__(PC_THREADS) void woq_gemm_w4_pc_kernel(
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
   const int a_row = wm * 128 + (lane & 31);
-  const int a_sw = ((lane & 31) >> 1) & 7;
+  const int a_sw = XStage::swz(lane & 31);
   const int a_hi = lane >> 5;
   const int b_off = (wn * 2 * 4 * 64 + lane) * 16;
   // prologue: x tile 0 complete, tile 1 in flight (4 requests)
@@ -242,7 +231,7 @@ __global__ __launch_bounds__(PC_THREADS) void woq_gemm_w4_pc_kernel(
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) {
       uint4 xa[4], wbv[2];
-      const int chunk = ((2 * kk + a_hi) ^ a_sw) << 4;
+      const int chunk = XStage::chunk_off(2 * kk + a_hi, a_sw);
       if constexpr ((ABL & 16) != 0) {
         asm volatile("" : "=v"(wbv[0].x), "=v"(wbv[0].y), "=v"(wbv[0].z), "=v"(wbv[0].w), "=v"(wbv[1].x), "=v"(wbv[1].y), "=v"(wbv[1].z), "=v"(wbv[1].w));
 #pragma unroll
@@ -280,8 +269,8 @@ __global__ __launch_bounds__(PC_THREADS) void woq_gemm_w4_pc_kernel(
     pc_store_tile<IS_BF16>(smem, &acc[0][0], bias, y, m0, n0, N, wm, wn, lane, tid, true);
     return;
   }
-  // epilogue: D row i = n-offset (r&3) + 8*(r>>2) + 4*(lane>>5), col j = m-offset lane&31
-  if (partial) {  // split-K: raw fp32 tile into this split's slab (bias and conversion happen in the finalize kernel)
+  if (partial) {  // split-K: raw fp32 tile into this split's slab (bias and conversion happen in the finalize kernel).  The frame's walk
+    // written out: through tile256_walk the compiler split the 16-byte store into 12 + 4 bytes and the slab launches lost 10-16 %
     float* slab = partial + (int64_t)blockIdx.y * M * N;
 #pragma unroll
     for (int nf = 0; nf < 2; ++nf)
@@ -304,33 +293,12 @@ __global__ __launch_bounds__(PC_THREADS) void woq_gemm_w4_pc_kernel(
       }
     return;
   }
-#pragma unroll
-  for (int nf = 0; nf < 2; ++nf) {
-#pragma unroll
-    for (int rq = 0; rq < 4; ++rq) {
-      const int64_t nb = n0 + wn * 64 + nf * 32 + 8 * rq + 4 * (lane >> 5);
-      float bv[4] = {0.f, 0.f, 0.f, 0.f};
-      if (bias) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          if (nb + e < N) bv[e] = cvt16<IS_BF16>(bias[nb + e]);
-      }
-#pragma unroll
-      for (int mf = 0; mf < 4; ++mf) {
-        const int64_t m = m0 + wm * 128 + mf * 32 + (lane & 31);
-        if (m >= M) continue;
-        const float v0 = acc[nf][mf][4 * rq + 0] + bv[0], v1 = acc[nf][mf][4 * rq + 1] + bv[1];
-        const float v2 = acc[nf][mf][4 * rq + 2] + bv[2], v3 = acc[nf][mf][4 * rq + 3] + bv[3];
-        uint16_t* dst = y + m * N + nb;
-        if ((y_vec_ok & 1) && nb + 4 <= N) {
-          *reinterpret_cast<uint2*>(dst) = make_uint2(cvt_pair<IS_BF16>(v0, v1), cvt_pair<IS_BF16>(v2, v3));
-        } else {
-          const float vv[4] = {v0, v1, v2, v3};
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            if (nb + e < N) dst[e] = IS_BF16 ? f32_to_bf16_bits(vv[e]) : f32_to_f16_bits(vv[e]);
-        }
-      }
-    }
-  }
+  tile256_walk(
+      m0, n0, wm, wn, lane, [&](int64_t nb) { return load_bias_quad<IS_BF16>(bias, nb, N); },
+      [&](int nf, int mf, int rq, int64_t m, int64_t nb, const BiasQuad& bq) {
+        if (m >= M) return;
+        const float v[4] = {acc[nf][mf][4 * rq + 0] + bq.b[0], acc[nf][mf][4 * rq + 1] + bq.b[1], acc[nf][mf][4 * rq + 2] + bq.b[2],
+                            acc[nf][mf][4 * rq + 3] + bq.b[3]};
+        store_quad16<IS_BF16>(y, m, nb, N, y_vec_ok & 1, v);
+      });
 }
