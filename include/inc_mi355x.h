@@ -646,15 +646,32 @@ int inc_w8a8_gemm_rowscale(const int8_t* xq, const int8_t* wq, const float* row_
  * inc_mx_gemm: the product above for (xfmt, wfmt) = (fp8, fp8), (fp8, fp4), (fp4, fp4); any other pair is INC_ERR_UNSUPPORTED.
  *   xq [M, Kp or Kp/2], xs [M, Kp/32], wq [N, Kp or Kp/2], ws [N, Kp/32] as stored by inc_mx_quant, xq / wq 16-byte and xs / ws
  *   4-byte aligned; bias [N] in ydtype or NULL; y [M,N] bf16 / fp16, any M >= 1 and N >= 1 (8-byte stores when N % 4 == 0 and y is
- *   8-byte aligned, 2-byte stores otherwise).  256 x 256 x 128 tiles, one workgroup per tile: no decode GEMV and no split-K tail.
- * Both validate their arguments before any HIP call.                                                                            */
+ *   8-byte aligned, 2-byte stores otherwise).  256 x 256 x 128 tiles, one workgroup per tile, no split-K tail; the decode route for
+ *   M <= 16 is inc_mx_gemv.
+ * inc_mx_gemv (csrc/gemm_mx_gemv.hip): the product of inc_mx_gemm for 1 <= M <= INC_MX_GEMV_MAX_M on v_mfma_scale_f32_16x16x128_f8f6f4:
+ *   the same operands, storage, alignment rules, format pairs and arithmetic (fp32 accumulation, fp32 bias add, one rounding), any
+ *   N >= 1, the same store rule for y.  One workgroup per strip of 16 weight rows, K split over its waves, the partials added in a
+ *   fixed order through LDS: no workspace, and repeated calls are bit-identical.  Reads nothing past row M - 1 of x or row N - 1 of W.
+ *   INC_ERR_UNSUPPORTED (nothing launched) for M > 16, an unbuilt pair, Kp % 128 != 0 or a ydtype other than bf16 / fp16;
+ *   INC_ERR_BAD_ARG for a NULL operand or M, N < 1.
+ * inc_mx_gemv_multi: 2 <= n <= 8 weight matrices that multiply the SAME x (q / k / v; gate / up) in ONE launch over the strips of all
+ *   members.  wq, ws, bias, y and N are HOST arrays of n entries (the convention of inc_woq_gemv_anyw_multi); bias may be NULL or hold
+ *   NULL for a member without one; x, the format pair, ydtype and Kp are common.  y[i] is bit-identical to inc_mx_gemv on member i
+ *   alone (the same strip body).  Rejections as for inc_mx_gemv, and INC_ERR_UNSUPPORTED for n outside 2 .. 8.
+ * All four validate their arguments before any HIP call.                                                                        */
 #define INC_MX_FP8_E4M3 0
 #define INC_MX_FP4_E2M1 4
 #define INC_MX_KTILE 128
+#define INC_MX_GEMV_MAX_M 16
 int inc_mx_quant(const void* x, int xdtype, int64_t M, int64_t K, int64_t Kp, int fmt, uint8_t* codes, uint8_t* scales,
                  inc_stream_t stream);
 int inc_mx_gemm(const uint8_t* xq, const uint8_t* xs, int xfmt, const uint8_t* wq, const uint8_t* ws, int wfmt, const void* bias,
                 void* y, int ydtype, int64_t M, int64_t N, int64_t Kp, inc_stream_t stream);
+int inc_mx_gemv(const uint8_t* xq, const uint8_t* xs, int xfmt, const uint8_t* wq, const uint8_t* ws, int wfmt, const void* bias,
+                void* y, int ydtype, int64_t M, int64_t N, int64_t Kp, inc_stream_t stream);
+int inc_mx_gemv_multi(int n, const uint8_t* xq, const uint8_t* xs, int xfmt, const uint8_t* const* wq, const uint8_t* const* ws,
+                      int wfmt, const void* const* bias, void* const* y, int ydtype, int64_t M, const int64_t* N, int64_t Kp,
+                      inc_stream_t stream);
 
 /* ---- measured ceilings (bench.py `ceilings`) -- measurement helpers, not on the hot path ------------- *
  * inc_probe_hbm_triad: a <- b + s*c over n fp32 (n % 4 == 0): 12 n bytes of HBM traffic per call.

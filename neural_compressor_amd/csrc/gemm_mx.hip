@@ -18,7 +18,7 @@
 // (before that step's DMA is issued; they are first touched behind the barrier that ends the step, so no wait for them is placed in
 // front of an MFMA), shifts them right by 8 * (l >> 5) once -- the two lane halves supply different blocks -- and the two 64-wide
 // steps of a tile take bytes 0 and 2 of the result through opsel.
-// One workgroup per tile: no decode GEMV (M <= 16 runs this kernel with clamped source rows) and no split-K tail.
+// One workgroup per tile and no split-K tail; M <= 16 has a kernel of its own (gemm_mx_gemv.hip), this one serves it with clamped rows.
 // Algorithmic work per launch: 2*M*N*Kp flop; bytes (M + N) * Kp * (1 or 1/2) + (M + N) * Kp / 32 + 2*M*N.
 #include "tile256_frame.hpp"
 

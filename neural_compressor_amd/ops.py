@@ -1672,14 +1672,20 @@ def mx_quant(x2d, fmt, Kp=None):
     return codes, scales
 
 
-def mx_gemm(xq, xs, xfmt, wq, ws, wfmt, bias, out_dtype):
-    """y[m,n] = sum_blocks 2^(xs + ws - 254) * sum_{k in block} x_k * w_k + bias[n] on v_mfma_scale_f32_32x32x64_f8f6f4 (K16)."""
-    dev = _dev(xq, xs, wq, ws, bias)
-    M, N = xq.shape[0], wq.shape[0]
+def _mx_check_operands(xq, xs, xfmt, wq, ws, wfmt):
+    """The shapes the MX products take -> Kp."""
     Kp = xs.shape[1] * 32
     assert ws.shape[1] * 32 == Kp and xq.dtype == torch.uint8 and wq.dtype == torch.uint8
     assert xq.shape[1] == (Kp if xfmt == MX_FP8_E4M3 else Kp // 2) and wq.shape[1] == (Kp if wfmt == MX_FP8_E4M3 else Kp // 2)
     assert xq.is_contiguous() and xs.is_contiguous() and wq.is_contiguous() and ws.is_contiguous()
+    return Kp
+
+
+def mx_gemm(xq, xs, xfmt, wq, ws, wfmt, bias, out_dtype):
+    """y[m,n] = sum_blocks 2^(xs + ws - 254) * sum_{k in block} x_k * w_k + bias[n] on v_mfma_scale_f32_32x32x64_f8f6f4 (K16)."""
+    dev = _dev(xq, xs, wq, ws, bias)
+    M, N = xq.shape[0], wq.shape[0]
+    Kp = _mx_check_operands(xq, xs, xfmt, wq, ws, wfmt)
     if bias is not None and bias.dtype != out_dtype:
         bias = bias.to(out_dtype)
     y = torch.empty((M, N), dtype=out_dtype, device=dev)
@@ -1687,3 +1693,43 @@ def mx_gemm(xq, xs, xfmt, wq, ws, wfmt, bias, out_dtype):
         check(lib.inc_mx_gemm(_ptr(xq), _ptr(xs), int(xfmt), _ptr(wq), _ptr(ws), int(wfmt), _ptr(bias), _ptr(y), dtype_code(out_dtype),
                               M, N, Kp, _stream()), "inc_mx_gemm")
     return y
+
+
+MX_GEMV_MAX_M = 16      # INC_MX_GEMV_MAX_M: rows of x the decode route takes
+MX_GEMV_MAX_MEMBERS = 8
+
+
+def mx_gemv(xq, xs, xfmt, wq, ws, wfmt, bias, out_dtype):
+    """mx_gemm's product for up to MX_GEMV_MAX_M rows of x on v_mfma_scale_f32_16x16x128_f8f6f4 (K16b, inc_mx_gemv): one workgroup per
+    16 weight rows, K split over its waves, no workspace."""
+    dev = _dev(xq, xs, wq, ws, bias)
+    M, N = xq.shape[0], wq.shape[0]
+    Kp = _mx_check_operands(xq, xs, xfmt, wq, ws, wfmt)
+    if bias is not None and bias.dtype != out_dtype:
+        bias = bias.to(out_dtype)
+    y = torch.empty((M, N), dtype=out_dtype, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.inc_mx_gemv(_ptr(xq), _ptr(xs), int(xfmt), _ptr(wq), _ptr(ws), int(wfmt), _ptr(bias), _ptr(y), dtype_code(out_dtype),
+                              M, N, Kp, _stream()), "inc_mx_gemv")
+    return y
+
+
+def mx_gemv_multi(xq, xs, xfmt, wqs, wss, wfmt, biases, out_dtype):
+    """[mx_gemv(xq, xs, xfmt, wq_i, ws_i, wfmt, bias_i, out_dtype) for i] for 2 .. MX_GEMV_MAX_MEMBERS weight matrices in ONE launch
+    (inc_mx_gemv_multi); every output is the single call's bit for bit.  `biases`: a list with None for a member without one."""
+    import ctypes
+
+    n = len(wqs)
+    biases = [None if b is None else (b if b.dtype == out_dtype else b.to(out_dtype)) for b in biases]
+    dev = _dev(xq, xs, *wqs, *wss, *biases)
+    M = xq.shape[0]
+    Kp = xs.shape[1] * 32
+    for wq, ws in zip(wqs, wss):
+        assert _mx_check_operands(xq, xs, xfmt, wq, ws, wfmt) == Kp
+    ys = [torch.empty((M, wq.shape[0]), dtype=out_dtype, device=dev) for wq in wqs]
+    arr = lambda ts: (ctypes.c_void_p * n)(*[_ptr(t) for t in ts])  # noqa: E731
+    Ns = (ctypes.c_int64 * n)(*[wq.shape[0] for wq in wqs])
+    with torch.cuda.device(dev):
+        check(lib.inc_mx_gemv_multi(n, _ptr(xq), _ptr(xs), int(xfmt), arr(wqs), arr(wss), int(wfmt), arr(biases), arr(ys),
+                                    dtype_code(out_dtype), M, Ns, Kp, _stream()), "inc_mx_gemv_multi")
+    return ys

@@ -1,4 +1,4 @@
-from .mx_quant import MXLinear, MXQuantizer
+from .mx_quant import MXLinear, MXQuantizer, mx_linear_group
 from .save_load import load, save
 
-__all__ = ["MXLinear", "MXQuantizer", "save", "load"]
+__all__ = ["MXLinear", "MXQuantizer", "mx_linear_group", "save", "load"]

@@ -4,9 +4,10 @@
 The reference emulates MX: it fake-quantises weights and activations in float and calls F.linear.  Here the same configuration
 executes: the weight is quantised once to e4m3 / e2m1 codes with one E8M0 scale per 32 elements along in_features
 (`inc_mx_quant`), the activation rows are quantised the same way at run time, and `inc_mx_gemm` multiplies the codes on
-v_mfma_scale_f32_32x32x64_f8f6f4, which applies both block scales inside the matrix pipe.  The specification in bits is the comment
-of the two entry points in include/inc_mi355x.h.  The algorithm is data-free: `prepare` returns the model
-unchanged and `convert` swaps every selected nn.Linear.
+v_mfma_scale_f32_32x32x64_f8f6f4, which applies both block scales inside the matrix pipe; a decode-sized batch (up to 16 rows) takes
+`inc_mx_gemv` on the 16x16x128 form of the instruction, and `mx_linear_group` sends modules that share an activation out in one
+launch.  The specification in bits is the comment of the entry points in include/inc_mi355x.h.  The algorithm
+is data-free: `prepare` returns the model unchanged and `convert` swaps every selected nn.Linear.
 """
 
 import torch
@@ -31,7 +32,13 @@ def _code_values(fmt):
 class MXLinear(torch.nn.Module):
     """nn.Linear with MX weights and MX activations.  Buffers: qweight uint8 [N, Kp] (fp8) or [N, Kp/2] (fp4, element 2i in the low
     nibble), w_scale uint8 [N, Kp/32] (E8M0 bytes), bias.  Kp = in_features rounded up to 128; the padding columns are zero codes.
-    forward = inc_mx_quant(x) -> inc_mx_gemm; nothing is read back to the host."""
+    forward = inc_mx_quant(x) -> inc_mx_gemv up to DECODE_MAX_M rows (while DECODE_GEMV is on), inc_mx_gemm above; nothing is read
+    back to the host."""
+
+    # True = up to DECODE_MAX_M rows go through the decode GEMV (inc_mx_gemv: one workgroup per 16 weight rows, K split over its waves);
+    # False = every batch takes the 256 x 256 tile kernel.  Times of both: profiles/mx/mx_gemv_time.log, DESIGN section 8b.
+    DECODE_GEMV = True
+    DECODE_MAX_M = ops.MX_GEMV_MAX_M
 
     def __init__(self, in_features, out_features, bias=False, w_dtype="fp8_e4m3", act_dtype="fp8_e4m3", device="cuda",
                  float_type=torch.float16):
@@ -73,10 +80,14 @@ class MXLinear(torch.nn.Module):
         if x2d.shape[0] == 0:
             return torch.empty((*lead, self.out_features), dtype=torch.float32 if x.dtype == torch.float32 else out_dtype, device=x.device)
         xq, xs = ops.mx_quant(x2d, self.act_fmt, self.kp)
-        y = ops.mx_gemm(xq, xs, self.act_fmt, self.qweight, self.w_scale, self.w_fmt, self.bias, out_dtype)
+        product = ops.mx_gemv if self._decodes(x2d.shape[0]) else ops.mx_gemm
+        y = product(xq, xs, self.act_fmt, self.qweight, self.w_scale, self.w_fmt, self.bias, out_dtype)
         if x.dtype == torch.float32:  # an fp32 model keeps seeing fp32 activations (the kernel's epilogue emits 16-bit)
             y = y.float()
         return y.reshape(*lead, self.out_features)
+
+    def _decodes(self, rows):
+        return self.DECODE_GEMV and rows <= min(self.DECODE_MAX_M, ops.MX_GEMV_MAX_M)
 
     def recover(self, dtype=None):
         """Dequantised weight [N, K] (a table lookup times 2^(byte - 127); every value is exact in fp32), in `dtype` or float_type."""
@@ -91,6 +102,39 @@ class MXLinear(torch.nn.Module):
     def extra_repr(self):
         return (f"in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}, "
                 f"w_dtype={self.w_dtype}, act_dtype={self.act_dtype}, blocksize=32")
+
+
+def mx_linear_group(x, modules):
+    """[m(x) for m in modules], bit for bit, for MXLinear modules that multiply the SAME activation -- q / k / v of an attention block,
+    gate / up of an MLP: x is quantised ONCE (each member's own forward quantises it again), and up to MXLinear.DECODE_MAX_M rows the
+    products are ONE launch over the strips of all members (inc_mx_gemv_multi: the strip body of inc_mx_gemv); above that, inc_mx_gemm
+    per member on the shared codes.  Every member keeps its buffers and state-dict keys.  Anything else -- a member that is not an
+    MXLinear, mixed formats or widths, fewer than 2 or more than 8 members, x elsewhere or empty, a decode-sized x with DECODE_GEMV off
+    -- is the plain list of single forwards."""
+    mods = list(modules)
+    m0 = mods[0] if mods else None
+    ok = (2 <= len(mods) <= ops.MX_GEMV_MAX_MEMBERS and all(isinstance(m, MXLinear) for m in mods) and x.is_cuda and x.numel() > 0
+          and x.shape[-1] == m0.in_features and x.device == m0.qweight.device
+          and all((m.in_features, m.w_dtype, m.act_dtype, m.qweight.device) == (m0.in_features, m0.w_dtype, m0.act_dtype, m0.qweight.device)
+                  for m in mods))
+    if ok:
+        half = x.dtype in (torch.float16, torch.bfloat16)
+        out_dtype = x.dtype if half else m0.float_type
+        x2d = x.reshape(-1, m0.in_features)
+        rows = x2d.shape[0]
+        decode = [m._decodes(rows) for m in mods]
+        ok = (half or all(m.float_type == out_dtype for m in mods)) and (all(decode) or rows > ops.MX_GEMV_MAX_M)
+    if not ok:
+        return [m(x) for m in mods]
+    xq, xs = ops.mx_quant(x2d, m0.act_fmt, m0.kp)
+    if all(decode):
+        ys = ops.mx_gemv_multi(xq, xs, m0.act_fmt, [m.qweight for m in mods], [m.w_scale for m in mods], m0.w_fmt,
+                               [m.bias for m in mods], out_dtype)
+    else:
+        ys = [ops.mx_gemm(xq, xs, m.act_fmt, m.qweight, m.w_scale, m.w_fmt, m.bias, out_dtype) for m in mods]
+    if x.dtype == torch.float32:
+        ys = [y.float() for y in ys]
+    return [y.reshape(*x.shape[:-1], m.out_features) for y, m in zip(ys, mods)]
 
 
 class MXQuantizer(Quantizer):
