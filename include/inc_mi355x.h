@@ -658,7 +658,24 @@ int inc_w8a8_gemm_rowscale(const int8_t* xq, const int8_t* wq, const float* row_
  *   members.  wq, ws, bias, y and N are HOST arrays of n entries (the convention of inc_woq_gemv_anyw_multi); bias may be NULL or hold
  *   NULL for a member without one; x, the format pair, ydtype and Kp are common.  y[i] is bit-identical to inc_mx_gemv on member i
  *   alone (the same strip body).  Rejections as for inc_mx_gemv, and INC_ERR_UNSUPPORTED for n outside 2 .. 8.
- * All four validate their arguments before any HIP call.                                                                        */
+ * inc_mx_moe_gemm (csrc/gemm_mx_moe.hip, K16e): the product of inc_mx_gemm per expert over the rows inc_moe_route sorted -- the two
+ *   F.linear of transformers' MixtralExperts.forward (also the Qwen2-MoE / Qwen3-MoE / OLMoE experts) for MX experts.  One forward is
+ *   inc_moe_route -> inc_mx_quant(x) -> inc_mx_moe_gemm(0) -> inc_mx_quant(h) -> inc_mx_moe_gemm(1) -> inc_moe_combine on `stream`.
+ *   `route` is K4e's buffer, unchanged ([0] tile count, offsets [E+1], order [S], pos [S], tiles of 64 rows; S = T * top_k).
+ *   wq [E, N, Kp] (fp8) or [E, N, Kp/2] (fp4), ws [E, N, Kp/32]: slice e is exactly what inc_mx_quant writes for expert e's [N, K]
+ *   matrix.  acc[p, n] = the product above without bias, for position p of the sorted order and the expert e whose range holds p,
+ *   summed in fp32 in a fixed order (repeated calls are bit-identical):
+ *     mode 2 (plain, gathered):   aq [T, Kp or Kp/2], as [T, Kp/32]; row p is token order[p] / top_k; out [S, N] fp32 = acc
+ *     mode 0 (gate_up, gathered, N = 2I): gate rows 0 .. I-1 and up rows I .. 2I-1 of the expert; out [S, I] of odtype (INC_BF16 /
+ *            INC_F16), out[p, j] = rd(g / (1.f + expf(-g)) * u), g = acc[p, j], u = acc[p, I + j], formed in fp32, rounded once
+ *     mode 1 (down, in place):    aq [S, Kp or Kp/2], as [S, Kp/32] in sorted order; out [S, N] fp32 = w[order[p]] * acc[p, n] (one
+ *            fp32 multiply), routing_weights w [T, top_k] of wdtype INC_F32 / INC_BF16 / INC_F16
+ *   odtype is INC_F32 in modes 1 and 2.  Positions >= offsets[E] are never written and source rows that no valid position names are
+ *   never read.  aq / wq 16-byte aligned; out is stored 4 columns at a time when its width is a multiple of 4 and it is aligned to
+ *   that store, element by element otherwise.  No workspace and no counters.
+ *   INC_ERR_UNSUPPORTED (nothing launched) for a pair other than inc_mx_gemm's three, Kp % 128 != 0, E > 512, S > 2^22, mode 0 with odd
+ *   N, a bad odtype or (mode 1) wdtype; INC_ERR_BAD_ARG for a NULL operand (routing_weights: mode 1 only) or a size < 1.
+ * All five validate their arguments before any HIP call.                                                                        */
 #define INC_MX_FP8_E4M3 0
 #define INC_MX_FP4_E2M1 4
 #define INC_MX_KTILE 128
@@ -672,6 +689,9 @@ int inc_mx_gemv(const uint8_t* xq, const uint8_t* xs, int xfmt, const uint8_t* w
 int inc_mx_gemv_multi(int n, const uint8_t* xq, const uint8_t* xs, int xfmt, const uint8_t* const* wq, const uint8_t* const* ws,
                       int wfmt, const void* const* bias, void* const* y, int ydtype, int64_t M, const int64_t* N, int64_t Kp,
                       inc_stream_t stream);
+int inc_mx_moe_gemm(int mode, const uint8_t* aq, const uint8_t* as, int afmt, const int32_t* route, const uint8_t* wq,
+                    const uint8_t* ws, int wfmt, const void* routing_weights, int wdtype, void* out, int odtype, int64_t T, int top_k,
+                    int64_t E, int64_t N, int64_t Kp, inc_stream_t stream);
 
 /* ---- measured ceilings (bench.py `ceilings`) -- measurement helpers, not on the hot path ------------- *
  * inc_probe_hbm_triad: a <- b + s*c over n fp32 (n % 4 == 0): 12 n bytes of HBM traffic per call.

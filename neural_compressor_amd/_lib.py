@@ -99,6 +99,10 @@ SIGNATURES = {
     "inc_mx_gemm": (c_int, [_P, _P, c_int, _P, _P, c_int, _P, _P, c_int, c_int64, c_int64, c_int64, _P]),
     "inc_mx_gemv": (c_int, [_P, _P, c_int, _P, _P, c_int, _P, _P, c_int, c_int64, c_int64, c_int64, _P]),
     "inc_mx_gemv_multi": (c_int, [c_int, _P, _P, c_int, _P, _P, c_int, _P, _P, c_int, c_int64, _P, c_int64, _P]),
+    "inc_mx_moe_gemm": (
+        c_int,
+        [c_int, _P, _P, c_int, _P, _P, _P, c_int, _P, c_int, _P, c_int, c_int64, c_int, c_int64, c_int64, c_int64, _P],
+    ),
     "inc_awq_repack": (c_int, [_P, _P, c_int64, c_int64, c_int64, c_int, _P, _P, _P]),
     "inc_gptq_find_params_mse": (
         c_int,

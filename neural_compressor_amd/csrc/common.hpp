@@ -103,6 +103,10 @@ __device__ __forceinline__ float round_to(float v) {
   else return bf16_bits_to_f32(f32_to_bf16_bits(v));
 }
 
+// silu(g) * u of a gated MLP, formed in fp32 (the caller rounds once): the epilogue of every fused gate / up product -- the grouped MoE
+// GEMMs' mode 0 (gemm_moe.hip, gemm_mx_moe.hip) and the gated launch of the streaming GEMV (gemm_stream.hip)
+__device__ __forceinline__ float silu_mul_f32(float g, float u) { return g / (1.f + expf(-g)) * u; }
+
 // ---- wave64 reductions --------------------------------------------------------------------
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll

@@ -24,32 +24,15 @@
 // workgroups: fp32 partial slabs written through (sc1), one relaxed agent-scope ticket per (tile, strip), the last arriver sums the
 // slabs in slice order (the hand-off of gemm_lut.hip), so repeated calls are bit-identical and the counters re-arm themselves.
 #include "gemm_common.hpp"
+#include "moe_common.hpp"  // the route buffer's layout, the routing-weight load
 
 namespace {
 
-constexpr int MOE_BM = 64;           // rows (slots) per tile
 constexpr int MOE_BN = 256;          // output columns per workgroup (4 waves x 64)
 constexpr int MOE_ROUTE_WAVES = 16;  // route kernel: 1024 threads
-constexpr int MOE_MAX_E = 512;
-constexpr int64_t MOE_MAX_SLOTS = 1 << 22;
 // split-K arrival counters: a fixed region at the start of the workspace (a split runs only while (tile slot, strip) pairs are fewer
 // than 512), so one workspace serves every call shape and both GEMMs -- the partials of one call never land on another's counters
 constexpr int64_t MOE_COUNTER_BYTES = 4 << 10;
-
-// int32 offsets inside the route buffer
-struct RouteLayout {
-  int64_t offsets, order, pos, tiles, total;
-};
-__host__ __device__ inline int64_t moe_tiles_max(int64_t S, int64_t E) { return (S + MOE_BM - 1) / MOE_BM + (E < S ? E : S); }
-__host__ __device__ inline RouteLayout moe_route_layout(int64_t S, int64_t E) {
-  RouteLayout L;
-  L.offsets = 1;  // [0] = number of tiles
-  L.order = L.offsets + E + 1;
-  L.pos = L.order + S;
-  L.tiles = L.pos + S;
-  L.total = L.tiles + 2 * moe_tiles_max(S, E);
-  return L;
-}
 
 __device__ __forceinline__ int moe_bucket(const void* idx, int idx8, int64_t i, int E) {
   const int64_t e = idx8 ? static_cast<const int64_t*>(idx)[i] : (int64_t) static_cast<const int32_t*>(idx)[i];
@@ -127,12 +110,6 @@ __global__ __launch_bounds__(1024) void moe_route_kernel(const void* __restrict_
       pending &= ~m;
     }
   }
-}
-
-__device__ __forceinline__ float moe_load_weight(const void* p, int64_t i, int dt) {
-  if (dt == INC_F32) return static_cast<const float*>(p)[i];
-  const uint16_t b = static_cast<const uint16_t*>(p)[i];
-  return dt == INC_F16 ? f16_bits_to_f32(b) : bf16_bits_to_f32(b);
 }
 
 // MODE 0 gate_up (N = 2I, output h [S, I] of x's dtype), 1 down (output fp32 [S, N] x routing weight), 2 plain (fp32 [S, N]).
@@ -291,7 +268,7 @@ __global__ __launch_bounds__(256) void woq_moe_gemm_kernel(
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
           const float g = acc[0][b][c][r], u = acc[1][b][c][r];
-          v[c] = g / (1.f + expf(-g)) * u;
+          v[c] = silu_mul_f32(g, u);
         }
         uint2 o;
         o.x = pack2<IS_BF16>(v[0], v[1]);

@@ -21,7 +21,7 @@
 // Algorithmic bytes per launch: N * Kp * (1 or 1/2) + N * Kp / 32 + M * Kp * (1 or 1/2) + M * Kp / 32 + 2 * M * N.
 #include <type_traits>
 
-#include "common.hpp"
+#include "mx_strip.hpp"  // the operand fragments of the 16x16x128 form
 
 #ifndef INC_MX_GEMV_WAVES
 #define INC_MX_GEMV_WAVES 8  // W: 4, 8 or 16 (scripts/mx_gemv_time.py; the rejected values are in profiles/NOTES.md)
@@ -29,13 +29,8 @@
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) int i32x8;
-typedef __attribute__((ext_vector_type(4))) int i32x4;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
 constexpr int GW = INC_MX_GEMV_WAVES;  // waves of a workgroup = ways of the in-workgroup K split
 constexpr int STRIP = 16;              // weight rows of a workgroup: the instruction's M
-constexpr int XK = INC_MX_KTILE;
 constexpr int UNROLL = 4;              // K-tiles of a wave whose loads are in flight together
 constexpr int MAX_MEMBERS = 8;
 static_assert(GW == 4 || GW == 8 || GW == 16, "W is 4, 8 or 16");
@@ -52,21 +47,6 @@ struct MxGemvMembers {
   int n;
 };
 
-__host__ __device__ constexpr int gemv_tile_bytes(int fmt) { return fmt == INC_MX_FP8_E4M3 ? XK : XK / 2; }  // of one row and K-tile
-
-// what a lane supplies of its row for the K-tile at `p` (= row + tile + 16 g), as the instruction wants it
-template <int F, bool NT>
-__device__ __forceinline__ i32x8 gemv_frag(const uint8_t* p) {
-  const i32x4* q = reinterpret_cast<const i32x4*>(p);
-  const i32x4 lo = NT ? __builtin_nontemporal_load(q) : q[0];
-  i32x4 hi = {0, 0, 0, 0};
-  if constexpr (F == INC_MX_FP8_E4M3) hi = NT ? __builtin_nontemporal_load(q + 4) : q[4];
-  i32x8 f;
-  f[0] = lo[0]; f[1] = lo[1]; f[2] = lo[2]; f[3] = lo[3];
-  f[4] = hi[0]; f[5] = hi[1]; f[6] = hi[2]; f[7] = hi[3];
-  return f;
-}
-
 template <bool IS_BF16, int XF, int WF>
 __global__ __launch_bounds__(GW * 64) void mx_gemv_kernel(const uint8_t* __restrict__ xq, const uint8_t* __restrict__ xs,
                                                           const MxGemvMembers mem, int M, int64_t Kp) {
@@ -81,7 +61,7 @@ __global__ __launch_bounds__(GW * 64) void mx_gemv_kernel(const uint8_t* __restr
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int r = lane & 15, g = lane >> 4;
-  constexpr int TX = gemv_tile_bytes(XF), TW = gemv_tile_bytes(WF);
+  constexpr int TX = mx_tile_bytes(XF), TW = mx_tile_bytes(WF);
   const int64_t sld = Kp / 32;  // scale bytes per row
   int64_t wrow = n0 + r;
   if (wrow > N - 1) wrow = N - 1;
@@ -102,9 +82,9 @@ __global__ __launch_bounds__(GW * 64) void mx_gemv_kernel(const uint8_t* __restr
 #pragma unroll
     for (int u = 0; u < C; ++u) {
       const int64_t t = kt + u * GW;
-      wf[u] = gemv_frag<WF, true>(wp + t * TW);
+      wf[u] = mx_frag<WF, true>(wp + t * TW);
       sw[u] = wsp[t * 4];
-      xf[u] = gemv_frag<XF, false>(xp + t * TX);
+      xf[u] = mx_frag<XF, false>(xp + t * TX);
       sx[u] = xsp[t * 4];
     }
 #pragma unroll

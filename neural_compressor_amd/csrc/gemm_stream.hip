@@ -177,7 +177,7 @@ __device__ __forceinline__ void woq_gemv_w4_body(
     for (int i = 0; i < NOUT; ++i)
       if (out.ok[i]) {
         const float g = gs[i], u = us[i];
-        const float v = g / (1.f + expf(-g)) * u;
+        const float v = silu_mul_f32(g, u);
         y[out.off[i]] = IS_BF16 ? f32_to_bf16_bits(v) : f32_to_f16_bits(v);
       }
   } else {

@@ -1733,3 +1733,30 @@ def mx_gemv_multi(xq, xs, xfmt, wqs, wss, wfmt, biases, out_dtype):
         check(lib.inc_mx_gemv_multi(n, _ptr(xq), _ptr(xs), int(xfmt), arr(wqs), arr(wss), int(wfmt), arr(biases), arr(ys),
                                     dtype_code(out_dtype), M, Ns, Kp, _stream()), "inc_mx_gemv_multi")
     return ys
+
+
+def mx_moe_gemm(mode, aq, as_, afmt, route, wq, ws, wfmt, T, top_k, routing_weights=None, out=None, out_dtype=None):
+    """inc_mx_moe_gemm (K16e): mx_gemm's product per expert over the rows of the route's sorted order.  wq [E, N, Kp or Kp/2],
+    ws [E, N, Kp/32] (slice e = mx_quant of expert e's matrix).  mode 0: gate_up + SiLU product -> [T*k, N/2] of `out_dtype` (bf16 /
+    fp16) from aq [T, ...]; mode 1: down x routing weight -> fp32 [T*k, N] from aq [T*k, ...] in sorted order; mode 2: plain -> fp32
+    [T*k, N] from aq [T, ...].  Rows past the route's valid positions are not written."""
+    dev = _dev(aq, as_, route, wq, ws, routing_weights)
+    E, N = wq.shape[0], wq.shape[1]
+    Kp, S = ws.shape[2] * 32, T * top_k
+    assert aq.dtype == torch.uint8 and as_.dtype == torch.uint8 and wq.dtype == torch.uint8 and ws.dtype == torch.uint8
+    assert aq.shape[0] == (S if mode == 1 else T) and as_.shape == (aq.shape[0], Kp // 32) and ws.shape[:2] == (E, N)
+    assert aq.shape[1] == (Kp if afmt == MX_FP8_E4M3 else Kp // 2) and wq.shape[2] == (Kp if wfmt == MX_FP8_E4M3 else Kp // 2)
+    assert aq.is_contiguous() and as_.is_contiguous() and wq.is_contiguous() and ws.is_contiguous()
+    if mode == 0:
+        odt = out.dtype if out is not None else out_dtype
+        if odt not in (torch.bfloat16, torch.float16):
+            raise TypeError("mx_moe_gemm mode 0 writes bf16 or fp16: pass out_dtype")
+    else:
+        odt = torch.float32
+    if out is None:
+        out = torch.empty((S, N // 2 if mode == 0 else N), dtype=odt, device=dev)
+    wdt = dtype_code(routing_weights.dtype) if routing_weights is not None else INC_F32
+    with torch.cuda.device(dev):
+        check(lib.inc_mx_moe_gemm(mode, _ptr(aq), _ptr(as_), int(afmt), _ptr(route), _ptr(wq), _ptr(ws), int(wfmt), _ptr(routing_weights),
+                                  wdt, _ptr(out), dtype_code(odt), T, top_k, E, N, Kp, _stream()), "inc_mx_moe_gemm")
+    return out

@@ -1,0 +1,174 @@
+"""MX fused MoE experts for MI355X.
+
+transformers (5.x) holds the experts of a Mixtral / Qwen2-MoE / Qwen3-MoE / OLMoE layer in one `*Experts` module with two 3-D
+parameters, `gate_up_proj [E, 2I, H]` (gate rows 0..I-1, up rows I..2I-1) and `down_proj [E, H, I]`, and a
+`forward(hidden_states, top_k_index, top_k_weights)` that loops over the experts that were hit.  `MXExperts` replaces such a module
+under `MXQuantConfig(quant_experts=True)`: every expert's two matrices are MX-quantised as `MXLinear` quantises a weight (slice e of
+every buffer is byte for byte what `inc_mx_quant` writes for expert e's matrix), and forward is six HIP launches with no host
+synchronisation: route -> quantise x -> gate_up product with the SiLU product (`inc_mx_moe_gemm` mode 0) -> quantise h -> down product
+with the routing weight (mode 1) -> combine (include/inc_mi355x.h, K16e).
+"""
+
+import torch
+
+from .... import ops
+from .mx_quant import FORMATS, PAIRS, _code_values
+
+MAX_EXPERTS = 512  # of inc_moe_route and inc_mx_moe_gemm
+
+
+def _is_silu(act_fn):
+    return isinstance(act_fn, torch.nn.SiLU) or type(act_fn).__name__ in ("SiLU", "SiLUActivation")
+
+
+def _cols(fmt, kp):
+    return kp if fmt == ops.MX_FP8_E4M3 else kp // 2
+
+
+class MXExperts(torch.nn.Module):
+    """Fused experts with MX weights and MX activations.  Buffers (Kp = K rounded up to 128, uint8): gate_up_qweight [E, 2I, Kp(H)]
+    (fp8) or [E, 2I, Kp(H)/2] (fp4), gate_up_w_scale [E, 2I, Kp(H)/32], down_qweight [E, H, Kp(I) or Kp(I)/2], down_w_scale
+    [E, H, Kp(I)/32]."""
+
+    # True: the fused route (six launches, no host wait).  False: the dense route -- per expert that was hit (host waits), gather its
+    # rows and run MXLinear's own kernels (inc_mx_quant, inc_mx_gemv / inc_mx_gemm) on that expert's slices: the referee
+    MOE_FUSED = True
+    # the fused route serves up to this many routed rows per expert on average (T * top_k <= MOE_MAX_ROWS * E); larger batches take the
+    # dense route.  Measured (scripts/mx_moe_time.py, profiles/mx/mx_moe_time.log; the rule is the script's last line): Mixtral
+    # (E 8, k 2) fused 1.15 - 1.36 x faster than dense at T = 1024 (256 rows per expert), dense 2.1 - 2.5 x faster at T = 4096 (1024);
+    # Qwen3-MoE (E 128, k 8) fused 10.8 - 13.8 x faster at T = 4096 (256 per expert)
+    MOE_MAX_ROWS = 256
+
+    def __init__(self, num_experts, hidden_dim, intermediate_dim, w_dtype="fp8_e4m3", act_dtype="fp8_e4m3", act_fn=None, device="cuda",
+                 float_type=torch.float16):
+        super().__init__()
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise RuntimeError(f"MXExperts needs a HIP device ('cuda[:N]'), got '{device}'. There is no CPU implementation.")
+        if (w_dtype, act_dtype) not in PAIRS:
+            raise NotImplementedError(f"MXQuant on MI355X: (w_dtype, act_dtype) must be one of {PAIRS}, got {(w_dtype, act_dtype)}")
+        E, H, I = num_experts, hidden_dim, intermediate_dim
+        self.num_experts, self.hidden_dim, self.intermediate_dim = E, H, I
+        self.w_dtype, self.act_dtype = w_dtype, act_dtype
+        self.w_fmt, self.act_fmt = FORMATS[w_dtype], FORMATS[act_dtype]
+        self.kp_h, self.kp_i = ops.mx_padded_k(H), ops.mx_padded_k(I)
+        self.float_type = float_type
+        self.act_fn = act_fn if act_fn is not None else torch.nn.SiLU()
+        for prefix, N, kp in (("gate_up", 2 * I, self.kp_h), ("down", H, self.kp_i)):
+            self.register_buffer(f"{prefix}_qweight", torch.zeros((E, N, _cols(self.w_fmt, kp)), dtype=torch.uint8, device=dev))
+            self.register_buffer(f"{prefix}_w_scale", torch.zeros((E, N, kp // 32), dtype=torch.uint8, device=dev))
+
+    @classmethod
+    @torch.no_grad()
+    def from_float(cls, module, w_dtype="fp8_e4m3", act_dtype="fp8_e4m3", device="cuda"):
+        """One inc_mx_quant on the [E * N, K] view of each parameter: MX blocks run along K inside a row, so this is each expert
+        quantised on its own."""
+        E, N2, H = module.gate_up_proj.shape
+        I = N2 // 2
+        pd = module.gate_up_proj.dtype
+        new = cls(E, H, I, w_dtype=w_dtype, act_dtype=act_dtype, act_fn=module.act_fn, device=device,
+                  float_type=pd if pd in (torch.float16, torch.bfloat16) else torch.float16)
+        dev = new.gate_up_qweight.device
+        for prefix, p, N, K, kp in (("gate_up", module.gate_up_proj, N2, H, new.kp_h), ("down", module.down_proj, H, I, new.kp_i)):
+            codes, scales = ops.mx_quant(p.detach().to(dev).reshape(E * N, K), new.w_fmt, kp)
+            new._buffers[f"{prefix}_qweight"].copy_(codes.view(E, N, -1))
+            new._buffers[f"{prefix}_w_scale"].copy_(scales.view(E, N, -1))
+        return new
+
+    def recover(self, dtype=None, expert=None):
+        """Dequantised weights (gate_up [E, 2I, H], down [E, H, I]) in `dtype` or float_type, or expert `expert`'s two matrices
+        [2I, H], [H, I]: a table lookup times 2^(byte - 127), every value exact in fp32 (MXLinear.recover per slice)."""
+        dtype = self.float_type if dtype is None else dtype
+        sel = slice(None) if expert is None else slice(int(expert), int(expert) + 1)
+        out = []
+        for prefix, K, kp in (("gate_up", self.hidden_dim, self.kp_h), ("down", self.intermediate_dim, self.kp_i)):
+            q, s = self._buffers[f"{prefix}_qweight"][sel], self._buffers[f"{prefix}_w_scale"][sel]
+            if self.w_fmt == ops.MX_FP4_E2M1:
+                q = torch.stack([q & 0xF, q >> 4], dim=3).reshape(q.shape[0], q.shape[1], -1)
+            vals = _code_values(self.w_fmt).to(q.device)[q.long()]
+            scale = torch.ldexp(torch.ones((), dtype=torch.float32, device=q.device), s.to(torch.int32) - 127)
+            w = (vals.view(q.shape[0], q.shape[1], kp // 32, 32) * scale[..., None]).view(q.shape[0], q.shape[1], kp)[..., :K].to(dtype)
+            out.append(w if expert is None else w[0])
+        return tuple(out)
+
+    def _fusable(self):
+        # inc_moe_combine stores four columns at a time
+        return _is_silu(self.act_fn) and self.num_experts <= MAX_EXPERTS and self.hidden_dim % 4 == 0
+
+    def forward(self, hidden_states, top_k_index, top_k_weights):
+        """transformers' experts signature: hidden_states [T, H], top_k_index / top_k_weights [T, k] -> [T, H] of hidden_states' dtype.
+        bf16 / fp16 compute in their own dtype, fp32 computes in float_type and is cast back (as MXLinear.forward).  Expert ids outside
+        0..E-1 (a "no expert" sentinel such as -1) contribute nothing, on both routes."""
+        x = hidden_states
+        x2d = x.reshape(-1, self.hidden_dim)
+        cdt = x.dtype if x.dtype in (torch.float16, torch.bfloat16) else self.float_type
+        T = x2d.shape[0]
+        if T == 0 or top_k_index.numel() == 0:
+            return torch.zeros_like(x)
+        idx = top_k_index.reshape(T, -1)
+        k = idx.shape[1]
+        if self.MOE_FUSED and T * k <= self.MOE_MAX_ROWS * self.num_experts and self._fusable():
+            if idx.dtype not in (torch.int64, torch.int32):
+                idx = idx.long()
+            w = top_k_weights.reshape(T, k)
+            if w.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+                w = w.float()
+            y = self._fused_forward(x2d, idx.contiguous(), w.contiguous(), cdt)
+        else:
+            y = self._dense_forward(x2d, idx, top_k_weights.reshape(T, k), cdt)
+        return y.to(x.dtype).reshape(x.shape)
+
+    def _fused_forward(self, x2d, idx, w, cdt):
+        """Six launches in stream order; every buffer is allocated per call and nothing is kept.  Rows of h past the route's valid
+        positions hold whatever torch.empty gave: the quantiser is total on any bit pattern and nothing reads its output there."""
+        T, k = idx.shape
+        E, af, wf = self.num_experts, self.act_fmt, self.w_fmt
+        route = ops.moe_route(idx, E)
+        xq, xs = ops.mx_quant(x2d, af, self.kp_h)
+        h = ops.mx_moe_gemm(0, xq, xs, af, route, self.gate_up_qweight, self.gate_up_w_scale, wf, T, k, out_dtype=cdt)
+        hq, hs = ops.mx_quant(h, af, self.kp_i)
+        y = ops.mx_moe_gemm(1, hq, hs, af, route, self.down_qweight, self.down_w_scale, wf, T, k, routing_weights=w)
+        return ops.moe_combine(y, route, T, k, E, cdt)
+
+    def _product(self, a, prefix, e, kp, cdt):
+        aq, as_ = ops.mx_quant(a, self.act_fmt, kp)
+        product = ops.mx_gemv if a.shape[0] <= ops.MX_GEMV_MAX_M else ops.mx_gemm
+        return product(aq, as_, self.act_fmt, self._buffers[f"{prefix}_qweight"][e], self._buffers[f"{prefix}_w_scale"][e], self.w_fmt,
+                       None, cdt)
+
+    def _dense_forward(self, x, top_k_index, top_k_weights, cdt):
+        """transformers' MixtralExperts.forward with MXLinear's products on the slices of every expert that was hit (host waits:
+        nonzero / where)."""
+        out = torch.zeros((x.shape[0], self.hidden_dim), dtype=cdt, device=x.device)
+        E = self.num_experts
+        with torch.no_grad():
+            # ids outside 0..E-1 go to an extra class E that is never visited: they contribute nothing, as on the fused route
+            ids = torch.where((top_k_index >= 0) & (top_k_index < E), top_k_index, torch.full_like(top_k_index, E)).long()
+            mask = torch.nn.functional.one_hot(ids, num_classes=E + 1)[..., :E].permute(2, 1, 0)
+            hit = torch.greater(mask.sum(dim=(-1, -2)), 0).nonzero()
+        for e in hit:
+            e = int(e[0])
+            top_k_pos, token_idx = torch.where(mask[e])
+            gate, up = self._product(x[token_idx], "gate_up", e, self.kp_h, cdt).chunk(2, dim=-1)
+            y = self._product((self.act_fn(gate) * up).contiguous(), "down", e, self.kp_i, cdt)
+            y = y * top_k_weights[token_idx, top_k_pos, None]
+            out.index_add_(0, token_idx, y.to(cdt))
+        return out
+
+    def extra_repr(self):
+        return (f"num_experts={self.num_experts}, hidden_dim={self.hidden_dim}, intermediate_dim={self.intermediate_dim}, "
+                f"w_dtype={self.w_dtype}, act_dtype={self.act_dtype}, blocksize=32")
+
+
+def unsupported_reason(module, cfg):
+    """Why MXQuant leaves the fused-experts `module` in float under `cfg` (None = it converts it)."""
+    E = module.gate_up_proj.shape[0]
+    pair = (cfg.get("w_dtype"), cfg.get("act_dtype"))
+    if pair not in PAIRS:
+        return f"(w_dtype, act_dtype)={pair} is not one of {PAIRS}"
+    if not _is_silu(getattr(module, "act_fn", None)):
+        return f"activation {type(getattr(module, 'act_fn', None)).__name__} is not SiLU"
+    if E > MAX_EXPERTS:
+        return f"E={E} must be at most {MAX_EXPERTS}"
+    return None
+

@@ -14,7 +14,7 @@ import torch
 
 from .... import ops
 from ....common.utils import logger
-from ...utils.utility import get_module, set_module
+from ...utils.utility import get_module, is_fused_experts, set_module
 from ..base_algorithm import Quantizer
 
 FORMATS = {"fp8_e4m3": ops.MX_FP8_E4M3, "fp4": ops.MX_FP4_E2M1}
@@ -138,9 +138,13 @@ def mx_linear_group(x, modules):
 
 
 class MXQuantizer(Quantizer):
-    """quant_config: {layer name: {"w_dtype", "act_dtype", ...}} (mx_quant_entry).  A layer whose w_dtype is "fp32" stays float."""
+    """quant_config: {layer name: {"w_dtype", "act_dtype", ...}} (mx_quant_entry).  A layer whose w_dtype is "fp32" stays float.
+    Besides nn.Linear the names may be fused MoE experts modules (is_fused_experts; they are in the mapping under
+    MXQuantConfig(quant_experts=True)), which become MXExperts."""
 
     def _selected(self, model):
+        from .experts import unsupported_reason
+
         out = []
         for name, cfg in self.quant_config.items():
             if cfg.get("w_dtype", "fp32") == "fp32":
@@ -148,6 +152,12 @@ class MXQuantizer(Quantizer):
             mod = get_module(model, name)
             if isinstance(mod, torch.nn.Linear):
                 out.append(name)
+            elif is_fused_experts(mod):
+                why = unsupported_reason(mod, cfg)
+                if why is None:
+                    out.append(name)
+                else:
+                    logger.warning("MXQuant: experts module %s stays in floating point: %s", name, why)
         return out
 
     def prepare(self, model, *args, **kwargs):
@@ -155,6 +165,8 @@ class MXQuantizer(Quantizer):
 
     @torch.no_grad()
     def convert(self, model, *args, **kwargs):
+        from .experts import MXExperts
+
         dev = torch.device("cuda", torch.cuda.current_device())
         model.to(dev)
         model.eval()
@@ -163,6 +175,8 @@ class MXQuantizer(Quantizer):
             logger.warning("MXQuant: no nn.Linear selected, the model is returned unchanged")
         for name in names:
             cfg = self.quant_config[name]
-            set_module(model, name, MXLinear.from_float(get_module(model, name), cfg["w_dtype"], cfg["act_dtype"], device=dev))
+            mod = get_module(model, name)
+            cls = MXLinear if isinstance(mod, torch.nn.Linear) else MXExperts
+            set_module(model, name, cls.from_float(mod, cfg["w_dtype"], cfg["act_dtype"], device=dev))
         model.mx_info = {"blocksize": 32, "round_method": "nearest"}
         return model

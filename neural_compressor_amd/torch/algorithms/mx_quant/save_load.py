@@ -1,6 +1,9 @@
 """save / load of an MX model (`model.save(output_dir)`, `load(output_dir, original_model)`), the files of smooth_quant/save_load.py:
   quantized_weight.pt   state_dict: uint8 `qweight`, uint8 `w_scale`, bias of every MXLinear; the float parameters of everything else
-  qconfig.json          {"mx_quant": {blocksize, round_method}, "mx_modules": {name: [w_dtype, act_dtype]}}
+  qconfig.json          {"mx_quant": {blocksize, round_method}, "mx_modules": {name: [w_dtype, act_dtype]},
+                         "mx_experts": {name: [w_dtype, act_dtype, E, H, I]}}
+MXExperts modules save their four uint8 buffers under their own names.  The "mx_experts" key is written only when the model has such
+modules; a directory without it (a model without them, or one written before MXExperts existed) loads as before.
 """
 
 import json
@@ -8,20 +11,39 @@ import os
 
 import torch
 
-from ...utils.utility import get_module, set_module
+from ...utils.utility import get_module, is_fused_experts, set_module
+from .experts import MXExperts
 from .mx_quant import MXLinear
 
 WEIGHT_NAME = "quantized_weight.pt"
 QCONFIG_NAME = "qconfig.json"
 
 
+def qconfig_of(model):
+    """The content of qconfig.json."""
+    mods = {n: [m.w_dtype, m.act_dtype] for n, m in model.named_modules() if isinstance(m, MXLinear)}
+    experts = {n: [m.w_dtype, m.act_dtype, m.num_experts, m.hidden_dim, m.intermediate_dim] for n, m in model.named_modules()
+               if isinstance(m, MXExperts)}
+    cfg = {"mx_quant": dict(getattr(model, "mx_info", {})), "mx_modules": mods}
+    if experts:  # a model without MXExperts writes the file it always wrote
+        cfg["mx_experts"] = experts
+    return cfg
+
+
+def _take(state, name, new, dev):
+    """Load `name.*` of `state` into `new` (strict) and drop those keys."""
+    own = {k[len(name) + 1:]: v for k, v in state.items() if k.startswith(name + ".")}
+    new.load_state_dict({k: v.to(dev) for k, v in own.items()}, strict=True)
+    for k in own:
+        state.pop(name + "." + k)
+
+
 def save(model, output_dir="./saved_results"):
     os.makedirs(output_dir, exist_ok=True)
     if torch.cuda.is_available():
         torch.cuda.synchronize()
-    mods = {n: [m.w_dtype, m.act_dtype] for n, m in model.named_modules() if isinstance(m, MXLinear)}
     with open(os.path.join(output_dir, QCONFIG_NAME), "w") as f:
-        json.dump({"mx_quant": dict(getattr(model, "mx_info", {})), "mx_modules": mods}, f, indent=2)
+        json.dump(qconfig_of(model), f, indent=2)
     torch.save({k: v.detach().cpu() for k, v in model.state_dict().items()}, os.path.join(output_dir, WEIGHT_NAME))
 
 
@@ -38,10 +60,15 @@ def load(output_dir, original_model, device="cuda"):
             lin.weight.dtype if lin.weight.dtype in (torch.float16, torch.bfloat16) else torch.float16)
         new = MXLinear(lin.in_features, lin.out_features, bias=(name + ".bias") in state, w_dtype=w_dtype, act_dtype=act_dtype,
                        device=dev, float_type=ft)
-        own = {k[len(name) + 1:]: v for k, v in state.items() if k.startswith(name + ".")}
-        new.load_state_dict({k: v.to(dev) for k, v in own.items()}, strict=True)
-        for k in own:
-            state.pop(name + "." + k)
+        _take(state, name, new, dev)
+        set_module(original_model, name, new)
+    for name, (w_dtype, act_dtype, E, H, I) in cfg.get("mx_experts", {}).items():
+        old = get_module(original_model, name)
+        assert is_fused_experts(old), f"{name}: expected a fused experts module in the float architecture, got {type(old).__name__}"
+        pd = old.gate_up_proj.dtype
+        new = MXExperts(E, H, I, w_dtype=w_dtype, act_dtype=act_dtype, act_fn=old.act_fn, device=dev,
+                        float_type=pd if pd in (torch.float16, torch.bfloat16) else torch.float16)
+        _take(state, name, new, dev)
         set_module(original_model, name, new)
     original_model.load_state_dict(state, strict=False, assign=True)
     original_model.to(dev)

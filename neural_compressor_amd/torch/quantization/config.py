@@ -307,7 +307,8 @@ class MXQuantConfig(TorchBaseConfig):
     so the defaults here are `w_dtype="fp8_e4m3", act_dtype="fp8_e4m3"` -- a deliberate deviation.  Supported (w_dtype, act_dtype):
     ("fp8_e4m3", "fp8_e4m3"), ("fp4", "fp8_e4m3"), ("fp4", "fp4"), "fp4" being e2m1; `blocksize=32`, `round_method="nearest"`,
     `weight_only=False`; `out_dtype` is accepted and unused (the output has the activation's type).  `w_dtype="fp32"` (through
-    `set_local`) leaves a layer float; lm_head stays float unless `quant_lm_head=True`."""
+    `set_local`) leaves a layer float; lm_head stays float unless `quant_lm_head=True`.  `quant_experts=True` (an extension of the
+    reference's fields; off by default) also converts the fused MoE experts modules (is_fused_experts) to MXExperts."""
 
     name = MX_QUANT
     supported_configs: List = []
@@ -322,11 +323,13 @@ class MXQuantConfig(TorchBaseConfig):
         round_method: str = "nearest",
         weight_only: bool = False,
         quant_lm_head: bool = False,
+        quant_experts: bool = False,
         white_list: Optional[List] = DEFAULT_WHITE_LIST,
         **kwargs,
     ):
         super().__init__(white_list=white_list)
-        _assign(self, locals(), ["w_dtype", "act_dtype", "out_dtype", "blocksize", "round_method", "weight_only", "quant_lm_head"])
+        _assign(self, locals(), ["w_dtype", "act_dtype", "out_dtype", "blocksize", "round_method", "weight_only", "quant_lm_head",
+                                 "quant_experts"])
         if w_dtype != "fp32":
             unsupported = []
             if (w_dtype, act_dtype) not in self.PAIRS:
@@ -340,6 +343,16 @@ class MXQuantConfig(TorchBaseConfig):
             if unsupported:
                 raise NotImplementedError("MXQuant on MI355X: " + "; ".join(unsupported))
         self._post_init()
+
+    def extend_model_info(self, model, model_info):
+        """`quant_experts=True`: the fused MoE experts modules join the Linears (as GPTQConfig.extend_model_info), so they get
+        (name, type) keys in the config mapping and MXQuantizer converts them (algorithms/mx_quant/experts.py).  `get_model_info`
+        itself keeps returning the Linears only."""
+        if not self.quant_experts:
+            return model_info
+        have = set(model_info)
+        extra = [(name, type(m).__name__) for name, m in model.named_modules() if is_fused_experts(m)]
+        return list(model_info) + [e for e in extra if e not in have]
 
     def to_config_mapping(self, config_list=None, model_info=None):
         if not self.quant_lm_head:
