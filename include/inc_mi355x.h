@@ -693,6 +693,42 @@ int inc_mx_moe_gemm(int mode, const uint8_t* aq, const uint8_t* as, int afmt, co
                     const uint8_t* ws, int wfmt, const void* routing_weights, int wdtype, void* out, int odtype, int64_t T, int top_k,
                     int64_t E, int64_t N, int64_t Kp, inc_stream_t stream);
 
+/* ---- FP8 per-token / per-channel: OCP e4m3 codes, one fp32 scale per row of x and one per row of W ------- *
+ * The "FP8 dynamic" cell: csrc/sq.hip (the quantiser, next to the int8 token kernel it shares its structure with) and
+ * csrc/gemm_fp8.hip (the products, on v_mfma_f32_32x32x64_f8f6f4 and v_mfma_f32_16x16x128_f8f6f4).  This text is the specification.
+ * Inputs are finite; for a row with a NaN or an infinity nothing is promised except that every write stays in bounds.
+ * inc_fp8_quant_rows: x bf16 / fp16 / fp32 [M,K] contiguous, of any alignment; in_scale fp32 [K] or NULL.
+ *     t            = float(x[m,k]) * in_scale[k]                       (one fp32 multiply; t = float(x[m,k]) without in_scale)
+ *     row_scale[m] = max(max_k |t| / 448.0f, 0x1p-60f)                 (fp32, true division; the floor only keeps an all-zero row
+ *                                                                       finite -- e4m3 has a dynamic range of its own)
+ *     codes[m,k]   = e4m3(t / row_scale[m])                            (fp32 true division, then round to nearest, ties to even,
+ *                    onto the OCP e4m3fn grid -- subnormals down to 2^-9 kept -- saturating at +-448: the quotient can exceed 448
+ *                    by one rounding; the element rounding of inc_mx_quant for INC_MX_FP8_E4M3, the same device function)
+ *   The sign bit of a code is the sign bit of t, for zeros too; the NaN codes 0x7f / 0xff are never written.  Columns K .. Kp-1 are
+ *   code 0.  codes uint8 [M,Kp] 16-byte aligned, Kp >= K a multiple of INC_MX_KTILE = 128; row_scale fp32 [M].  One workgroup per
+ *   row; a row is read from HBM once for Kp <= 16384 and twice above.  max is order-free, so codes and row_scale have one right
+ *   answer, bit for bit.  A weight [N,K] with one scale per output channel is the same call, row-wise.
+ *   INC_ERR_UNSUPPORTED (nothing launched) for an unknown dtype or Kp % 128 != 0.
+ * inc_fp8_gemm: y[m,n] = rd16((row_scale[m] * alpha[n]) * acc[m,n] + bias[n]), acc[m,n] = sum_k xq[m,k] * wq[n,k] accumulated in
+ *   fp32 by the matrix pipe over the K-tiles of 128 in ascending order (the order inside an instruction is not documented; the
+ *   accumulator is bit for bit that of inc_mx_gemm (fp8, fp8) with every scale byte 127).  The factor product is one fp32 multiply;
+ *   the multiply by acc and the bias add may contract to one fma, as in inc_w8a8_gemm_rowscale.  xq [M,Kp], wq [N,Kp] uint8, 16-byte
+ *   aligned; row_scale fp32 [M], alpha fp32 [N] (= the weight's row_scale); bias [N] in ydtype or NULL; y [M,N] bf16 / fp16, any
+ *   M >= 1 and N >= 1 (8-byte stores when N % 4 == 0 and y is 8-byte aligned, 2-byte stores otherwise).  256 x 256 x 128 tiles, one
+ *   workgroup per tile, no split-K tail, no workspace.
+ * inc_fp8_gemv: the same product for 1 <= M <= INC_MX_GEMV_MAX_M: one workgroup per strip of 16 weight rows, K split over its 8 waves
+ *   (wave w takes the K-tiles w, w + 8, ... in ascending order), the 8 partials added in wave order through LDS, then the epilogue
+ *   above: no workspace, repeated calls are bit-identical, and acc is bit for bit that of inc_mx_gemv with every scale byte 127.
+ *   Reads nothing past row M - 1 of xq or row N - 1 of wq.
+ * Both products: INC_ERR_UNSUPPORTED (nothing launched) for Kp % 128 != 0, a ydtype other than bf16 / fp16 or (gemv) M > 16;
+ *   INC_ERR_BAD_ARG for a NULL operand, a size < 1 or a misaligned pointer.  All three validate their arguments before any HIP call. */
+int inc_fp8_quant_rows(const void* x, int xdtype, int64_t M, int64_t K, int64_t Kp, const float* in_scale, uint8_t* codes,
+                       float* row_scale, inc_stream_t stream);
+int inc_fp8_gemm(const uint8_t* xq, const float* row_scale, const uint8_t* wq, const float* alpha, const void* bias, void* y, int ydtype,
+                 int64_t M, int64_t N, int64_t Kp, inc_stream_t stream);
+int inc_fp8_gemv(const uint8_t* xq, const float* row_scale, const uint8_t* wq, const float* alpha, const void* bias, void* y, int ydtype,
+                 int64_t M, int64_t N, int64_t Kp, inc_stream_t stream);
+
 /* ---- measured ceilings (bench.py `ceilings`) -- measurement helpers, not on the hot path ------------- *
  * inc_probe_hbm_triad: a <- b + s*c over n fp32 (n % 4 == 0): 12 n bytes of HBM traffic per call.
  * inc_probe_mfma_bf16: `blocks` workgroups x 4 waves x `iters` x 8 v_mfma_f32_32x32x16_bf16 on operands read from `src`

@@ -8,6 +8,7 @@ from enum import Enum
 RTN, GPTQ, AWQ = "rtn", "gptq", "awq"
 SMOOTH_QUANT = "smooth_quant"  # constants.py:31
 MX_QUANT = "mx_quant"  # constants.py:34
+FP8_QUANT = "fp8_quant"  # the reference's name for its (Gaudi) FP8 algorithm; here the per-token e4m3 cell
 DEFAULT_WHITE_LIST = "*"  # constants.py:22
 EMPTY_WHITE_LIST = None  # constants.py:23
 

@@ -20,43 +20,15 @@
 // steps of a tile take bytes 0 and 2 of the result through opsel.
 // One workgroup per tile and no split-K tail; M <= 16 has a kernel of its own (gemm_mx_gemv.hip), this one serves it with clamped rows.
 // Algorithmic work per launch: 2*M*N*Kp flop; bytes (M + N) * Kp * (1 or 1/2) + (M + N) * Kp / 32 + 2*M*N.
-#include "tile256_frame.hpp"
+#include "mx_stage.hpp"  // the frame's row stage issued as 1 KiB pieces, and the operand of the scaled MFMA read from it
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) int i32x8;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 constexpr int XM = 256, XN = 256, XK = INC_MX_KTILE;
 
 __host__ __device__ constexpr int mx_row_bytes(int fmt) { return fmt == INC_MX_FP8_E4M3 ? XK : XK / 2; }  // of one K-tile
-
-// the row stage of the frame, issued as single 1 KiB pieces, and the operand of the scaled MFMA read from it
-template <int RB>
-struct MxStage : RowStage<RB> {
-  using RowStage<RB>::NI;
-  using RowStage<RB>::chunk_off;
-  __device__ static __forceinline__ void issue(const uint8_t* src, uint32_t lds_tile, int wave, const uint32_t (&off)[NI]) {
-#pragma unroll
-    for (int i = 0; i < NI; ++i) lds_dma_1k(src, __builtin_amdgcn_readfirstlane(lds_tile + (wave * NI + i) * 1024), off[i]);
-  }
-  // what lane half h supplies of `row` for the 64-wide step kk of the tile, as the instruction wants it; `sw` = swz(row)
-  __device__ static __forceinline__ i32x8 frag(const char* tile, int row, int kk, int h, int sw) {
-    i32x8 f;
-    if constexpr (RB == 128) {
-      const int slot = chunk_off(4 * kk + h, sw);  // 16-byte chunks h and 2 + h of the step's four
-      const uint4 lo = *reinterpret_cast<const uint4*>(tile + row * 128 + slot);
-      const uint4 hi = *reinterpret_cast<const uint4*>(tile + row * 128 + (slot ^ 32));
-      f[0] = (int)lo.x; f[1] = (int)lo.y; f[2] = (int)lo.z; f[3] = (int)lo.w;
-      f[4] = (int)hi.x; f[5] = (int)hi.y; f[6] = (int)hi.z; f[7] = (int)hi.w;
-    } else {
-      const uint4 lo = *reinterpret_cast<const uint4*>(tile + row * 64 + chunk_off(2 * kk + h, sw));  // block 2 kk + h
-      f[0] = (int)lo.x; f[1] = (int)lo.y; f[2] = (int)lo.z; f[3] = (int)lo.w;
-      f[4] = 0; f[5] = 0; f[6] = 0; f[7] = 0;  // fp4 occupies the first four registers; the instruction reads no more
-    }
-    return f;
-  }
-};
 
 template <bool IS_BF16, int XF, int WF>
 __global__ __launch_bounds__(512) void mx_gemm_kernel(const uint8_t* __restrict__ xq, const uint8_t* __restrict__ xs,

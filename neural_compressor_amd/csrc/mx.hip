@@ -8,30 +8,14 @@
 //   code  = RNE(v) onto the element grid, saturating, with the sign bit of x
 // One lane owns one block, so max|x| needs no exchange between lanes and every code has one right answer, bit for bit: the row is
 // read once (16-byte loads where K and the pointer allow it), the 32 codes leave as two (fp8) or one (fp4) 16-byte store.
-// The rounding is done in fp32 arithmetic, not with v_cvt_scalef32_pk_*: with e = max(expfield(|v|), expfield(min normal)) the
-// grid step at |v| is 2^(e - 127 - MB) (MB mantissa bits), t = rint(|v| / step) is an integer in [0, 2^(MB+1)] and
-// ((e - expfield(min normal)) << MB) + t is the code -- the carry of t = 2^(MB+1) lands in the exponent field by itself and the
-// subnormal codes are the case e == expfield(min normal).
-#include "common.hpp"
+// The element rounding is mx_encode of mx_format.hpp (shared with the per-token FP8 quantiser).
+#include "mx_format.hpp"
 
 namespace {
 
-template <int FMT> struct MxFmt;
-template <> struct MxFmt<INC_MX_FP8_E4M3> { static constexpr int EMAX = 8, MB = 3, EMINF = 127 - 6; static constexpr float SAT = 448.f; };
-template <> struct MxFmt<INC_MX_FP4_E2M1> { static constexpr int EMAX = 2, MB = 1, EMINF = 127; static constexpr float SAT = 6.f; };
-
 template <int FMT>
 __device__ __forceinline__ uint32_t mx_code(float x, float mult) {
-  using F = MxFmt<FMT>;
-  const float v = x * mult;
-  const float a = fminf(fabsf(v), F::SAT);
-  int e = (int)(__float_as_uint(a) >> 23);
-  e = e < F::EMINF ? F::EMINF : e;
-  const float inv_step = __uint_as_float((uint32_t)(254 + F::MB - e) << 23);
-  const uint32_t t = (uint32_t)(int)rintf(a * inv_step);
-  const uint32_t mag = ((uint32_t)(e - F::EMINF) << F::MB) + t;
-  const uint32_t sign = __float_as_uint(x) >> 31;
-  return mag | (sign << (FMT == INC_MX_FP8_E4M3 ? 7 : 3));
+  return mx_encode<FMT>(x * mult, __float_as_uint(x) >> 31);
 }
 
 // the 32 values of block k0 .. k0 + 31 of the row that starts at element `row`; 0 from K on

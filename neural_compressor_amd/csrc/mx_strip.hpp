@@ -1,5 +1,5 @@
 // mx_strip.hpp -- the operand fragments of v_mfma_scale_f32_16x16x128_f8f6f4 as the strip kernels of the MX cell load them: the decode
-// GEMV (gemm_mx_gemv.hip) and the routed experts GEMM (gemm_mx_moe.hip).  Operand map (tools/mx_lab.hip): lane l
+// GEMV (gemm_mx_gemv.hip), the routed experts GEMM (gemm_mx_moe.hip) and the FP8 per-token decode GEMV (gemm_fp8.hip).  Operand map (tools/mx_lab.hip): lane l
 // holds row l & 15, lane group g = l >> 4; fp8: registers 0 .. 3 are the 16 bytes at 16 g of the K-tile and 4 .. 7 the 16 bytes at
 // 64 + 16 g; fp4: registers 0 .. 3 are the 16 bytes of block g; either format: the scale byte of block g.
 #pragma once

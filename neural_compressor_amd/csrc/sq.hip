@@ -12,7 +12,7 @@
 #include <float.h>
 #include <math.h>
 
-#include "common.hpp"
+#include "mx_format.hpp"  // the e4m3 element rounding of the FP8 per-token cell
 
 namespace {
 
@@ -291,7 +291,19 @@ __device__ __forceinline__ uint4 token_pack16(const float (&t)[16], float s) {
   return make_uint4(w[0], w[1], w[2], w[3]);
 }
 
-template <int DT, bool HELD>
+// the FP8 cell's pack step (inc_fp8_quant_rows): e4m3 codes of t / s through the MX quantiser's element rounding (mx_format.hpp);
+// a code carries the sign of t, zeros included
+__device__ __forceinline__ uint4 fp8_pack16(const float (&t)[16], float s) {
+  uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+  for (int j = 0; j < 16; ++j) w[j >> 2] |= mx_encode<INC_MX_FP8_E4M3>(t[j] / s, __float_as_uint(t[j]) >> 31) << (8 * (j & 3));
+  return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+// FP8 = false: the int8 cell above.  FP8 = true: the per-token e4m3 cell, s[m] = max(max_k |t| / 448, 2^-60) (the floor only keeps an
+// all-zero row finite: e4m3 has a dynamic range of its own) and xq holds e4m3 codes; everything but the scale rule and the pack step
+// is shared.
+template <int DT, bool HELD, bool FP8 = false>
 __global__ __launch_bounds__(256) void quant_act_token_kernel(const void* __restrict__ x, int64_t K, int64_t Kp,
                                                               const float* __restrict__ in_scale, int8_t* __restrict__ xq,
                                                               float* __restrict__ row_scale) {
@@ -320,16 +332,17 @@ __global__ __launch_bounds__(256) void quant_act_token_kernel(const void* __rest
   if (lane == 0) red[wave] = amax;
   __syncthreads();
   amax = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-  const float s = fmaxf(amax / 127.0f, FLT_EPSILON);
+  const float s = FP8 ? fmaxf(amax / 448.0f, 0x1p-60f) : fmaxf(amax / 127.0f, FLT_EPSILON);
   int8_t* const out = xq + m * Kp;
+  auto pack = [](const float (&v)[16], float sc) { return FP8 ? fp8_pack16(v, sc) : token_pack16(v, sc); };
   if constexpr (HELD) {
 #pragma unroll
     for (int j = 0; j < QT_HELD; ++j)
-      if (tid + 256 * j < chunks) *reinterpret_cast<uint4*>(out + (int64_t)(tid + 256 * j) * 16) = token_pack16(t[j], s);
+      if (tid + 256 * j < chunks) *reinterpret_cast<uint4*>(out + (int64_t)(tid + 256 * j) * 16) = pack(t[j], s);
   } else {
     for (int c = tid; c < chunks; c += 256) {
       token_load16<DT>(x, row, (int64_t)c * 16, K, vec, in_scale, t[0]);
-      *reinterpret_cast<uint4*>(out + (int64_t)c * 16) = token_pack16(t[0], s);
+      *reinterpret_cast<uint4*>(out + (int64_t)c * 16) = pack(t[0], s);
     }
   }
   if (tid == 0) row_scale[m] = s;
@@ -390,6 +403,24 @@ int inc_sq_quant_act_token(const void* x, int xdtype, int64_t M, int64_t K, int6
   INC_DISPATCH_DTYPE(xdtype, DT, {
     if (held) quant_act_token_kernel<DT, true><<<(unsigned)M, 256, 0, inc_s(stream)>>>(x, K, Kp, in_scale, xq, row_scale);
     else quant_act_token_kernel<DT, false><<<(unsigned)M, 256, 0, inc_s(stream)>>>(x, K, Kp, in_scale, xq, row_scale);
+  })
+  INC_LAUNCH_RETURN();
+}
+
+// The per-token / per-channel e4m3 quantiser of the FP8 cell: the token kernel above with the e4m3 scale rule and
+// pack step.  Serves activation rows at run time and weight rows (one scale per output channel) at convert time.
+int inc_fp8_quant_rows(const void* x, int xdtype, int64_t M, int64_t K, int64_t Kp, const float* in_scale, uint8_t* codes,
+                       float* row_scale, inc_stream_t stream) {
+  INC_CHECK_ARG(x && codes && row_scale && M > 0 && K > 0 && Kp >= K);
+  if (xdtype != INC_F32 && xdtype != INC_F16 && xdtype != INC_BF16) return INC_ERR_UNSUPPORTED;
+  if ((Kp % INC_MX_KTILE) != 0) return INC_ERR_UNSUPPORTED;
+  INC_CHECK_ARG(M <= 0x7fffffff && Kp <= 0x7fffffff);
+  INC_CHECK_ARG((reinterpret_cast<uintptr_t>(codes) & 15) == 0);
+  const bool held = Kp <= (int64_t)QT_HELD * 256 * 16;
+  int8_t* const out = reinterpret_cast<int8_t*>(codes);
+  INC_DISPATCH_DTYPE(xdtype, DT, {
+    if (held) quant_act_token_kernel<DT, true, true><<<(unsigned)M, 256, 0, inc_s(stream)>>>(x, K, Kp, in_scale, out, row_scale);
+    else quant_act_token_kernel<DT, false, true><<<(unsigned)M, 256, 0, inc_s(stream)>>>(x, K, Kp, in_scale, out, row_scale);
   })
   INC_LAUNCH_RETURN();
 }

@@ -1,4 +1,4 @@
-// tile256_frame.hpp -- the wave frame every 256 x 256 MFMA GEMM of the library is built on (gemm_tile256.hip, gemm_i8.hip, gemm_mx.hip,
+// tile256_frame.hpp -- the wave frame every 256 x 256 MFMA GEMM of the library is built on (gemm_tile256.hip, gemm_i8.hip, gemm_mx.hip, gemm_fp8.hip,
 // tools/kbench_gemm_1.inc; gemm_d2r.hip and tools/gemm_d2r8.hip take the row stage only).  A kernel file keeps what is its own -- the
 // K-loop schedule, the MFMA, the dequantisation or scales -- and takes the rest from here.
 //

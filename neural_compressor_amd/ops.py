@@ -1760,3 +1760,49 @@ def mx_moe_gemm(mode, aq, as_, afmt, route, wq, ws, wfmt, T, top_k, routing_weig
         check(lib.inc_mx_moe_gemm(mode, _ptr(aq), _ptr(as_), int(afmt), _ptr(route), _ptr(wq), _ptr(ws), int(wfmt), _ptr(routing_weights),
                                   wdt, _ptr(out), dtype_code(odt), T, top_k, E, N, Kp, _stream()), "inc_mx_moe_gemm")
     return out
+
+
+# ---------------------------------------------------------------------------------------------------
+# K17 FP8 per-token / per-channel: e4m3 codes with one fp32 scale per row (include/inc_mi355x.h has the specification)
+# ---------------------------------------------------------------------------------------------------
+FP8_GEMV_MAX_M = MX_GEMV_MAX_M
+
+
+def fp8_quant_rows(x2d, in_scale=None, Kp=None):
+    """The per-row e4m3 quantiser (inc_fp8_quant_rows): x [M,K] bf16 / fp16 / fp32 -> (codes uint8 [M,Kp], row_scale fp32 [M]) with
+    row_scale = max(max_k |x * in_scale| / 448, 2^-60) and codes = e4m3(x * in_scale / row_scale).  Activation rows and weight rows alike."""
+    x2d = x2d.contiguous()
+    in_scale = None if in_scale is None else in_scale.to(torch.float32).contiguous()
+    dev = _dev(x2d, in_scale)
+    M, K = x2d.shape
+    Kp = mx_padded_k(K) if Kp is None else int(Kp)
+    codes = torch.empty((M, Kp), dtype=torch.uint8, device=dev)
+    row_scale = torch.empty(M, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.inc_fp8_quant_rows(_ptr(x2d), dtype_code(x2d.dtype), M, K, Kp, _ptr(in_scale), _ptr(codes), _ptr(row_scale), _stream()),
+              "inc_fp8_quant_rows")
+    return codes, row_scale
+
+
+def _fp8_product(fn, name, xq, row_scale, wq, alpha, bias, out_dtype):
+    dev = _dev(xq, row_scale, wq, alpha, bias)
+    (M, Kp), N = xq.shape, wq.shape[0]
+    assert wq.shape[1] == Kp and xq.dtype == torch.uint8 and wq.dtype == torch.uint8
+    assert row_scale.dtype == torch.float32 and row_scale.numel() == M and alpha.dtype == torch.float32 and alpha.numel() == N
+    if bias is not None and bias.dtype != out_dtype:
+        bias = bias.to(out_dtype)
+    y = torch.empty((M, N), dtype=out_dtype, device=dev)
+    with torch.cuda.device(dev):
+        check(fn(_ptr(xq), _ptr(row_scale), _ptr(wq), _ptr(alpha), _ptr(bias), _ptr(y), dtype_code(out_dtype), M, N, Kp, _stream()), name)
+    return y
+
+
+def fp8_gemm(xq, row_scale, wq, alpha, bias, out_dtype):
+    """y[m,n] = (row_scale[m] * alpha[n]) * sum_k x_k * w_k + bias[n] over e4m3 codes on v_mfma_f32_32x32x64_f8f6f4 (inc_fp8_gemm)."""
+    return _fp8_product(lib.inc_fp8_gemm, "inc_fp8_gemm", xq, row_scale, wq, alpha, bias, out_dtype)
+
+
+def fp8_gemv(xq, row_scale, wq, alpha, bias, out_dtype):
+    """fp8_gemm's product for up to FP8_GEMV_MAX_M rows of x on v_mfma_f32_16x16x128_f8f6f4 (inc_fp8_gemv): one workgroup per 16 weight
+    rows, K split over its waves, no workspace."""
+    return _fp8_product(lib.inc_fp8_gemv, "inc_fp8_gemv", xq, row_scale, wq, alpha, bias, out_dtype)

@@ -1,0 +1,103 @@
+"""FP8Linear / FP8Quantizer: per-token / per-channel FP8 linears (the "FP8 dynamic" cell).
+
+The weight is quantised once to OCP e4m3 codes with one fp32 scale per output channel, the activation rows are quantised at run time
+with one fp32 scale per token (`inc_fp8_quant_rows` for both), and `inc_fp8_gemm` multiplies the codes on v_mfma_f32_32x32x64_f8f6f4
+and applies `row_scale[m] * w_scale[n]` in its epilogue; a decode-sized batch (up to 16 rows) takes `inc_fp8_gemv` on the 16x16x128
+form of the instruction.  The specification in bits is the comment of the entry points in include/inc_mi355x.h.
+The algorithm is data-free: `prepare` returns the model unchanged and `convert` swaps every selected nn.Linear.
+"""
+
+import torch
+
+from .... import ops
+from ....common.utils import logger
+from ...utils.utility import get_module, set_module
+from ..base_algorithm import Quantizer
+
+
+class FP8Linear(torch.nn.Module):
+    """nn.Linear with e4m3 weights (per output channel) and e4m3 activations (per token).  Buffers: qweight uint8 [N, Kp], w_scale
+    fp32 [N], bias.  Kp = in_features rounded up to 128; the padding columns are zero codes.  forward = inc_fp8_quant_rows(x) ->
+    inc_fp8_gemv up to DECODE_MAX_M rows (while DECODE_GEMV is on), inc_fp8_gemm above; nothing is read back to the host."""
+
+    # True = up to DECODE_MAX_M rows go through the decode GEMV (inc_fp8_gemv: one workgroup per 16 weight rows, K split over its waves);
+    # False = every batch takes the 256 x 256 tile kernel.  Times of both: profiles/fp8/fp8_gemm_time.log, DESIGN section 8c.
+    DECODE_GEMV = True
+    DECODE_MAX_M = ops.FP8_GEMV_MAX_M
+
+    def __init__(self, in_features, out_features, bias=False, device="cuda", float_type=torch.float16):
+        super().__init__()
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise RuntimeError(f"FP8Linear needs a HIP device ('cuda[:N]'), got '{device}'. There is no CPU implementation.")
+        self.in_features, self.out_features = in_features, out_features
+        self.kp = ops.mx_padded_k(in_features)
+        self.float_type = float_type
+        self.register_buffer("qweight", torch.zeros((out_features, self.kp), dtype=torch.uint8, device=dev))
+        self.register_buffer("w_scale", torch.zeros(out_features, dtype=torch.float32, device=dev))
+        self.register_buffer("bias", torch.zeros(out_features, dtype=float_type, device=dev) if bias else None)
+
+    @classmethod
+    @torch.no_grad()
+    def from_float(cls, linear, device="cuda"):
+        ft = linear.weight.dtype if linear.weight.dtype in (torch.float16, torch.bfloat16) else torch.float16
+        new = cls(linear.in_features, linear.out_features, bias=linear.bias is not None, device=device, float_type=ft)
+        dev = new.qweight.device
+        codes, scale = ops.fp8_quant_rows(linear.weight.detach().to(dev), None, new.kp)
+        new.qweight.copy_(codes)
+        new.w_scale.copy_(scale)
+        if linear.bias is not None:
+            new.bias.copy_(linear.bias.detach().to(ft))
+        return new
+
+    def forward(self, input):
+        x = input
+        lead = x.shape[:-1]
+        x2d = x.reshape(-1, self.in_features)
+        out_dtype = x.dtype if x.dtype in (torch.float16, torch.bfloat16) else self.float_type
+        if x2d.shape[0] == 0:
+            return torch.empty((*lead, self.out_features), dtype=torch.float32 if x.dtype == torch.float32 else out_dtype, device=x.device)
+        xq, row_scale = ops.fp8_quant_rows(x2d, None, self.kp)
+        product = ops.fp8_gemv if self._decodes(x2d.shape[0]) else ops.fp8_gemm
+        y = product(xq, row_scale, self.qweight, self.w_scale, self.bias, out_dtype)
+        if x.dtype == torch.float32:  # an fp32 model keeps seeing fp32 activations (the kernel's epilogue emits 16-bit)
+            y = y.float()
+        return y.reshape(*lead, self.out_features)
+
+    def _decodes(self, rows):
+        return self.DECODE_GEMV and rows <= min(self.DECODE_MAX_M, ops.FP8_GEMV_MAX_M)
+
+    def recover(self, dtype=None):
+        """Dequantised weight [N, K]: the code table times w_scale (one fp32 multiply per element), in `dtype` or float_type."""
+        table = torch.arange(256, dtype=torch.uint8).view(torch.float8_e4m3fn).float().to(self.qweight.device)
+        w = table[self.qweight.long()] * self.w_scale[:, None]
+        return w[:, : self.in_features].to(self.float_type if dtype is None else dtype)
+
+    def extra_repr(self):
+        return (f"in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}, "
+                f"fp8_config=E4M3, act_granularity=per_token, w_granularity=per_channel")
+
+
+class FP8Quantizer(Quantizer):
+    """quant_config: {layer name: {"fp8_config"}} (fp8_quant_entry).  A layer whose fp8_config is "fp32" stays float; only nn.Linear
+    modules are converted (fused MoE experts modules are left alone)."""
+
+    def _selected(self, model):
+        return [name for name, cfg in self.quant_config.items()
+                if cfg.get("fp8_config", "fp32") != "fp32" and isinstance(get_module(model, name), torch.nn.Linear)]
+
+    def prepare(self, model, *args, **kwargs):
+        return model  # data-free: nothing to calibrate
+
+    @torch.no_grad()
+    def convert(self, model, *args, **kwargs):
+        dev = torch.device("cuda", torch.cuda.current_device())
+        model.to(dev)
+        model.eval()
+        names = self._selected(model)
+        if not names:
+            logger.warning("FP8: no nn.Linear selected, the model is returned unchanged")
+        for name in names:
+            set_module(model, name, FP8Linear.from_float(get_module(model, name), device=dev))
+        model.fp8_info = {"fp8_config": "E4M3", "act_granularity": "per_token", "w_granularity": "per_channel"}
+        return model

@@ -1,0 +1,54 @@
+"""save / load of an FP8 model (`model.save(output_dir)`, `load(output_dir, original_model)`), the files of mx_quant/save_load.py:
+  quantized_weight.pt   state_dict: uint8 `qweight`, fp32 `w_scale`, bias of every FP8Linear; the float parameters of everything else
+  qconfig.json          {"fp8_quant": {fp8_config, act_granularity, w_granularity}, "fp8_modules": [name, ...]}
+"""
+
+import json
+import os
+
+import torch
+
+from ...utils.utility import get_module, set_module
+from .fp8_quant import FP8Linear
+
+WEIGHT_NAME = "quantized_weight.pt"
+QCONFIG_NAME = "qconfig.json"
+
+
+def qconfig_of(model):
+    """The content of qconfig.json."""
+    return {"fp8_quant": dict(getattr(model, "fp8_info", {})),
+            "fp8_modules": [n for n, m in model.named_modules() if isinstance(m, FP8Linear)]}
+
+
+def save(model, output_dir="./saved_results"):
+    os.makedirs(output_dir, exist_ok=True)
+    if torch.cuda.is_available():
+        torch.cuda.synchronize()
+    with open(os.path.join(output_dir, QCONFIG_NAME), "w") as f:
+        json.dump(qconfig_of(model), f, indent=2)
+    torch.save({k: v.detach().cpu() for k, v in model.state_dict().items()}, os.path.join(output_dir, WEIGHT_NAME))
+
+
+def load(output_dir, original_model, device="cuda"):
+    """Rebuild the FP8 model from the float architecture `original_model` (weights may be on any device, "meta" included)."""
+    with open(os.path.join(output_dir, QCONFIG_NAME)) as f:
+        cfg = json.load(f)
+    state = torch.load(os.path.join(output_dir, WEIGHT_NAME), map_location="cpu", weights_only=True)
+    dev = torch.device(device)
+    for name in cfg["fp8_modules"]:
+        lin = get_module(original_model, name)
+        assert isinstance(lin, torch.nn.Linear), f"{name}: expected nn.Linear in the float architecture, got {type(lin).__name__}"
+        ft = state[name + ".bias"].dtype if (name + ".bias") in state else (
+            lin.weight.dtype if lin.weight.dtype in (torch.float16, torch.bfloat16) else torch.float16)
+        new = FP8Linear(lin.in_features, lin.out_features, bias=(name + ".bias") in state, device=dev, float_type=ft)
+        own = {k[len(name) + 1:]: v for k, v in state.items() if k.startswith(name + ".")}
+        new.load_state_dict({k: v.to(dev) for k, v in own.items()}, strict=True)
+        for k in own:
+            state.pop(name + "." + k)
+        set_module(original_model, name, new)
+    original_model.load_state_dict(state, strict=False, assign=True)
+    original_model.to(dev)
+    original_model.eval()
+    original_model.fp8_info = cfg.get("fp8_quant", {})
+    return original_model

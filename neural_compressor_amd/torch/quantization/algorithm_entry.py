@@ -9,7 +9,7 @@ from types import MethodType
 
 import torch
 
-from ...common.utils import AWQ, GPTQ, MX_QUANT, RTN, SMOOTH_QUANT, Mode, logger
+from ...common.utils import AWQ, FP8_QUANT, GPTQ, MX_QUANT, RTN, SMOOTH_QUANT, Mode, logger
 from ..utils.utility import get_quantizer, postprocess_model, register_algo
 
 
@@ -203,5 +203,32 @@ def mx_quant_entry(model, configs_mapping, mode=Mode.QUANTIZE, *args, **kwargs):
     model.qconfig = configs_mapping
     if mode != Mode.PREPARE:
         model.save = MethodType(_mx_save, model)
+    postprocess_model(model, mode, quantizer)
+    return model
+
+
+def _fp8_save(self, output_dir="./saved_results", **kwargs):
+    from ..algorithms.fp8_quant import save
+
+    return save(self, output_dir)
+
+
+@register_algo(FP8_QUANT)
+@torch.no_grad()
+def fp8_quant_entry(model, configs_mapping, mode=Mode.QUANTIZE, *args, **kwargs):
+    """The per-token / per-channel e4m3 cell: the plain dict per Linear goes to FP8Quantizer; the result carries FP8Linear modules.
+    Data-free: prepare changes nothing."""
+    from ..algorithms.fp8_quant import FP8Quantizer
+
+    quant_config = {}
+    for (op_name, op_type), cfg in configs_mapping.items():
+        if cfg.name != FP8_QUANT:
+            continue
+        quant_config[op_name] = {"fp8_config": cfg.fp8_config}
+    quantizer = get_quantizer(model, quantizer_cls=FP8Quantizer, quant_config=quant_config)
+    model = quantizer.execute(model, mode=mode)
+    model.qconfig = configs_mapping
+    if mode != Mode.PREPARE:
+        model.save = MethodType(_fp8_save, model)
     postprocess_model(model, mode, quantizer)
     return model

@@ -12,16 +12,16 @@ from typing import List, Optional
 import torch
 
 from ...common.base_config import BaseConfig, register_config
-from ...common.utils import AWQ, DEFAULT_WHITE_LIST, GPTQ, MX_QUANT, RTN, SMOOTH_QUANT
+from ...common.utils import AWQ, DEFAULT_WHITE_LIST, FP8_QUANT, GPTQ, MX_QUANT, RTN, SMOOTH_QUANT
 from ..utils.utility import (
-    LM_HEAD_NAMES, PRIORITY_AWQ, PRIORITY_GPTQ, PRIORITY_MX_QUANT, PRIORITY_RTN, PRIORITY_SMOOTH_QUANT, WOQ_WHITE_LIST, is_fused_experts,
+    LM_HEAD_NAMES, PRIORITY_AWQ, PRIORITY_FP8_QUANT, PRIORITY_GPTQ, PRIORITY_MX_QUANT, PRIORITY_RTN, PRIORITY_SMOOTH_QUANT, WOQ_WHITE_LIST, is_fused_experts,
 )
 
 FRAMEWORK_NAME = "torch"
 
 __all__ = [
     "RTNConfig", "GPTQConfig", "AWQConfig", "get_default_rtn_config", "get_default_gptq_config",
-    "get_default_awq_config", "SmoothQuantConfig", "get_default_sq_config", "MXQuantConfig", "get_default_mx_config", "FRAMEWORK_NAME",
+    "get_default_awq_config", "SmoothQuantConfig", "get_default_sq_config", "MXQuantConfig", "get_default_mx_config", "FP8Config", "get_default_fp8_config", "FRAMEWORK_NAME",
 ]
 
 
@@ -370,3 +370,66 @@ class MXQuantConfig(TorchBaseConfig):
 
 def get_default_mx_config() -> MXQuantConfig:
     return MXQuantConfig()
+
+
+@register_config(framework_name=FRAMEWORK_NAME, algo_name=FP8_QUANT, priority=PRIORITY_FP8_QUANT)
+class FP8Config(TorchBaseConfig):
+    """FP8 linears: OCP e4m3 weights with one fp32 scale per output channel and e4m3 activations with one fp32 scale per token,
+    computed at run time ("FP8 dynamic"), on the f8f6f4 matrix instruction of the MI355X.
+
+    The class name is the reference's; the fields are this cell's.  The reference's FP8Config drives a Gaudi workflow (measure / quantize
+    modes, scale methods, measurement dump files) that is not reproduced here: this algorithm is data-free and has exactly one cell, so
+    the fields name that cell and every other value raises NotImplementedError -- a deliberate deviation, of the same kind as
+    MXQuantConfig's defaults.
+      fp8_config="E4M3"             the element format ("E5M2" is not built); "fp32" (through `set_local`) leaves a layer float
+      act_granularity="per_token"   one activation scale per row of the flattened input, from that row's max |x|
+      w_granularity="per_channel"   one weight scale per output channel
+      dynamic_quantization=True     activation scales come from the data of the call; static (calibrated) scales are not built
+      quant_lm_head=False           lm_head stays float unless set
+    Fused MoE experts modules are left alone."""
+
+    name = FP8_QUANT
+    supported_configs: List = []
+
+    def __init__(
+        self,
+        fp8_config: str = "E4M3",
+        act_granularity: str = "per_token",
+        w_granularity: str = "per_channel",
+        dynamic_quantization: bool = True,
+        quant_lm_head: bool = False,
+        white_list: Optional[List] = DEFAULT_WHITE_LIST,
+        **kwargs,
+    ):
+        super().__init__(white_list=white_list)
+        _assign(self, locals(), ["fp8_config", "act_granularity", "w_granularity", "dynamic_quantization", "quant_lm_head"])
+        if fp8_config != "fp32":
+            unsupported = []
+            if fp8_config != "E4M3":
+                unsupported.append(f'fp8_config must be "E4M3" (OCP e4m3fn), got {fp8_config!r}')
+            if act_granularity != "per_token":
+                unsupported.append(f'act_granularity must be "per_token", got {act_granularity!r}')
+            if w_granularity != "per_channel":
+                unsupported.append(f'w_granularity must be "per_channel", got {w_granularity!r}')
+            if dynamic_quantization is not True:
+                unsupported.append("dynamic_quantization must be True (static activation scales are not built)")
+            if unsupported:
+                raise NotImplementedError("FP8 on MI355X: " + "; ".join(unsupported))
+        self._post_init()
+
+    def to_config_mapping(self, config_list=None, model_info=None):
+        if not self.quant_lm_head:
+            self.set_local(LM_HEAD_NAMES, self.__class__(fp8_config="fp32"))
+        return super().to_config_mapping(config_list, model_info)
+
+    @staticmethod
+    def get_model_info(model: torch.nn.Module, example_inputs=None):
+        return [(name, type(m).__name__) for name, m in model.named_modules() if isinstance(m, torch.nn.Linear)]
+
+    @classmethod
+    def register_supported_configs(cls):
+        cls.supported_configs = []
+
+
+def get_default_fp8_config() -> FP8Config:
+    return FP8Config()

@@ -39,6 +39,7 @@ LM_HEAD_NAMES = [".*lm_head", ".*output_layer", ".*embed_out"]  # reference torc
 PRIORITY_GPTQ, PRIORITY_RTN, PRIORITY_AWQ = 90, 80, 70  # reference torch/utils/constants.py:45-48
 PRIORITY_SMOOTH_QUANT = 60
 PRIORITY_MX_QUANT = 50
+PRIORITY_FP8_QUANT = 40
 
 algos_mapping = {}
 

@@ -18,6 +18,8 @@
 // A mixed fp4 x fp8 product also runs with the fp4 nibbles swapped (hypothesis N'), which must FAIL: it shows the data tells the two
 // nibble orders apart.  A same-format product cannot see the element order inside a lane, and no product can see a relabelling of
 // the blocks applied to A, B and both scales alike: H is established up to those, which is all a kernel can depend on.
+// Last case (for gemm_fp8.hip): the UNSCALED opcode v_mfma_f32_*_f8f6f4 against the scaled one with every scale byte
+// 127, fp8 x fp8 on the same data, both shapes -- they must agree bit for bit and with the exact product.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -42,6 +44,25 @@ __global__ void one_mfma(const int* __restrict__ a, const int* __restrict__ b, c
   } else {
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     acc = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(av, bv, acc, CB, BL, OA, sa[l], OB, sb[l]);
+    for (int r = 0; r < 4; ++r) c[l * 16 + r] = acc[r];
+  }
+}
+
+// the same instruction through the builtin with LITERAL zero scale operands, which the compiler emits as the unscaled opcode
+// v_mfma_f32_*_f8f6f4 (no scale register): gemm_fp8.hip relies on it meaning "both scales 1.0" -- a RUNTIME scale byte of 0 is 2^-127
+template <int R>
+__global__ void one_mfma_unscaled(const int* __restrict__ a, const int* __restrict__ b, const int*, const int*, float* __restrict__ c) {
+  const int l = threadIdx.x;
+  i32x8 av, bv;
+  for (int d = 0; d < 8; ++d) { av[d] = a[l * 8 + d]; bv[d] = b[l * 8 + d]; }
+  if constexpr (R == 32) {
+    f32x16 acc;
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(av, bv, acc, 0, 0, 0, 0, 0, 0);
+    for (int r = 0; r < 16; ++r) c[l * 16 + r] = acc[r];
+  } else {
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    acc = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(av, bv, acc, 0, 0, 0, 0, 0, 0);
     for (int r = 0; r < 4; ++r) c[l * 16 + r] = acc[r];
   }
 }
@@ -190,6 +211,23 @@ int main() {
     printf("scale bytes A=%3d B=%3d, 1 * 1: C[0][0] = %.9g (0x%08x), 2^(A + B - 254) = %.9g  %s\n", e.sa, e.sb, (double)out[0], bits,
            e.want, ok ? "ok" : "DIFFERS");
     failures += !ok;
+  }
+  // unscaled opcode against the scaled one with every scale byte 127, fp8 x fp8, on the asymmetric data above, both shapes
+  for (const int R : {32, 16}) {
+    static float scaled[1024], unscaled[1024];
+    fill(p, R);
+    for (int i = 0; i < R; ++i)
+      for (int b = 0; b < 4; ++b) { p.SA[i][b] = 127; p.SB[i][b] = 127; }
+    const Variant vs = {R, 0, 0, 0, 0, R == 32 ? one_mfma<32, 0, 0, 0, 0> : one_mfma<16, 0, 0, 0, 0>};
+    const Variant vu = {R, 0, 0, 0, 0, R == 32 ? one_mfma_unscaled<32> : one_mfma_unscaled<16>};
+    if (run(p, vs, false, false, scaled) || run(p, vu, false, false, unscaled)) return 2;
+    const int nr = R == 32 ? 16 : 4;
+    int differ = 0;
+    for (int l = 0; l < 64; ++l) differ += memcmp(&scaled[l * 16], &unscaled[l * 16], nr * 4) != 0;
+    const int bad_s = mismatches(p, scaled), bad_u = mismatches(p, unscaled);
+    printf("%dx%dx%d  fp8 x fp8, unscaled opcode against scaled with bytes 127: %d / 64 lanes differ in bits; against the exact product: "
+           "scaled %d, unscaled %d of %d differ  %s\n", R, R, p.KD, differ, bad_s, bad_u, R * R, differ || bad_s || bad_u ? "DIFFERS" : "ok");
+    failures += differ || bad_s || bad_u;
   }
   printf("%s\n", failures ? "MX LAB: FINDINGS CONTRADICT THE HYPOTHESIS" : "MX LAB: hypothesis H holds");
   return failures ? 1 : 0;
