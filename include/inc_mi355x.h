@@ -721,13 +721,40 @@ int inc_mx_moe_gemm(int mode, const uint8_t* aq, const uint8_t* as, int afmt, co
  *   above: no workspace, repeated calls are bit-identical, and acc is bit for bit that of inc_mx_gemv with every scale byte 127.
  *   Reads nothing past row M - 1 of xq or row N - 1 of wq.
  * Both products: INC_ERR_UNSUPPORTED (nothing launched) for Kp % 128 != 0, a ydtype other than bf16 / fp16 or (gemv) M > 16;
- *   INC_ERR_BAD_ARG for a NULL operand, a size < 1 or a misaligned pointer.  All three validate their arguments before any HIP call. */
+ *   INC_ERR_BAD_ARG for a NULL operand, a size < 1 or a misaligned pointer.  All three validate their arguments before any HIP call.
+ * inc_fp8_moe_gemm (csrc/gemm_fp8_moe.hip, K17e): the product of inc_fp8_gemm per expert over the rows inc_moe_route sorted -- the two
+ *   F.linear of transformers' MixtralExperts.forward (also the Qwen2-MoE / Qwen3-MoE / OLMoE experts) for FP8 experts.  One forward is
+ *   inc_moe_route -> inc_fp8_quant_rows(x) -> inc_fp8_moe_gemm(0) -> inc_fp8_quant_rows(h) -> inc_fp8_moe_gemm(1) -> inc_moe_combine
+ *   on `stream`.  `route` is K4e's buffer, unchanged ([0] tile count, offsets [E+1], order [S], pos [S], tiles of 64 rows; S = T *
+ *   top_k).  wq [E, N, Kp] uint8, alpha fp32 [E, N]: slice e of both is exactly what inc_fp8_quant_rows writes for expert e's [N, K]
+ *   matrix.  For position p of the sorted order and the expert e whose range holds p, acc[p, n] = sum_k aq[row, k] * wq[e, n, k] is
+ *   the fp32 accumulator of v_mfma_f32_16x16x128_f8f6f4 over the row's K-tiles in inc_mx_moe_gemm's fixed order (wave w of 8 takes
+ *   the tiles w, w + 8, ... ascending, the 8 partials are added in wave order; repeated calls are bit-identical; bit for bit the
+ *   accumulator of inc_mx_moe_gemm (fp8, fp8) with every scale byte 127, and for one expert's rows that of inc_fp8_gemv), and
+ *   f(r, n) = a_scale[r] * alpha[e, n] is one fp32 multiply:
+ *     mode 2 (plain, gathered):   aq [T, Kp], a_scale [T]; r = order[p] / top_k; out [S, N] fp32 = f(r, n) * acc[p, n] (one fp32
+ *            multiply)
+ *     mode 0 (gate_up, gathered, N = 2I): gate rows 0 .. I-1 and up rows I .. 2I-1 of the expert; r as in mode 2; out [S, I] of odtype
+ *            (INC_BF16 / INC_F16), out[p, j] = rd(g / (1.f + expf(-g)) * u), g = f(r, j) * acc[p, j], u = f(r, I + j) * acc[p, I + j],
+ *            formed in fp32, rounded once
+ *     mode 1 (down, in place):    aq [S, Kp], a_scale [S] in sorted order, r = p; out [S, N] fp32 = w[order[p]] * (f(p, n) * acc[p, n])
+ *            (three fp32 multiplies in that association; no add, so nothing contracts), routing_weights w [T, top_k] of wdtype
+ *            INC_F32 / INC_BF16 / INC_F16
+ *   odtype is INC_F32 in modes 1 and 2.  Positions >= offsets[E] are never written, and source rows that no valid position names are
+ *   never read, their a_scale entry included.  aq / wq 16-byte aligned, a_scale / alpha 4-byte aligned; out is stored 4 columns at a
+ *   time when its width is a multiple of 4 and it is aligned to that store, element by element otherwise.  No workspace, no counters.
+ *   INC_ERR_UNSUPPORTED (nothing launched) for Kp % 128 != 0, E > 512, S > 2^22, mode 0 with odd N, a bad odtype or (mode 1) wdtype;
+ *   INC_ERR_BAD_ARG for a NULL operand (routing_weights: mode 1 only), a size < 1 or a misaligned pointer.  Validated before any HIP
+ *   call.                                                                                                                          */
 int inc_fp8_quant_rows(const void* x, int xdtype, int64_t M, int64_t K, int64_t Kp, const float* in_scale, uint8_t* codes,
                        float* row_scale, inc_stream_t stream);
 int inc_fp8_gemm(const uint8_t* xq, const float* row_scale, const uint8_t* wq, const float* alpha, const void* bias, void* y, int ydtype,
                  int64_t M, int64_t N, int64_t Kp, inc_stream_t stream);
 int inc_fp8_gemv(const uint8_t* xq, const float* row_scale, const uint8_t* wq, const float* alpha, const void* bias, void* y, int ydtype,
                  int64_t M, int64_t N, int64_t Kp, inc_stream_t stream);
+int inc_fp8_moe_gemm(int mode, const uint8_t* aq, const float* a_scale, const int32_t* route, const uint8_t* wq, const float* alpha,
+                     const void* routing_weights, int wdtype, void* out, int odtype, int64_t T, int top_k, int64_t E, int64_t N,
+                     int64_t Kp, inc_stream_t stream);
 
 /* ---- measured ceilings (bench.py `ceilings`) -- measurement helpers, not on the hot path ------------- *
  * inc_probe_hbm_triad: a <- b + s*c over n fp32 (n % 4 == 0): 12 n bytes of HBM traffic per call.

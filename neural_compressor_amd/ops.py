@@ -1806,3 +1806,29 @@ def fp8_gemv(xq, row_scale, wq, alpha, bias, out_dtype):
     """fp8_gemm's product for up to FP8_GEMV_MAX_M rows of x on v_mfma_f32_16x16x128_f8f6f4 (inc_fp8_gemv): one workgroup per 16 weight
     rows, K split over its waves, no workspace."""
     return _fp8_product(lib.inc_fp8_gemv, "inc_fp8_gemv", xq, row_scale, wq, alpha, bias, out_dtype)
+
+
+def fp8_moe_gemm(mode, aq, a_scale, route, wq, alpha, T, top_k, routing_weights=None, out=None, out_dtype=None):
+    """inc_fp8_moe_gemm (K17e): fp8_gemm's product per expert over the rows of the route's sorted order.  wq [E, N, Kp], alpha fp32
+    [E, N] (slice e = fp8_quant_rows of expert e's matrix).  mode 0: gate_up + SiLU product -> [T*k, N/2] of `out_dtype` (bf16 / fp16)
+    from aq [T, Kp], a_scale [T]; mode 1: down x routing weight -> fp32 [T*k, N] from aq [T*k, Kp], a_scale [T*k] in sorted order;
+    mode 2: plain -> fp32 [T*k, N] from aq [T, Kp].  Rows past the route's valid positions are not written."""
+    dev = _dev(aq, a_scale, route, wq, alpha, routing_weights)
+    E, N, Kp = wq.shape
+    S = T * top_k
+    assert aq.dtype == torch.uint8 and wq.dtype == torch.uint8 and a_scale.dtype == torch.float32 and alpha.dtype == torch.float32
+    assert aq.shape == ((S if mode == 1 else T), Kp) and a_scale.numel() == aq.shape[0] and alpha.shape == (E, N)
+    assert aq.is_contiguous() and a_scale.is_contiguous() and wq.is_contiguous() and alpha.is_contiguous()
+    if mode == 0:
+        odt = out.dtype if out is not None else out_dtype
+        if odt not in (torch.bfloat16, torch.float16):
+            raise TypeError("fp8_moe_gemm mode 0 writes bf16 or fp16: pass out_dtype")
+    else:
+        odt = torch.float32
+    if out is None:
+        out = torch.empty((S, N // 2 if mode == 0 else N), dtype=odt, device=dev)
+    wdt = dtype_code(routing_weights.dtype) if routing_weights is not None else INC_F32
+    with torch.cuda.device(dev):
+        check(lib.inc_fp8_moe_gemm(mode, _ptr(aq), _ptr(a_scale), _ptr(route), _ptr(wq), _ptr(alpha), _ptr(routing_weights), wdt,
+                                   _ptr(out), dtype_code(odt), T, top_k, E, N, Kp, _stream()), "inc_fp8_moe_gemm")
+    return out

@@ -1,3 +1,4 @@
+from .experts import FP8Experts  # noqa: F401  (importable from here; __all__ keeps the four names tests/test_fp8_cpu.py pins)
 from .fp8_quant import FP8Linear, FP8Quantizer
 from .save_load import load, save
 

@@ -4,14 +4,15 @@ The weight is quantised once to OCP e4m3 codes with one fp32 scale per output ch
 with one fp32 scale per token (`inc_fp8_quant_rows` for both), and `inc_fp8_gemm` multiplies the codes on v_mfma_f32_32x32x64_f8f6f4
 and applies `row_scale[m] * w_scale[n]` in its epilogue; a decode-sized batch (up to 16 rows) takes `inc_fp8_gemv` on the 16x16x128
 form of the instruction.  The specification in bits is the comment of the entry points in include/inc_mi355x.h.
-The algorithm is data-free: `prepare` returns the model unchanged and `convert` swaps every selected nn.Linear.
+The algorithm is data-free: `prepare` returns the model unchanged and `convert` swaps every selected nn.Linear and, under
+`FP8Config(moe_experts=True)`, every selected fused MoE experts module (FP8Experts, experts.py).
 """
 
 import torch
 
 from .... import ops
 from ....common.utils import logger
-from ...utils.utility import get_module, set_module
+from ...utils.utility import get_module, is_fused_experts, set_module
 from ..base_algorithm import Quantizer
 
 
@@ -79,18 +80,35 @@ class FP8Linear(torch.nn.Module):
 
 
 class FP8Quantizer(Quantizer):
-    """quant_config: {layer name: {"fp8_config"}} (fp8_quant_entry).  A layer whose fp8_config is "fp32" stays float; only nn.Linear
-    modules are converted (fused MoE experts modules are left alone)."""
+    """quant_config: {layer name: {"fp8_config"}} (fp8_quant_entry).  A layer whose fp8_config is "fp32" stays float.  Besides
+    nn.Linear the names may be fused MoE experts modules (is_fused_experts; they are in the mapping under
+    FP8Config(moe_experts=True) only), which become FP8Experts."""
 
     def _selected(self, model):
-        return [name for name, cfg in self.quant_config.items()
-                if cfg.get("fp8_config", "fp32") != "fp32" and isinstance(get_module(model, name), torch.nn.Linear)]
+        from .experts import unsupported_reason
+
+        out = []
+        for name, cfg in self.quant_config.items():
+            if cfg.get("fp8_config", "fp32") == "fp32":
+                continue
+            mod = get_module(model, name)
+            if isinstance(mod, torch.nn.Linear):
+                out.append(name)
+            elif is_fused_experts(mod):
+                why = unsupported_reason(mod, cfg)
+                if why is None:
+                    out.append(name)
+                else:
+                    logger.warning("FP8: experts module %s stays in floating point: %s", name, why)
+        return out
 
     def prepare(self, model, *args, **kwargs):
         return model  # data-free: nothing to calibrate
 
     @torch.no_grad()
     def convert(self, model, *args, **kwargs):
+        from .experts import FP8Experts
+
         dev = torch.device("cuda", torch.cuda.current_device())
         model.to(dev)
         model.eval()
@@ -98,6 +116,8 @@ class FP8Quantizer(Quantizer):
         if not names:
             logger.warning("FP8: no nn.Linear selected, the model is returned unchanged")
         for name in names:
-            set_module(model, name, FP8Linear.from_float(get_module(model, name), device=dev))
+            mod = get_module(model, name)
+            cls = FP8Linear if isinstance(mod, torch.nn.Linear) else FP8Experts
+            set_module(model, name, cls.from_float(mod, device=dev))
         model.fp8_info = {"fp8_config": "E4M3", "act_granularity": "per_token", "w_granularity": "per_channel"}
         return model

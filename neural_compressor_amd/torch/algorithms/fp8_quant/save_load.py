@@ -1,6 +1,9 @@
 """save / load of an FP8 model (`model.save(output_dir)`, `load(output_dir, original_model)`), the files of mx_quant/save_load.py:
   quantized_weight.pt   state_dict: uint8 `qweight`, fp32 `w_scale`, bias of every FP8Linear; the float parameters of everything else
-  qconfig.json          {"fp8_quant": {fp8_config, act_granularity, w_granularity}, "fp8_modules": [name, ...]}
+  qconfig.json          {"fp8_quant": {fp8_config, act_granularity, w_granularity}, "fp8_modules": [name, ...],
+                         "fp8_experts": {name: [E, H, I]}}
+FP8Experts modules save their four buffers under their own names.  The "fp8_experts" key is written only when the model has such
+modules; a directory without it (a model without them, or one written before FP8Experts existed) loads as before.
 """
 
 import json
@@ -8,7 +11,8 @@ import os
 
 import torch
 
-from ...utils.utility import get_module, set_module
+from ...utils.utility import get_module, is_fused_experts, set_module
+from .experts import FP8Experts
 from .fp8_quant import FP8Linear
 
 WEIGHT_NAME = "quantized_weight.pt"
@@ -17,8 +21,20 @@ QCONFIG_NAME = "qconfig.json"
 
 def qconfig_of(model):
     """The content of qconfig.json."""
-    return {"fp8_quant": dict(getattr(model, "fp8_info", {})),
-            "fp8_modules": [n for n, m in model.named_modules() if isinstance(m, FP8Linear)]}
+    cfg = {"fp8_quant": dict(getattr(model, "fp8_info", {})),
+           "fp8_modules": [n for n, m in model.named_modules() if isinstance(m, FP8Linear)]}
+    experts = {n: [m.num_experts, m.hidden_dim, m.intermediate_dim] for n, m in model.named_modules() if isinstance(m, FP8Experts)}
+    if experts:  # a model without FP8Experts writes the file it always wrote
+        cfg["fp8_experts"] = experts
+    return cfg
+
+
+def _take(state, name, new, dev):
+    """Load `name.*` of `state` into `new` (strict) and drop those keys."""
+    own = {k[len(name) + 1:]: v for k, v in state.items() if k.startswith(name + ".")}
+    new.load_state_dict({k: v.to(dev) for k, v in own.items()}, strict=True)
+    for k in own:
+        state.pop(name + "." + k)
 
 
 def save(model, output_dir="./saved_results"):
@@ -42,10 +58,14 @@ def load(output_dir, original_model, device="cuda"):
         ft = state[name + ".bias"].dtype if (name + ".bias") in state else (
             lin.weight.dtype if lin.weight.dtype in (torch.float16, torch.bfloat16) else torch.float16)
         new = FP8Linear(lin.in_features, lin.out_features, bias=(name + ".bias") in state, device=dev, float_type=ft)
-        own = {k[len(name) + 1:]: v for k, v in state.items() if k.startswith(name + ".")}
-        new.load_state_dict({k: v.to(dev) for k, v in own.items()}, strict=True)
-        for k in own:
-            state.pop(name + "." + k)
+        _take(state, name, new, dev)
+        set_module(original_model, name, new)
+    for name, (E, H, I) in cfg.get("fp8_experts", {}).items():
+        old = get_module(original_model, name)
+        assert is_fused_experts(old), f"{name}: expected a fused experts module in the float architecture, got {type(old).__name__}"
+        pd = old.gate_up_proj.dtype
+        new = FP8Experts(E, H, I, act_fn=old.act_fn, device=dev, float_type=pd if pd in (torch.float16, torch.bfloat16) else torch.float16)
+        _take(state, name, new, dev)
         set_module(original_model, name, new)
     original_model.load_state_dict(state, strict=False, assign=True)
     original_model.to(dev)

@@ -216,8 +216,8 @@ def _fp8_save(self, output_dir="./saved_results", **kwargs):
 @register_algo(FP8_QUANT)
 @torch.no_grad()
 def fp8_quant_entry(model, configs_mapping, mode=Mode.QUANTIZE, *args, **kwargs):
-    """The per-token / per-channel e4m3 cell: the plain dict per Linear goes to FP8Quantizer; the result carries FP8Linear modules.
-    Data-free: prepare changes nothing."""
+    """The per-token / per-channel e4m3 cell: the plain dict per Linear (and, under FP8Config(moe_experts=True), per fused experts
+    module) goes to FP8Quantizer; the result carries FP8Linear and FP8Experts modules.  Data-free: prepare changes nothing."""
     from ..algorithms.fp8_quant import FP8Quantizer
 
     quant_config = {}

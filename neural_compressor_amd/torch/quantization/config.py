@@ -386,7 +386,12 @@ class FP8Config(TorchBaseConfig):
       w_granularity="per_channel"   one weight scale per output channel
       dynamic_quantization=True     activation scales come from the data of the call; static (calibrated) scales are not built
       quant_lm_head=False           lm_head stays float unless set
-    Fused MoE experts modules are left alone."""
+      moe_experts=False             True also converts the fused MoE experts modules (is_fused_experts: Mixtral / Qwen2-MoE / Qwen3-MoE /
+                                    OLMoE `*Experts` with SiLU, up to 512 experts) to FP8Experts; `set_local(name,
+                                    FP8Config(fp8_config="fp32"))` keeps one of them float.  GPTQConfig and MXQuantConfig call their
+                                    switch `quant_experts`; this one is `moe_experts` -- a deliberate deviation in the name: an
+                                    FP8Config has no `quant_experts` attribute (tests/test_fp8_cpu.py pins that).
+    Without the flag fused MoE experts modules stay float."""
 
     name = FP8_QUANT
     supported_configs: List = []
@@ -398,11 +403,13 @@ class FP8Config(TorchBaseConfig):
         w_granularity: str = "per_channel",
         dynamic_quantization: bool = True,
         quant_lm_head: bool = False,
+        moe_experts: bool = False,
         white_list: Optional[List] = DEFAULT_WHITE_LIST,
         **kwargs,
     ):
         super().__init__(white_list=white_list)
-        _assign(self, locals(), ["fp8_config", "act_granularity", "w_granularity", "dynamic_quantization", "quant_lm_head"])
+        _assign(self, locals(), ["fp8_config", "act_granularity", "w_granularity", "dynamic_quantization", "quant_lm_head",
+                                 "moe_experts"])
         if fp8_config != "fp32":
             unsupported = []
             if fp8_config != "E4M3":
@@ -416,6 +423,16 @@ class FP8Config(TorchBaseConfig):
             if unsupported:
                 raise NotImplementedError("FP8 on MI355X: " + "; ".join(unsupported))
         self._post_init()
+
+    def extend_model_info(self, model, model_info):
+        """`moe_experts=True`: the fused MoE experts modules join the Linears (as MXQuantConfig.extend_model_info), so they get
+        (name, type) keys in the config mapping and FP8Quantizer converts them (algorithms/fp8_quant/experts.py).  `get_model_info`
+        itself keeps returning the Linears only."""
+        if not self.moe_experts:
+            return model_info
+        have = set(model_info)
+        extra = [(name, type(m).__name__) for name, m in model.named_modules() if is_fused_experts(m)]
+        return list(model_info) + [e for e in extra if e not in have]
 
     def to_config_mapping(self, config_list=None, model_info=None):
         if not self.quant_lm_head:
