@@ -778,7 +778,8 @@ int inc_trace_marker(int id, inc_stream_t stream);
  * inc_fwd_rope: q [B, Hq, T, D], k [B, Hk, T, D] (Hk may differ: GQA), cos / sin contiguous [cs_batch, T, D] with cs_batch 1 or B;
  *   out[.., d] = DT(DT(x[d] * cos[d]) + DT(r[d] * sin[d])), r[d] = -x[d + D/2] for d < D/2, else x[d - D/2].  `strides`: HOST array
  *   of 12 element strides, (b, h, t) of q, k, q_out, k_out in that order (the d stride is 1); each a non-negative multiple of 8.
- *   INC_ERR_UNSUPPORTED unless D % 16 == 0 and B * T * (Hq + Hk) * D / 16 < 2^31.
+ *   INC_ERR_UNSUPPORTED unless D % 16 == 0 and B * T * (Hq + Hk) * D / 16 < 2^31.  D / 16 a power of two up to 64 (D = 16 .. 1024) runs
+ *   the walker (a wave per token, cos / sin pieces held in registers across the heads), any other D one lane per 16-byte piece.
  * inc_fwd_rmsnorm: LlamaRMSNorm.forward on row-major contiguous x [rows, cols], weight [cols]:
  *   out = DT(float(w) * float(DT(float(x) * rsqrt(mean(float(x)^2) + eps)))), the mean summed in the order of torch's reduction
  *   kernel for this shape (fwd_elementwise.hip).  INC_ERR_UNSUPPORTED unless rows >= 8, cols % 8 == 0 and 256 <= cols <= 16384:
@@ -787,6 +788,10 @@ int inc_fwd_silu_mul(const void* gate, const void* up, void* out, int64_t n, int
 int inc_fwd_rope(const void* q, const void* k, const void* cos, const void* sin, void* q_out, void* k_out, int64_t B, int64_t Hq,
                  int64_t Hk, int64_t T, int64_t D, const int64_t* strides, int64_t cs_batch, int dtype, inc_stream_t stream);
 int inc_fwd_rmsnorm(const void* x, const void* w, void* out, int64_t rows, int64_t cols, float eps, int dtype, inc_stream_t stream);
+/* inc_probe_round16: out[i] = DT(in[i]) for n fp32 values through the rounding helper of the three kernels above (pair-wise hardware
+ *   conversion for bf16 with torch's NaN rule -- every NaN becomes 0x7FC0 --, the hardware conversion for fp16), so that the helper can
+ *   be compared with torch's own `.to(dtype)` over every fp32 bit pattern.  `in` and `out` 16-byte aligned, any n > 0.           */
+int inc_probe_round16(const float* in, uint16_t* out, int64_t n, int dtype, inc_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -135,6 +135,7 @@ SIGNATURES = {
     "inc_awq_weight_scale_workspace_bytes": (c_int64, [c_int64, c_int64, c_int]),
     "inc_awq_weight_scale": (c_int, [_P, c_int, c_int64, c_int64, c_int, _P, _P, c_int64, _P]),
     "inc_fwd_silu_mul": (c_int, [_P, _P, _P, c_int64, c_int, _P]),
+    "inc_probe_round16": (c_int, [_P, _P, c_int64, c_int, _P]),
     "inc_fwd_rope": (c_int, [_P, _P, _P, _P, _P, _P, c_int64, c_int64, c_int64, c_int64, c_int64, _P, c_int64, c_int, _P]),
     "inc_fwd_rmsnorm": (c_int, [_P, _P, _P, c_int64, c_int64, c_float, c_int, _P]),
 }

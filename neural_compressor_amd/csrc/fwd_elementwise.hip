@@ -36,6 +36,48 @@ __device__ __forceinline__ float t_f32(uint16_t b) {
 template <int DT>
 __device__ __forceinline__ float t_rf(float f) { return t_f32<DT>(t_round<DT>(f)); }  // round to DT, back in fp32
 
+// The same roundings, eight values (one 16-byte piece) at a time.  bf16 goes through the hardware conversion, two values per
+// v_cvt_pk_bf16_f32 (round to nearest even, denormals kept) instead of ~6 integer instructions per value; what the hardware does NOT do
+// is torch's NaN rule (it keeps a NaN's sign and payload bits), so a piece that holds a NaN -- one unordered compare per pair tells --
+// is redone with t_round.  fp16 is the hardware conversion either way.
+template <int DT>
+__device__ __forceinline__ u32x4 round8(const float (&f)[8]) {
+  u32x4 v;
+  if constexpr (DT == INC_BF16) {
+    bool nan = false;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      v[i] = cvt_pair<true>(f[2 * i], f[2 * i + 1]);
+      nan |= __builtin_isunordered(f[2 * i], f[2 * i + 1]);
+    }
+    if (__builtin_expect(nan, 0)) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) v[i] = static_cast<uint32_t>(t_round<DT>(f[2 * i])) | (static_cast<uint32_t>(t_round<DT>(f[2 * i + 1])) << 16);
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) v[i] = static_cast<uint32_t>(t_round<DT>(f[2 * i])) | (static_cast<uint32_t>(t_round<DT>(f[2 * i + 1])) << 16);
+  }
+  return v;
+}
+// round to DT and back to fp32, in place: an INTERMEDIATE of a chain.  A NaN stays a NaN here (every value that gets here is the result
+// of an fp32 operation, so its NaN is quiet and the quiet bit survives the conversion) and its payload never reaches memory: whatever
+// is computed from it is a NaN again, and the chain's last rounding (round8) writes torch's 0x7FC0 for it.
+template <int DT>
+__device__ __forceinline__ void rf8(float (&f)[8]) {
+  if constexpr (DT == INC_BF16) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const uint32_t r = cvt_pair<true>(f[2 * i], f[2 * i + 1]);
+      f[2 * i] = __uint_as_float(r << 16);
+      f[2 * i + 1] = __uint_as_float(r & 0xffff0000u);
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) f[i] = t_rf<DT>(f[i]);
+  }
+}
+
 template <int DT>
 __device__ __forceinline__ void unpack8(const u32x4 v, float (&e)[8]) {
 #pragma unroll
@@ -43,12 +85,6 @@ __device__ __forceinline__ void unpack8(const u32x4 v, float (&e)[8]) {
     e[2 * i] = t_f32<DT>(static_cast<uint16_t>(v[i] & 0xffffu));
     e[2 * i + 1] = t_f32<DT>(static_cast<uint16_t>(v[i] >> 16));
   }
-}
-__device__ __forceinline__ u32x4 pack8(const uint16_t (&b)[8]) {
-  u32x4 v;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) v[i] = static_cast<uint32_t>(b[2 * i]) | (static_cast<uint32_t>(b[2 * i + 1]) << 16);
-  return v;
 }
 __device__ __forceinline__ u32x4 ld_nt(const void* p, int64_t i16) { return __builtin_nontemporal_load(static_cast<const u32x4*>(p) + i16); }
 __device__ __forceinline__ void st_nt(void* p, int64_t i16, u32x4 v) { __builtin_nontemporal_store(v, static_cast<u32x4*>(p) + i16); }
@@ -67,13 +103,16 @@ __global__ __launch_bounds__(256) void fwd_silu_mul_kernel(const void* __restric
   const int64_t n8 = n >> 3;
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i < n8) {
+#pragma clang fp contract(off)
     float g[8], u[8];
     unpack8<DT>(ld_nt(gate, i), g);
     unpack8<DT>(ld_nt(up, i), u);
-    uint16_t r[8];
 #pragma unroll
-    for (int e = 0; e < 8; ++e) r[e] = silu_mul_one<DT>(g[e], u[e]);
-    st_nt(out, i, pack8(r));
+    for (int e = 0; e < 8; ++e) g[e] = g[e] / (1.0f + expf(-g[e]));
+    rf8<DT>(g);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) g[e] = g[e] * u[e];
+    st_nt(out, i, round8<DT>(g));
   } else {
     const int64_t e = n8 * 8 + (i - n8);  // the n % 8 tail, one element per lane
     if (e < n) {
@@ -91,11 +130,119 @@ struct RopeStrides {
   int64_t q[3], k[3], qo[3], ko[3];  // element strides of the b, h, t dimensions; the d stride is 1
 };
 
+// one head of one token: the 16-byte pieces at d and d + D/2 and the four cos / sin pieces (unpacked) that go with them.
+// `sign2` is 0x80008000, handed in as a kernel ARGUMENT: eager negates x2 in a kernel of its own, so a NaN there has its sign flipped
+// before the multiply, and an fp16 result carries that sign to memory.  A negation the compiler can see is one it may move -- to sin, or
+// to the product (it did both: `v_pk_mul_f32 .. neg_lo:[0,1]`, `v_sub_f16`) -- which is the same number for everything but a NaN.  An
+// exclusive-or of the 16-bit patterns with a value it does not know stays where eager has it.  (bf16 writes 0x7FC0 for every NaN: no need.)
+template <int DT>
+__device__ __forceinline__ void rope_pieces(const u32x4 v_lo, const u32x4 v_hi, const float (&c_lo)[8], const float (&c_hi)[8],
+                                            const float (&s_lo)[8], const float (&s_hi)[8], const uint32_t sign2, u32x4& o_lo, u32x4& o_hi) {
+#pragma clang fp contract(off)
+  float lo[8], hi[8], a[8], b[8];
+  unpack8<DT>(v_lo, lo);
+  unpack8<DT>(v_hi, hi);
+  if constexpr (DT == INC_BF16) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) b[e] = -hi[e];
+  } else {
+    u32x4 n_hi;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) n_hi[i] = v_hi[i] ^ sign2;
+    unpack8<DT>(n_hi, b);
+  }
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    a[e] = lo[e] * c_lo[e];
+    b[e] = b[e] * s_lo[e];
+  }
+  rf8<DT>(a);
+  rf8<DT>(b);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) a[e] = a[e] + b[e];
+  o_lo = round8<DT>(a);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    a[e] = hi[e] * c_hi[e];
+    b[e] = lo[e] * s_hi[e];
+  }
+  rf8<DT>(a);
+  rf8<DT>(b);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) a[e] = a[e] + b[e];
+  o_hi = round8<DT>(a);
+}
+
+// The walker: one WAVE per token (b, t).  A lane owns one 16-byte piece of d (with its partner at d + D/2): it decodes its offsets once,
+// loads its four cos / sin pieces once and keeps them unpacked in registers, then walks the heads -- the q heads, then the k heads, each
+// tensor with its own strides.  D / 16 lanes cover a head, so the wave takes HPI = 64 / (D / 16) consecutive heads per iteration (8 for
+// D = 128: 2 KiB contiguous in the model's [B, T, H * D] layout) and strides by HPI heads; U iterations' loads are issued before the
+// first of them is used (2 U loads of 16 bytes in flight per lane).  D / 16 must be a power of two up to 64.
+constexpr int ROPE_WALK_U = 4;
+constexpr uint32_t ROPE_SIGN2 = 0x80008000u;  // the sign bits of two 16-bit values (see rope_pieces)
+
+template <int DT>
+__device__ __forceinline__ void rope_walk(const char* __restrict__ src, char* __restrict__ dst, const int64_t in_base, const int64_t out_base,
+                                          const int64_t in_hs, const int64_t out_hs, const uint32_t H, const uint32_t hsub, const uint32_t hpi,
+                                          const int64_t half, const float (&c_lo)[8], const float (&c_hi)[8], const float (&s_lo)[8],
+                                          const float (&s_hi)[8], const uint32_t sign2) {
+  for (uint32_t h0 = 0; h0 < H; h0 += hpi * ROPE_WALK_U) {  // (uniform over the wave)
+    u32x4 v_lo[ROPE_WALK_U], v_hi[ROPE_WALK_U];
+#pragma unroll
+    for (int u = 0; u < ROPE_WALK_U; ++u) {
+      const uint32_t h = h0 + u * hpi + hsub;
+      if (h < H) {
+        const int64_t off = in_base + (int64_t)h * in_hs;  // elements; a multiple of 8
+        v_lo[u] = ld_nt(src, off >> 3);
+        v_hi[u] = ld_nt(src, (off + half) >> 3);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < ROPE_WALK_U; ++u) {
+      const uint32_t h = h0 + u * hpi + hsub;
+      if (h < H) {
+        u32x4 o_lo, o_hi;
+        rope_pieces<DT>(v_lo[u], v_hi[u], c_lo, c_hi, s_lo, s_hi, sign2, o_lo, o_hi);
+        const int64_t off = out_base + (int64_t)h * out_hs;
+        st_nt(dst, off >> 3, o_lo);
+        st_nt(dst, (off + half) >> 3, o_hi);
+      }
+    }
+  }
+}
+
+template <int DT>
+__global__ __launch_bounds__(256) void fwd_rope_walk_kernel(const void* __restrict__ q, const void* __restrict__ k, const void* __restrict__ cosp,
+                                                            const void* __restrict__ sinp, void* __restrict__ q_out, void* __restrict__ k_out,
+                                                            uint32_t tokens, uint32_t Hq, uint32_t Hk, uint32_t T, uint32_t D, uint32_t d16_log2,
+                                                            uint32_t cs_batch, uint32_t sign2, RopeStrides st) {
+  const uint32_t token = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6));  // the same for the whole wave
+  if (token >= tokens) return;
+  const uint32_t b = token / T, t = token - b * T;
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t dc = lane & ((1u << d16_log2) - 1u), hsub = lane >> d16_log2, hpi = 64u >> d16_log2;
+  const int64_t half = D >> 1;
+  const int64_t cs_off = ((int64_t)(cs_batch == 1 ? 0 : b) * T + t) * D + dc * 8;
+
+  float c_lo[8], c_hi[8], s_lo[8], s_hi[8];
+  unpack8<DT>(static_cast<const u32x4*>(cosp)[cs_off >> 3], c_lo);
+  unpack8<DT>(static_cast<const u32x4*>(cosp)[(cs_off + half) >> 3], c_hi);
+  unpack8<DT>(static_cast<const u32x4*>(sinp)[cs_off >> 3], s_lo);
+  unpack8<DT>(static_cast<const u32x4*>(sinp)[(cs_off + half) >> 3], s_hi);
+
+  rope_walk<DT>(static_cast<const char*>(q), static_cast<char*>(q_out), (int64_t)b * st.q[0] + (int64_t)t * st.q[2] + dc * 8,
+                (int64_t)b * st.qo[0] + (int64_t)t * st.qo[2] + dc * 8, st.q[1], st.qo[1], Hq, hsub, hpi, half, c_lo, c_hi, s_lo, s_hi, sign2);
+  rope_walk<DT>(static_cast<const char*>(k), static_cast<char*>(k_out), (int64_t)b * st.k[0] + (int64_t)t * st.k[2] + dc * 8,
+                (int64_t)b * st.ko[0] + (int64_t)t * st.ko[2] + dc * 8, st.k[1], st.ko[1], Hk, hsub, hpi, half, c_lo, c_hi, s_lo, s_hi, sign2);
+}
+
+// the item-per-lane form: every (b, t, head, piece) is a lane of its own.  Kept for head sizes the walker does not take (D / 16 no power
+// of two, or above 64)
 template <int DT>
 __global__ __launch_bounds__(256) void fwd_rope_kernel(const void* __restrict__ q, const void* __restrict__ k, const void* __restrict__ cosp,
                                                        const void* __restrict__ sinp, void* __restrict__ q_out, void* __restrict__ k_out,
                                                        uint32_t total, uint32_t Hq, uint32_t Hk, uint32_t T, uint32_t D, uint32_t cs_batch,
-                                                       RopeStrides st) {
+                                                       uint32_t sign2, RopeStrides st) {
 #pragma clang fp contract(off)
   const uint32_t idx = blockIdx.x * 256u + threadIdx.x;
   if (idx >= total) return;
@@ -117,21 +264,16 @@ __global__ __launch_bounds__(256) void fwd_rope_kernel(const void* __restrict__ 
   const int64_t cs_off = ((int64_t)(cs_batch == 1 ? 0 : b) * T + t) * D + dc * 8;
   const int64_t half = D >> 1;
 
-  float lo[8], hi[8], c_lo[8], c_hi[8], s_lo[8], s_hi[8];
-  unpack8<DT>(ld_nt(src, in_off >> 3), lo);
-  unpack8<DT>(ld_nt(src, (in_off + half) >> 3), hi);
+  float c_lo[8], c_hi[8], s_lo[8], s_hi[8];
+  const u32x4 v_lo = ld_nt(src, in_off >> 3), v_hi = ld_nt(src, (in_off + half) >> 3);
   unpack8<DT>(static_cast<const u32x4*>(cosp)[cs_off >> 3], c_lo);
   unpack8<DT>(static_cast<const u32x4*>(cosp)[(cs_off + half) >> 3], c_hi);
   unpack8<DT>(static_cast<const u32x4*>(sinp)[cs_off >> 3], s_lo);
   unpack8<DT>(static_cast<const u32x4*>(sinp)[(cs_off + half) >> 3], s_hi);
-  uint16_t o_lo[8], o_hi[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    o_lo[e] = t_round<DT>(t_rf<DT>(lo[e] * c_lo[e]) + t_rf<DT>(-hi[e] * s_lo[e]));
-    o_hi[e] = t_round<DT>(t_rf<DT>(hi[e] * c_hi[e]) + t_rf<DT>(lo[e] * s_hi[e]));
-  }
-  st_nt(dst, out_off >> 3, pack8(o_lo));
-  st_nt(dst, (out_off + half) >> 3, pack8(o_hi));
+  u32x4 o_lo, o_hi;
+  rope_pieces<DT>(v_lo, v_hi, c_lo, c_hi, s_lo, s_hi, sign2, o_lo, o_hi);
+  st_nt(dst, out_off >> 3, o_lo);
+  st_nt(dst, (out_off + half) >> 3, o_hi);
 }
 
 // ---- RMSNorm --------------------------------------------------------------------------------------------------------------------
@@ -204,10 +346,12 @@ __global__ __launch_bounds__(WAVES == 1 ? 256 : 512) void fwd_rmsnorm_kernel(con
       float e[8], g[8];
       unpack8<DT>(v[j], e);
       unpack8<DT>(static_cast<const u32x4*>(w)[u], g);
-      uint16_t r[8];
 #pragma unroll
-      for (int i = 0; i < 8; ++i) r[i] = t_round<DT>(g[i] * t_rf<DT>(e[i] * rs));
-      st_nt(out, base + u, pack8(r));
+      for (int i = 0; i < 8; ++i) e[i] = e[i] * rs;
+      rf8<DT>(e);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) e[i] = g[i] * e[i];
+      st_nt(out, base + u, round8<DT>(e));
     }
   }
 }
@@ -216,6 +360,26 @@ template <int DT, int WAVES, int J>
 void rmsnorm_launch(const void* x, const void* w, void* out, int64_t rows, int cols, float eps, float factor, hipStream_t s) {
   constexpr int THREADS = WAVES == 1 ? 256 : 512, ROWS_PER_BLOCK = THREADS / 32 / WAVES;
   fwd_rmsnorm_kernel<DT, WAVES, J><<<(unsigned)ceil_div64(rows, ROWS_PER_BLOCK), THREADS, 0, s>>>(x, w, out, rows, cols, eps, factor);
+}
+
+// ---- the rounding helper on its own (inc_probe_round16): out[i] = DT(in[i]) through round8, the n % 8 tail through t_round -----------
+template <int DT>
+__global__ __launch_bounds__(256) void probe_round16_kernel(const float* __restrict__ in, uint16_t* __restrict__ out, int64_t n) {
+  const int64_t n8 = n >> 3;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n8) {
+    const u32x4 a = static_cast<const u32x4*>(static_cast<const void*>(in))[2 * i], b = static_cast<const u32x4*>(static_cast<const void*>(in))[2 * i + 1];
+    float f[8];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      f[e] = __uint_as_float(a[e]);
+      f[4 + e] = __uint_as_float(b[e]);
+    }
+    static_cast<u32x4*>(static_cast<void*>(out))[i] = round8<DT>(f);
+  } else {
+    const int64_t e = n8 * 8 + (i - n8);
+    if (e < n) out[e] = t_round<DT>(in[e]);
+  }
 }
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
@@ -254,12 +418,33 @@ int inc_fwd_rope(const void* q, const void* k, const void* cos, const void* sin,
   if (B >= (1ll << 31) || T >= (1ll << 31) || Hq + Hk >= (1ll << 31)) return INC_ERR_UNSUPPORTED;
   const double items = (double)B * (double)T * (double)(Hq + Hk) * (double)(D / 16);
   if (items >= 2147483648.0 - 256.0) return INC_ERR_UNSUPPORTED;  // the kernel decodes a 32-bit item index
+  const uint32_t d16 = (uint32_t)(D / 16);
+  if ((d16 & (d16 - 1u)) == 0 && d16 <= 64u) {  // the walker: one wave per token (B * T < 2^31 by the item count above)
+    const uint32_t tokens = (uint32_t)(B * T), lg = (uint32_t)__builtin_ctz(d16);
+    const unsigned wblocks = (tokens + 3u) / 4u;
+    if (dtype == INC_BF16)
+      fwd_rope_walk_kernel<INC_BF16><<<wblocks, 256, 0, inc_s(stream)>>>(q, k, cos, sin, q_out, k_out, tokens, (uint32_t)Hq, (uint32_t)Hk, (uint32_t)T, (uint32_t)D, lg, (uint32_t)cs_batch, ROPE_SIGN2, st);
+    else
+      fwd_rope_walk_kernel<INC_F16><<<wblocks, 256, 0, inc_s(stream)>>>(q, k, cos, sin, q_out, k_out, tokens, (uint32_t)Hq, (uint32_t)Hk, (uint32_t)T, (uint32_t)D, lg, (uint32_t)cs_batch, ROPE_SIGN2, st);
+    INC_LAUNCH_RETURN();
+  }
   const uint32_t total = (uint32_t)(B * T * (Hq + Hk) * (D / 16));
   const unsigned blocks = (total + 255u) / 256u;
   if (dtype == INC_BF16)
-    fwd_rope_kernel<INC_BF16><<<blocks, 256, 0, inc_s(stream)>>>(q, k, cos, sin, q_out, k_out, total, (uint32_t)Hq, (uint32_t)Hk, (uint32_t)T, (uint32_t)D, (uint32_t)cs_batch, st);
+    fwd_rope_kernel<INC_BF16><<<blocks, 256, 0, inc_s(stream)>>>(q, k, cos, sin, q_out, k_out, total, (uint32_t)Hq, (uint32_t)Hk, (uint32_t)T, (uint32_t)D, (uint32_t)cs_batch, ROPE_SIGN2, st);
   else
-    fwd_rope_kernel<INC_F16><<<blocks, 256, 0, inc_s(stream)>>>(q, k, cos, sin, q_out, k_out, total, (uint32_t)Hq, (uint32_t)Hk, (uint32_t)T, (uint32_t)D, (uint32_t)cs_batch, st);
+    fwd_rope_kernel<INC_F16><<<blocks, 256, 0, inc_s(stream)>>>(q, k, cos, sin, q_out, k_out, total, (uint32_t)Hq, (uint32_t)Hk, (uint32_t)T, (uint32_t)D, (uint32_t)cs_batch, ROPE_SIGN2, st);
+  INC_LAUNCH_RETURN();
+}
+
+int inc_probe_round16(const float* in, uint16_t* out, int64_t n, int dtype, inc_stream_t stream) {
+  INC_CHECK_ARG(in && out && n > 0);
+  if (dtype != INC_BF16 && dtype != INC_F16) return INC_ERR_UNSUPPORTED;
+  if (!aligned16(in) || !aligned16(out)) return INC_ERR_UNSUPPORTED;
+  const int64_t blocks = ceil_div64((n >> 3) + (n & 7), 256);
+  if (blocks > 0x7fffffff) return INC_ERR_UNSUPPORTED;
+  if (dtype == INC_BF16) probe_round16_kernel<INC_BF16><<<(unsigned)blocks, 256, 0, inc_s(stream)>>>(in, out, n);
+  else probe_round16_kernel<INC_F16><<<(unsigned)blocks, 256, 0, inc_s(stream)>>>(in, out, n);
   INC_LAUNCH_RETURN();
 }
 

@@ -508,7 +508,7 @@ extern "C" {
 // 12: + inc_gptq_hessian_accum_routed (GPTQ Hessians of fused MoE experts from routed rows)
 // (still 12: + inc_woq_gemm_multi_perm, inc_woq_gemm_gated[_workspace_bytes] -- new entry points only, no signature of 12 changed, and
 // tests/test_moe_gptq_cpu.py pins the number; the bindings fail loudly on a library that lacks a symbol; likewise inc_woq_gemv_anyw,
-// inc_woq_gemv_anyw_perm and inc_woq_gemv_anyw_multi[_workspace_bytes])
+// inc_woq_gemv_anyw_perm and inc_woq_gemv_anyw_multi[_workspace_bytes]; likewise inc_probe_round16)
 int inc_abi_version(void) { return 12; }
 const char* inc_target_arch(void) { return "gfx950"; }
 const char* inc_error_string(int code) {

@@ -1396,6 +1396,17 @@ def fwd_rope(q, k, cos, sin, q_out_strides, k_out_strides):
     return (q_out, k_out) if ok else None
 
 
+def probe_round16(x, dtype):
+    """fp32 `x` (contiguous) rounded to `dtype` (bf16 / fp16) by the rounding helper of the forward kernels (inc_probe_round16): what
+    tests compare with torch's own `x.to(dtype)` bit for bit."""
+    dev = _dev(x)
+    assert x.dtype == torch.float32 and dtype in (torch.bfloat16, torch.float16)
+    out = torch.empty(x.shape, dtype=dtype, device=x.device)
+    with torch.cuda.device(dev):
+        check(lib.inc_probe_round16(_ptr(x), _ptr(out), x.numel(), dtype_code(dtype), _stream()), "inc_probe_round16")
+    return out
+
+
 _HIP_RT = None
 
 

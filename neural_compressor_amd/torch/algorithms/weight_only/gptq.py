@@ -242,6 +242,10 @@ class HessianAccumulator:
     # eligible batch is still copied, and its version counter is compared when the update is launched (after the forward);
     # only if it is unchanged do the later forwards skip the copy.  A model that edits a Linear's input in place later in
     # the same forward therefore simply keeps the copying path.  (A class attribute: tests set it to False to force the copy.)
+    # The block driver carries an earned verdict (`_zc_ok is True`, never False or None) to the accumulators of the same layer in later
+    # blocks of the same class (RAWGPTQuantizer.quantize_block), which then skip the first copy and its [65536, K] buffer as well.  The
+    # version check at launch time (`_launch_item`) stays: a block that does write a Linear's input in place after the verdict gets
+    # that RuntimeError, not a silent copy.
     ZERO_COPY = True
 
     def __init__(self, columns, device):
@@ -694,6 +698,9 @@ class RAWGPTQuantizer(object):
         self._block_writes_input = None  # decided by the first block forward (see _run_block)
         self._fused = FusedForward()  # per-run state of the fused elementwise chains inside _run_block's forwards
         self._stacks = {}  # first batch index of a forward group -> (stacked hidden states, the list entries that are its slices)
+        # what a capture pass learns about a block CLASS and holds for every later block of it (quantize_block):
+        self._capture_order = {}  # (type(block), hooked names) -> order in which the hooked modules fired
+        self._zero_copy_ok = set()  # (type(block), layer name) whose accumulator earned HessianAccumulator._zc_ok = True
         self.block_callback = kwargs.get("block_callback", None)  # used by the multi-GPU driver
         # sample-sharded multi-GPU calibration: every rank feeds ITS calibration samples through prepare()/run_fn and the
         # per-layer Hessians are all-reduced before each solve; pass True (default process group) or a process group
@@ -1523,7 +1530,16 @@ class RAWGPTQuantizer(object):
             live, alias = {}, {}
             share = self.share_hessians
 
-            fired, seen, capture = [], set(), {"probe": True, "stop": None}
+            # The order in which the hooked modules run is learned by the first (complete) forward of a capture pass and REMEMBERED per
+            # block class and set of hooked names (the excluded layers are part of the key, one entry per `sequential`): a later block
+            # with the same key stops its very first forward at the last hooked module too.  A wrong memory costs only the early
+            # stop -- the hook never stops before every hooked module has been served -- and is dropped after the pass.
+            order_key = (type(block), tuple(layers))
+            remembered = self.__dict__.setdefault("_capture_order", {}).get(order_key) if CAPTURE_EARLY_STOP else None
+            if remembered is not None:
+                fired, seen, capture = list(remembered), set(), {"probe": False, "stop": remembered[-1], "stopped": False}
+            else:
+                fired, seen, capture = [], set(), {"probe": True, "stop": None, "stopped": False}
 
             def make_hook(name):
                 def body(inp):
@@ -1553,12 +1569,17 @@ class RAWGPTQuantizer(object):
 
             handles = [layers[n].register_forward_pre_hook(make_hook(n)) for n in layers]
             accs = [sv.acc for sv in solvers.values()]
-            for acc in accs:
-                acc.defer = True  # the Hessian updates of one forward go out as ONE launch, after that forward
+            zc_known = self.__dict__.setdefault("_zero_copy_ok", set())
+            for name, sv in solvers.items():
+                sv.acc.defer = True  # the Hessian updates of one forward go out as ONE launch, after that forward
+                if (type(block), name) in zc_known:
+                    sv.acc._zc_ok = True  # earned by an earlier block of this class (HessianAccumulator.ZERO_COPY)
 
             def after_forward(j, out):
                 live.clear()
                 seen.clear()
+                if out is None:
+                    capture["stopped"] = True  # _CaptureDone was raised: the forward ended at its last hooked module
                 HessianAccumulator.flush_many(accs, only_due=True)
                 if capture["probe"]:
                     # the first (complete) forward of the pass showed the order in which the hooked modules run: when each ran
@@ -1575,6 +1596,13 @@ class RAWGPTQuantizer(object):
                 acc.defer = False
             for h in handles:
                 h.remove()
+            if remembered is not None:
+                if not capture["stopped"]:  # this block runs its modules in another order: the next one probes again
+                    self._capture_order.pop(order_key, None)
+            elif capture["stop"] is not None:
+                self._capture_order[order_key] = tuple(fired)
+            zc_known.update((type(block), name) for name, sv in solvers.items() if sv.acc._zc_ok is True)
+
             def hybrid_gs(sv):  # group size of a hybrid-order solve (it shapes the factor: gptq.py:1203-1209), else 0
                 if not sv.cfg.get("hybrid_order", False):
                     return 0
