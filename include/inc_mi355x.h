@@ -722,6 +722,22 @@ int inc_mx_moe_gemm(int mode, const uint8_t* aq, const uint8_t* as, int afmt, co
  *   Reads nothing past row M - 1 of xq or row N - 1 of wq.
  * Both products: INC_ERR_UNSUPPORTED (nothing launched) for Kp % 128 != 0, a ydtype other than bf16 / fp16 or (gemv) M > 16;
  *   INC_ERR_BAD_ARG for a NULL operand, a size < 1 or a misaligned pointer.  All three validate their arguments before any HIP call.
+ * inc_fp8_gemv_multi (csrc/gemm_fp8_group.hip, K17g): 2 <= n <= 8 weight matrices that multiply the SAME x (q / k / v; gate / up) in
+ *   ONE launch over the strips of all members.  wq, alpha, bias, y and N are HOST arrays of n entries (the convention of
+ *   inc_mx_gemv_multi); bias may be NULL or hold NULL for a member without one; xq, row_scale, ydtype, M and Kp are common.  y[i] is
+ *   bit-identical to inc_fp8_gemv on member i alone (the same strip body) and nothing outside the [M, N[i]] elements at y[i] is
+ *   written.  Rejections as for inc_fp8_gemv, per member, and INC_ERR_UNSUPPORTED for n outside 2 .. 8.
+ * inc_fp8_gemv_gated (the same file): the gate / up pair of a gated MLP with the SiLU product in the epilogue, 1 <= M <= 16.
+ *   wq_gate, wq_up [N, Kp], alpha_gate, alpha_up fp32 [N], bias_gate, bias_up [N] in ydtype or NULL (each on its own); h [M, N]:
+ *     g = (row_scale[m] * alpha_gate[n]) * acc_gate[m,n] + bias_gate[n],  u = (row_scale[m] * alpha_up[n]) * acc_up[m,n] + bias_up[n]
+ *     h[m,n] = rd16(g / (1.f + expf(-g)) * u)
+ *   acc_gate / acc_up are inc_fp8_gemv's sums over the gate / up weight (one workgroup owns strip s of both, the 8 waves split K as
+ *   there, the two sets of 8 partials are added in wave order); g and u are inc_fp8_gemv's values BEFORE its rounding (the same
+ *   expression, the same possible contraction), the SiLU product is formed in fp32 and h is rounded once.  Without a bias h is bit
+ *   for bit inc_fp8_moe_gemm's mode 0 for one expert with weight cat(gate, up), alpha cat(alpha_gate, alpha_up) and every row routed
+ *   to it.  Below g ~ -88.7 expf(-g) is +inf and silu(g) is -0, which is the rounded exact value; g = -inf gives NaN.  The store rule
+ *   of y, the reads (nothing past row M - 1 of xq or row N - 1 of a weight) and the rejections are inc_fp8_gemv's.
+ *   Both validate their arguments before any HIP call; no workspace, no counters, repeated calls are bit-identical.
  * inc_fp8_moe_gemm (csrc/gemm_fp8_moe.hip, K17e): the product of inc_fp8_gemm per expert over the rows inc_moe_route sorted -- the two
  *   F.linear of transformers' MixtralExperts.forward (also the Qwen2-MoE / Qwen3-MoE / OLMoE experts) for FP8 experts.  One forward is
  *   inc_moe_route -> inc_fp8_quant_rows(x) -> inc_fp8_moe_gemm(0) -> inc_fp8_quant_rows(h) -> inc_fp8_moe_gemm(1) -> inc_moe_combine
@@ -752,6 +768,12 @@ int inc_fp8_gemm(const uint8_t* xq, const float* row_scale, const uint8_t* wq, c
                  int64_t M, int64_t N, int64_t Kp, inc_stream_t stream);
 int inc_fp8_gemv(const uint8_t* xq, const float* row_scale, const uint8_t* wq, const float* alpha, const void* bias, void* y, int ydtype,
                  int64_t M, int64_t N, int64_t Kp, inc_stream_t stream);
+int inc_fp8_gemv_multi(int n, const uint8_t* xq, const float* row_scale, const uint8_t* const* wq, const float* const* alpha,
+                       const void* const* bias, void* const* y, int ydtype, int64_t M, const int64_t* N, int64_t Kp,
+                       inc_stream_t stream);
+int inc_fp8_gemv_gated(const uint8_t* xq, const float* row_scale, const uint8_t* wq_gate, const float* alpha_gate,
+                       const void* bias_gate, const uint8_t* wq_up, const float* alpha_up, const void* bias_up, void* h, int ydtype,
+                       int64_t M, int64_t N, int64_t Kp, inc_stream_t stream);
 int inc_fp8_moe_gemm(int mode, const uint8_t* aq, const float* a_scale, const int32_t* route, const uint8_t* wq, const float* alpha,
                      const void* routing_weights, int wdtype, void* out, int odtype, int64_t T, int top_k, int64_t E, int64_t N,
                      int64_t Kp, inc_stream_t stream);

@@ -106,6 +106,8 @@ SIGNATURES = {
     "inc_fp8_quant_rows": (c_int, [_P, c_int, c_int64, c_int64, c_int64, _P, _P, _P, _P]),
     "inc_fp8_gemm": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int64, c_int64, c_int64, _P]),
     "inc_fp8_gemv": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int64, c_int64, c_int64, _P]),
+    "inc_fp8_gemv_multi": (c_int, [c_int, _P, _P, _P, _P, _P, _P, c_int, c_int64, _P, c_int64, _P]),
+    "inc_fp8_gemv_gated": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int64, c_int64, c_int64, _P]),
     "inc_fp8_moe_gemm": (
         c_int,
         [c_int, _P, _P, _P, _P, _P, _P, c_int, _P, c_int, c_int64, c_int, c_int64, c_int64, c_int64, _P],

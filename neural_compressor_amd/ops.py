@@ -1819,6 +1819,59 @@ def fp8_gemv(xq, row_scale, wq, alpha, bias, out_dtype):
     return _fp8_product(lib.inc_fp8_gemv, "inc_fp8_gemv", xq, row_scale, wq, alpha, bias, out_dtype)
 
 
+FP8_GEMV_MAX_MEMBERS = 8
+
+
+def _fp8_check_member(xq, wq, alpha):
+    assert wq.dtype == torch.uint8 and wq.shape[1] == xq.shape[1] and wq.is_contiguous()
+    assert alpha.dtype == torch.float32 and alpha.numel() == wq.shape[0] and alpha.is_contiguous()
+
+
+def fp8_gemv_multi(xq, row_scale, wqs, alphas, biases, out_dtype, outs=None):
+    """[fp8_gemv(xq, row_scale, wq_i, alpha_i, bias_i, out_dtype) for i] for 2 .. FP8_GEMV_MAX_MEMBERS weight matrices in ONE launch
+    (inc_fp8_gemv_multi); every output is the single call's bit for bit.  `biases`: a list with None for a member without one.
+    `outs`: contiguous [M, N_i] tensors of out_dtype to write into (allocated when None)."""
+    import ctypes
+
+    n = len(wqs)
+    biases = [None if b is None else (b if b.dtype == out_dtype else b.to(out_dtype)) for b in biases]
+    dev = _dev(xq, row_scale, *wqs, *alphas, *biases)
+    M = xq.shape[0]
+    Kp = xq.shape[1]
+    assert xq.dtype == torch.uint8 and xq.is_contiguous() and row_scale.dtype == torch.float32 and row_scale.numel() == M
+    for wq, alpha in zip(wqs, alphas):
+        _fp8_check_member(xq, wq, alpha)
+    if outs is None:
+        ys = [torch.empty((M, wq.shape[0]), dtype=out_dtype, device=dev) for wq in wqs]
+    else:
+        ys = list(outs)
+        assert len(ys) == n and all(y.shape == (M, wq.shape[0]) and y.dtype == out_dtype and y.is_contiguous() for y, wq in zip(ys, wqs))
+    arr = lambda ts: (ctypes.c_void_p * n)(*[_ptr(t) for t in ts])  # noqa: E731
+    Ns = (ctypes.c_int64 * n)(*[wq.shape[0] for wq in wqs])
+    with torch.cuda.device(dev):
+        check(lib.inc_fp8_gemv_multi(n, _ptr(xq), _ptr(row_scale), arr(wqs), arr(alphas), arr(biases), arr(ys), dtype_code(out_dtype),
+                                     M, Ns, Kp, _stream()), "inc_fp8_gemv_multi")
+    return ys
+
+
+def fp8_gemv_gated(xq, row_scale, gate_wq, gate_alpha, gate_bias, up_wq, up_alpha, up_bias, out_dtype):
+    """silu(g) * u of a gated MLP for up to FP8_GEMV_MAX_M rows in ONE launch (inc_fp8_gemv_gated): g and u are fp8_gemv's values on
+    the gate / up weight before their rounding, the product is formed in fp32 and rounded once to `out_dtype` (bf16 / fp16)."""
+    dev = _dev(xq, row_scale, gate_wq, gate_alpha, gate_bias, up_wq, up_alpha, up_bias)
+    (M, Kp), N = xq.shape, gate_wq.shape[0]
+    assert xq.dtype == torch.uint8 and xq.is_contiguous() and row_scale.dtype == torch.float32 and row_scale.numel() == M
+    assert up_wq.shape == gate_wq.shape
+    _fp8_check_member(xq, gate_wq, gate_alpha)
+    _fp8_check_member(xq, up_wq, up_alpha)
+    gate_bias, up_bias = [None if b is None else (b if b.dtype == out_dtype else b.to(out_dtype)) for b in (gate_bias, up_bias)]
+    h = torch.empty((M, N), dtype=out_dtype, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.inc_fp8_gemv_gated(_ptr(xq), _ptr(row_scale), _ptr(gate_wq), _ptr(gate_alpha), _ptr(gate_bias), _ptr(up_wq),
+                                     _ptr(up_alpha), _ptr(up_bias), _ptr(h), dtype_code(out_dtype), M, N, Kp, _stream()),
+              "inc_fp8_gemv_gated")
+    return h
+
+
 def fp8_moe_gemm(mode, aq, a_scale, route, wq, alpha, T, top_k, routing_weights=None, out=None, out_dtype=None):
     """inc_fp8_moe_gemm (K17e): fp8_gemm's product per expert over the rows of the route's sorted order.  wq [E, N, Kp], alpha fp32
     [E, N] (slice e = fp8_quant_rows of expert e's matrix).  mode 0: gate_up + SiLU product -> [T*k, N/2] of `out_dtype` (bf16 / fp16)

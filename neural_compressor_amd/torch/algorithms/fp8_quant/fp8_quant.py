@@ -6,6 +6,8 @@ and applies `row_scale[m] * w_scale[n]` in its epilogue; a decode-sized batch (u
 form of the instruction.  The specification in bits is the comment of the entry points in include/inc_mi355x.h.
 The algorithm is data-free: `prepare` returns the model unchanged and `convert` swaps every selected nn.Linear and, under
 `FP8Config(moe_experts=True)`, every selected fused MoE experts module (FP8Experts, experts.py).
+`fp8_linear_group` and `fp8_gated_pair` run modules that multiply the same activation as one decode launch (`inc_fp8_gemv_multi`,
+`inc_fp8_gemv_gated`).
 """
 
 import torch
@@ -77,6 +79,77 @@ class FP8Linear(torch.nn.Module):
     def extra_repr(self):
         return (f"in_features={self.in_features}, out_features={self.out_features}, bias={self.bias is not None}, "
                 f"fp8_config=E4M3, act_granularity=per_token, w_granularity=per_channel")
+
+
+def _group_plan(x, mods):
+    """What FP8Linear members that multiply the same x share, or None where the group is the plain list of forwards: (x2d, out_dtype,
+    every member decodes)."""
+    m0 = mods[0] if mods else None
+    ok = (2 <= len(mods) <= ops.FP8_GEMV_MAX_MEMBERS and all(isinstance(m, FP8Linear) for m in mods) and x.is_cuda and x.numel() > 0
+          and x.shape[-1] == m0.in_features and x.device == m0.qweight.device
+          and all((m.in_features, m.qweight.device) == (m0.in_features, m0.qweight.device) for m in mods))
+    if not ok:
+        return None
+    half = x.dtype in (torch.float16, torch.bfloat16)
+    out_dtype = x.dtype if half else m0.float_type
+    x2d = x.reshape(-1, m0.in_features)
+    rows = x2d.shape[0]
+    decode = [m._decodes(rows) for m in mods]
+    if not (half or all(m.float_type == out_dtype for m in mods)) or not (all(decode) or rows > ops.FP8_GEMV_MAX_M):
+        return None
+    return x2d, out_dtype, all(decode)
+
+
+def fp8_linear_group(x, modules):
+    """[m(x) for m in modules], bit for bit, for FP8Linear modules that multiply the SAME activation -- q / k / v of an attention block,
+    gate / up of an MLP: x is quantised ONCE (each member's own forward quantises it again), and up to FP8Linear.DECODE_MAX_M rows the
+    products are ONE launch over the strips of all members (inc_fp8_gemv_multi: the strip body of inc_fp8_gemv); above that,
+    inc_fp8_gemm per member on the shared codes.  Every member keeps its buffers and state-dict keys.  Anything else -- a member that
+    is not an FP8Linear, mixed widths, fewer than 2 or more than 8 members, x elsewhere or empty, a decode-sized x with DECODE_GEMV off
+    -- is the plain list of single forwards."""
+    mods = list(modules)
+    plan = _group_plan(x, mods)
+    if plan is None:
+        return [m(x) for m in mods]
+    x2d, out_dtype, decode = plan
+    xq, row_scale = ops.fp8_quant_rows(x2d, None, mods[0].kp)
+    if decode:
+        ys = ops.fp8_gemv_multi(xq, row_scale, [m.qweight for m in mods], [m.w_scale for m in mods], [m.bias for m in mods], out_dtype)
+    else:
+        ys = [ops.fp8_gemm(xq, row_scale, m.qweight, m.w_scale, m.bias, out_dtype) for m in mods]
+    if x.dtype == torch.float32:
+        ys = [y.float() for y in ys]
+    return [y.reshape(*x.shape[:-1], m.out_features) for y, m in zip(ys, mods)]
+
+
+# gate / up of a dense gated MLP: True = fp8_gated_pair forms silu(gate(x)) * up(x) inside the decode launch (inc_fp8_gemv_gated),
+# False = fp8_linear_group + the activation + the product as torch kernels.  Times of both: profiles/fp8/fp8_group_time.log, DESIGN
+# section 8c
+GATED_FUSED = True
+
+
+def fp8_gated_pair(x, gate, up, act_fn=None):
+    """act_fn(gate(x)) * up(x) -- the first half of a gated MLP (transformers' LlamaMLP.forward) -- in ONE product launch for a
+    decode-sized batch (inc_fp8_gemv_gated): x is quantised once, both products and the SiLU product are one kernel, the product is
+    formed in fp32 from the two fp32 values and rounded once.  The unfused form rounds three times (g, u, silu(g)) before its last
+    rounding, so the two agree within output rounding, not bit for bit.  act_fn: None (SiLU) or a SiLU module.
+
+    Fused when both members are FP8Linear of one in_features, out_features, device and float_type, x is on that device with
+    x.shape[-1] == in_features, the row count decodes on both, act_fn is None or SiLU and GATED_FUSED is on.  Otherwise exactly
+    act(g) * u with g, u = fp8_linear_group(x, [gate, up]) and act = F.silu by default.  fp32 x and the reshape: FP8Linear.forward's."""
+    from .experts import _is_silu
+
+    if GATED_FUSED and (act_fn is None or _is_silu(act_fn)):
+        plan = _group_plan(x, [gate, up])
+        if (plan is not None and plan[2] and gate.out_features == up.out_features and gate.float_type == up.float_type):
+            x2d, out_dtype, _ = plan
+            xq, row_scale = ops.fp8_quant_rows(x2d, None, gate.kp)
+            h = ops.fp8_gemv_gated(xq, row_scale, gate.qweight, gate.w_scale, gate.bias, up.qweight, up.w_scale, up.bias, out_dtype)
+            if x.dtype == torch.float32:
+                h = h.float()
+            return h.reshape(*x.shape[:-1], gate.out_features)
+    g, u = fp8_linear_group(x, [gate, up])
+    return (torch.nn.functional.silu(g) if act_fn is None else act_fn(g)) * u
 
 
 class FP8Quantizer(Quantizer):
