@@ -658,7 +658,7 @@ int inc_w8a8_gemm_rowscale(const int8_t* xq, const int8_t* wq, const float* row_
  *   members.  wq, ws, bias, y and N are HOST arrays of n entries (the convention of inc_woq_gemv_anyw_multi); bias may be NULL or hold
  *   NULL for a member without one; x, the format pair, ydtype and Kp are common.  y[i] is bit-identical to inc_mx_gemv on member i
  *   alone (the same strip body).  Rejections as for inc_mx_gemv, and INC_ERR_UNSUPPORTED for n outside 2 .. 8.
- * inc_mx_moe_gemm (csrc/gemm_mx_moe.hip, K16e): the product of inc_mx_gemm per expert over the rows inc_moe_route sorted -- the two
+ * inc_mx_moe_gemm (csrc/gemm_strip_moe.hip, K16e): the product of inc_mx_gemm per expert over the rows inc_moe_route sorted -- the two
  *   F.linear of transformers' MixtralExperts.forward (also the Qwen2-MoE / Qwen3-MoE / OLMoE experts) for MX experts.  One forward is
  *   inc_moe_route -> inc_mx_quant(x) -> inc_mx_moe_gemm(0) -> inc_mx_quant(h) -> inc_mx_moe_gemm(1) -> inc_moe_combine on `stream`.
  *   `route` is K4e's buffer, unchanged ([0] tile count, offsets [E+1], order [S], pos [S], tiles of 64 rows; S = T * top_k).
@@ -695,7 +695,7 @@ int inc_mx_moe_gemm(int mode, const uint8_t* aq, const uint8_t* as, int afmt, co
 
 /* ---- FP8 per-token / per-channel: OCP e4m3 codes, one fp32 scale per row of x and one per row of W ------- *
  * The "FP8 dynamic" cell: csrc/sq.hip (the quantiser, next to the int8 token kernel it shares its structure with) and
- * csrc/gemm_fp8.hip (the products, on v_mfma_f32_32x32x64_f8f6f4 and v_mfma_f32_16x16x128_f8f6f4).  This text is the specification.
+ * csrc/gemm_fp8.hip and csrc/gemm_fp8_group.hip (the products, on v_mfma_f32_32x32x64_f8f6f4 and v_mfma_f32_16x16x128_f8f6f4).  This text is the specification.
  * Inputs are finite; for a row with a NaN or an infinity nothing is promised except that every write stays in bounds.
  * inc_fp8_quant_rows: x bf16 / fp16 / fp32 [M,K] contiguous, of any alignment; in_scale fp32 [K] or NULL.
  *     t            = float(x[m,k]) * in_scale[k]                       (one fp32 multiply; t = float(x[m,k]) without in_scale)
@@ -738,7 +738,7 @@ int inc_mx_moe_gemm(int mode, const uint8_t* aq, const uint8_t* as, int afmt, co
  *   to it.  Below g ~ -88.7 expf(-g) is +inf and silu(g) is -0, which is the rounded exact value; g = -inf gives NaN.  The store rule
  *   of y, the reads (nothing past row M - 1 of xq or row N - 1 of a weight) and the rejections are inc_fp8_gemv's.
  *   Both validate their arguments before any HIP call; no workspace, no counters, repeated calls are bit-identical.
- * inc_fp8_moe_gemm (csrc/gemm_fp8_moe.hip, K17e): the product of inc_fp8_gemm per expert over the rows inc_moe_route sorted -- the two
+ * inc_fp8_moe_gemm (csrc/gemm_strip_moe.hip, K17e): the product of inc_fp8_gemm per expert over the rows inc_moe_route sorted -- the two
  *   F.linear of transformers' MixtralExperts.forward (also the Qwen2-MoE / Qwen3-MoE / OLMoE experts) for FP8 experts.  One forward is
  *   inc_moe_route -> inc_fp8_quant_rows(x) -> inc_fp8_moe_gemm(0) -> inc_fp8_quant_rows(h) -> inc_fp8_moe_gemm(1) -> inc_moe_combine
  *   on `stream`.  `route` is K4e's buffer, unchanged ([0] tile count, offsets [E+1], order [S], pos [S], tiles of 64 rows; S = T *

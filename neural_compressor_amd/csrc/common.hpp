@@ -104,7 +104,7 @@ __device__ __forceinline__ float round_to(float v) {
 }
 
 // silu(g) * u of a gated MLP, formed in fp32 (the caller rounds once): the epilogue of every fused gate / up product -- the grouped MoE
-// GEMMs' mode 0 (gemm_moe.hip, gemm_mx_moe.hip) and the gated launch of the streaming GEMV (gemm_stream.hip)
+// GEMMs' mode 0 (gemm_moe.hip, gemm_strip_moe.hip) and the gated launch of the streaming GEMV (gemm_stream.hip)
 __device__ __forceinline__ float silu_mul_f32(float g, float u) { return g / (1.f + expf(-g)) * u; }
 
 // ---- wave64 reductions --------------------------------------------------------------------

@@ -1,33 +1,26 @@
-// gemm_fp8.hip -- K17: the per-token / per-channel FP8 (OCP e4m3) cell on the f8f6f4 matrix instructions of gfx950.
+// gemm_fp8.hip -- K17: the per-token / per-channel FP8 (OCP e4m3) GEMM on the f8f6f4 matrix instructions of gfx950.
 //
 //   y[m, n] = rd16((row_scale[m] * alpha[n]) * sum_k x[m,k] * w[n,k]  +  bias[n])
 //
 // xq / wq are the e4m3 codes and row_scale / alpha the fp32 scales of inc_fp8_quant_rows (include/inc_mi355x.h has the specification,
-// DESIGN section 8c).  The codes are the MX cell's fp8 codes without block scales, so both kernels are the MX kernels of the (fp8, fp8)
-// pair with the scale path taken out -- no scale pointers, no scale loads, no scale registers -- and the two factors applied in the
-// epilogue, as inc_w8a8_gemm_rowscale applies them:
-//   inc_fp8_gemm  gemm_mx.hip's kernel: the wave frame of tile256_frame.hpp, 256 x 256 x 128 tiles, both operands K-contiguous rows of
-//                 128 bytes through MxStage<128> (mx_stage.hpp), two stages, the DMA of tile t+1 issued at the top of step t, one
-//                 workgroup per tile, no split-K tail.  16 x v_mfma_f32_32x32x64_f8f6f4 per wave and K-tile.
-//   inc_fp8_gemv  gemm_mx_gemv.hip's strip body for 1 <= M <= 16: one workgroup per 16 weight rows, the weights non-temporal from HBM
-//                 straight into the instruction's registers (mx_frag of mx_strip.hpp), K split over the 8 waves with 4 K-tiles in
-//                 flight per round, the partials added by wave 0 in wave order through LDS.  v_mfma_f32_16x16x128_f8f6f4.
+// DESIGN section 8c).  The codes are the MX cell's fp8 codes without block scales, so inc_fp8_gemm is gemm_mx.hip's kernel of the
+// (fp8, fp8) pair with the scale path taken out -- no scale pointers, no scale loads, no scale registers -- and the two factors applied
+// in the epilogue, as inc_w8a8_gemm_rowscale applies them: the wave frame of tile256_frame.hpp, 256 x 256 x 128 tiles, both operands
+// K-contiguous rows of 128 bytes through MxStage<128> (mx_stage.hpp), two stages, the DMA of tile t+1 issued at the top of step t, one
+// workgroup per tile, no split-K tail.  16 x v_mfma_f32_32x32x64_f8f6f4 per wave and K-tile.  The decode route for 1 <= M <= 16
+// (inc_fp8_gemv and its group launches) is gemm_fp8_group.hip.
 // The instruction is issued through the scale builtin with literal zero scale operands, which the compiler emits as the UNSCALED opcode
 // (no scale register); tools/mx_lab.hip shows on the device that it equals the scaled opcode with both scale bytes 127 bit for bit
-// (profiles/mx/mx_lab.log), so the accumulator is what inc_mx_gemm / inc_mx_gemv compute for scale bytes 127.
-// Operand maps: gemm_mx.hip and gemm_mx_gemv.hip.  Rows past M / N re-read the last row (GEMM) or supply zero codes (GEMV rows of x);
-// what they produce is never stored.
+// (profiles/mx/mx_lab.log), so the accumulator is what inc_mx_gemm computes for scale bytes 127.
+// Operand map: gemm_mx.hip.  Rows past M / N re-read the last row; what they produce is never stored.
 // Algorithmic work per launch: 2*M*N*Kp flop; bytes (M + N) * Kp + 4 * (M + N) + 2*M*N.
-#include <type_traits>
-
 #include "mx_stage.hpp"
-#include "mx_strip.hpp"
 
 namespace {
 
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 
-constexpr int FM = 256, FN = 256;  // the tile; its K is XK = 128 (mx_strip.hpp)
+constexpr int FM = 256, FN = 256, XK = INC_MX_KTILE;  // the tile
 constexpr int E4M3 = INC_MX_FP8_E4M3;
 
 template <bool IS_BF16>
@@ -133,82 +126,10 @@ __global__ __launch_bounds__(512) void fp8_gemm_kernel(const uint8_t* __restrict
       });
 }
 
-// ---- the decode route: the strip body of gemm_mx_gemv.hip ------------------------------------------------------------------------
-constexpr int GW = 8;      // waves of a workgroup = ways of the in-workgroup K split
-constexpr int STRIP = 16;  // weight rows of a workgroup: the instruction's M
-constexpr int UNROLL = 4;  // K-tiles of a wave whose loads are in flight together
-
-template <bool IS_BF16>
-__global__ __launch_bounds__(GW * 64) void fp8_gemv_kernel(const uint8_t* __restrict__ xq, const float* __restrict__ row_scale,
-                                                           const uint8_t* __restrict__ wq, const float* __restrict__ alpha,
-                                                           const uint16_t* __restrict__ bias, uint16_t* __restrict__ y, int M,
-                                                           int64_t N, int64_t Kp, int y_vec_ok) {
-  __shared__ f32x4 part[GW][64];
-  const int64_t n0 = (int64_t)blockIdx.x * STRIP;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int r = lane & 15, g = lane >> 4;
-  int64_t wrow = n0 + r;
-  if (wrow > N - 1) wrow = N - 1;
-  const int xrow = r < M ? r : M - 1;
-  const int xkeep = r < M ? -1 : 0;
-  const uint8_t* const wp = wq + wrow * Kp + 16 * g;
-  const uint8_t* const xp = xq + (int64_t)xrow * Kp + 16 * g;
-  const int nk = (int)(Kp / XK);
-
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  // C rounds of the wave's K-tiles kt, kt + GW, ...: every load first, then the MFMAs in K order
-  auto round = [&](int kt, auto count) {
-    constexpr int C = decltype(count)::value;
-    i32x8 wf[C], xf[C];
-#pragma unroll
-    for (int u = 0; u < C; ++u) {
-      const int64_t t = kt + u * GW;
-      wf[u] = mx_frag<E4M3, true>(wp + t * XK);
-      xf[u] = mx_frag<E4M3, false>(xp + t * XK);
-    }
-#pragma unroll
-    for (int u = 0; u < C; ++u) {
-#pragma unroll
-      for (int d = 0; d < 8; ++d) xf[u][d] &= xkeep;
-      acc = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wf[u], xf[u], acc, E4M3, E4M3, 0, 0, 0, 0);
-    }
-  };
-  int kt = wave;
-  for (; kt + (UNROLL - 1) * GW < nk; kt += UNROLL * GW) round(kt, std::integral_constant<int, UNROLL>{});
-  const int left = kt < nk ? (nk - kt + GW - 1) / GW : 0;  // 0 .. UNROLL - 1 tiles of this wave remain
-  if (left == 3) round(kt, std::integral_constant<int, 3>{});
-  else if (left == 2) round(kt, std::integral_constant<int, 2>{});
-  else if (left == 1) round(kt, std::integral_constant<int, 1>{});
-
-  part[wave][lane] = acc;
-  __syncthreads();
-  if (wave != 0) return;
-  f32x4 sum = part[0][lane];
-#pragma unroll
-  for (int w = 1; w < GW; ++w) sum += part[w][lane];
-
-  // C/D map of the 16 x 16 MFMA: register e of lane l is D[4 (l >> 4) + e][l & 15] = y[m = l & 15][n0 + 4 g + e]
-  const int m = r;
-  if (m >= M) return;
-  const int64_t nb = n0 + 4 * g;
-  if (nb >= N) return;
-  const float rs = row_scale[m];
-  const BiasQuad bq = load_bias_quad<IS_BF16>(bias, nb, N);
-  float v[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const float al = nb + e < N ? alpha[nb + e] : 0.f;
-    v[e] = (rs * al) * sum[e] + bq.b[e];
-  }
-  store_quad16<IS_BF16>(y, m, nb, N, y_vec_ok, v);
-}
-
-// the checks both entry points share, in inc_mx_gemm's order
+// the argument checks, in inc_mx_gemm's order
 int fp8_check(const void* xq, const void* row_scale, const void* wq, const void* alpha, const void* y, int ydtype, int64_t M, int64_t N,
-              int64_t Kp, int64_t max_m) {
+              int64_t Kp) {
   INC_CHECK_ARG(xq && row_scale && wq && alpha && y && M > 0 && N > 0 && Kp > 0);
-  if (M > max_m) return INC_ERR_UNSUPPORTED;
   if (ydtype != INC_BF16 && ydtype != INC_F16) return INC_ERR_UNSUPPORTED;
   if ((Kp % XK) != 0) return INC_ERR_UNSUPPORTED;
   INC_CHECK_ARG(((reinterpret_cast<uintptr_t>(xq) | reinterpret_cast<uintptr_t>(wq)) & 15) == 0);
@@ -220,7 +141,7 @@ int fp8_check(const void* xq, const void* row_scale, const void* wq, const void*
 
 extern "C" int inc_fp8_gemm(const uint8_t* xq, const float* row_scale, const uint8_t* wq, const float* alpha, const void* bias, void* y,
                             int ydtype, int64_t M, int64_t N, int64_t Kp, inc_stream_t stream) {
-  const int rc = fp8_check(xq, row_scale, wq, alpha, y, ydtype, M, N, Kp, INT64_MAX);
+  const int rc = fp8_check(xq, row_scale, wq, alpha, y, ydtype, M, N, Kp);
   if (rc != INC_OK) return rc;
   INC_CHECK_ARG((int64_t)FM * Kp < ((int64_t)1 << 32));  // 32-bit DMA offsets inside a tile
   INC_CHECK_ARG(ceil_div64(M, FM) * ceil_div64(N, FN) < ((int64_t)1 << 31));
@@ -237,19 +158,5 @@ extern "C" int inc_fp8_gemm(const uint8_t* xq, const float* row_scale, const uin
     fp8_gemm_kernel<true><<<grid, 512, smem, inc_s(stream)>>>(xq, row_scale, wq, alpha, (const uint16_t*)bias, (uint16_t*)y, M, N, Kp, y_vec_ok);
   else
     fp8_gemm_kernel<false><<<grid, 512, smem, inc_s(stream)>>>(xq, row_scale, wq, alpha, (const uint16_t*)bias, (uint16_t*)y, M, N, Kp, y_vec_ok);
-  INC_LAUNCH_RETURN();
-}
-
-extern "C" int inc_fp8_gemv(const uint8_t* xq, const float* row_scale, const uint8_t* wq, const float* alpha, const void* bias, void* y,
-                            int ydtype, int64_t M, int64_t N, int64_t Kp, inc_stream_t stream) {
-  const int rc = fp8_check(xq, row_scale, wq, alpha, y, ydtype, M, N, Kp, INC_MX_GEMV_MAX_M);
-  if (rc != INC_OK) return rc;
-  INC_CHECK_ARG(ceil_div64(N, STRIP) < ((int64_t)1 << 31));
-  const unsigned grid = (unsigned)ceil_div64(N, STRIP);
-  const int y_vec_ok = (N % 4 == 0) && ((reinterpret_cast<uintptr_t>(y) & 7) == 0);
-  if (ydtype == INC_BF16)
-    fp8_gemv_kernel<true><<<grid, GW * 64, 0, inc_s(stream)>>>(xq, row_scale, wq, alpha, (const uint16_t*)bias, (uint16_t*)y, (int)M, N, Kp, y_vec_ok);
-  else
-    fp8_gemv_kernel<false><<<grid, GW * 64, 0, inc_s(stream)>>>(xq, row_scale, wq, alpha, (const uint16_t*)bias, (uint16_t*)y, (int)M, N, Kp, y_vec_ok);
   INC_LAUNCH_RETURN();
 }

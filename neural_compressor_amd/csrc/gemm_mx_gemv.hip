@@ -3,25 +3,19 @@
 //
 //   y[m, n] = sum_blocks 2^(xs[m,b] + ws[n,b] - 254) * sum_{k in block b} x[m,k] * w[n,k]  +  bias[n]
 //
-// Operands, storage and arithmetic are inc_mx_gemm's (include/inc_mi355x.h has the specification).  A workgroup owns one strip of 16
-// weight rows over all of K.  The 16 weight rows are the A operand of the instruction and the up-to-16 rows of x the B operand, so a
-// K-tile of 128 elements is ONE instruction per wave and the accumulator's rows are output columns (a lane owns 4 adjacent ones).
-// Operand map of the 16x16x128 form (tools/mx_lab.hip, profiles/mx/mx_lab.log): lane l holds row r = l & 15, lane
-// group g = l >> 4.  fp8: registers 0 .. 3 are the 16 bytes at 16 g of the K-tile and registers 4 .. 7 the 16 bytes at 64 + 16 g;
-// fp4: registers 0 .. 3 are the 16 bytes of block g (registers 4 .. 7 are not read); either format: the scale byte of block g, in
-// the byte of the scale register that opsel names.  So a lane loads what the instruction wants of its row straight from global
-// memory into VGPRs -- two (fp8) or one (fp4) 16-byte loads and one scale byte per operand and K-tile, non-temporal for the weights
-// (streamed once), plain for x (every strip re-reads it from L2) -- with no LDS round trip and no shuffle.
-// K is split INSIDE the workgroup: wave w of W takes the K-tiles w, w + W, ..., UNROLL of them per round with every load of the round
-// issued in front of its first MFMA, and leaves its 16 x 16 fp32 partial in LDS; wave 0 adds the W partials in wave order, adds the
-// bias in fp32 and rounds once.  No global hand-off, no counters, no workspace: repeated calls are bit-identical.
+// Operands, storage and arithmetic are inc_mx_gemm's (include/inc_mi355x.h has the specification).  This is the strip scheme of
+// strip_frame.hpp with block scales (SCALED = true), one weight strip and one block of x rows: a workgroup owns one strip of 16 weight
+// rows over all of K; a lane loads what the instruction wants of its row straight from global memory into VGPRs -- two (fp8) or one
+// (fp4) 16-byte loads and one scale byte per operand and K-tile, non-temporal for the weights (streamed once), plain for x (every
+// strip re-reads it from L2) -- with no LDS round trip and no shuffle.  K is split over the W waves of the workgroup, UNROLL tiles per
+// round and the cascade tail; wave 0 adds the W partials in wave order, adds the bias in fp32 and rounds once.  No global hand-off, no
+// counters, no workspace: repeated calls are bit-identical.
 // Lanes of an x row >= M supply zero codes, lanes of a weight row >= N re-read row N - 1; what they produce is never stored.
 // inc_mx_gemv_multi is the same kernel over the strips of up to 8 weight matrices one after another: a workgroup finds its member in
-// a table passed by value and then runs the same strip body, so member i's output is inc_mx_gemv's bit for bit.
+// a table passed by value (StripMembers) and then runs the same strip, so member i's output is inc_mx_gemv's bit for bit; inc_mx_gemv
+// is the launch with a table of one member.
 // Algorithmic bytes per launch: N * Kp * (1 or 1/2) + N * Kp / 32 + M * Kp * (1 or 1/2) + M * Kp / 32 + 2 * M * N.
-#include <type_traits>
-
-#include "mx_strip.hpp"  // the operand fragments of the 16x16x128 form
+#include "strip_frame.hpp"
 
 #ifndef INC_MX_GEMV_WAVES
 #define INC_MX_GEMV_WAVES 8  // W: 4, 8 or 16 (scripts/mx_gemv_time.py; the rejected values are in profiles/NOTES.md)
@@ -30,31 +24,22 @@
 namespace {
 
 constexpr int GW = INC_MX_GEMV_WAVES;  // waves of a workgroup = ways of the in-workgroup K split
-constexpr int STRIP = 16;              // weight rows of a workgroup: the instruction's M
 constexpr int UNROLL = 4;              // K-tiles of a wave whose loads are in flight together
-constexpr int MAX_MEMBERS = 8;
 static_assert(GW == 4 || GW == 8 || GW == 16, "W is 4, 8 or 16");
 
-// the weight matrices of one launch; member i owns the strips first[i] .. first[i + 1] - 1 of the grid
-struct MxGemvMembers {
-  const uint8_t* wq[MAX_MEMBERS];
-  const uint8_t* ws[MAX_MEMBERS];
-  const uint16_t* bias[MAX_MEMBERS];
-  uint16_t* y[MAX_MEMBERS];
-  int64_t N[MAX_MEMBERS];
-  int first[MAX_MEMBERS + 1];
-  int y_vec_ok[MAX_MEMBERS];
-  int n;
-};
+using MxGemvMembers = StripMembers<uint8_t>;  // ws: the member's scale bytes
 
+// The kernel is kept in written-out form around the frame's member table and mx_frag: its K loop is strip_partials<WF, XF, true, 1, 1,
+// UNROLL, GW, true, true>, its sum strip_sum_wave0, in the parent's own text.  Through the frame's functions the compiler scheduled
+// the same instructions differently (80 / 76 / 62 instead of 72 / 66 / 60 VGPRs) and the a8w8 / a8w4 launches measured 0.5 - 2.5 %
+// slower (profiles/strip_frame/README.md).  Any change to the tile-to-wave map, the K order or the sum order here must be made in
+// strip_frame.hpp too: the experts kernel's one-expert identity rests on their being equal.
 template <bool IS_BF16, int XF, int WF>
 __global__ __launch_bounds__(GW * 64) void mx_gemv_kernel(const uint8_t* __restrict__ xq, const uint8_t* __restrict__ xs,
                                                           const MxGemvMembers mem, int M, int64_t Kp) {
   __shared__ f32x4 part[GW][64];
   const int strip = blockIdx.x;
-  int mi = 0;
-  for (int i = 1; i < mem.n; ++i)
-    if (strip >= mem.first[i]) mi = i;
+  const int mi = strip_member(mem, strip);
   const int64_t N = mem.N[mi];
   const int64_t n0 = (int64_t)(strip - mem.first[mi]) * STRIP;
 
@@ -155,21 +140,8 @@ int gemv_run(int n, const uint8_t* xq, const uint8_t* xs, int xfmt, const uint8_
   if (!p88 && !p84 && !p44) return INC_ERR_UNSUPPORTED;
   INC_CHECK_ARG((reinterpret_cast<uintptr_t>(xq) & 15) == 0 && (reinterpret_cast<uintptr_t>(xs) & 3) == 0);
   MxGemvMembers mem = {};
-  int64_t strips = 0;
-  for (int i = 0; i < n; ++i) {
-    INC_CHECK_ARG((reinterpret_cast<uintptr_t>(wq[i]) & 15) == 0 && (reinterpret_cast<uintptr_t>(ws[i]) & 3) == 0);
-    mem.wq[i] = wq[i];
-    mem.ws[i] = ws[i];
-    mem.bias[i] = bias ? static_cast<const uint16_t*>(bias[i]) : nullptr;
-    mem.y[i] = static_cast<uint16_t*>(y[i]);
-    mem.N[i] = N[i];
-    mem.first[i] = (int)strips;
-    mem.y_vec_ok[i] = (N[i] % 4 == 0) && ((reinterpret_cast<uintptr_t>(y[i]) & 7) == 0);
-    strips += ceil_div64(N[i], STRIP);
-    INC_CHECK_ARG(strips < ((int64_t)1 << 31));
-  }
-  mem.first[n] = (int)strips;
-  mem.n = n;
+  const int rc = strip_members_fill(mem, n, wq, ws, bias, y, N);
+  if (rc != INC_OK) return rc;
   if (p88) return gemv_launch<INC_MX_FP8_E4M3, INC_MX_FP8_E4M3>(xq, xs, mem, ydtype, M, Kp, stream);
   if (p84) return gemv_launch<INC_MX_FP8_E4M3, INC_MX_FP4_E2M1>(xq, xs, mem, ydtype, M, Kp, stream);
   return gemv_launch<INC_MX_FP4_E2M1, INC_MX_FP4_E2M1>(xq, xs, mem, ydtype, M, Kp, stream);
@@ -186,6 +158,6 @@ extern "C" int inc_mx_gemv_multi(int n, const uint8_t* xq, const uint8_t* xs, in
                                  const uint8_t* const* ws, int wfmt, const void* const* bias, void* const* y, int ydtype, int64_t M,
                                  const int64_t* N, int64_t Kp, inc_stream_t stream) {
   INC_CHECK_ARG(wq && ws && y && N);
-  if (n < 2 || n > MAX_MEMBERS) return INC_ERR_UNSUPPORTED;
+  if (n < 2 || n > STRIP_MAX_MEMBERS) return INC_ERR_UNSUPPORTED;
   return gemv_run(n, xq, xs, xfmt, wq, ws, wfmt, bias, y, ydtype, M, N, Kp, stream);
 }

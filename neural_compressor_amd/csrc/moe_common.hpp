@@ -1,5 +1,5 @@
 // moe_common.hpp -- what the routed MoE kernels share: the layout of the route buffer inc_moe_route writes (gemm_moe.hip) and the
-// routing-weight load.  Readers: the INT4 grouped GEMM and combine (gemm_moe.hip) and the MX grouped GEMM (gemm_mx_moe.hip).
+// routing-weight load.  Readers: the INT4 grouped GEMM and combine (gemm_moe.hip) and the MX / FP8 grouped GEMM (gemm_strip_moe.hip).
 #pragma once
 #include "common.hpp"
 

@@ -27,7 +27,9 @@ MAX_MEMBERS = 8
 MULTI_NS = [4, 17, 260]          # below one strip; a last strip with one valid column and no vector store; several strips, ragged tail
 MULTI_NS8 = [MULTI_NS[i % 3] for i in range(MAX_MEMBERS)]
 MS = [1, 15, 16]
-TILES = [1, 9, 33]               # Kp / 128: one tile (7 idle waves), a second round of one wave, full rounds of 4 plus one left over
+# Kp / 128: one tile (7 idle waves), a second round of one wave, 2 and 3 tiles for every wave (the `left == 2` and `left == 3` tails, no
+# full round), full rounds of 4 plus one left over
+TILES = [1, 9, 16, 24, 33]
 GATED_MS = [1, 5, 16]
 GATED_NS = [20, 7, 260]          # the experts case table's accepted widths (mx_moe_cases.CASES); 7 is no multiple of 16 (or of 4)
 OUT_DTYPES = F.OUT_DTYPES

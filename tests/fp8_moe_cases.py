@@ -1,5 +1,5 @@
 """Shared by tests/test_fp8_moe_cpu.py and tests/test_gpu_fp8_moe.py (a helper module, not a conftest): the cases and the float64 oracle
-of the routed FP8 GEMM of the fused MoE experts (inc_fp8_moe_gemm, neural_compressor_amd/csrc/gemm_fp8_moe.hip).  No GPU code.
+of the routed FP8 GEMM of the fused MoE experts (inc_fp8_moe_gemm, neural_compressor_amd/csrc/gemm_strip_moe.hip).  No GPU code.
 
 The case table and the routings are those of tests/mx_moe_cases.py (CASES, route_of) and tests/moe_stage_cases.py, the quantiser oracle,
 the code table and the random codes those of tests/fp8_cases.py.

@@ -1,5 +1,5 @@
 """Shared by tests/test_mx_moe_cpu.py and tests/test_gpu_mx_moe.py (a helper module, not a conftest): the cases and the float64 oracle
-of the routed MX GEMM of the fused MoE experts (inc_mx_moe_gemm, neural_compressor_amd/csrc/gemm_mx_moe.hip).  No GPU code.
+of the routed MX GEMM of the fused MoE experts (inc_mx_moe_gemm, neural_compressor_amd/csrc/gemm_strip_moe.hip).  No GPU code.
 
 Routings and the route oracle come from tests/moe_stage_cases.py, formats, the quantiser oracle and the bounds from tests/mx_cases.py.
 
