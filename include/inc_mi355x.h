@@ -675,7 +675,23 @@ int inc_w8a8_gemm_rowscale(const int8_t* xq, const int8_t* wq, const float* row_
  *   that store, element by element otherwise.  No workspace and no counters.
  *   INC_ERR_UNSUPPORTED (nothing launched) for a pair other than inc_mx_gemm's three, Kp % 128 != 0, E > 512, S > 2^22, mode 0 with odd
  *   N, a bad odtype or (mode 1) wdtype; INC_ERR_BAD_ARG for a NULL operand (routing_weights: mode 1 only) or a size < 1.
- * All five validate their arguments before any HIP call.                                                                        */
+ * inc_mx_moe_gemm_glu (the same kernel with a second epilogue): inc_mx_moe_gemm for the experts of GPT-OSS (transformers'
+ *   GptOssExperts) -- a per-expert bias in every mode and a clamped SwiGLU instead of the SiLU product in mode 0.  Everything not
+ *   named here is inc_mx_moe_gemm's: the operands, the route, the three format pairs, the tile / strip map, the in-workgroup K split,
+ *   the output dtypes per mode and the argument checks in their order.  acc is that kernel's fp32 sum (the same waves in the same
+ *   order: bit-identical).  bias fp32 [E, N], 4-byte aligned, or NULL; b(e, n) = bias[e * N + n], and with bias == NULL no add is
+ *   made.  Mode 0 keeps the row convention: gate rows 0 .. I-1 and up rows I .. 2I-1 of wq, ws and bias (GPT-OSS interleaves gate and
+ *   up; the caller de-interleaves once, at conversion).
+ *     mode 0:  g = acc[p, j] + b(e, j);  u = acc[p, I + j] + b(e, I + j)                    (one fp32 add each)
+ *              g = fminf(g, limit);      u = fminf(fmaxf(u, -limit), limit)
+ *              out[p, j] = rd16( (u + 1.f) * (g / (1.f + expf(-(alpha * g)))) )             (fp32, no contraction, ONE rounding)
+ *     mode 1:  out[p, n] = w[order[p]] * (acc[p, n] + b(e, n))                              (fp32; HF: (h @ W + bias) * weight)
+ *     mode 2:  out[p, n] = acc[p, n] + b(e, n)                                              (fp32)
+ *   alpha and limit are used in mode 0 only (GPT-OSS: 1.702 and 7.0); limit = +inf is no clamp.  On top of inc_mx_moe_gemm's checks:
+ *   INC_ERR_BAD_ARG unless limit > 0 and alpha == alpha, and for a bias that is not 4-byte aligned.  With a NaN accumulator (NaN
+ *   codes or 0xFF scale bytes, which inc_mx_quant never writes for finite input) the output is unspecified.  bias is read after the
+ *   LDS sum, by the lanes that store, for the columns they store.
+ * All six validate their arguments before any HIP call.                                                                         */
 #define INC_MX_FP8_E4M3 0
 #define INC_MX_FP4_E2M1 4
 #define INC_MX_KTILE 128
@@ -692,6 +708,10 @@ int inc_mx_gemv_multi(int n, const uint8_t* xq, const uint8_t* xs, int xfmt, con
 int inc_mx_moe_gemm(int mode, const uint8_t* aq, const uint8_t* as, int afmt, const int32_t* route, const uint8_t* wq,
                     const uint8_t* ws, int wfmt, const void* routing_weights, int wdtype, void* out, int odtype, int64_t T, int top_k,
                     int64_t E, int64_t N, int64_t Kp, inc_stream_t stream);
+int inc_mx_moe_gemm_glu(int mode, const uint8_t* aq, const uint8_t* as, int afmt, const int32_t* route, const uint8_t* wq,
+                        const uint8_t* ws, int wfmt, const float* bias, float alpha, float limit, const void* routing_weights,
+                        int wdtype, void* out, int odtype, int64_t T, int top_k, int64_t E, int64_t N, int64_t Kp,
+                        inc_stream_t stream);
 
 /* ---- FP8 per-token / per-channel: OCP e4m3 codes, one fp32 scale per row of x and one per row of W ------- *
  * The "FP8 dynamic" cell: csrc/sq.hip (the quantiser, next to the int8 token kernel it shares its structure with) and

@@ -103,6 +103,10 @@ SIGNATURES = {
         c_int,
         [c_int, _P, _P, c_int, _P, _P, _P, c_int, _P, c_int, _P, c_int, c_int64, c_int, c_int64, c_int64, c_int64, _P],
     ),
+    "inc_mx_moe_gemm_glu": (
+        c_int,
+        [c_int, _P, _P, c_int, _P, _P, _P, c_int, _P, c_float, c_float, _P, c_int, _P, c_int, c_int64, c_int, c_int64, c_int64, c_int64, _P],
+    ),
     "inc_fp8_quant_rows": (c_int, [_P, c_int, c_int64, c_int64, c_int64, _P, _P, _P, _P]),
     "inc_fp8_gemm": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int64, c_int64, c_int64, _P]),
     "inc_fp8_gemv": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int64, c_int64, c_int64, _P]),

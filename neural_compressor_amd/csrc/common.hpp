@@ -106,6 +106,14 @@ __device__ __forceinline__ float round_to(float v) {
 // silu(g) * u of a gated MLP, formed in fp32 (the caller rounds once): the epilogue of every fused gate / up product -- the grouped MoE
 // GEMMs' mode 0 (gemm_moe.hip, gemm_strip_moe.hip) and the gated launch of the streaming GEMV (gemm_stream.hip)
 __device__ __forceinline__ float silu_mul_f32(float g, float u) { return g / (1.f + expf(-g)) * u; }
+// the clamped SwiGLU of the GPT-OSS experts (transformers' GptOssExperts._apply_gate), formed in fp32 (the caller rounds once):
+// g = min(g, limit), u = clamp(u, -limit, limit), (u + 1) * g * sigmoid(alpha * g).  limit = +inf is no clamp.  Nothing here is a
+// multiply feeding an add, so no contraction can change a bit.  The epilogue of inc_mx_moe_gemm_glu's mode 0 (gemm_strip_moe.hip)
+__device__ __forceinline__ float glu_clamped_f32(float g, float u, float alpha, float limit) {
+  g = fminf(g, limit);
+  u = fminf(fmaxf(u, -limit), limit);
+  return (u + 1.f) * (g / (1.f + expf(-(alpha * g))));
+}
 
 // ---- wave64 reductions --------------------------------------------------------------------
 __device__ __forceinline__ float wave_max(float v) {

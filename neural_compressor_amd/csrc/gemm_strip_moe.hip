@@ -32,9 +32,13 @@
 //             bit); as = a_scale[rows] and ws = alpha[E, N] are fp32 and f(r, n) = a_scale[r] * alpha[e, n] is one
 //             fp32 multiply in the epilogue; a_scale is read by the lanes that store only.  (fp8, fp8) alone; W = 8 is inc_fp8_gemv's
 //             split, hence fixed.
+// The epilogues (an Args type says which): PlainEpi is the above; GluEpi (inc_mx_moe_gemm_glu, the experts of GPT-OSS) adds a per-expert
+// fp32 bias b(e, n) to acc in every mode -- read after the LDS sum by the lanes that store, for the columns they store -- and replaces
+// the SiLU product of mode 0 by the clamped SwiGLU glu_clamped_f32(g, u, alpha, limit) of common.hpp; the K loop is the same code.
 // Algorithmic bytes per launch: the weights and scales of the experts that were hit once per 64-row tile, the activation rows once.
 #include "moe_common.hpp"
 #include "strip_frame.hpp"
+#include <type_traits>
 
 #ifndef INC_MX_MOE_WAVES
 #define INC_MX_MOE_WAVES 8  // W: 4, 8 or 16
@@ -71,6 +75,19 @@ struct StripMoeArgs {
   int64_t N, Kp;
   int wdt, out_bf16, inplace, vec_ok, S, top_k, E, strips;
 };
+// The epilogue policy: PlainEpi is the kernel argument of inc_mx_moe_gemm / inc_fp8_moe_gemm as it is (SiLU product, no bias); GluEpi
+// adds what inc_mx_moe_gemm_glu has on top -- a per-expert fp32 bias [E, N] (NULL: none) in every mode and the clamped SwiGLU of the
+// GPT-OSS experts in mode 0
+template <class Scale>
+struct PlainEpi : StripMoeArgs<Scale> {
+  static constexpr bool GLU = false;
+};
+template <class Scale>
+struct GluEpi : StripMoeArgs<Scale> {
+  static constexpr bool GLU = true;
+  const float* bias;
+  float alpha, limit;
+};
 
 // K-tiles of a wave whose loads are in flight together: up to 64 fragment registers per round, so that every instantiation stays
 // inside 128 VGPRs (two workgroups per CU) without scratch.  Without the scale registers deeper rounds fit the FP8 cell (6 / 4 / 3 / 2:
@@ -79,8 +96,8 @@ struct StripMoeArgs {
 __host__ __device__ constexpr int moe_unroll(int ns, int nb) { return ns + nb <= 2 ? 4 : ns + nb <= 4 ? 2 : 1; }
 
 // one (strip, tile) with NB row blocks; part: the workgroup's LDS
-template <class Cell, int AF, int WF, bool GATED, int NB>
-__device__ __forceinline__ void moe_body(const StripMoeArgs<typename Cell::Scale>& a, f32x4 (&part)[Cell::MW][RB][64], int e, int p0, int rows,
+template <class Cell, class Args, int AF, int WF, bool GATED, int NB>
+__device__ __forceinline__ void moe_body(const Args& a, f32x4 (&part)[Cell::MW][RB][64], int e, int p0, int rows,
                                          int strip) {
   constexpr int NS = GATED ? 2 : 1;  // weight strips: gate and up rows of the same j
   constexpr bool SC = Cell::SCALED;
@@ -134,10 +151,24 @@ __device__ __forceinline__ void moe_body(const StripMoeArgs<typename Cell::Scale
       for (int i = 0; i < 4; ++i) res[s][i] = (rs * (nb + i < Nout ? al[i] : 0.f)) * res[s][i];
     }
   }
+  if constexpr (Args::GLU) {
+    // b(e, n): one fp32 add on the LDS sum, read by the lanes that store only (as the FP8 cell's factors above)
+    if (a.bias) {
+#pragma unroll
+      for (int s = 0; s < NS; ++s) {
+        const float* bs = a.bias + (int64_t)e * a.N + s * Nout + nb;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) res[s][i] = res[s][i] + (nb + i < Nout ? bs[i] : 0.f);
+      }
+    }
+  }
   if constexpr (GATED) {
     float v[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = silu_mul_f32(res[0][i], res[1][i]);
+    for (int i = 0; i < 4; ++i) {
+      if constexpr (Args::GLU) v[i] = glu_clamped_f32(res[0][i], res[1][i], a.alpha, a.limit);
+      else v[i] = silu_mul_f32(res[0][i], res[1][i]);
+    }
     uint16_t* dst = static_cast<uint16_t*>(a.out) + p * Nout + nb;  // the 16-bit type is a launch argument here: no store_quad16
     if (vec) {
       *reinterpret_cast<uint2*>(dst) = a.out_bf16 ? make_uint2(cvt_pair<true>(v[0], v[1]), cvt_pair<true>(v[2], v[3]))
@@ -165,8 +196,8 @@ __device__ __forceinline__ void moe_body(const StripMoeArgs<typename Cell::Scale
   }
 }
 
-template <class Cell, int AF, int WF, bool GATED>
-__global__ __launch_bounds__(Cell::MW * 64, 4) void strip_moe_gemm_kernel(const StripMoeArgs<typename Cell::Scale> a) {
+template <class Cell, class Args, int AF, int WF, bool GATED>
+__global__ __launch_bounds__(Cell::MW * 64, 4) void strip_moe_gemm_kernel(const Args a) {
   __shared__ f32x4 part[Cell::MW][RB][64];
   const int tile = (int)(blockIdx.x / (unsigned)a.strips), strip = (int)(blockIdx.x - (unsigned)tile * (unsigned)a.strips);
   if (tile >= a.route[0]) return;  // more tile slots than tiles
@@ -175,29 +206,32 @@ __global__ __launch_bounds__(Cell::MW * 64, 4) void strip_moe_gemm_kernel(const 
   const int pe = a.route[L.offsets + e + 1];
   const int rows = pe - p0 < MOE_BM ? pe - p0 : MOE_BM;
   const int blocks = __builtin_amdgcn_readfirstlane((rows + 15) >> 4);  // row blocks of this tile: the same for the whole workgroup
-  if (blocks == 1) moe_body<Cell, AF, WF, GATED, 1>(a, part, e, p0, rows, strip);
-  else if (blocks == 2) moe_body<Cell, AF, WF, GATED, 2>(a, part, e, p0, rows, strip);
-  else if (blocks == 3) moe_body<Cell, AF, WF, GATED, 3>(a, part, e, p0, rows, strip);
-  else moe_body<Cell, AF, WF, GATED, 4>(a, part, e, p0, rows, strip);
+  if (blocks == 1) moe_body<Cell, Args, AF, WF, GATED, 1>(a, part, e, p0, rows, strip);
+  else if (blocks == 2) moe_body<Cell, Args, AF, WF, GATED, 2>(a, part, e, p0, rows, strip);
+  else if (blocks == 3) moe_body<Cell, Args, AF, WF, GATED, 3>(a, part, e, p0, rows, strip);
+  else moe_body<Cell, Args, AF, WF, GATED, 4>(a, part, e, p0, rows, strip);
 }
 
-template <class Cell, int AF, int WF>
-void moe_launch(bool gated, unsigned grid, const StripMoeArgs<typename Cell::Scale>& a, inc_stream_t stream) {
+template <class Cell, class Args, int AF, int WF>
+void moe_launch(bool gated, unsigned grid, const Args& a, inc_stream_t stream) {
   if (gated)
-    strip_moe_gemm_kernel<Cell, AF, WF, true><<<grid, Cell::MW * 64, 0, inc_s(stream)>>>(a);
+    strip_moe_gemm_kernel<Cell, Args, AF, WF, true><<<grid, Cell::MW * 64, 0, inc_s(stream)>>>(a);
   else
-    strip_moe_gemm_kernel<Cell, AF, WF, false><<<grid, Cell::MW * 64, 0, inc_s(stream)>>>(a);
+    strip_moe_gemm_kernel<Cell, Args, AF, WF, false><<<grid, Cell::MW * 64, 0, inc_s(stream)>>>(a);
 }
 
-// the argument checks both entry points share, in their order, then the launch.  The FP8 cell has the (fp8, fp8) pair alone
-template <class Cell>
+// the argument checks the entry points share, in their order, then the launch.  The FP8 cell has the (fp8, fp8) pair alone; bias,
+// alpha and limit are the GLU epilogue's and are neither checked nor carried without it
+template <class Cell, bool GLU = false>
 int moe_run(int mode, const uint8_t* aq, const typename Cell::Scale* as, int afmt, const int32_t* route, const uint8_t* wq,
             const typename Cell::Scale* ws, int wfmt, const void* routing_weights, int wdtype, void* out, int odtype, int64_t T, int top_k,
-            int64_t E, int64_t N, int64_t Kp, inc_stream_t stream) {
+            int64_t E, int64_t N, int64_t Kp, inc_stream_t stream, const float* bias = nullptr, float alpha = 1.f, float limit = 1.f) {
+  using Args = std::conditional_t<GLU, GluEpi<typename Cell::Scale>, PlainEpi<typename Cell::Scale>>;
   constexpr int F8 = INC_MX_FP8_E4M3, F4 = INC_MX_FP4_E2M1;
   INC_CHECK_ARG(mode >= 0 && mode <= 2);
   INC_CHECK_ARG(aq && as && route && wq && ws && out && T > 0 && top_k > 0 && E > 0 && N > 0 && Kp > 0);
   INC_CHECK_ARG(mode != 1 || routing_weights);
+  if constexpr (GLU) INC_CHECK_ARG(limit > 0.f && alpha == alpha);
   const bool p88 = afmt == F8 && wfmt == F8;
   const bool p84 = Cell::SCALED && afmt == F8 && wfmt == F4;
   const bool p44 = Cell::SCALED && afmt == F4 && wfmt == F4;
@@ -209,20 +243,24 @@ int moe_run(int mode, const uint8_t* aq, const typename Cell::Scale* as, int afm
   if (mode == 1 && wdtype != INC_F32 && wdtype != INC_F16 && wdtype != INC_BF16) return INC_ERR_UNSUPPORTED;
   INC_CHECK_ARG(((reinterpret_cast<uintptr_t>(aq) | reinterpret_cast<uintptr_t>(wq)) & 15) == 0);
   INC_CHECK_ARG(((reinterpret_cast<uintptr_t>(as) | reinterpret_cast<uintptr_t>(ws)) & (Cell::SCALE_ALIGN - 1)) == 0);
+  if constexpr (GLU) INC_CHECK_ARG((reinterpret_cast<uintptr_t>(bias) & 3) == 0);
   const int64_t S = T * top_k, Nout = mode == 0 ? N / 2 : N;
   const int64_t strips = ceil_div64(Nout, STRIP), units = strips * moe_tiles_max(S, E);
   if (units >= ((int64_t)1 << 31)) return INC_ERR_UNSUPPORTED;
-  StripMoeArgs<typename Cell::Scale> a = {};
+  Args a = {};
+  if constexpr (GLU) {
+    a.bias = bias; a.alpha = alpha; a.limit = limit;
+  }
   a.aq = aq; a.as = as; a.route = route; a.wq = wq; a.ws = ws; a.rw = routing_weights; a.out = out;
   a.N = N; a.Kp = Kp;
   a.wdt = wdtype; a.out_bf16 = odtype == INC_BF16; a.inplace = mode == 1;
   a.vec_ok = (Nout % 4 == 0) && (reinterpret_cast<uintptr_t>(out) & (mode == 0 ? 7 : 15)) == 0;
   a.S = (int)S; a.top_k = top_k; a.E = (int)E; a.strips = (int)strips;
   const unsigned grid = (unsigned)units;
-  if (p88) moe_launch<Cell, F8, F8>(mode == 0, grid, a, stream);
+  if (p88) moe_launch<Cell, Args, F8, F8>(mode == 0, grid, a, stream);
   if constexpr (Cell::SCALED) {
-    if (p84) moe_launch<Cell, F8, F4>(mode == 0, grid, a, stream);
-    if (p44) moe_launch<Cell, F4, F4>(mode == 0, grid, a, stream);
+    if (p84) moe_launch<Cell, Args, F8, F4>(mode == 0, grid, a, stream);
+    if (p44) moe_launch<Cell, Args, F4, F4>(mode == 0, grid, a, stream);
   }
   INC_LAUNCH_RETURN();
 }
@@ -233,6 +271,14 @@ extern "C" int inc_mx_moe_gemm(int mode, const uint8_t* aq, const uint8_t* as, i
                                const uint8_t* ws, int wfmt, const void* routing_weights, int wdtype, void* out, int odtype, int64_t T,
                                int top_k, int64_t E, int64_t N, int64_t Kp, inc_stream_t stream) {
   return moe_run<MxCell>(mode, aq, as, afmt, route, wq, ws, wfmt, routing_weights, wdtype, out, odtype, T, top_k, E, N, Kp, stream);
+}
+
+extern "C" int inc_mx_moe_gemm_glu(int mode, const uint8_t* aq, const uint8_t* as, int afmt, const int32_t* route, const uint8_t* wq,
+                                   const uint8_t* ws, int wfmt, const float* bias, float alpha, float limit, const void* routing_weights,
+                                   int wdtype, void* out, int odtype, int64_t T, int top_k, int64_t E, int64_t N, int64_t Kp,
+                                   inc_stream_t stream) {
+  return moe_run<MxCell, true>(mode, aq, as, afmt, route, wq, ws, wfmt, routing_weights, wdtype, out, odtype, T, top_k, E, N, Kp, stream,
+                               bias, alpha, limit);
 }
 
 extern "C" int inc_fp8_moe_gemm(int mode, const uint8_t* aq, const float* a_scale, const int32_t* route, const uint8_t* wq,

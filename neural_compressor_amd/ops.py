@@ -1773,6 +1773,35 @@ def mx_moe_gemm(mode, aq, as_, afmt, route, wq, ws, wfmt, T, top_k, routing_weig
     return out
 
 
+def mx_moe_gemm_glu(mode, aq, as_, afmt, route, wq, ws, wfmt, T, top_k, bias=None, alpha=1.702, limit=7.0, routing_weights=None, out=None,
+                    out_dtype=None):
+    """inc_mx_moe_gemm_glu: mx_moe_gemm with a per-expert fp32 bias [E, N] (None: no add) in every mode and, in mode 0, the clamped
+    SwiGLU of the GPT-OSS experts instead of the SiLU product: g = min(g, limit), u = clamp(u, -limit, limit), (u + 1) * g *
+    sigmoid(alpha * g), on gate rows 0..I-1 and up rows I..2I-1 of wq / ws / bias.  Shapes, dtypes and modes as mx_moe_gemm."""
+    dev = _dev(aq, as_, route, wq, ws, routing_weights, bias)
+    E, N = wq.shape[0], wq.shape[1]
+    Kp, S = ws.shape[2] * 32, T * top_k
+    assert aq.dtype == torch.uint8 and as_.dtype == torch.uint8 and wq.dtype == torch.uint8 and ws.dtype == torch.uint8
+    assert aq.shape[0] == (S if mode == 1 else T) and as_.shape == (aq.shape[0], Kp // 32) and ws.shape[:2] == (E, N)
+    assert aq.shape[1] == (Kp if afmt == MX_FP8_E4M3 else Kp // 2) and wq.shape[2] == (Kp if wfmt == MX_FP8_E4M3 else Kp // 2)
+    assert aq.is_contiguous() and as_.is_contiguous() and wq.is_contiguous() and ws.is_contiguous()
+    assert bias is None or (bias.dtype == torch.float32 and tuple(bias.shape) == (E, N) and bias.is_contiguous())
+    if mode == 0:
+        odt = out.dtype if out is not None else out_dtype
+        if odt not in (torch.bfloat16, torch.float16):
+            raise TypeError("mx_moe_gemm_glu mode 0 writes bf16 or fp16: pass out_dtype")
+    else:
+        odt = torch.float32
+    if out is None:
+        out = torch.empty((S, N // 2 if mode == 0 else N), dtype=odt, device=dev)
+    wdt = dtype_code(routing_weights.dtype) if routing_weights is not None else INC_F32
+    with torch.cuda.device(dev):
+        check(lib.inc_mx_moe_gemm_glu(mode, _ptr(aq), _ptr(as_), int(afmt), _ptr(route), _ptr(wq), _ptr(ws), int(wfmt), _ptr(bias),
+                                      float(alpha), float(limit), _ptr(routing_weights), wdt, _ptr(out), dtype_code(odt), T, top_k, E, N,
+                                      Kp, _stream()), "inc_mx_moe_gemm_glu")
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------
 # K17 FP8 per-token / per-channel: e4m3 codes with one fp32 scale per row (include/inc_mi355x.h has the specification)
 # ---------------------------------------------------------------------------------------------------

@@ -7,11 +7,16 @@ under `MXQuantConfig(quant_experts=True)`: every expert's two matrices are MX-qu
 every buffer is byte for byte what `inc_mx_quant` writes for expert e's matrix), and forward is six HIP launches with no host
 synchronisation: route -> quantise x -> gate_up product with the SiLU product (`inc_mx_moe_gemm` mode 0) -> quantise h -> down product
 with the routing weight (mode 1) -> combine (include/inc_mi355x.h, K16e).
+
+`MXGptOssExperts` does the same for transformers' `GptOssExperts` (`gate_up_proj [E, H, 2I]` with gate and up interleaved,
+`down_proj [E, I, H]`, two biases, a clamped SwiGLU) through `inc_mx_moe_gemm_glu`, and `from_mxfp4` takes the tensors of an MXFP4
+checkpoint as they are.
 """
 
 import torch
 
 from .... import ops
+from ...utils.utility import is_gpt_oss_experts
 from .mx_quant import FORMATS, PAIRS, _code_values
 
 MAX_EXPERTS = 512  # of inc_moe_route and inc_mx_moe_gemm
@@ -166,9 +171,187 @@ def unsupported_reason(module, cfg):
     pair = (cfg.get("w_dtype"), cfg.get("act_dtype"))
     if pair not in PAIRS:
         return f"(w_dtype, act_dtype)={pair} is not one of {PAIRS}"
+    if is_gpt_oss_experts(module):  # no act_fn: the clamped SwiGLU is the kernel's; there is no dense-only fall-back to keep
+        if E > MAX_EXPERTS:
+            return f"E={E} must be at most {MAX_EXPERTS}"
+        if module.gate_up_proj.shape[1] % 4:
+            return f"H={module.gate_up_proj.shape[1]} must be a multiple of 4"
+        return None
     if not _is_silu(getattr(module, "act_fn", None)):
         return f"activation {type(getattr(module, 'act_fn', None)).__name__} is not SiLU"
     if E > MAX_EXPERTS:
         return f"E={E} must be at most {MAX_EXPERTS}"
     return None
+
+
+# ---- GPT-OSS experts ----------------------------------------------------------------------------------------------------------------
+def gpt_oss_rows(gate_up_proj):
+    """transformers' GptOssExperts.gate_up_proj [E, H, 2I] (gate = columns 0::2, up = columns 1::2) -> the kernel's row order
+    [E, 2I, H]: gate rows 0..I-1, then up rows I..2I-1."""
+    w = gate_up_proj.transpose(1, 2)
+    return torch.cat([w[:, 0::2], w[:, 1::2]], 1)
+
+
+def gpt_oss_rows_inverse(rows):
+    """[E, 2I, H] in the kernel's row order -> [E, H, 2I] interleaved (the inverse of gpt_oss_rows)."""
+    E, N2, H = rows.shape
+    return torch.stack([rows[:, :N2 // 2], rows[:, N2 // 2:]], 2).reshape(E, N2, H).transpose(1, 2)
+
+
+def gpt_oss_bias_rows(bias):
+    """gate_up_proj_bias [E, 2I] interleaved -> gate entries first, then up entries (the reordering of gpt_oss_rows)."""
+    return torch.cat([bias[:, 0::2], bias[:, 1::2]], 1)
+
+
+def gpt_oss_bias_rows_inverse(bias):
+    E, N2 = bias.shape
+    return torch.stack([bias[:, :N2 // 2], bias[:, N2 // 2:]], 2).reshape(E, N2)
+
+
+def mxfp4_buffers(blocks, scales, Kp, interleaved=False):
+    """MXFP4 checkpoint tensors (openai/gpt-oss-*: `*_blocks [E, R, K/32, 16]` uint8, two e2m1 codes a byte with the low nibble first,
+    and `*_scales [E, R, K/32]` uint8 E8M0 with bias 127) -> (qweight [E, R, Kp/2], w_scale [E, R, Kp/32]) of the (w_dtype="fp4") cell
+    WITHOUT re-quantising: the format is the same byte for byte.  Columns are padded to Kp with zero bytes and the scales with byte 0,
+    which is what inc_mx_quant writes for an all-padding block.  interleaved: the rows R = 2I are gate_up's (gate = rows 0::2) and
+    come out de-interleaved, gate rows first."""
+    E, R, G, B = blocks.shape
+    assert blocks.dtype == torch.uint8 and scales.dtype == torch.uint8 and B == 16 and tuple(scales.shape) == (E, R, G)
+    assert Kp % 128 == 0 and Kp >= 32 * G
+    q = torch.zeros((E, R, Kp // 2), dtype=torch.uint8, device=blocks.device)
+    s = torch.zeros((E, R, Kp // 32), dtype=torch.uint8, device=blocks.device)
+    q[:, :, :16 * G] = blocks.reshape(E, R, 16 * G)
+    s[:, :, :G] = scales
+    if interleaved:
+        q, s = torch.cat([q[:, 0::2], q[:, 1::2]], 1), torch.cat([s[:, 0::2], s[:, 1::2]], 1)
+    return q.contiguous(), s.contiguous()
+
+
+class MXGptOssExperts(MXExperts):
+    """transformers' GptOssExperts with MX weights and MX activations.  MXExperts' four buffers in the kernel's row order (gate rows
+    first, then up rows: the module de-interleaves once, at conversion) plus gate_up_bias [E, 2I] (the same order) and down_bias
+    [E, H], fp32.  forward is MXExperts' with inc_mx_moe_gemm_glu in place of inc_mx_moe_gemm: the biases in both products and the
+    clamped SwiGLU (alpha, limit) instead of the SiLU product."""
+
+    # MXExperts' value, kept.  Measured on the GPT-OSS shapes (scripts/mx_gpt_oss_time.py, profiles/mx/mx_gpt_oss_time.log): the fused
+    # route is 8.7 - 41.7 x faster than the dense route at every measured point, up to 128 rows per expert (gpt-oss-20b, T = 1024),
+    # which is as far as the script goes and hence what its rule prints; between 128 and 256 rows per expert it is not measured
+    MOE_MAX_ROWS = 256
+
+    def __init__(self, num_experts, hidden_dim, intermediate_dim, w_dtype="fp8_e4m3", act_dtype="fp8_e4m3", alpha=1.702, limit=7.0,
+                 device="cuda", float_type=torch.float16):
+        if torch.device(device).type != "cuda":
+            raise RuntimeError(f"MXGptOssExperts needs a HIP device ('cuda[:N]'), got '{device}'. There is no CPU implementation.")
+        super().__init__(num_experts, hidden_dim, intermediate_dim, w_dtype=w_dtype, act_dtype=act_dtype, device=device,
+                         float_type=float_type)
+        del self.act_fn  # the activation is the clamped SwiGLU of the kernel
+        self.alpha, self.limit = float(alpha), float(limit)
+        dev = self.gate_up_qweight.device
+        self.register_buffer("gate_up_bias", torch.zeros((num_experts, 2 * intermediate_dim), dtype=torch.float32, device=dev))
+        self.register_buffer("down_bias", torch.zeros((num_experts, hidden_dim), dtype=torch.float32, device=dev))
+
+    @classmethod
+    @torch.no_grad()
+    def from_float(cls, module, w_dtype="fp8_e4m3", act_dtype="fp8_e4m3", device="cuda"):
+        """One inc_mx_quant on the [E * N, K] view of each matrix in the kernel's row order; biases to fp32."""
+        E, H, N2 = module.gate_up_proj.shape
+        I = N2 // 2
+        pd = module.gate_up_proj.dtype
+        new = cls(E, H, I, w_dtype=w_dtype, act_dtype=act_dtype, alpha=module.alpha, limit=module.limit, device=device,
+                  float_type=pd if pd in (torch.float16, torch.bfloat16) else torch.float16)
+        dev = new.gate_up_qweight.device
+        mats = (("gate_up", gpt_oss_rows(module.gate_up_proj.detach().to(dev)), N2, H, new.kp_h),
+                ("down", module.down_proj.detach().to(dev).transpose(1, 2), H, I, new.kp_i))
+        for prefix, p, N, K, kp in mats:
+            codes, scales = ops.mx_quant(p.contiguous().reshape(E * N, K), new.w_fmt, kp)
+            new._buffers[f"{prefix}_qweight"].copy_(codes.view(E, N, -1))
+            new._buffers[f"{prefix}_w_scale"].copy_(scales.view(E, N, -1))
+        new.gate_up_bias.copy_(gpt_oss_bias_rows(module.gate_up_proj_bias.detach().to(dev).float()))
+        new.down_bias.copy_(module.down_proj_bias.detach().to(dev).float())
+        return new
+
+    @classmethod
+    @torch.no_grad()
+    def from_mxfp4(cls, gate_up_blocks, gate_up_scales, gate_up_bias, down_blocks, down_scales, down_bias, act_dtype="fp8_e4m3",
+                   alpha=1.702, limit=7.0, device="cuda", float_type=torch.bfloat16):
+        """The loader for openai/gpt-oss-* checkpoint tensors: gate_up_proj_blocks [E, 2I, H/32, 16], gate_up_proj_scales
+        [E, 2I, H/32], gate_up_proj_bias [E, 2I] (rows interleaved), down_proj_blocks [E, H, I/32, 16], down_proj_scales [E, H, I/32],
+        down_proj_bias [E, H].  w_dtype = "fp4"; the codes and scale bytes are taken as they are (mxfp4_buffers)."""
+        E, N2, GH, _ = gate_up_blocks.shape
+        H, I = 32 * GH, N2 // 2
+        assert tuple(down_blocks.shape[:2]) == (E, H) and down_blocks.shape[2] * 32 == I
+        new = cls(E, H, I, w_dtype="fp4", act_dtype=act_dtype, alpha=alpha, limit=limit, device=device, float_type=float_type)
+        dev = new.gate_up_qweight.device
+        q, s = mxfp4_buffers(gate_up_blocks.to(dev), gate_up_scales.to(dev), new.kp_h, interleaved=True)
+        new.gate_up_qweight.copy_(q)
+        new.gate_up_w_scale.copy_(s)
+        q, s = mxfp4_buffers(down_blocks.to(dev), down_scales.to(dev), new.kp_i)
+        new.down_qweight.copy_(q)
+        new.down_w_scale.copy_(s)
+        new.gate_up_bias.copy_(gpt_oss_bias_rows(gate_up_bias.to(dev).float()))
+        new.down_bias.copy_(down_bias.to(dev).float())
+        return new
+
+    def recover(self, dtype=None, expert=None):
+        """Dequantised weights in the GPT-OSS layout, so that they drop into a float GptOssExperts: gate_up [E, H, 2I] interleaved and
+        down [E, I, H], or expert `expert`'s [H, 2I], [I, H]."""
+        gu, dn = super().recover(dtype, expert)
+        if expert is not None:
+            gu, dn = gu[None], dn[None]
+        gu, dn = gpt_oss_rows_inverse(gu).contiguous(), dn.transpose(1, 2).contiguous()
+        return (gu, dn) if expert is None else (gu[0], dn[0])
+
+    def recover_biases(self, dtype=None):
+        """(gate_up_proj_bias [E, 2I] interleaved, down_proj_bias [E, H]) in `dtype` or float_type."""
+        dtype = self.float_type if dtype is None else dtype
+        return gpt_oss_bias_rows_inverse(self.gate_up_bias).to(dtype), self.down_bias.to(dtype)
+
+    def _fusable(self):
+        # inc_moe_combine stores four columns at a time
+        return self.num_experts <= MAX_EXPERTS and self.hidden_dim % 4 == 0
+
+    def forward(self, hidden_states, router_indices, routing_weights):
+        """GptOssExperts.forward's signature; MXExperts.forward's contract (ids outside 0..E-1, the router's mask class E among them,
+        contribute nothing on both routes)."""
+        return super().forward(hidden_states, router_indices, routing_weights)
+
+    def _fused_forward(self, x2d, idx, w, cdt):
+        T, k = idx.shape
+        E, af, wf = self.num_experts, self.act_fmt, self.w_fmt
+        route = ops.moe_route(idx, E)
+        xq, xs = ops.mx_quant(x2d, af, self.kp_h)
+        h = ops.mx_moe_gemm_glu(0, xq, xs, af, route, self.gate_up_qweight, self.gate_up_w_scale, wf, T, k, bias=self.gate_up_bias,
+                                alpha=self.alpha, limit=self.limit, out_dtype=cdt)
+        hq, hs = ops.mx_quant(h, af, self.kp_i)
+        y = ops.mx_moe_gemm_glu(1, hq, hs, af, route, self.down_qweight, self.down_w_scale, wf, T, k, bias=self.down_bias,
+                                routing_weights=w)
+        return ops.moe_combine(y, route, T, k, E, cdt)
+
+    def _product(self, a, prefix, e, kp, cdt):
+        aq, as_ = ops.mx_quant(a, self.act_fmt, kp)
+        product = ops.mx_gemv if a.shape[0] <= ops.MX_GEMV_MAX_M else ops.mx_gemm
+        return product(aq, as_, self.act_fmt, self._buffers[f"{prefix}_qweight"][e], self._buffers[f"{prefix}_w_scale"][e], self.w_fmt,
+                       self._buffers[f"{prefix}_bias"][e].to(cdt), cdt)
+
+    def _dense_forward(self, x, top_k_index, top_k_weights, cdt):
+        """GptOssExperts.forward with MXLinear's products (and their bias add) on the slices of every expert that was hit, and
+        _apply_gate's arithmetic in the compute dtype (host waits: nonzero / where)."""
+        out = torch.zeros((x.shape[0], self.hidden_dim), dtype=cdt, device=x.device)
+        E, I = self.num_experts, self.intermediate_dim
+        with torch.no_grad():
+            ids = torch.where((top_k_index >= 0) & (top_k_index < E), top_k_index, torch.full_like(top_k_index, E)).long()
+            mask = torch.nn.functional.one_hot(ids, num_classes=E + 1)[..., :E].permute(2, 1, 0)
+            hit = torch.greater(mask.sum(dim=(-1, -2)), 0).nonzero()
+        for e in hit:
+            e = int(e[0])
+            top_k_pos, token_idx = torch.where(mask[e])
+            y = self._product(x[token_idx], "gate_up", e, self.kp_h, cdt)
+            gate, up = y[:, :I].clamp(min=None, max=self.limit), y[:, I:].clamp(min=-self.limit, max=self.limit)
+            glu = gate * torch.sigmoid(gate * self.alpha)
+            y = self._product(((up + 1) * glu).contiguous(), "down", e, self.kp_i, cdt)
+            y = y * top_k_weights[token_idx, top_k_pos, None]
+            out.index_add_(0, token_idx, y.to(cdt))
+        return out
+
+    def extra_repr(self):
+        return super().extra_repr() + f", alpha={self.alpha}, limit={self.limit}"
 

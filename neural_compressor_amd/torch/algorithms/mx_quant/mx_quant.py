@@ -14,7 +14,7 @@ import torch
 
 from .... import ops
 from ....common.utils import logger
-from ...utils.utility import get_module, is_fused_experts, set_module
+from ...utils.utility import get_module, is_fused_experts, is_gpt_oss_experts, set_module
 from ..base_algorithm import Quantizer
 
 FORMATS = {"fp8_e4m3": ops.MX_FP8_E4M3, "fp4": ops.MX_FP4_E2M1}
@@ -140,7 +140,9 @@ def mx_linear_group(x, modules):
 class MXQuantizer(Quantizer):
     """quant_config: {layer name: {"w_dtype", "act_dtype", ...}} (mx_quant_entry).  A layer whose w_dtype is "fp32" stays float.
     Besides nn.Linear the names may be fused MoE experts modules (is_fused_experts; they are in the mapping under
-    MXQuantConfig(quant_experts=True)), which become MXExperts."""
+    MXQuantConfig(quant_experts=True)), which become MXExperts, and GPT-OSS experts modules (is_gpt_oss_experts), which become
+    MXGptOssExperts when their dict carries "gpt_oss_experts": True (mx_quant_entry sets it under quant_experts=True; without the key
+    such a module stays float)."""
 
     def _selected(self, model):
         from .experts import unsupported_reason
@@ -152,7 +154,7 @@ class MXQuantizer(Quantizer):
             mod = get_module(model, name)
             if isinstance(mod, torch.nn.Linear):
                 out.append(name)
-            elif is_fused_experts(mod):
+            elif is_fused_experts(mod) or (is_gpt_oss_experts(mod) and cfg.get("gpt_oss_experts")):
                 why = unsupported_reason(mod, cfg)
                 if why is None:
                     out.append(name)
@@ -165,7 +167,7 @@ class MXQuantizer(Quantizer):
 
     @torch.no_grad()
     def convert(self, model, *args, **kwargs):
-        from .experts import MXExperts
+        from .experts import MXExperts, MXGptOssExperts
 
         dev = torch.device("cuda", torch.cuda.current_device())
         model.to(dev)
@@ -176,7 +178,7 @@ class MXQuantizer(Quantizer):
         for name in names:
             cfg = self.quant_config[name]
             mod = get_module(model, name)
-            cls = MXLinear if isinstance(mod, torch.nn.Linear) else MXExperts
+            cls = MXLinear if isinstance(mod, torch.nn.Linear) else MXGptOssExperts if is_gpt_oss_experts(mod) else MXExperts
             set_module(model, name, cls.from_float(mod, cfg["w_dtype"], cfg["act_dtype"], device=dev))
         model.mx_info = {"blocksize": 32, "round_method": "nearest"}
         return model

@@ -1,9 +1,11 @@
 """save / load of an MX model (`model.save(output_dir)`, `load(output_dir, original_model)`), the files of smooth_quant/save_load.py:
   quantized_weight.pt   state_dict: uint8 `qweight`, uint8 `w_scale`, bias of every MXLinear; the float parameters of everything else
   qconfig.json          {"mx_quant": {blocksize, round_method}, "mx_modules": {name: [w_dtype, act_dtype]},
-                         "mx_experts": {name: [w_dtype, act_dtype, E, H, I]}}
-MXExperts modules save their four uint8 buffers under their own names.  The "mx_experts" key is written only when the model has such
-modules; a directory without it (a model without them, or one written before MXExperts existed) loads as before.
+                         "mx_experts": {name: [w_dtype, act_dtype, E, H, I]},
+                         "mx_gpt_oss_experts": {name: [w_dtype, act_dtype, E, H, I, alpha, limit]}}
+MXExperts modules save their four uint8 buffers under their own names, MXGptOssExperts modules those and their two fp32 biases.  The
+"mx_experts" / "mx_gpt_oss_experts" keys are written only when the model has such modules; a directory without them (a model without
+them, or one written before the modules existed) loads as before.
 """
 
 import json
@@ -11,8 +13,8 @@ import os
 
 import torch
 
-from ...utils.utility import get_module, is_fused_experts, set_module
-from .experts import MXExperts
+from ...utils.utility import get_module, is_fused_experts, is_gpt_oss_experts, set_module
+from .experts import MXExperts, MXGptOssExperts
 from .mx_quant import MXLinear
 
 WEIGHT_NAME = "quantized_weight.pt"
@@ -23,10 +25,14 @@ def qconfig_of(model):
     """The content of qconfig.json."""
     mods = {n: [m.w_dtype, m.act_dtype] for n, m in model.named_modules() if isinstance(m, MXLinear)}
     experts = {n: [m.w_dtype, m.act_dtype, m.num_experts, m.hidden_dim, m.intermediate_dim] for n, m in model.named_modules()
-               if isinstance(m, MXExperts)}
+               if isinstance(m, MXExperts) and not isinstance(m, MXGptOssExperts)}
+    oss = {n: [m.w_dtype, m.act_dtype, m.num_experts, m.hidden_dim, m.intermediate_dim, m.alpha, m.limit]
+           for n, m in model.named_modules() if isinstance(m, MXGptOssExperts)}
     cfg = {"mx_quant": dict(getattr(model, "mx_info", {})), "mx_modules": mods}
     if experts:  # a model without MXExperts writes the file it always wrote
         cfg["mx_experts"] = experts
+    if oss:
+        cfg["mx_gpt_oss_experts"] = oss
     return cfg
 
 
@@ -68,6 +74,14 @@ def load(output_dir, original_model, device="cuda"):
         pd = old.gate_up_proj.dtype
         new = MXExperts(E, H, I, w_dtype=w_dtype, act_dtype=act_dtype, act_fn=old.act_fn, device=dev,
                         float_type=pd if pd in (torch.float16, torch.bfloat16) else torch.float16)
+        _take(state, name, new, dev)
+        set_module(original_model, name, new)
+    for name, (w_dtype, act_dtype, E, H, I, alpha, limit) in cfg.get("mx_gpt_oss_experts", {}).items():
+        old = get_module(original_model, name)
+        assert is_gpt_oss_experts(old), f"{name}: expected a GPT-OSS experts module in the float architecture, got {type(old).__name__}"
+        pd = old.gate_up_proj.dtype
+        new = MXGptOssExperts(E, H, I, w_dtype=w_dtype, act_dtype=act_dtype, alpha=alpha, limit=limit, device=dev,
+                              float_type=pd if pd in (torch.float16, torch.bfloat16) else torch.float16)
         _take(state, name, new, dev)
         set_module(original_model, name, new)
     original_model.load_state_dict(state, strict=False, assign=True)

@@ -198,6 +198,8 @@ def mx_quant_entry(model, configs_mapping, mode=Mode.QUANTIZE, *args, **kwargs):
             continue
         quant_config[op_name] = {"w_dtype": cfg.w_dtype, "act_dtype": cfg.act_dtype, "blocksize": cfg.blocksize,
                                  "round_method": cfg.round_method}
+        if getattr(cfg, "quant_experts", False):  # what lets MXQuantizer convert a GPT-OSS experts module
+            quant_config[op_name]["gpt_oss_experts"] = True
     quantizer = get_quantizer(model, quantizer_cls=MXQuantizer, quant_config=quant_config)
     model = quantizer.execute(model, mode=mode)
     model.qconfig = configs_mapping

@@ -14,7 +14,7 @@ import torch
 from ...common.base_config import BaseConfig, register_config
 from ...common.utils import AWQ, DEFAULT_WHITE_LIST, FP8_QUANT, GPTQ, MX_QUANT, RTN, SMOOTH_QUANT
 from ..utils.utility import (
-    LM_HEAD_NAMES, PRIORITY_AWQ, PRIORITY_FP8_QUANT, PRIORITY_GPTQ, PRIORITY_MX_QUANT, PRIORITY_RTN, PRIORITY_SMOOTH_QUANT, WOQ_WHITE_LIST, is_fused_experts,
+    LM_HEAD_NAMES, PRIORITY_AWQ, PRIORITY_FP8_QUANT, PRIORITY_GPTQ, PRIORITY_MX_QUANT, PRIORITY_RTN, PRIORITY_SMOOTH_QUANT, WOQ_WHITE_LIST, is_fused_experts, is_gpt_oss_experts,
 )
 
 FRAMEWORK_NAME = "torch"
@@ -351,7 +351,8 @@ class MXQuantConfig(TorchBaseConfig):
         if not self.quant_experts:
             return model_info
         have = set(model_info)
-        extra = [(name, type(m).__name__) for name, m in model.named_modules() if is_fused_experts(m)]
+        # GPT-OSS experts (is_gpt_oss_experts: transposed, interleaved, biased, clamped SwiGLU) become MXGptOssExperts
+        extra = [(name, type(m).__name__) for name, m in model.named_modules() if is_fused_experts(m) or is_gpt_oss_experts(m)]
         return list(model_info) + [e for e in extra if e not in have]
 
     def to_config_mapping(self, config_list=None, model_info=None):

@@ -35,6 +35,24 @@ def is_fused_experts(module):
     return hasattr(module, "act_fn")
 
 
+def is_gpt_oss_experts(module):
+    """A transformers GPT-OSS experts module (`GptOssExperts`), recognised by shape: 3-D `gate_up_proj [E, H, 2I]` (gate = columns
+    0::2, up = columns 1::2) and `down_proj [E, I, H]`, parameters `gate_up_proj_bias [E, 2I]` and `down_proj_bias [E, H]`, numeric
+    attributes `alpha` and `limit` (the clamped SwiGLU).  MXQuantConfig(quant_experts=True) converts it to MXGptOssExperts."""
+    gu, dn = getattr(module, "gate_up_proj", None), getattr(module, "down_proj", None)
+    if not isinstance(gu, torch.Tensor) or not isinstance(dn, torch.Tensor) or gu.dim() != 3 or dn.dim() != 3:
+        return False
+    E, H, N2 = gu.shape
+    if N2 % 2 or tuple(dn.shape) != (E, N2 // 2, H):
+        return False
+    params = dict(module.named_parameters(recurse=False))
+    gb, db = params.get("gate_up_proj_bias"), params.get("down_proj_bias")
+    if gb is None or db is None or tuple(gb.shape) != (E, N2) or tuple(db.shape) != (E, H):
+        return False
+    num = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool)  # noqa: E731
+    return num(getattr(module, "alpha", None)) and num(getattr(module, "limit", None))
+
+
 LM_HEAD_NAMES = [".*lm_head", ".*output_layer", ".*embed_out"]  # reference torch/utils/constants.py:69
 PRIORITY_GPTQ, PRIORITY_RTN, PRIORITY_AWQ = 90, 80, 70  # reference torch/utils/constants.py:45-48
 PRIORITY_SMOOTH_QUANT = 60
