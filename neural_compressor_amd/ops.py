@@ -1746,27 +1746,40 @@ def mx_gemv_multi(xq, xs, xfmt, wqs, wss, wfmt, biases, out_dtype):
     return ys
 
 
-def mx_moe_gemm(mode, aq, as_, afmt, route, wq, ws, wfmt, T, top_k, routing_weights=None, out=None, out_dtype=None):
-    """inc_mx_moe_gemm (K16e): mx_gemm's product per expert over the rows of the route's sorted order.  wq [E, N, Kp or Kp/2],
-    ws [E, N, Kp/32] (slice e = mx_quant of expert e's matrix).  mode 0: gate_up + SiLU product -> [T*k, N/2] of `out_dtype` (bf16 /
-    fp16) from aq [T, ...]; mode 1: down x routing weight -> fp32 [T*k, N] from aq [T*k, ...] in sorted order; mode 2: plain -> fp32
-    [T*k, N] from aq [T, ...].  Rows past the route's valid positions are not written."""
-    dev = _dev(aq, as_, route, wq, ws, routing_weights)
+def _moe_gemm_out(mode, out, out_dtype, S, N, dev, routing_weights, name):
+    """(out, its dtype, the routing weights' dtype code) of a routed GEMM wrapper `name` (mx_moe_gemm, mx_moe_gemm_glu, fp8_moe_gemm):
+    mode 0 writes [S, N/2] of out's dtype or `out_dtype` (bf16 / fp16), modes 1 and 2 fp32 [S, N]; `out` is allocated when None."""
+    if mode == 0:
+        odt = out.dtype if out is not None else out_dtype
+        if odt not in (torch.bfloat16, torch.float16):
+            raise TypeError(f"{name} mode 0 writes bf16 or fp16: pass out_dtype")
+    else:
+        odt = torch.float32
+    if out is None:
+        out = torch.empty((S, N // 2 if mode == 0 else N), dtype=odt, device=dev)
+    wdt = dtype_code(routing_weights.dtype) if routing_weights is not None else INC_F32
+    return out, odt, wdt
+
+
+def _mx_moe_check_operands(mode, aq, as_, afmt, wq, ws, wfmt, T, top_k):
+    """The operand checks of mx_moe_gemm and mx_moe_gemm_glu -> (E, N, Kp, S)."""
     E, N = wq.shape[0], wq.shape[1]
     Kp, S = ws.shape[2] * 32, T * top_k
     assert aq.dtype == torch.uint8 and as_.dtype == torch.uint8 and wq.dtype == torch.uint8 and ws.dtype == torch.uint8
     assert aq.shape[0] == (S if mode == 1 else T) and as_.shape == (aq.shape[0], Kp // 32) and ws.shape[:2] == (E, N)
     assert aq.shape[1] == (Kp if afmt == MX_FP8_E4M3 else Kp // 2) and wq.shape[2] == (Kp if wfmt == MX_FP8_E4M3 else Kp // 2)
     assert aq.is_contiguous() and as_.is_contiguous() and wq.is_contiguous() and ws.is_contiguous()
-    if mode == 0:
-        odt = out.dtype if out is not None else out_dtype
-        if odt not in (torch.bfloat16, torch.float16):
-            raise TypeError("mx_moe_gemm mode 0 writes bf16 or fp16: pass out_dtype")
-    else:
-        odt = torch.float32
-    if out is None:
-        out = torch.empty((S, N // 2 if mode == 0 else N), dtype=odt, device=dev)
-    wdt = dtype_code(routing_weights.dtype) if routing_weights is not None else INC_F32
+    return E, N, Kp, S
+
+
+def mx_moe_gemm(mode, aq, as_, afmt, route, wq, ws, wfmt, T, top_k, routing_weights=None, out=None, out_dtype=None):
+    """inc_mx_moe_gemm (K16e): mx_gemm's product per expert over the rows of the route's sorted order.  wq [E, N, Kp or Kp/2],
+    ws [E, N, Kp/32] (slice e = mx_quant of expert e's matrix).  mode 0: gate_up + SiLU product -> [T*k, N/2] of `out_dtype` (bf16 /
+    fp16) from aq [T, ...]; mode 1: down x routing weight -> fp32 [T*k, N] from aq [T*k, ...] in sorted order; mode 2: plain -> fp32
+    [T*k, N] from aq [T, ...].  Rows past the route's valid positions are not written."""
+    dev = _dev(aq, as_, route, wq, ws, routing_weights)
+    E, N, Kp, S = _mx_moe_check_operands(mode, aq, as_, afmt, wq, ws, wfmt, T, top_k)
+    out, odt, wdt = _moe_gemm_out(mode, out, out_dtype, S, N, dev, routing_weights, "mx_moe_gemm")
     with torch.cuda.device(dev):
         check(lib.inc_mx_moe_gemm(mode, _ptr(aq), _ptr(as_), int(afmt), _ptr(route), _ptr(wq), _ptr(ws), int(wfmt), _ptr(routing_weights),
                                   wdt, _ptr(out), dtype_code(odt), T, top_k, E, N, Kp, _stream()), "inc_mx_moe_gemm")
@@ -1779,22 +1792,9 @@ def mx_moe_gemm_glu(mode, aq, as_, afmt, route, wq, ws, wfmt, T, top_k, bias=Non
     SwiGLU of the GPT-OSS experts instead of the SiLU product: g = min(g, limit), u = clamp(u, -limit, limit), (u + 1) * g *
     sigmoid(alpha * g), on gate rows 0..I-1 and up rows I..2I-1 of wq / ws / bias.  Shapes, dtypes and modes as mx_moe_gemm."""
     dev = _dev(aq, as_, route, wq, ws, routing_weights, bias)
-    E, N = wq.shape[0], wq.shape[1]
-    Kp, S = ws.shape[2] * 32, T * top_k
-    assert aq.dtype == torch.uint8 and as_.dtype == torch.uint8 and wq.dtype == torch.uint8 and ws.dtype == torch.uint8
-    assert aq.shape[0] == (S if mode == 1 else T) and as_.shape == (aq.shape[0], Kp // 32) and ws.shape[:2] == (E, N)
-    assert aq.shape[1] == (Kp if afmt == MX_FP8_E4M3 else Kp // 2) and wq.shape[2] == (Kp if wfmt == MX_FP8_E4M3 else Kp // 2)
-    assert aq.is_contiguous() and as_.is_contiguous() and wq.is_contiguous() and ws.is_contiguous()
+    E, N, Kp, S = _mx_moe_check_operands(mode, aq, as_, afmt, wq, ws, wfmt, T, top_k)
     assert bias is None or (bias.dtype == torch.float32 and tuple(bias.shape) == (E, N) and bias.is_contiguous())
-    if mode == 0:
-        odt = out.dtype if out is not None else out_dtype
-        if odt not in (torch.bfloat16, torch.float16):
-            raise TypeError("mx_moe_gemm_glu mode 0 writes bf16 or fp16: pass out_dtype")
-    else:
-        odt = torch.float32
-    if out is None:
-        out = torch.empty((S, N // 2 if mode == 0 else N), dtype=odt, device=dev)
-    wdt = dtype_code(routing_weights.dtype) if routing_weights is not None else INC_F32
+    out, odt, wdt = _moe_gemm_out(mode, out, out_dtype, S, N, dev, routing_weights, "mx_moe_gemm_glu")
     with torch.cuda.device(dev):
         check(lib.inc_mx_moe_gemm_glu(mode, _ptr(aq), _ptr(as_), int(afmt), _ptr(route), _ptr(wq), _ptr(ws), int(wfmt), _ptr(bias),
                                       float(alpha), float(limit), _ptr(routing_weights), wdt, _ptr(out), dtype_code(odt), T, top_k, E, N,
@@ -1912,15 +1912,7 @@ def fp8_moe_gemm(mode, aq, a_scale, route, wq, alpha, T, top_k, routing_weights=
     assert aq.dtype == torch.uint8 and wq.dtype == torch.uint8 and a_scale.dtype == torch.float32 and alpha.dtype == torch.float32
     assert aq.shape == ((S if mode == 1 else T), Kp) and a_scale.numel() == aq.shape[0] and alpha.shape == (E, N)
     assert aq.is_contiguous() and a_scale.is_contiguous() and wq.is_contiguous() and alpha.is_contiguous()
-    if mode == 0:
-        odt = out.dtype if out is not None else out_dtype
-        if odt not in (torch.bfloat16, torch.float16):
-            raise TypeError("fp8_moe_gemm mode 0 writes bf16 or fp16: pass out_dtype")
-    else:
-        odt = torch.float32
-    if out is None:
-        out = torch.empty((S, N // 2 if mode == 0 else N), dtype=odt, device=dev)
-    wdt = dtype_code(routing_weights.dtype) if routing_weights is not None else INC_F32
+    out, odt, wdt = _moe_gemm_out(mode, out, out_dtype, S, N, dev, routing_weights, "fp8_moe_gemm")
     with torch.cuda.device(dev):
         check(lib.inc_fp8_moe_gemm(mode, _ptr(aq), _ptr(a_scale), _ptr(route), _ptr(wq), _ptr(alpha), _ptr(routing_weights), wdt,
                                    _ptr(out), dtype_code(odt), T, top_k, E, N, Kp, _stream()), "inc_fp8_moe_gemm")

@@ -6,28 +6,24 @@ parameters, `gate_up_proj [E, 2I, H]` (gate rows 0..I-1, up rows I..2I-1) and `d
 under `FP8Config(moe_experts=True)`: every expert's two matrices are quantised as `FP8Linear` quantises a weight (slice e of every
 buffer is byte for byte what `inc_fp8_quant_rows` writes for expert e's matrix), and forward is six HIP launches with no host
 synchronisation: route -> quantise x -> gate_up product with the SiLU product (`inc_fp8_moe_gemm` mode 0) -> quantise h -> down
-product with the routing weight (mode 1) -> combine (include/inc_mi355x.h, K17e).
+product with the routing weight (mode 1) -> combine (include/inc_mi355x.h, K17e).  The forward contract and the
+dense route's loop are FusedExperts' (fused_experts.py).
 """
 
 import torch
 
 from .... import ops
-
-MAX_EXPERTS = 512  # of inc_moe_route and inc_fp8_moe_gemm
-
-
-def _is_silu(act_fn):
-    return isinstance(act_fn, torch.nn.SiLU) or type(act_fn).__name__ in ("SiLU", "SiLUActivation")
+from ...utils.utility import half_or_fp16
+from ..fused_experts import MAX_EXPERTS, FusedExperts, is_silu
 
 
-class FP8Experts(torch.nn.Module):
+class FP8Experts(FusedExperts):
     """Fused experts with e4m3 weights (one fp32 scale per output channel of every expert) and e4m3 activations (one fp32 scale per
     token, from the data of the call).  Buffers (Kp = K rounded up to 128): gate_up_qweight uint8 [E, 2I, Kp(H)], gate_up_w_scale fp32
-    [E, 2I], down_qweight uint8 [E, H, Kp(I)], down_w_scale fp32 [E, H]."""
+    [E, 2I], down_qweight uint8 [E, H, Kp(I)], down_w_scale fp32 [E, H].  bf16 / fp16 compute in their own dtype, fp32 computes in
+    float_type and is cast back (as FP8Linear.forward).  The dense route (the referee) runs FP8Linear's own kernels
+    (inc_fp8_quant_rows, inc_fp8_gemv / inc_fp8_gemm) on the slices of every expert that was hit."""
 
-    # True: the fused route (six launches, no host wait).  False: the dense route -- per expert that was hit (host waits), gather its
-    # rows and run FP8Linear's own kernels (inc_fp8_quant_rows, inc_fp8_gemv / inc_fp8_gemm) on that expert's slices: the referee
-    MOE_FUSED = True
     # the fused route serves up to this many routed rows per expert on average (T * top_k <= MOE_MAX_ROWS * E); larger batches take the
     # dense route.  Measured (scripts/fp8_moe_time.py, profiles/fp8/fp8_moe_time.log; the rule is the script's last line): Mixtral
     # (E 8, k 2) fused 1.09 x faster than dense at T = 1024 (256 rows per expert), dense 2.4 x faster at T = 4096 (1024); Qwen3-MoE
@@ -35,15 +31,13 @@ class FP8Experts(torch.nn.Module):
     MOE_MAX_ROWS = 256
 
     def __init__(self, num_experts, hidden_dim, intermediate_dim, act_fn=None, device="cuda", float_type=torch.float16):
-        super().__init__()
         dev = torch.device(device)
         if dev.type != "cuda":
             raise RuntimeError(f"FP8Experts needs a HIP device ('cuda[:N]'), got '{device}'. There is no CPU implementation.")
+        super().__init__(num_experts, hidden_dim, intermediate_dim, act_fn)
         E, H, I = num_experts, hidden_dim, intermediate_dim
-        self.num_experts, self.hidden_dim, self.intermediate_dim = E, H, I
         self.kp_h, self.kp_i = ops.mx_padded_k(H), ops.mx_padded_k(I)
         self.float_type = float_type
-        self.act_fn = act_fn if act_fn is not None else torch.nn.SiLU()
         for prefix, N, kp in (("gate_up", 2 * I, self.kp_h), ("down", H, self.kp_i)):
             self.register_buffer(f"{prefix}_qweight", torch.zeros((E, N, kp), dtype=torch.uint8, device=dev))
             self.register_buffer(f"{prefix}_w_scale", torch.zeros((E, N), dtype=torch.float32, device=dev))
@@ -55,8 +49,7 @@ class FP8Experts(torch.nn.Module):
         its own."""
         E, N2, H = module.gate_up_proj.shape
         I = N2 // 2
-        pd = module.gate_up_proj.dtype
-        new = cls(E, H, I, act_fn=module.act_fn, device=device, float_type=pd if pd in (torch.float16, torch.bfloat16) else torch.float16)
+        new = cls(E, H, I, act_fn=module.act_fn, device=device, float_type=half_or_fp16(module.gate_up_proj.dtype))
         dev = new.gate_up_qweight.device
         for prefix, p, N, K, kp in (("gate_up", module.gate_up_proj, N2, H, new.kp_h), ("down", module.down_proj, H, I, new.kp_i)):
             codes, scale = ops.fp8_quant_rows(p.detach().to(dev).reshape(E * N, K), None, kp)
@@ -79,30 +72,10 @@ class FP8Experts(torch.nn.Module):
 
     def _fusable(self):
         # inc_moe_combine stores four columns at a time
-        return _is_silu(self.act_fn) and self.num_experts <= MAX_EXPERTS and self.hidden_dim % 4 == 0
+        return is_silu(self.act_fn) and self.num_experts <= MAX_EXPERTS and self.hidden_dim % 4 == 0
 
-    def forward(self, hidden_states, top_k_index, top_k_weights):
-        """transformers' experts signature: hidden_states [T, H], top_k_index / top_k_weights [T, k] -> [T, H] of hidden_states' dtype.
-        bf16 / fp16 compute in their own dtype, fp32 computes in float_type and is cast back (as FP8Linear.forward).  Expert ids outside
-        0..E-1 (a "no expert" sentinel such as -1) contribute nothing, on both routes."""
-        x = hidden_states
-        x2d = x.reshape(-1, self.hidden_dim)
-        cdt = x.dtype if x.dtype in (torch.float16, torch.bfloat16) else self.float_type
-        T = x2d.shape[0]
-        if T == 0 or top_k_index.numel() == 0:
-            return torch.zeros_like(x)
-        idx = top_k_index.reshape(T, -1)
-        k = idx.shape[1]
-        if self.MOE_FUSED and T * k <= self.MOE_MAX_ROWS * self.num_experts and self._fusable():
-            if idx.dtype not in (torch.int64, torch.int32):
-                idx = idx.long()
-            w = top_k_weights.reshape(T, k)
-            if w.dtype not in (torch.float32, torch.bfloat16, torch.float16):
-                w = w.float()
-            y = self._fused_forward(x2d, idx.contiguous(), w.contiguous(), cdt)
-        else:
-            y = self._dense_forward(x2d, idx, top_k_weights.reshape(T, k), cdt)
-        return y.to(x.dtype).reshape(x.shape)
+    def _compute_dtype(self, x):
+        return x.dtype if x.dtype in (torch.float16, torch.bfloat16) else self.float_type
 
     def _fused_forward(self, x2d, idx, w, cdt):
         """Six launches in stream order; every buffer is allocated per call and nothing is kept.  Rows of h past the route's valid
@@ -123,24 +96,9 @@ class FP8Experts(torch.nn.Module):
         product = ops.fp8_gemv if a.shape[0] <= ops.FP8_GEMV_MAX_M else ops.fp8_gemm
         return product(aq, as_, self._buffers[f"{prefix}_qweight"][e], self._buffers[f"{prefix}_w_scale"][e], None, cdt)
 
-    def _dense_forward(self, x, top_k_index, top_k_weights, cdt):
-        """transformers' MixtralExperts.forward with FP8Linear's products on the slices of every expert that was hit (host waits:
-        nonzero / where)."""
-        out = torch.zeros((x.shape[0], self.hidden_dim), dtype=cdt, device=x.device)
-        E = self.num_experts
-        with torch.no_grad():
-            # ids outside 0..E-1 go to an extra class E that is never visited: they contribute nothing, as on the fused route
-            ids = torch.where((top_k_index >= 0) & (top_k_index < E), top_k_index, torch.full_like(top_k_index, E)).long()
-            mask = torch.nn.functional.one_hot(ids, num_classes=E + 1)[..., :E].permute(2, 1, 0)
-            hit = torch.greater(mask.sum(dim=(-1, -2)), 0).nonzero()
-        for e in hit:
-            e = int(e[0])
-            top_k_pos, token_idx = torch.where(mask[e])
-            gate, up = self._product(x[token_idx], "gate_up", e, self.kp_h, cdt).chunk(2, dim=-1)
-            y = self._product((self.act_fn(gate) * up).contiguous(), "down", e, self.kp_i, cdt)
-            y = y * top_k_weights[token_idx, top_k_pos, None]
-            out.index_add_(0, token_idx, y.to(cdt))
-        return out
+    def _expert_mlp(self, rows, e, cdt):
+        gate, up = self._product(rows, "gate_up", e, self.kp_h, cdt).chunk(2, dim=-1)
+        return self._product((self.act_fn(gate) * up).contiguous(), "down", e, self.kp_i, cdt)
 
     def extra_repr(self):
         return (f"num_experts={self.num_experts}, hidden_dim={self.hidden_dim}, intermediate_dim={self.intermediate_dim}, "
@@ -150,7 +108,7 @@ class FP8Experts(torch.nn.Module):
 def unsupported_reason(module, cfg):
     """Why FP8Quantizer leaves the fused-experts `module` in float under `cfg` (None = it converts it)."""
     E = module.gate_up_proj.shape[0]
-    if not _is_silu(getattr(module, "act_fn", None)):
+    if not is_silu(getattr(module, "act_fn", None)):
         return f"activation {type(getattr(module, 'act_fn', None)).__name__} is not SiLU"
     if E > MAX_EXPERTS:
         return f"E={E} must be at most {MAX_EXPERTS}"

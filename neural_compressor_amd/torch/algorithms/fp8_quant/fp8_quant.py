@@ -14,8 +14,9 @@ import torch
 
 from .... import ops
 from ....common.utils import logger
-from ...utils.utility import get_module, is_fused_experts, set_module
+from ...utils.utility import get_module, half_or_fp16, is_fused_experts, linear_group_plan, set_module
 from ..base_algorithm import Quantizer
+from ..fused_experts import is_silu
 
 
 class FP8Linear(torch.nn.Module):
@@ -43,7 +44,7 @@ class FP8Linear(torch.nn.Module):
     @classmethod
     @torch.no_grad()
     def from_float(cls, linear, device="cuda"):
-        ft = linear.weight.dtype if linear.weight.dtype in (torch.float16, torch.bfloat16) else torch.float16
+        ft = half_or_fp16(linear.weight.dtype)
         new = cls(linear.in_features, linear.out_features, bias=linear.bias is not None, device=device, float_type=ft)
         dev = new.qweight.device
         codes, scale = ops.fp8_quant_rows(linear.weight.detach().to(dev), None, new.kp)
@@ -82,22 +83,7 @@ class FP8Linear(torch.nn.Module):
 
 
 def _group_plan(x, mods):
-    """What FP8Linear members that multiply the same x share, or None where the group is the plain list of forwards: (x2d, out_dtype,
-    every member decodes)."""
-    m0 = mods[0] if mods else None
-    ok = (2 <= len(mods) <= ops.FP8_GEMV_MAX_MEMBERS and all(isinstance(m, FP8Linear) for m in mods) and x.is_cuda and x.numel() > 0
-          and x.shape[-1] == m0.in_features and x.device == m0.qweight.device
-          and all((m.in_features, m.qweight.device) == (m0.in_features, m0.qweight.device) for m in mods))
-    if not ok:
-        return None
-    half = x.dtype in (torch.float16, torch.bfloat16)
-    out_dtype = x.dtype if half else m0.float_type
-    x2d = x.reshape(-1, m0.in_features)
-    rows = x2d.shape[0]
-    decode = [m._decodes(rows) for m in mods]
-    if not (half or all(m.float_type == out_dtype for m in mods)) or not (all(decode) or rows > ops.FP8_GEMV_MAX_M):
-        return None
-    return x2d, out_dtype, all(decode)
+    return linear_group_plan(x, mods, FP8Linear, ops.FP8_GEMV_MAX_MEMBERS, ops.FP8_GEMV_MAX_M, lambda m: (m.in_features, m.qweight.device))
 
 
 def fp8_linear_group(x, modules):
@@ -137,9 +123,7 @@ def fp8_gated_pair(x, gate, up, act_fn=None):
     Fused when both members are FP8Linear of one in_features, out_features, device and float_type, x is on that device with
     x.shape[-1] == in_features, the row count decodes on both, act_fn is None or SiLU and GATED_FUSED is on.  Otherwise exactly
     act(g) * u with g, u = fp8_linear_group(x, [gate, up]) and act = F.silu by default.  fp32 x and the reshape: FP8Linear.forward's."""
-    from .experts import _is_silu
-
-    if GATED_FUSED and (act_fn is None or _is_silu(act_fn)):
+    if GATED_FUSED and (act_fn is None or is_silu(act_fn)):
         plan = _group_plan(x, [gate, up])
         if (plan is not None and plan[2] and gate.out_features == up.out_features and gate.float_type == up.float_type):
             x2d, out_dtype, _ = plan

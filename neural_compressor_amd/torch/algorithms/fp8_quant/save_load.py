@@ -11,7 +11,7 @@ import os
 
 import torch
 
-from ...utils.utility import get_module, is_fused_experts, set_module
+from ...utils.utility import _take, _take_experts, get_module, half_or_fp16, is_fused_experts, set_module
 from .experts import FP8Experts
 from .fp8_quant import FP8Linear
 
@@ -27,14 +27,6 @@ def qconfig_of(model):
     if experts:  # a model without FP8Experts writes the file it always wrote
         cfg["fp8_experts"] = experts
     return cfg
-
-
-def _take(state, name, new, dev):
-    """Load `name.*` of `state` into `new` (strict) and drop those keys."""
-    own = {k[len(name) + 1:]: v for k, v in state.items() if k.startswith(name + ".")}
-    new.load_state_dict({k: v.to(dev) for k, v in own.items()}, strict=True)
-    for k in own:
-        state.pop(name + "." + k)
 
 
 def save(model, output_dir="./saved_results"):
@@ -55,18 +47,13 @@ def load(output_dir, original_model, device="cuda"):
     for name in cfg["fp8_modules"]:
         lin = get_module(original_model, name)
         assert isinstance(lin, torch.nn.Linear), f"{name}: expected nn.Linear in the float architecture, got {type(lin).__name__}"
-        ft = state[name + ".bias"].dtype if (name + ".bias") in state else (
-            lin.weight.dtype if lin.weight.dtype in (torch.float16, torch.bfloat16) else torch.float16)
+        ft = state[name + ".bias"].dtype if (name + ".bias") in state else half_or_fp16(lin.weight.dtype)
         new = FP8Linear(lin.in_features, lin.out_features, bias=(name + ".bias") in state, device=dev, float_type=ft)
         _take(state, name, new, dev)
         set_module(original_model, name, new)
     for name, (E, H, I) in cfg.get("fp8_experts", {}).items():
-        old = get_module(original_model, name)
-        assert is_fused_experts(old), f"{name}: expected a fused experts module in the float architecture, got {type(old).__name__}"
-        pd = old.gate_up_proj.dtype
-        new = FP8Experts(E, H, I, act_fn=old.act_fn, device=dev, float_type=pd if pd in (torch.float16, torch.bfloat16) else torch.float16)
-        _take(state, name, new, dev)
-        set_module(original_model, name, new)
+        _take_experts(state, original_model, name, dev, is_fused_experts,
+                      lambda old: FP8Experts(E, H, I, act_fn=old.act_fn, device=dev, float_type=half_or_fp16(old.gate_up_proj.dtype)))
     original_model.load_state_dict(state, strict=False, assign=True)
     original_model.to(dev)
     original_model.eval()

@@ -10,34 +10,28 @@ with the routing weight (mode 1) -> combine (include/inc_mi355x.h, K16e; DESIGN 
 
 `MXGptOssExperts` does the same for transformers' `GptOssExperts` (`gate_up_proj [E, H, 2I]` with gate and up interleaved,
 `down_proj [E, I, H]`, two biases, a clamped SwiGLU) through `inc_mx_moe_gemm_glu`, and `from_mxfp4` takes the tensors of an MXFP4
-checkpoint as they are.
+checkpoint as they are.  The forward contract and the dense route's loop are FusedExperts' (fused_experts.py).
 """
 
 import torch
 
 from .... import ops
-from ...utils.utility import is_gpt_oss_experts
+from ...utils.utility import half_or_fp16, is_gpt_oss_experts
+from ..fused_experts import MAX_EXPERTS, FusedExperts, is_silu
 from .mx_quant import FORMATS, PAIRS, _code_values
-
-MAX_EXPERTS = 512  # of inc_moe_route and inc_mx_moe_gemm
-
-
-def _is_silu(act_fn):
-    return isinstance(act_fn, torch.nn.SiLU) or type(act_fn).__name__ in ("SiLU", "SiLUActivation")
 
 
 def _cols(fmt, kp):
     return kp if fmt == ops.MX_FP8_E4M3 else kp // 2
 
 
-class MXExperts(torch.nn.Module):
+class MXExperts(FusedExperts):
     """Fused experts with MX weights and MX activations.  Buffers (Kp = K rounded up to 128, uint8): gate_up_qweight [E, 2I, Kp(H)]
     (fp8) or [E, 2I, Kp(H)/2] (fp4), gate_up_w_scale [E, 2I, Kp(H)/32], down_qweight [E, H, Kp(I) or Kp(I)/2], down_w_scale
-    [E, H, Kp(I)/32]."""
+    [E, H, Kp(I)/32].  bf16 / fp16 compute in their own dtype, fp32 computes in float_type and is cast back (as MXLinear.forward).
+    The dense route (the referee) runs MXLinear's own kernels (inc_mx_quant, inc_mx_gemv / inc_mx_gemm) on the slices of every expert
+    that was hit."""
 
-    # True: the fused route (six launches, no host wait).  False: the dense route -- per expert that was hit (host waits), gather its
-    # rows and run MXLinear's own kernels (inc_mx_quant, inc_mx_gemv / inc_mx_gemm) on that expert's slices: the referee
-    MOE_FUSED = True
     # the fused route serves up to this many routed rows per expert on average (T * top_k <= MOE_MAX_ROWS * E); larger batches take the
     # dense route.  Measured (scripts/mx_moe_time.py, profiles/mx/mx_moe_time.log; the rule is the script's last line): Mixtral
     # (E 8, k 2) fused 1.15 - 1.36 x faster than dense at T = 1024 (256 rows per expert), dense 2.1 - 2.5 x faster at T = 4096 (1024);
@@ -46,19 +40,17 @@ class MXExperts(torch.nn.Module):
 
     def __init__(self, num_experts, hidden_dim, intermediate_dim, w_dtype="fp8_e4m3", act_dtype="fp8_e4m3", act_fn=None, device="cuda",
                  float_type=torch.float16):
-        super().__init__()
         dev = torch.device(device)
         if dev.type != "cuda":
             raise RuntimeError(f"MXExperts needs a HIP device ('cuda[:N]'), got '{device}'. There is no CPU implementation.")
         if (w_dtype, act_dtype) not in PAIRS:
             raise NotImplementedError(f"MXQuant on MI355X: (w_dtype, act_dtype) must be one of {PAIRS}, got {(w_dtype, act_dtype)}")
+        super().__init__(num_experts, hidden_dim, intermediate_dim, act_fn)
         E, H, I = num_experts, hidden_dim, intermediate_dim
-        self.num_experts, self.hidden_dim, self.intermediate_dim = E, H, I
         self.w_dtype, self.act_dtype = w_dtype, act_dtype
         self.w_fmt, self.act_fmt = FORMATS[w_dtype], FORMATS[act_dtype]
         self.kp_h, self.kp_i = ops.mx_padded_k(H), ops.mx_padded_k(I)
         self.float_type = float_type
-        self.act_fn = act_fn if act_fn is not None else torch.nn.SiLU()
         for prefix, N, kp in (("gate_up", 2 * I, self.kp_h), ("down", H, self.kp_i)):
             self.register_buffer(f"{prefix}_qweight", torch.zeros((E, N, _cols(self.w_fmt, kp)), dtype=torch.uint8, device=dev))
             self.register_buffer(f"{prefix}_w_scale", torch.zeros((E, N, kp // 32), dtype=torch.uint8, device=dev))
@@ -70,15 +62,19 @@ class MXExperts(torch.nn.Module):
         quantised on its own."""
         E, N2, H = module.gate_up_proj.shape
         I = N2 // 2
-        pd = module.gate_up_proj.dtype
         new = cls(E, H, I, w_dtype=w_dtype, act_dtype=act_dtype, act_fn=module.act_fn, device=device,
-                  float_type=pd if pd in (torch.float16, torch.bfloat16) else torch.float16)
+                  float_type=half_or_fp16(module.gate_up_proj.dtype))
         dev = new.gate_up_qweight.device
-        for prefix, p, N, K, kp in (("gate_up", module.gate_up_proj, N2, H, new.kp_h), ("down", module.down_proj, H, I, new.kp_i)):
-            codes, scales = ops.mx_quant(p.detach().to(dev).reshape(E * N, K), new.w_fmt, kp)
-            new._buffers[f"{prefix}_qweight"].copy_(codes.view(E, N, -1))
-            new._buffers[f"{prefix}_w_scale"].copy_(scales.view(E, N, -1))
+        new._quantize(module.gate_up_proj.detach().to(dev), module.down_proj.detach().to(dev))
         return new
+
+    def _quantize(self, gate_up, down):
+        """Float matrices in the kernel's order (gate_up [E, 2I, H], down [E, H, I], on the module's device) -> the four buffers."""
+        E, H, I = self.num_experts, self.hidden_dim, self.intermediate_dim
+        for prefix, p, N, K, kp in (("gate_up", gate_up, 2 * I, H, self.kp_h), ("down", down, H, I, self.kp_i)):
+            codes, scales = ops.mx_quant(p.contiguous().reshape(E * N, K), self.w_fmt, kp)
+            self._buffers[f"{prefix}_qweight"].copy_(codes.view(E, N, -1))
+            self._buffers[f"{prefix}_w_scale"].copy_(scales.view(E, N, -1))
 
     def recover(self, dtype=None, expert=None):
         """Dequantised weights (gate_up [E, 2I, H], down [E, H, I]) in `dtype` or float_type, or expert `expert`'s two matrices
@@ -98,30 +94,10 @@ class MXExperts(torch.nn.Module):
 
     def _fusable(self):
         # inc_moe_combine stores four columns at a time
-        return _is_silu(self.act_fn) and self.num_experts <= MAX_EXPERTS and self.hidden_dim % 4 == 0
+        return is_silu(self.act_fn) and self.num_experts <= MAX_EXPERTS and self.hidden_dim % 4 == 0
 
-    def forward(self, hidden_states, top_k_index, top_k_weights):
-        """transformers' experts signature: hidden_states [T, H], top_k_index / top_k_weights [T, k] -> [T, H] of hidden_states' dtype.
-        bf16 / fp16 compute in their own dtype, fp32 computes in float_type and is cast back (as MXLinear.forward).  Expert ids outside
-        0..E-1 (a "no expert" sentinel such as -1) contribute nothing, on both routes."""
-        x = hidden_states
-        x2d = x.reshape(-1, self.hidden_dim)
-        cdt = x.dtype if x.dtype in (torch.float16, torch.bfloat16) else self.float_type
-        T = x2d.shape[0]
-        if T == 0 or top_k_index.numel() == 0:
-            return torch.zeros_like(x)
-        idx = top_k_index.reshape(T, -1)
-        k = idx.shape[1]
-        if self.MOE_FUSED and T * k <= self.MOE_MAX_ROWS * self.num_experts and self._fusable():
-            if idx.dtype not in (torch.int64, torch.int32):
-                idx = idx.long()
-            w = top_k_weights.reshape(T, k)
-            if w.dtype not in (torch.float32, torch.bfloat16, torch.float16):
-                w = w.float()
-            y = self._fused_forward(x2d, idx.contiguous(), w.contiguous(), cdt)
-        else:
-            y = self._dense_forward(x2d, idx, top_k_weights.reshape(T, k), cdt)
-        return y.to(x.dtype).reshape(x.shape)
+    def _compute_dtype(self, x):
+        return x.dtype if x.dtype in (torch.float16, torch.bfloat16) else self.float_type
 
     def _fused_forward(self, x2d, idx, w, cdt):
         """Six launches in stream order; every buffer is allocated per call and nothing is kept.  Rows of h past the route's valid
@@ -141,24 +117,9 @@ class MXExperts(torch.nn.Module):
         return product(aq, as_, self.act_fmt, self._buffers[f"{prefix}_qweight"][e], self._buffers[f"{prefix}_w_scale"][e], self.w_fmt,
                        None, cdt)
 
-    def _dense_forward(self, x, top_k_index, top_k_weights, cdt):
-        """transformers' MixtralExperts.forward with MXLinear's products on the slices of every expert that was hit (host waits:
-        nonzero / where)."""
-        out = torch.zeros((x.shape[0], self.hidden_dim), dtype=cdt, device=x.device)
-        E = self.num_experts
-        with torch.no_grad():
-            # ids outside 0..E-1 go to an extra class E that is never visited: they contribute nothing, as on the fused route
-            ids = torch.where((top_k_index >= 0) & (top_k_index < E), top_k_index, torch.full_like(top_k_index, E)).long()
-            mask = torch.nn.functional.one_hot(ids, num_classes=E + 1)[..., :E].permute(2, 1, 0)
-            hit = torch.greater(mask.sum(dim=(-1, -2)), 0).nonzero()
-        for e in hit:
-            e = int(e[0])
-            top_k_pos, token_idx = torch.where(mask[e])
-            gate, up = self._product(x[token_idx], "gate_up", e, self.kp_h, cdt).chunk(2, dim=-1)
-            y = self._product((self.act_fn(gate) * up).contiguous(), "down", e, self.kp_i, cdt)
-            y = y * top_k_weights[token_idx, top_k_pos, None]
-            out.index_add_(0, token_idx, y.to(cdt))
-        return out
+    def _expert_mlp(self, rows, e, cdt):
+        gate, up = self._product(rows, "gate_up", e, self.kp_h, cdt).chunk(2, dim=-1)
+        return self._product((self.act_fn(gate) * up).contiguous(), "down", e, self.kp_i, cdt)
 
     def extra_repr(self):
         return (f"num_experts={self.num_experts}, hidden_dim={self.hidden_dim}, intermediate_dim={self.intermediate_dim}, "
@@ -177,7 +138,7 @@ def unsupported_reason(module, cfg):
         if module.gate_up_proj.shape[1] % 4:
             return f"H={module.gate_up_proj.shape[1]} must be a multiple of 4"
         return None
-    if not _is_silu(getattr(module, "act_fn", None)):
+    if not is_silu(getattr(module, "act_fn", None)):
         return f"activation {type(getattr(module, 'act_fn', None)).__name__} is not SiLU"
     if E > MAX_EXPERTS:
         return f"E={E} must be at most {MAX_EXPERTS}"
@@ -230,7 +191,9 @@ class MXGptOssExperts(MXExperts):
     """transformers' GptOssExperts with MX weights and MX activations.  MXExperts' four buffers in the kernel's row order (gate rows
     first, then up rows: the module de-interleaves once, at conversion) plus gate_up_bias [E, 2I] (the same order) and down_bias
     [E, H], fp32.  forward is MXExperts' with inc_mx_moe_gemm_glu in place of inc_mx_moe_gemm: the biases in both products and the
-    clamped SwiGLU (alpha, limit) instead of the SiLU product."""
+    clamped SwiGLU (alpha, limit) instead of the SiLU product.  GptOssExperts.forward names its arguments (hidden_states,
+    router_indices, routing_weights); they are FusedExperts.forward's three, in its order and under its contract (ids outside 0..E-1,
+    the router's mask class E among them, contribute nothing on both routes)."""
 
     # MXExperts' value, kept.  Measured on the GPT-OSS shapes (scripts/mx_gpt_oss_time.py, profiles/mx/mx_gpt_oss_time.log): the fused
     # route is 8.7 - 41.7 x faster than the dense route at every measured point, up to 128 rows per expert (gpt-oss-20b, T = 1024),
@@ -255,16 +218,10 @@ class MXGptOssExperts(MXExperts):
         """One inc_mx_quant on the [E * N, K] view of each matrix in the kernel's row order; biases to fp32."""
         E, H, N2 = module.gate_up_proj.shape
         I = N2 // 2
-        pd = module.gate_up_proj.dtype
         new = cls(E, H, I, w_dtype=w_dtype, act_dtype=act_dtype, alpha=module.alpha, limit=module.limit, device=device,
-                  float_type=pd if pd in (torch.float16, torch.bfloat16) else torch.float16)
+                  float_type=half_or_fp16(module.gate_up_proj.dtype))
         dev = new.gate_up_qweight.device
-        mats = (("gate_up", gpt_oss_rows(module.gate_up_proj.detach().to(dev)), N2, H, new.kp_h),
-                ("down", module.down_proj.detach().to(dev).transpose(1, 2), H, I, new.kp_i))
-        for prefix, p, N, K, kp in mats:
-            codes, scales = ops.mx_quant(p.contiguous().reshape(E * N, K), new.w_fmt, kp)
-            new._buffers[f"{prefix}_qweight"].copy_(codes.view(E, N, -1))
-            new._buffers[f"{prefix}_w_scale"].copy_(scales.view(E, N, -1))
+        new._quantize(gpt_oss_rows(module.gate_up_proj.detach().to(dev)), module.down_proj.detach().to(dev).transpose(1, 2))
         new.gate_up_bias.copy_(gpt_oss_bias_rows(module.gate_up_proj_bias.detach().to(dev).float()))
         new.down_bias.copy_(module.down_proj_bias.detach().to(dev).float())
         return new
@@ -309,11 +266,6 @@ class MXGptOssExperts(MXExperts):
         # inc_moe_combine stores four columns at a time
         return self.num_experts <= MAX_EXPERTS and self.hidden_dim % 4 == 0
 
-    def forward(self, hidden_states, router_indices, routing_weights):
-        """GptOssExperts.forward's signature; MXExperts.forward's contract (ids outside 0..E-1, the router's mask class E among them,
-        contribute nothing on both routes)."""
-        return super().forward(hidden_states, router_indices, routing_weights)
-
     def _fused_forward(self, x2d, idx, w, cdt):
         T, k = idx.shape
         E, af, wf = self.num_experts, self.act_fmt, self.w_fmt
@@ -332,25 +284,14 @@ class MXGptOssExperts(MXExperts):
         return product(aq, as_, self.act_fmt, self._buffers[f"{prefix}_qweight"][e], self._buffers[f"{prefix}_w_scale"][e], self.w_fmt,
                        self._buffers[f"{prefix}_bias"][e].to(cdt), cdt)
 
-    def _dense_forward(self, x, top_k_index, top_k_weights, cdt):
-        """GptOssExperts.forward with MXLinear's products (and their bias add) on the slices of every expert that was hit, and
-        _apply_gate's arithmetic in the compute dtype (host waits: nonzero / where)."""
-        out = torch.zeros((x.shape[0], self.hidden_dim), dtype=cdt, device=x.device)
-        E, I = self.num_experts, self.intermediate_dim
-        with torch.no_grad():
-            ids = torch.where((top_k_index >= 0) & (top_k_index < E), top_k_index, torch.full_like(top_k_index, E)).long()
-            mask = torch.nn.functional.one_hot(ids, num_classes=E + 1)[..., :E].permute(2, 1, 0)
-            hit = torch.greater(mask.sum(dim=(-1, -2)), 0).nonzero()
-        for e in hit:
-            e = int(e[0])
-            top_k_pos, token_idx = torch.where(mask[e])
-            y = self._product(x[token_idx], "gate_up", e, self.kp_h, cdt)
-            gate, up = y[:, :I].clamp(min=None, max=self.limit), y[:, I:].clamp(min=-self.limit, max=self.limit)
-            glu = gate * torch.sigmoid(gate * self.alpha)
-            y = self._product(((up + 1) * glu).contiguous(), "down", e, self.kp_i, cdt)
-            y = y * top_k_weights[token_idx, top_k_pos, None]
-            out.index_add_(0, token_idx, y.to(cdt))
-        return out
+    def _expert_mlp(self, rows, e, cdt):
+        """GptOssExperts.forward's MLP with MXLinear's products (and their bias add) on expert e's slices, and _apply_gate's
+        arithmetic in the compute dtype."""
+        I = self.intermediate_dim
+        y = self._product(rows, "gate_up", e, self.kp_h, cdt)
+        gate, up = y[:, :I].clamp(min=None, max=self.limit), y[:, I:].clamp(min=-self.limit, max=self.limit)
+        glu = gate * torch.sigmoid(gate * self.alpha)
+        return self._product(((up + 1) * glu).contiguous(), "down", e, self.kp_i, cdt)
 
     def extra_repr(self):
         return super().extra_repr() + f", alpha={self.alpha}, limit={self.limit}"

@@ -14,7 +14,7 @@ import torch
 
 from .... import ops
 from ....common.utils import logger
-from ...utils.utility import get_module, is_fused_experts, is_gpt_oss_experts, set_module
+from ...utils.utility import get_module, half_or_fp16, is_fused_experts, is_gpt_oss_experts, linear_group_plan, set_module
 from ..base_algorithm import Quantizer
 
 FORMATS = {"fp8_e4m3": ops.MX_FP8_E4M3, "fp4": ops.MX_FP4_E2M1}
@@ -61,7 +61,7 @@ class MXLinear(torch.nn.Module):
     @classmethod
     @torch.no_grad()
     def from_float(cls, linear, w_dtype="fp8_e4m3", act_dtype="fp8_e4m3", device="cuda"):
-        ft = linear.weight.dtype if linear.weight.dtype in (torch.float16, torch.bfloat16) else torch.float16
+        ft = half_or_fp16(linear.weight.dtype)
         new = cls(linear.in_features, linear.out_features, bias=linear.bias is not None, w_dtype=w_dtype, act_dtype=act_dtype,
                   device=device, float_type=ft)
         dev = new.qweight.device
@@ -112,22 +112,14 @@ def mx_linear_group(x, modules):
     MXLinear, mixed formats or widths, fewer than 2 or more than 8 members, x elsewhere or empty, a decode-sized x with DECODE_GEMV off
     -- is the plain list of single forwards."""
     mods = list(modules)
-    m0 = mods[0] if mods else None
-    ok = (2 <= len(mods) <= ops.MX_GEMV_MAX_MEMBERS and all(isinstance(m, MXLinear) for m in mods) and x.is_cuda and x.numel() > 0
-          and x.shape[-1] == m0.in_features and x.device == m0.qweight.device
-          and all((m.in_features, m.w_dtype, m.act_dtype, m.qweight.device) == (m0.in_features, m0.w_dtype, m0.act_dtype, m0.qweight.device)
-                  for m in mods))
-    if ok:
-        half = x.dtype in (torch.float16, torch.bfloat16)
-        out_dtype = x.dtype if half else m0.float_type
-        x2d = x.reshape(-1, m0.in_features)
-        rows = x2d.shape[0]
-        decode = [m._decodes(rows) for m in mods]
-        ok = (half or all(m.float_type == out_dtype for m in mods)) and (all(decode) or rows > ops.MX_GEMV_MAX_M)
-    if not ok:
+    plan = linear_group_plan(x, mods, MXLinear, ops.MX_GEMV_MAX_MEMBERS, ops.MX_GEMV_MAX_M,
+                             lambda m: (m.in_features, m.qweight.device, m.w_dtype, m.act_dtype))
+    if plan is None:
         return [m(x) for m in mods]
+    x2d, out_dtype, decode = plan
+    m0 = mods[0]
     xq, xs = ops.mx_quant(x2d, m0.act_fmt, m0.kp)
-    if all(decode):
+    if decode:
         ys = ops.mx_gemv_multi(xq, xs, m0.act_fmt, [m.qweight for m in mods], [m.w_scale for m in mods], m0.w_fmt,
                                [m.bias for m in mods], out_dtype)
     else:

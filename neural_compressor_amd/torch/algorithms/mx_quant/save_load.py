@@ -13,7 +13,7 @@ import os
 
 import torch
 
-from ...utils.utility import get_module, is_fused_experts, is_gpt_oss_experts, set_module
+from ...utils.utility import _take, _take_experts, get_module, half_or_fp16, is_fused_experts, is_gpt_oss_experts, set_module
 from .experts import MXExperts, MXGptOssExperts
 from .mx_quant import MXLinear
 
@@ -36,14 +36,6 @@ def qconfig_of(model):
     return cfg
 
 
-def _take(state, name, new, dev):
-    """Load `name.*` of `state` into `new` (strict) and drop those keys."""
-    own = {k[len(name) + 1:]: v for k, v in state.items() if k.startswith(name + ".")}
-    new.load_state_dict({k: v.to(dev) for k, v in own.items()}, strict=True)
-    for k in own:
-        state.pop(name + "." + k)
-
-
 def save(model, output_dir="./saved_results"):
     os.makedirs(output_dir, exist_ok=True)
     if torch.cuda.is_available():
@@ -62,28 +54,19 @@ def load(output_dir, original_model, device="cuda"):
     for name, (w_dtype, act_dtype) in cfg["mx_modules"].items():
         lin = get_module(original_model, name)
         assert isinstance(lin, torch.nn.Linear), f"{name}: expected nn.Linear in the float architecture, got {type(lin).__name__}"
-        ft = state[name + ".bias"].dtype if (name + ".bias") in state else (
-            lin.weight.dtype if lin.weight.dtype in (torch.float16, torch.bfloat16) else torch.float16)
+        ft = state[name + ".bias"].dtype if (name + ".bias") in state else half_or_fp16(lin.weight.dtype)
         new = MXLinear(lin.in_features, lin.out_features, bias=(name + ".bias") in state, w_dtype=w_dtype, act_dtype=act_dtype,
                        device=dev, float_type=ft)
         _take(state, name, new, dev)
         set_module(original_model, name, new)
     for name, (w_dtype, act_dtype, E, H, I) in cfg.get("mx_experts", {}).items():
-        old = get_module(original_model, name)
-        assert is_fused_experts(old), f"{name}: expected a fused experts module in the float architecture, got {type(old).__name__}"
-        pd = old.gate_up_proj.dtype
-        new = MXExperts(E, H, I, w_dtype=w_dtype, act_dtype=act_dtype, act_fn=old.act_fn, device=dev,
-                        float_type=pd if pd in (torch.float16, torch.bfloat16) else torch.float16)
-        _take(state, name, new, dev)
-        set_module(original_model, name, new)
+        _take_experts(state, original_model, name, dev, is_fused_experts,
+                      lambda old: MXExperts(E, H, I, w_dtype=w_dtype, act_dtype=act_dtype, act_fn=old.act_fn, device=dev,
+                                            float_type=half_or_fp16(old.gate_up_proj.dtype)))
     for name, (w_dtype, act_dtype, E, H, I, alpha, limit) in cfg.get("mx_gpt_oss_experts", {}).items():
-        old = get_module(original_model, name)
-        assert is_gpt_oss_experts(old), f"{name}: expected a GPT-OSS experts module in the float architecture, got {type(old).__name__}"
-        pd = old.gate_up_proj.dtype
-        new = MXGptOssExperts(E, H, I, w_dtype=w_dtype, act_dtype=act_dtype, alpha=alpha, limit=limit, device=dev,
-                              float_type=pd if pd in (torch.float16, torch.bfloat16) else torch.float16)
-        _take(state, name, new, dev)
-        set_module(original_model, name, new)
+        _take_experts(state, original_model, name, dev, is_gpt_oss_experts,
+                      lambda old: MXGptOssExperts(E, H, I, w_dtype=w_dtype, act_dtype=act_dtype, alpha=alpha, limit=limit, device=dev,
+                                                  float_type=half_or_fp16(old.gate_up_proj.dtype)))
     original_model.load_state_dict(state, strict=False, assign=True)
     original_model.to(dev)
     original_model.eval()

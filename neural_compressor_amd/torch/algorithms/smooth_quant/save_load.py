@@ -14,7 +14,7 @@ import os
 
 import torch
 
-from ...utils.utility import get_module, set_module
+from ...utils.utility import get_module, half_or_fp16, set_module
 from .utility import W8A8Linear
 
 WEIGHT_NAME = "quantized_weight.pt"
@@ -42,8 +42,7 @@ def load(output_dir, original_model, device="cuda"):
     for name in cfg["w8a8_modules"]:
         lin = get_module(original_model, name)
         assert isinstance(lin, torch.nn.Linear), f"{name}: expected nn.Linear in the float architecture, got {type(lin).__name__}"
-        ft = state[name + ".bias"].dtype if (name + ".bias") in state else (
-            lin.weight.dtype if lin.weight.dtype in (torch.float16, torch.bfloat16) else torch.float16)
+        ft = state[name + ".bias"].dtype if (name + ".bias") in state else half_or_fp16(lin.weight.dtype)
         new = W8A8Linear(lin.in_features, lin.out_features, bias=(name + ".bias") in state,
                          has_input_scale=(name + ".input_scale") in state, device=dev, float_type=ft,
                          act_quant="static" if (name + ".act_scale") in state else "per_token")

@@ -17,7 +17,7 @@ import torch
 
 from .... import ops
 from ....common.utils import logger
-from ...utils.utility import get_module, set_module
+from ...utils.utility import get_module, half_or_fp16, set_module
 
 LM_NORM_NAMES = ("LlamaRMSNorm", "T5LayerNorm", "MistralRMSNorm", "Qwen2RMSNorm", "RMSNorm")  # weight-only norms (:2049)
 
@@ -209,7 +209,7 @@ class W8A8Linear(torch.nn.Module):
         wrapper = module if isinstance(module, SQLinearWrapper) else None
         lin = wrapper.sq_linear if wrapper is not None else module
         in_scale = wrapper.input_scale.float() if wrapper is not None else None
-        ft = lin.weight.dtype if lin.weight.dtype in (torch.float16, torch.bfloat16) else torch.float16
+        ft = half_or_fp16(lin.weight.dtype)
         new = cls(lin.in_features, lin.out_features, bias=lin.bias is not None, has_input_scale=in_scale is not None,
                   device=device, float_type=ft, act_quant=act_quant)
         dev = new.qweight.device

@@ -6,7 +6,8 @@ parameters, `gate_up_proj [E, 2I, H]` (gate rows 0..I-1, up rows I..2I-1) and `d
 such a module after RTN: every expert's two matrices are packed in the optimum layout of `MI355XWeightOnlyLinear`, stacked on a
 leading expert axis (slice e of every buffer is byte for byte what `MI355XWeightOnlyLinear.pack` writes for expert e), and forward is
 four HIP launches with no host synchronisation (ops.WoqMoeCall: route -> gate_up GEMM with the SiLU product -> down GEMM with the
-routing weight -> combine; include/inc_mi355x.h, K4e).
+routing weight -> combine; include/inc_mi355x.h, K4e).  The forward contract and the dense route's loop are FusedExperts'
+(fused_experts.py).
 """
 
 import math
@@ -15,39 +16,33 @@ import torch
 
 from .... import ops
 from ....common.utils import logger
+from ..fused_experts import MAX_EXPERTS, FusedExperts, is_silu
 from .modules import _hip_device
 
 _PARTS = ("qweight", "scales", "qzeros")
 
 
-def _is_silu(act_fn):
-    return isinstance(act_fn, torch.nn.SiLU) or type(act_fn).__name__ in ("SiLU", "SiLUActivation")
-
-
-class MI355XWeightOnlyExperts(torch.nn.Module):
+class MI355XWeightOnlyExperts(FusedExperts):
     """Packed INT4 experts (optimum layout per expert, stacked on the expert axis) with a fused HIP forward.
 
     Buffers: gate_up_qweight [E, H/8, 2I] int32, gate_up_scales [E, G_H, 2I] fp16, gate_up_qzeros [E, G_H, 2I/8] int32,
     down_qweight [E, I/8, H], down_scales [E, G_I, H], down_qzeros [E, G_I, H/8]; G_H = H / group_size, G_I = I / group_size
-    (one group per row for group_size = -1)."""
+    (one group per row for group_size = -1).  bf16 / fp16 compute in their own dtype; any other dtype computes in fp16 and is cast
+    back (warned once per module).  The dense route (the referee, and the escape hatch) recover()s the two matrices of every expert
+    that was hit and runs transformers' eager MLP on them."""
 
-    # True: the fused HIP route (ops.WoqMoeCall).  False: the dense route -- per expert that was hit, recover() its two matrices and run
-    # transformers' eager loop on them (the referee, and the escape hatch)
-    MOE_FUSED = True
     # the fused route serves up to this many routed rows per expert on average (T * top_k <= MOE_MAX_ROWS * E); larger batches take the
     # dense route.  Measured (profiles/r8/moe_woq_time.log): Mixtral (E 8, k 2) fused 1.49 x faster than dense at T = 1024 (256 rows per
     # expert), dense 1.39 x faster at T = 4096 (1024 per expert); Qwen3-MoE (E 128, k 8) fused 16.9 x faster at T = 4096 (256 per expert)
     MOE_MAX_ROWS = 256
 
     def __init__(self, num_experts, hidden_dim, intermediate_dim, bits=4, group_size=32, act_fn=None, dtype="int", device="cuda"):
-        super().__init__()
         if bits != 4 or dtype != "int":
             raise NotImplementedError(f"packed experts are INT4 (dtype='int', bits=4), got dtype={dtype!r} bits={bits}")
         dev = _hip_device(device)
+        super().__init__(num_experts, hidden_dim, intermediate_dim, act_fn)
         E, H, I = num_experts, hidden_dim, intermediate_dim
-        self.num_experts, self.hidden_dim, self.intermediate_dim = E, H, I
         self.bits, self.dtype, self.group_size = bits, dtype, group_size
-        self.act_fn = act_fn if act_fn is not None else torch.nn.SiLU()
         for prefix, N, K in (("gate_up", 2 * I, H), ("down", H, I)):
             G = math.ceil(K / self._gs(K))
             self.register_buffer(f"{prefix}_qweight", torch.zeros((E, math.ceil(K / 8), N), dtype=torch.int32, device=dev))
@@ -97,60 +92,34 @@ class MI355XWeightOnlyExperts(torch.nn.Module):
     def _fusable(self):
         H, I, gs = self.hidden_dim, self.intermediate_dim, self.group_size
         groups_ok = gs == -1 or (gs >= 32 and gs & (gs - 1) == 0 and H % gs == 0 and I % gs == 0)
-        return _is_silu(self.act_fn) and H % 32 == 0 and I % 32 == 0 and self.num_experts <= 512 and groups_ok
+        return is_silu(self.act_fn) and H % 32 == 0 and I % 32 == 0 and self.num_experts <= MAX_EXPERTS and groups_ok
 
-    def forward(self, hidden_states, top_k_index, top_k_weights):
-        """transformers' experts signature: hidden_states [T, H], top_k_index / top_k_weights [T, k] -> [T, H] of hidden_states' dtype.
-        bf16 / fp16 compute in their own dtype; any other dtype computes in fp16 and is cast back (warned once per module).  Expert ids
-        outside 0..E-1 (a "no expert" sentinel such as -1) contribute nothing, on both routes."""
-        x = hidden_states
-        x2d = x.reshape(-1, self.hidden_dim)
+    def _compute_dtype(self, x):
         cdt = x.dtype if x.dtype in (torch.bfloat16, torch.float16) else torch.float16
         if cdt is not x.dtype and not self.__dict__.get("_warned_dtype"):
             self.__dict__["_warned_dtype"] = True
             logger.warning("MI355XWeightOnlyExperts: %s activations are computed in fp16 (the packed kernels take bf16 / fp16)", x.dtype)
-        T = x2d.shape[0]
-        idx = top_k_index.reshape(T, -1)
-        k = idx.shape[1]
-        if T == 0 or k == 0:
-            return torch.zeros_like(x)
-        if self.MOE_FUSED and T * k <= self.MOE_MAX_ROWS * self.num_experts and self._fusable():
-            call = self.__dict__.get("_call")
-            gu, dn = self._bufs("gate_up"), self._bufs("down")
-            if call is None or not call.current(gu, dn):
-                call = self.__dict__["_call"] = ops.WoqMoeCall(gu, dn, self.num_experts, self.hidden_dim, self.intermediate_dim, self.group_size)
-            xin = x2d if x2d.dtype is cdt else x2d.to(cdt)
-            xin = xin.contiguous()
-            if xin.data_ptr() % 16:
-                xin = xin.clone()  # the kernels read x in 16-byte pieces; a fresh allocation is aligned
-            if idx.dtype not in (torch.int64, torch.int32):
-                idx = idx.long()
-            w = top_k_weights.reshape(T, k)
-            if w.dtype not in (torch.float32, torch.bfloat16, torch.float16):
-                w = w.float()
-            y = call(xin, idx.contiguous(), w.contiguous())
-        else:
-            y = self._dense_forward(x2d.to(cdt), idx, top_k_weights.reshape(T, k))
-        return y.to(x.dtype).reshape(x.shape)
+        return cdt
 
-    def _dense_forward(self, x, top_k_index, top_k_weights):
-        """transformers' MixtralExperts.forward on weights recovered per expert that was hit (host waits: nonzero / where)."""
-        out = torch.zeros_like(x)
-        E = self.num_experts
-        with torch.no_grad():
-            # ids outside 0..E-1 go to an extra class E that is never visited: they contribute nothing, as on the fused route
-            ids = torch.where((top_k_index >= 0) & (top_k_index < E), top_k_index, torch.full_like(top_k_index, E)).long()
-            mask = torch.nn.functional.one_hot(ids, num_classes=E + 1)[..., :E].permute(2, 1, 0)
-            hit = torch.greater(mask.sum(dim=(-1, -2)), 0).nonzero()
-        for e in hit:
-            e = int(e[0])
-            top_k_pos, token_idx = torch.where(mask[e])
-            gu, dn = self.recover(x.dtype, expert=e)
-            gate, up = torch.nn.functional.linear(x[token_idx], gu).chunk(2, dim=-1)
-            h = torch.nn.functional.linear(self.act_fn(gate) * up, dn)
-            h = h * top_k_weights[token_idx, top_k_pos, None]
-            out.index_add_(0, token_idx, h.to(out.dtype))
-        return out
+    def _fused_forward(self, x2d, idx, w, cdt):
+        call = self.__dict__.get("_call")
+        gu, dn = self._bufs("gate_up"), self._bufs("down")
+        if call is None or not call.current(gu, dn):
+            call = self.__dict__["_call"] = ops.WoqMoeCall(gu, dn, self.num_experts, self.hidden_dim, self.intermediate_dim, self.group_size)
+        xin = x2d if x2d.dtype is cdt else x2d.to(cdt)
+        xin = xin.contiguous()
+        if xin.data_ptr() % 16:
+            xin = xin.clone()  # the kernels read x in 16-byte pieces; a fresh allocation is aligned
+        return call(xin, idx, w)
+
+    def _dense_forward(self, x2d, idx, w, cdt):
+        return super()._dense_forward(x2d.to(cdt), idx, w, cdt)  # F.linear takes the weights' dtype: one cast, before the loop
+
+    def _expert_mlp(self, rows, e, cdt):
+        """transformers' MixtralExperts MLP on expert e's recovered weights."""
+        gu, dn = self.recover(cdt, expert=e)
+        gate, up = torch.nn.functional.linear(rows, gu).chunk(2, dim=-1)
+        return torch.nn.functional.linear(self.act_fn(gate) * up, dn)
 
     def extra_repr(self):
         return (f"num_experts={self.num_experts}, hidden_dim={self.hidden_dim}, intermediate_dim={self.intermediate_dim}, "
@@ -170,12 +139,12 @@ def unsupported_reason(module, cfg):
         return "double quantisation is not implemented for experts"
     if cfg.get("group_dim", 1) != 1:
         return "group_dim must be 1"
-    if not _is_silu(getattr(module, "act_fn", None)):
+    if not is_silu(getattr(module, "act_fn", None)):
         return f"activation {type(getattr(module, 'act_fn', None)).__name__} is not SiLU"
     if gs not in (32, 64, 128, 256, -1) or (gs != -1 and (H % gs or I % gs)):
         return f"group_size={gs} must be one of 32 / 64 / 128 / 256 / -1 and divide H={H} and I={I}"
-    if H % 32 or I % 32 or E > 512:
-        return f"H={H} and I={I} must be multiples of 32 and E={E} at most 512"
+    if H % 32 or I % 32 or E > MAX_EXPERTS:
+        return f"H={H} and I={I} must be multiples of 32 and E={E} at most {MAX_EXPERTS}"
     return None
 
 

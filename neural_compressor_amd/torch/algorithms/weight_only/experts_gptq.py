@@ -22,7 +22,8 @@ import torch
 from .... import ops
 from ....common.utils import logger
 from ...utils.utility import is_fused_experts, set_module
-from .experts import MI355XWeightOnlyExperts, _is_silu
+from ..fused_experts import is_silu
+from .experts import MI355XWeightOnlyExperts
 
 # False: fold the Hessians with one inc_gptq_hessian_accum per hit expert on host-sliced ranges (the only way before K5e; what the
 # calibration forward also does when the library declines a shape).  A module attribute for A/B runs and tests.
@@ -47,7 +48,7 @@ def gptq_unsupported_reason(module, cfg):
                       ("mse", "use_mse_search"), ("use_double_quant", "double quantisation"), ("fp8_aware", "fp8_aware")):
         if cfg.get(key, False):
             return f"{what} is not implemented for experts"
-    if not _is_silu(getattr(module, "act_fn", None)):
+    if not is_silu(getattr(module, "act_fn", None)):
         return f"activation {type(getattr(module, 'act_fn', None)).__name__} is not SiLU"
     if gs not in (32, 64, 128, 256, -1) or (gs != -1 and (H % gs or I % gs)):
         return f"group_size={gs} must be one of 32 / 64 / 128 / 256 / -1 and divide H={H} and I={I}"

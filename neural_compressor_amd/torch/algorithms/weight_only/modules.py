@@ -21,6 +21,7 @@ import torch
 
 from .... import ops
 from ....common.utils import logger
+from ..fused_experts import is_silu
 
 
 class UnpackedWeightOnlyLinearParams(dict):
@@ -602,10 +603,8 @@ def woq_gated_pair(x, gate, up, act_fn=None):
     modules' device with x.shape[-1] == K, the rows are within the entry's limit, act_fn is None or SiLU and GATED_FUSED is on.
     Otherwise exactly act(g) * u with g, u = woq_linear_group(x, [gate, up]) and act = F.silu by default.  The prepared call is a
     cache on `gate` (not state: it dies with the module, copies start without it, a replaced buffer rebuilds it)."""
-    from .experts import _is_silu
-
     cls = MI355XWeightOnlyLinear
-    if (GATED_FUSED and (act_fn is None or _is_silu(act_fn)) and isinstance(gate, cls) and isinstance(up, cls) and gate.bits == 4 and up.bits == 4
+    if (GATED_FUSED and (act_fn is None or is_silu(act_fn)) and isinstance(gate, cls) and isinstance(up, cls) and gate.bits == 4 and up.bits == 4
             and gate.bias is None and up.bias is None and gate.in_features == up.in_features and gate.out_features == up.out_features
             and gate.group_size == up.group_size and x.dtype in (torch.bfloat16, torch.float16) and x.is_cuda and x.numel() > 0
             and x.device == gate.qweight.device and x.shape[-1] == gate.in_features and x.numel() <= ops.WoqGatedCall.MAX_M * gate.in_features):

@@ -101,6 +101,50 @@ def set_module(model, op_name, new_module):
     setattr(parent, parts[-1], new_module)
 
 
+def _take(state, name, new, dev):
+    """Load `name.*` of `state` into `new` (strict) and drop those keys."""
+    own = {k[len(name) + 1:]: v for k, v in state.items() if k.startswith(name + ".")}
+    new.load_state_dict({k: v.to(dev) for k, v in own.items()}, strict=True)
+    for k in own:
+        state.pop(name + "." + k)
+
+
+def _take_experts(state, model, name, dev, recognise, build):
+    """The experts module `name` of a saved model, rebuilt from the float architecture `model`: the float module must pass `recognise`
+    (is_fused_experts / is_gpt_oss_experts), `build(old)` makes the empty quantised module, _take fills it and it takes the old one's
+    place."""
+    old = get_module(model, name)
+    what = "a GPT-OSS experts module" if recognise is is_gpt_oss_experts else "a fused experts module"
+    assert recognise(old), f"{name}: expected {what} in the float architecture, got {type(old).__name__}"
+    new = build(old)
+    _take(state, name, new, dev)
+    set_module(model, name, new)
+
+
+def half_or_fp16(dtype):
+    """The float type a quantised module keeps for a float module of `dtype`: bf16 / fp16 as they are, fp16 for anything else."""
+    return dtype if dtype in (torch.float16, torch.bfloat16) else torch.float16
+
+
+def linear_group_plan(x, mods, cls, max_members, max_rows, key):
+    """What `cls` members (FP8Linear / MXLinear) that multiply the same x share, or None where the group is the plain list of forwards:
+    (x2d, out_dtype, every member decodes).  2 .. max_members members of one `key(m)` (a tuple that starts with in_features and the
+    device), x there and not empty; an fp32 x needs one float_type; the row count decodes on every member or is above max_rows."""
+    m0 = mods[0] if mods else None
+    ok = (2 <= len(mods) <= max_members and all(isinstance(m, cls) for m in mods) and x.is_cuda and x.numel() > 0
+          and x.shape[-1] == m0.in_features and x.device == m0.qweight.device and all(key(m) == key(m0) for m in mods))
+    if not ok:
+        return None
+    half = x.dtype in (torch.float16, torch.bfloat16)
+    out_dtype = x.dtype if half else m0.float_type
+    x2d = x.reshape(-1, m0.in_features)
+    rows = x2d.shape[0]
+    decode = [m._decodes(rows) for m in mods]
+    if not (half or all(m.float_type == out_dtype for m in mods)) or not (all(decode) or rows > max_rows):
+        return None
+    return x2d, out_dtype, all(decode)
+
+
 get_attr = fetch_module
 
 

@@ -244,6 +244,21 @@ def test_max_rows_routing(hip, monkeypatch):
     assert calls
 
 
+def test_empty_batch_is_zeros(hip, monkeypatch):
+    m = _experts(hip, 8, 256, 512, 32, seed=11)
+    idx, w = _routing(hip, 4, 8, 2, seed=4)
+    x = torch.randn(4, 256, device=hip).to(torch.bfloat16)
+    for fused in (True, False):
+        monkeypatch.setattr(type(m), "MOE_FUSED", fused)
+        with torch.no_grad():
+            y = m(x[:0], idx[:0], w[:0])
+            y3 = m(x.reshape(1, 4, 256)[:, :0], idx[:0], w[:0])
+            yk = m(x, idx[:, :0], w[:, :0])
+        assert y.shape == (0, 256) and y.dtype == torch.bfloat16
+        assert y3.shape == (1, 0, 256) and y3.dtype == torch.bfloat16
+        assert yk.shape == x.shape and yk.dtype == torch.bfloat16 and not yk.any()
+
+
 # 8. model level ---------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("make", [tiny_mixtral, tiny_qwen3_moe])
 def test_rtn_model(hip, tmp_path, make):
