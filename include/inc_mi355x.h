@@ -798,6 +798,50 @@ int inc_fp8_moe_gemm(int mode, const uint8_t* aq, const float* a_scale, const in
                      const void* routing_weights, int wdtype, void* out, int odtype, int64_t T, int top_k, int64_t E, int64_t N,
                      int64_t Kp, inc_stream_t stream);
 
+/* ---- FP8 block-scaled: e4m3 codes, one fp32 scale per 128 x 128 block of W and per 1 x 128 group of x ------ *
+ * The scheme of DeepSeek-V3 / R1, Qwen3-FP8 and transformers' FineGrainedFP8Config checkpoints (`weight` float8_e4m3fn [N,K],
+ * `weight_scale_inv` fp32 [ceil(N/128), ceil(K/128)], activations quantised at run time per token and 128 channels): csrc/fp8_block_quant.hip
+ * (the two quantisers) and csrc/gemm_fp8_block.hip (the products).  This text is the specification.  All scales are fp32; Kp is K rounded
+ * up to INC_MX_KTILE = 128 (any larger multiple of 128 is taken too) and KB = Kp / 128.  Inputs are finite; for a NaN or an infinity
+ * nothing is promised except that every write stays in bounds.
+ * inc_fp8_quant_groups: x bf16 / fp16 / fp32 [M,K] contiguous, of any alignment.
+ *     t            = float(x[m,k])
+ *     scales[m,g]  = max(max_{k in group g} |t| / 448.0f, 0x1p-60f)    (fp32, true division; group g = columns 128 g .. 128 g + 127
+ *                                                                       below K; scales is [M,KB])
+ *     codes[m,k]   = e4m3(t / scales[m, k / 128])                      (fp32 true division, then the element rounding and the sign
+ *                                                                       rule of inc_fp8_quant_rows: the same device function)
+ *   Columns K .. Kp-1 are code 0 and a group that lies wholly in the padding gets the floor scale 2^-60.  codes uint8 [M,Kp] 16-byte
+ *   aligned, scales 4-byte aligned.  16 lanes own a group (16-byte loads of an aligned 16-bit input, the maximum by shuffles inside the
+ *   wave, no LDS); x is read from HBM once.  max is order-free, so codes and scales have one right answer, bit for bit.
+ * inc_fp8_quant_blocks: the same rule over the 128 x 128 blocks of a weight w [N,K]: scales[nb,kb] = max(max |t| / 448.0f, 0x1p-60f) over
+ *   rows 128 nb .. and columns 128 kb .. of the block, clipped to N and K; scales is [ceil(N/128), KB]; codes uint8 [N,Kp] as above.  One
+ *   workgroup per block; the block is read once and held in registers between the maximum and the rounding.  Bit-exact too.
+ *   Both: INC_ERR_UNSUPPORTED (nothing launched) for an unknown dtype or Kp % 128 != 0; INC_ERR_BAD_ARG for a NULL pointer, a size < 1,
+ *   Kp < K or a misaligned output.
+ * inc_fp8_block_gemm: for any M >= 1 and N >= 1
+ *     y[m,n] = rd16( sum_kt (xs[m,kt] * ws[n / 128, kt]) * acc_kt[m,n]  +  bias[n] )
+ *   acc_kt is the matrix pipe's fp32 sum over the 128 elements of K-tile kt alone, started from zero (v_mfma_f32_32x32x64_f8f6f4, the
+ *   unscaled opcode; the order inside an instruction is not documented).  The factor product is one fp32 multiply; the promotion into
+ *   the running fp32 sum is a multiply-add in ascending kt and may contract to an fma; the bias (0 without one) is added last, in
+ *   fp32, and y is rounded once.  xq [M,Kp], wq [N,Kp] uint8, 16-byte aligned; xs fp32 [M,KB], ws fp32 [ceil(N/128),KB], 4-byte aligned;
+ *   bias [N] in ydtype or NULL; y [M,N] bf16 / fp16 (8-byte stores when N % 4 == 0 and y is 8-byte aligned, 2-byte stores otherwise).
+ *   256 x 256 x 128 tiles, one workgroup per tile, no split-K tail, no workspace.  Reads nothing past row M - 1 of xq / xs, row N - 1
+ *   of wq or row ceil(N/128) - 1 of ws.
+ * inc_fp8_block_gemv: the same product for 1 <= M <= INC_MX_GEMV_MAX_M on v_mfma_f32_16x16x128_f8f6f4: one workgroup per strip of 16
+ *   weight rows, K split over its 8 waves as in inc_fp8_gemv (wave w takes the K-tiles w, w + 8, ... in ascending order and promotes
+ *   each one into its own fp32 partial), the 8 partials added in wave order through LDS, then the bias: no workspace, repeated calls
+ *   are bit-identical.  On operands whose every partial sum is exact in fp32 it equals inc_fp8_block_gemm bit for bit.
+ * Both products: INC_ERR_UNSUPPORTED (nothing launched) for Kp % 128 != 0, a ydtype other than bf16 / fp16 or (gemv) M > 16;
+ *   INC_ERR_BAD_ARG for a NULL operand, a size < 1 or a misaligned pointer.  All four validate their arguments before any HIP call.  */
+int inc_fp8_quant_groups(const void* x, int xdtype, int64_t M, int64_t K, int64_t Kp, uint8_t* codes, float* scales,
+                         inc_stream_t stream);
+int inc_fp8_quant_blocks(const void* w, int wdtype, int64_t N, int64_t K, int64_t Kp, uint8_t* codes, float* scales,
+                         inc_stream_t stream);
+int inc_fp8_block_gemm(const uint8_t* xq, const float* xs, const uint8_t* wq, const float* ws, const void* bias, void* y, int ydtype,
+                       int64_t M, int64_t N, int64_t Kp, inc_stream_t stream);
+int inc_fp8_block_gemv(const uint8_t* xq, const float* xs, const uint8_t* wq, const float* ws, const void* bias, void* y, int ydtype,
+                       int64_t M, int64_t N, int64_t Kp, inc_stream_t stream);
+
 /* ---- measured ceilings (bench.py `ceilings`) -- measurement helpers, not on the hot path ------------- *
  * inc_probe_hbm_triad: a <- b + s*c over n fp32 (n % 4 == 0): 12 n bytes of HBM traffic per call.
  * inc_probe_mfma_bf16: `blocks` workgroups x 4 waves x `iters` x 8 v_mfma_f32_32x32x16_bf16 on operands read from `src`

@@ -1848,6 +1848,60 @@ def fp8_gemv(xq, row_scale, wq, alpha, bias, out_dtype):
     return _fp8_product(lib.inc_fp8_gemv, "inc_fp8_gemv", xq, row_scale, wq, alpha, bias, out_dtype)
 
 
+# K18 FP8 block-scaled: one fp32 scale per 1 x 128 group of x and per 128 x 128 block of W (include/inc_mi355x.h has the specification)
+FP8_BLOCK = 128
+
+
+def _fp8_quant_blocked(fn, name, t2d, scale_rows, Kp):
+    t2d = t2d.contiguous()
+    dev = _dev(t2d)
+    R, K = t2d.shape
+    Kp = mx_padded_k(K) if Kp is None else int(Kp)
+    codes = torch.empty((R, Kp), dtype=torch.uint8, device=dev)
+    scales = torch.empty((scale_rows(R), Kp // FP8_BLOCK), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        check(fn(_ptr(t2d), dtype_code(t2d.dtype), R, K, Kp, _ptr(codes), _ptr(scales), _stream()), name)
+    return codes, scales
+
+
+def fp8_quant_groups(x2d, Kp=None):
+    """The activation quantiser of the block-scaled cell (inc_fp8_quant_groups): x [M,K] bf16 / fp16 / fp32 -> (codes uint8 [M,Kp],
+    scales fp32 [M, Kp/128]) with scales[m,g] = max(max over the group |x| / 448, 2^-60) and codes = e4m3(x / scales[m, k/128])."""
+    return _fp8_quant_blocked(lib.inc_fp8_quant_groups, "inc_fp8_quant_groups", x2d, lambda M: M, Kp)
+
+
+def fp8_quant_blocks(w, Kp=None):
+    """The weight quantiser of the block-scaled cell (inc_fp8_quant_blocks): w [N,K] -> (codes uint8 [N,Kp], scales fp32
+    [ceil(N/128), Kp/128]), the rule of fp8_quant_groups over 128 x 128 blocks clipped to N and K."""
+    return _fp8_quant_blocked(lib.inc_fp8_quant_blocks, "inc_fp8_quant_blocks", w, lambda N: (N + FP8_BLOCK - 1) // FP8_BLOCK, Kp)
+
+
+def _fp8_block_product(fn, name, xq, xs, wq, ws, bias, out_dtype):
+    dev = _dev(xq, xs, wq, ws, bias)
+    (M, Kp), N = xq.shape, wq.shape[0]
+    assert wq.shape[1] == Kp and xq.dtype == torch.uint8 and wq.dtype == torch.uint8
+    assert xs.dtype == torch.float32 and tuple(xs.shape) == (M, Kp // FP8_BLOCK)
+    assert ws.dtype == torch.float32 and tuple(ws.shape) == ((N + FP8_BLOCK - 1) // FP8_BLOCK, Kp // FP8_BLOCK)
+    if bias is not None and bias.dtype != out_dtype:
+        bias = bias.to(out_dtype)
+    y = torch.empty((M, N), dtype=out_dtype, device=dev)
+    with torch.cuda.device(dev):
+        check(fn(_ptr(xq), _ptr(xs), _ptr(wq), _ptr(ws), _ptr(bias), _ptr(y), dtype_code(out_dtype), M, N, Kp, _stream()), name)
+    return y
+
+
+def fp8_block_gemm(xq, xs, wq, ws, bias, out_dtype):
+    """y[m,n] = sum_kt (xs[m,kt] * ws[n/128,kt]) * (the K-tile's sum of x_k * w_k) + bias[n] over e4m3 codes: every K-tile's
+    v_mfma_f32_32x32x64_f8f6f4 sum is promoted into an fp32 accumulator inside the K loop (inc_fp8_block_gemm)."""
+    return _fp8_block_product(lib.inc_fp8_block_gemm, "inc_fp8_block_gemm", xq, xs, wq, ws, bias, out_dtype)
+
+
+def fp8_block_gemv(xq, xs, wq, ws, bias, out_dtype):
+    """fp8_block_gemm's product for up to FP8_GEMV_MAX_M rows of x on v_mfma_f32_16x16x128_f8f6f4 (inc_fp8_block_gemv): one workgroup
+    per 16 weight rows, K split over its waves, no workspace."""
+    return _fp8_block_product(lib.inc_fp8_block_gemv, "inc_fp8_block_gemv", xq, xs, wq, ws, bias, out_dtype)
+
+
 FP8_GEMV_MAX_MEMBERS = 8
 
 

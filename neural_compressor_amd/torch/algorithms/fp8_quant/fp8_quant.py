@@ -17,6 +17,14 @@ from ....common.utils import logger
 from ...utils.utility import get_module, half_or_fp16, is_fused_experts, linear_group_plan, set_module
 from ..base_algorithm import Quantizer
 from ..fused_experts import is_silu
+from .block import FP8BlockLinear
+
+BLOCK_CELL = ("per_group", "per_block")  # (act_granularity, w_granularity) of the block-scaled cell (block.py)
+
+
+def is_block_cell(cfg):
+    """Whether a layer's dict (fp8_quant_entry) names the block-scaled cell; a dict without the two keys is the per-token cell."""
+    return (cfg.get("act_granularity"), cfg.get("w_granularity")) == BLOCK_CELL
 
 
 class FP8Linear(torch.nn.Module):
@@ -137,7 +145,8 @@ def fp8_gated_pair(x, gate, up, act_fn=None):
 
 
 class FP8Quantizer(Quantizer):
-    """quant_config: {layer name: {"fp8_config"}} (fp8_quant_entry).  A layer whose fp8_config is "fp32" stays float.  Besides
+    """quant_config: {layer name: {"fp8_config", "act_granularity", "w_granularity"}} (fp8_quant_entry).  A layer whose fp8_config is
+    "fp32" stays float; a Linear whose granularities are BLOCK_CELL becomes an FP8BlockLinear, any other an FP8Linear.  Besides
     nn.Linear the names may be fused MoE experts modules (is_fused_experts; they are in the mapping under
     FP8Config(moe_experts=True) only), which become FP8Experts."""
 
@@ -174,7 +183,9 @@ class FP8Quantizer(Quantizer):
             logger.warning("FP8: no nn.Linear selected, the model is returned unchanged")
         for name in names:
             mod = get_module(model, name)
-            cls = FP8Linear if isinstance(mod, torch.nn.Linear) else FP8Experts
+            linear_cls = FP8BlockLinear if is_block_cell(self.quant_config[name]) else FP8Linear
+            cls = linear_cls if isinstance(mod, torch.nn.Linear) else FP8Experts
             set_module(model, name, cls.from_float(mod, device=dev))
-        model.fp8_info = {"fp8_config": "E4M3", "act_granularity": "per_token", "w_granularity": "per_channel"}
+        act, w = BLOCK_CELL if any(is_block_cell(self.quant_config[n]) for n in names) else ("per_token", "per_channel")
+        model.fp8_info = {"fp8_config": "E4M3", "act_granularity": act, "w_granularity": w}
         return model

@@ -2,7 +2,8 @@
   quantized_weight.pt   state_dict: uint8 `qweight`, fp32 `w_scale`, bias of every FP8Linear; the float parameters of everything else
   qconfig.json          {"fp8_quant": {fp8_config, act_granularity, w_granularity}, "fp8_modules": [name, ...],
                          "fp8_experts": {name: [E, H, I]}}
-FP8Experts modules save their four buffers under their own names.  The "fp8_experts" key is written only when the model has such
+"fp8_modules" lists FP8Linear and FP8BlockLinear alike; load tells them apart by the rank of `w_scale` ([N] against
+[ceil(N/128), Kp/128]), so one model may hold both.  FP8Experts modules save their four buffers under their own names.  The "fp8_experts" key is written only when the model has such
 modules; a directory without it (a model without them, or one written before FP8Experts existed) loads as before.
 """
 
@@ -12,6 +13,7 @@ import os
 import torch
 
 from ...utils.utility import _take, _take_experts, get_module, half_or_fp16, is_fused_experts, set_module
+from .block import FP8BlockLinear
 from .experts import FP8Experts
 from .fp8_quant import FP8Linear
 
@@ -22,7 +24,7 @@ QCONFIG_NAME = "qconfig.json"
 def qconfig_of(model):
     """The content of qconfig.json."""
     cfg = {"fp8_quant": dict(getattr(model, "fp8_info", {})),
-           "fp8_modules": [n for n, m in model.named_modules() if isinstance(m, FP8Linear)]}
+           "fp8_modules": [n for n, m in model.named_modules() if isinstance(m, (FP8Linear, FP8BlockLinear))]}
     experts = {n: [m.num_experts, m.hidden_dim, m.intermediate_dim] for n, m in model.named_modules() if isinstance(m, FP8Experts)}
     if experts:  # a model without FP8Experts writes the file it always wrote
         cfg["fp8_experts"] = experts
@@ -48,7 +50,8 @@ def load(output_dir, original_model, device="cuda"):
         lin = get_module(original_model, name)
         assert isinstance(lin, torch.nn.Linear), f"{name}: expected nn.Linear in the float architecture, got {type(lin).__name__}"
         ft = state[name + ".bias"].dtype if (name + ".bias") in state else half_or_fp16(lin.weight.dtype)
-        new = FP8Linear(lin.in_features, lin.out_features, bias=(name + ".bias") in state, device=dev, float_type=ft)
+        cls = FP8BlockLinear if state[name + ".w_scale"].dim() == 2 else FP8Linear  # [ceil(N/128), Kp/128] against [N]
+        new = cls(lin.in_features, lin.out_features, bias=(name + ".bias") in state, device=dev, float_type=ft)
         _take(state, name, new, dev)
         set_module(original_model, name, new)
     for name, (E, H, I) in cfg.get("fp8_experts", {}).items():

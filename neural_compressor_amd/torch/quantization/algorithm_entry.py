@@ -219,14 +219,15 @@ def _fp8_save(self, output_dir="./saved_results", **kwargs):
 @torch.no_grad()
 def fp8_quant_entry(model, configs_mapping, mode=Mode.QUANTIZE, *args, **kwargs):
     """The per-token / per-channel e4m3 cell: the plain dict per Linear (and, under FP8Config(moe_experts=True), per fused experts
-    module) goes to FP8Quantizer; the result carries FP8Linear and FP8Experts modules.  Data-free: prepare changes nothing."""
+    module) goes to FP8Quantizer; the result carries FP8Linear and FP8Experts modules -- FP8BlockLinear under the block-scaled pair
+    (per_group, per_block).  Data-free: prepare changes nothing."""
     from ..algorithms.fp8_quant import FP8Quantizer
 
     quant_config = {}
     for (op_name, op_type), cfg in configs_mapping.items():
         if cfg.name != FP8_QUANT:
             continue
-        quant_config[op_name] = {"fp8_config": cfg.fp8_config}
+        quant_config[op_name] = {"fp8_config": cfg.fp8_config, "act_granularity": cfg.act_granularity, "w_granularity": cfg.w_granularity}
     quantizer = get_quantizer(model, quantizer_cls=FP8Quantizer, quant_config=quant_config)
     model = quantizer.execute(model, mode=mode)
     model.qconfig = configs_mapping

@@ -385,6 +385,10 @@ class FP8Config(TorchBaseConfig):
       fp8_config="E4M3"             the element format ("E5M2" is not built); "fp32" (through `set_local`) leaves a layer float
       act_granularity="per_token"   one activation scale per row of the flattened input, from that row's max |x|
       w_granularity="per_channel"   one weight scale per output channel
+                                    The pair act_granularity="per_group", w_granularity="per_block" selects the block-scaled cell
+                                    instead (FP8BlockLinear: one scale per token and 128 channels, one per 128 x 128 weight block,
+                                    the scheme of DeepSeek-V3 / Qwen3-FP8 checkpoints; the block is 128 wide, there is no size
+                                    field).  Either value with another partner raises.
       dynamic_quantization=True     activation scales come from the data of the call; static (calibrated) scales are not built
       quant_lm_head=False           lm_head stays float unless set
       moe_experts=False             True also converts the fused MoE experts modules (is_fused_experts: Mixtral / Qwen2-MoE / Qwen3-MoE /
@@ -392,6 +396,7 @@ class FP8Config(TorchBaseConfig):
                                     FP8Config(fp8_config="fp32"))` keeps one of them float.  GPTQConfig and MXQuantConfig call their
                                     switch `quant_experts`; this one is `moe_experts` -- a deliberate deviation in the name: an
                                     FP8Config has no `quant_experts` attribute (tests/test_fp8_cpu.py pins that).
+                                    Block-scaled experts are not built: with the block pair they stay float with one warning.
     Without the flag fused MoE experts modules stay float."""
 
     name = FP8_QUANT
@@ -415,10 +420,11 @@ class FP8Config(TorchBaseConfig):
             unsupported = []
             if fp8_config != "E4M3":
                 unsupported.append(f'fp8_config must be "E4M3" (OCP e4m3fn), got {fp8_config!r}')
-            if act_granularity != "per_token":
-                unsupported.append(f'act_granularity must be "per_token", got {act_granularity!r}')
-            if w_granularity != "per_channel":
-                unsupported.append(f'w_granularity must be "per_channel", got {w_granularity!r}')
+            if (act_granularity, w_granularity) != ("per_group", "per_block"):  # the block-scaled cell: the pair, never one half
+                if act_granularity != "per_token":
+                    unsupported.append(f'act_granularity must be "per_token", got {act_granularity!r}')
+                if w_granularity != "per_channel":
+                    unsupported.append(f'w_granularity must be "per_channel", got {w_granularity!r}')
             if dynamic_quantization is not True:
                 unsupported.append("dynamic_quantization must be True (static activation scales are not built)")
             if unsupported:
