@@ -832,7 +832,36 @@ int inc_fp8_moe_gemm(int mode, const uint8_t* aq, const float* a_scale, const in
  *   each one into its own fp32 partial), the 8 partials added in wave order through LDS, then the bias: no workspace, repeated calls
  *   are bit-identical.  On operands whose every partial sum is exact in fp32 it equals inc_fp8_block_gemm bit for bit.
  * Both products: INC_ERR_UNSUPPORTED (nothing launched) for Kp % 128 != 0, a ydtype other than bf16 / fp16 or (gemv) M > 16;
- *   INC_ERR_BAD_ARG for a NULL operand, a size < 1 or a misaligned pointer.  All four validate their arguments before any HIP call.  */
+ *   INC_ERR_BAD_ARG for a NULL operand, a size < 1 or a misaligned pointer.  All four validate their arguments before any HIP call.
+ * inc_fp8_block_moe_gemm (csrc/gemm_fp8_block_moe.hip, K18e): the product of inc_fp8_block_gemv per expert over the rows inc_moe_route
+ *   sorted -- the two F.linear of transformers' MixtralExperts.forward (also the Qwen3-MoE / DeepSeek-V3 shaped experts) for experts
+ *   stored in this scheme.  One forward is
+ *   inc_moe_route -> inc_fp8_quant_groups(x) -> inc_fp8_block_moe_gemm(0) -> inc_fp8_quant_groups(h) -> inc_fp8_block_moe_gemm(1) ->
+ *   inc_moe_combine on `stream`.  `route` is K4e's buffer, unchanged; modes, outputs and store rules are inc_fp8_moe_gemm's.
+ *   aq [rows, Kp] uint8 and as fp32 [rows, KB] are exactly what inc_fp8_quant_groups writes (rows = T in modes 0 / 2, S = T * top_k in
+ *   sorted order in mode 1).  wq [E, N, Kp] uint8; ws fp32 [E, NBLK, KB] with NBLK = ceil(N / 128) in modes 1 / 2 and, in mode 0
+ *   (N = 2I), NBLK = 2 ceil(I / 128): the gate half (rows 0 .. I-1) and the up half (rows I .. 2I-1) are each blocked from their own
+ *   row 0 -- a checkpoint's gate_proj / up_proj `weight_scale_inv` of expert e, stacked.  blk(n) = n / 128 in modes 1 / 2; in mode 0
+ *   blk(j) = j / 128 for gate row j and ceil(I / 128) + j / 128 for up row I + j.  For position p of the sorted order, the expert e
+ *   whose range holds p and its source row r,
+ *     val[p, n] = sum over waves w = 0 .. 7 in wave order of
+ *                   ( sum over kt = w, w + 8, ... ascending of (as[r, kt] * ws[e, blk(n), kt]) * acc_kt[p, n] )
+ *   acc_kt is v_mfma_f32_16x16x128_f8f6f4 (the unscaled opcode) over the 128 elements of K-tile kt alone, started from a literal-zero C
+ *   operand; the factor product is one fp32 multiply; the promotion into the wave's fp32 partial is a multiply-add that may contract
+ *   to an fma (the expression of inc_fp8_block_gemv: for one expert's <= 16 rows val is that kernel's sum before its bias, bit for bit).
+ *     mode 2 (plain, gathered):   r = order[p] / top_k; out [S, N] fp32 = val[p, n]
+ *     mode 0 (gate_up, gathered): r as in mode 2; out [S, I] of odtype (INC_BF16 / INC_F16), out[p, j] = rd(g / (1.f + expf(-g)) * u),
+ *            g = val[p, j], u = val[p, I + j], formed in fp32, rounded once
+ *     mode 1 (down, in place):    r = p; out [S, N] fp32 = w[order[p]] * val[p, n] (one fp32 multiply), routing_weights w [T, top_k]
+ *            of wdtype INC_F32 / INC_BF16 / INC_F16
+ *   One workgroup per (16-column strip, 64-row route tile), the grid sized from S and E alone; only the ceil(rows / 16) row blocks a
+ *   tile has are loaded and multiplied; the 8 partials meet in LDS: no workspace, no counters, repeated calls are bit-identical.
+ *   Positions >= offsets[E] are never written.  Source rows that no valid position names are never read (aq and as alike), weight rows
+ *   past a strip's end re-read its last row, ws is never read past block row NBLK - 1.  aq / wq 16-byte aligned, as / ws 4-byte
+ *   aligned; out is stored 4 columns at a time when its width is a multiple of 4 and it is aligned to that store, element by element
+ *   otherwise.  INC_ERR_UNSUPPORTED (nothing launched) for Kp % 128 != 0, E > 512, S > 2^22, mode 0 with odd N, a bad odtype or
+ *   (mode 1) wdtype; INC_ERR_BAD_ARG for a NULL operand (routing_weights: mode 1 only), a size < 1 or a misaligned pointer.  Validated
+ *   before any HIP call.                                                                                                            */
 int inc_fp8_quant_groups(const void* x, int xdtype, int64_t M, int64_t K, int64_t Kp, uint8_t* codes, float* scales,
                          inc_stream_t stream);
 int inc_fp8_quant_blocks(const void* w, int wdtype, int64_t N, int64_t K, int64_t Kp, uint8_t* codes, float* scales,
@@ -841,6 +870,9 @@ int inc_fp8_block_gemm(const uint8_t* xq, const float* xs, const uint8_t* wq, co
                        int64_t M, int64_t N, int64_t Kp, inc_stream_t stream);
 int inc_fp8_block_gemv(const uint8_t* xq, const float* xs, const uint8_t* wq, const float* ws, const void* bias, void* y, int ydtype,
                        int64_t M, int64_t N, int64_t Kp, inc_stream_t stream);
+int inc_fp8_block_moe_gemm(int mode, const uint8_t* aq, const float* as, const int32_t* route, const uint8_t* wq, const float* ws,
+                           const void* routing_weights, int wdtype, void* out, int odtype, int64_t T, int top_k, int64_t E,
+                           int64_t N, int64_t Kp, inc_stream_t stream);
 
 /* ---- measured ceilings (bench.py `ceilings`) -- measurement helpers, not on the hot path ------------- *
  * inc_probe_hbm_triad: a <- b + s*c over n fp32 (n % 4 == 0): 12 n bytes of HBM traffic per call.

@@ -120,6 +120,10 @@ SIGNATURES = {
     "inc_fp8_quant_blocks": (c_int, [_P, c_int, c_int64, c_int64, c_int64, _P, _P, _P]),
     "inc_fp8_block_gemm": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int64, c_int64, c_int64, _P]),
     "inc_fp8_block_gemv": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int64, c_int64, c_int64, _P]),
+    "inc_fp8_block_moe_gemm": (
+        c_int,
+        [c_int, _P, _P, _P, _P, _P, _P, c_int, _P, c_int, c_int64, c_int, c_int64, c_int64, c_int64, _P],
+    ),
     "inc_awq_repack": (c_int, [_P, _P, c_int64, c_int64, c_int64, c_int, _P, _P, _P]),
     "inc_gptq_find_params_mse": (
         c_int,

@@ -1971,3 +1971,24 @@ def fp8_moe_gemm(mode, aq, a_scale, route, wq, alpha, T, top_k, routing_weights=
         check(lib.inc_fp8_moe_gemm(mode, _ptr(aq), _ptr(a_scale), _ptr(route), _ptr(wq), _ptr(alpha), _ptr(routing_weights), wdt,
                                    _ptr(out), dtype_code(odt), T, top_k, E, N, Kp, _stream()), "inc_fp8_moe_gemm")
     return out
+
+
+def fp8_block_moe_gemm(mode, aq, as_, route, wq, ws, T, top_k, routing_weights=None, out=None, out_dtype=None):
+    """inc_fp8_block_moe_gemm (K18e): fp8_block_gemv's product per expert over the rows of the route's sorted order, every K-tile's sum
+    promoted with as_[r, kt] * ws[e, block, kt] inside the K loop.  aq / as_ are fp8_quant_groups' outputs ([rows, Kp], fp32
+    [rows, Kp/128]); wq [E, N, Kp]; ws fp32 [E, NBLK, Kp/128] with NBLK = ceil(N/128) in modes 1 / 2 and 2 * ceil(N/2/128) in mode 0
+    (gate and up half each blocked from its own row 0; a [E, 2, ceil(I/128), Kp/128] tensor is taken as it is).  Modes, outputs and
+    `out` as fp8_moe_gemm."""
+    dev = _dev(aq, as_, route, wq, ws, routing_weights)
+    E, N, Kp = wq.shape
+    S, KB = T * top_k, Kp // FP8_BLOCK
+    nblk = 2 * ((N // 2 + FP8_BLOCK - 1) // FP8_BLOCK) if mode == 0 else (N + FP8_BLOCK - 1) // FP8_BLOCK
+    assert aq.dtype == torch.uint8 and wq.dtype == torch.uint8 and as_.dtype == torch.float32 and ws.dtype == torch.float32
+    assert aq.shape == ((S if mode == 1 else T), Kp) and as_.shape == (aq.shape[0], KB)
+    assert ws.shape[0] == E and ws.shape[-1] == KB and ws.numel() == E * nblk * KB
+    assert aq.is_contiguous() and as_.is_contiguous() and wq.is_contiguous() and ws.is_contiguous()
+    out, odt, wdt = _moe_gemm_out(mode, out, out_dtype, S, N, dev, routing_weights, "fp8_block_moe_gemm")
+    with torch.cuda.device(dev):
+        check(lib.inc_fp8_block_moe_gemm(mode, _ptr(aq), _ptr(as_), _ptr(route), _ptr(wq), _ptr(ws), _ptr(routing_weights), wdt,
+                                         _ptr(out), dtype_code(odt), T, top_k, E, N, Kp, _stream()), "inc_fp8_block_moe_gemm")
+    return out

@@ -1,4 +1,5 @@
 from .block import FP8BlockLinear  # noqa: F401  (importable from here, like FP8Experts)
+from .block_experts import FP8BlockExperts, convert_block_experts  # noqa: F401  (importable from here, like FP8Experts)
 from .experts import FP8Experts  # noqa: F401  (importable from here; __all__ keeps the four names tests/test_fp8_cpu.py pins)
 from .fp8_quant import FP8Linear, FP8Quantizer
 from .fp8_quant import fp8_gated_pair, fp8_linear_group  # noqa: F401  (importable from here, like FP8Experts)

@@ -6,7 +6,8 @@ float8_e4m3fn [N, K], `weight_scale_inv` fp32 [ceil(N/128), ceil(K/128)]): `from
 nothing re-quantised.  `inc_fp8_quant_groups` quantises the activation, `inc_fp8_block_gemm` multiplies the codes on
 v_mfma_f32_32x32x64_f8f6f4 and promotes every K-tile's sum with `xs[m, kt] * ws[n / 128, kt]` inside its K loop; a decode-sized batch
 (up to 16 rows) takes `inc_fp8_block_gemv` on the 16x16x128 form.  The specification in bits is the comment of the entry points in
-include/inc_mi355x.h.  Not built: experts, group launches and the gated pair (`fp8_linear_group` /
+include/inc_mi355x.h.  The fused MoE experts of such checkpoints are FP8BlockExperts (block_experts.py), reached
+through `convert_block_experts`, not yet through FP8Config.  Not built: group launches and the gated pair (`fp8_linear_group` /
 `fp8_gated_pair` see a module that is not an FP8Linear and run the plain forwards), static scales, UE8M0 scales.
 """
 

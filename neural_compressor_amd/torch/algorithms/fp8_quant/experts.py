@@ -109,7 +109,7 @@ def unsupported_reason(module, cfg):
     """Why FP8Quantizer leaves the fused-experts `module` in float under `cfg` (None = it converts it)."""
     E = module.gate_up_proj.shape[0]
     if (cfg.get("act_granularity"), cfg.get("w_granularity")) == ("per_group", "per_block"):
-        return "block-scaled (per_group / per_block) experts are not built"
+        return "block-scaled (per_group / per_block) experts are not wired into FP8Config yet: use convert_block_experts(model)"
     if not is_silu(getattr(module, "act_fn", None)):
         return f"activation {type(getattr(module, 'act_fn', None)).__name__} is not SiLU"
     if E > MAX_EXPERTS:

@@ -1,10 +1,11 @@
 """save / load of an FP8 model (`model.save(output_dir)`, `load(output_dir, original_model)`), the files of mx_quant/save_load.py:
   quantized_weight.pt   state_dict: uint8 `qweight`, fp32 `w_scale`, bias of every FP8Linear; the float parameters of everything else
   qconfig.json          {"fp8_quant": {fp8_config, act_granularity, w_granularity}, "fp8_modules": [name, ...],
-                         "fp8_experts": {name: [E, H, I]}}
+                         "fp8_experts": {name: [E, H, I]}, "fp8_block_experts": {name: [E, H, I]}}
 "fp8_modules" lists FP8Linear and FP8BlockLinear alike; load tells them apart by the rank of `w_scale` ([N] against
 [ceil(N/128), Kp/128]), so one model may hold both.  FP8Experts modules save their four buffers under their own names.  The "fp8_experts" key is written only when the model has such
-modules; a directory without it (a model without them, or one written before FP8Experts existed) loads as before.
+modules; a directory without it (a model without them, or one written before FP8Experts existed) loads as before.  The same holds for
+FP8BlockExperts modules and the "fp8_block_experts" key.
 """
 
 import json
@@ -14,6 +15,7 @@ import torch
 
 from ...utils.utility import _take, _take_experts, get_module, half_or_fp16, is_fused_experts, set_module
 from .block import FP8BlockLinear
+from .block_experts import FP8BlockExperts
 from .experts import FP8Experts
 from .fp8_quant import FP8Linear
 
@@ -28,6 +30,9 @@ def qconfig_of(model):
     experts = {n: [m.num_experts, m.hidden_dim, m.intermediate_dim] for n, m in model.named_modules() if isinstance(m, FP8Experts)}
     if experts:  # a model without FP8Experts writes the file it always wrote
         cfg["fp8_experts"] = experts
+    blocked = {n: [m.num_experts, m.hidden_dim, m.intermediate_dim] for n, m in model.named_modules() if isinstance(m, FP8BlockExperts)}
+    if blocked:
+        cfg["fp8_block_experts"] = blocked
     return cfg
 
 
@@ -54,9 +59,10 @@ def load(output_dir, original_model, device="cuda"):
         new = cls(lin.in_features, lin.out_features, bias=(name + ".bias") in state, device=dev, float_type=ft)
         _take(state, name, new, dev)
         set_module(original_model, name, new)
-    for name, (E, H, I) in cfg.get("fp8_experts", {}).items():
-        _take_experts(state, original_model, name, dev, is_fused_experts,
-                      lambda old: FP8Experts(E, H, I, act_fn=old.act_fn, device=dev, float_type=half_or_fp16(old.gate_up_proj.dtype)))
+    for key, cls in (("fp8_experts", FP8Experts), ("fp8_block_experts", FP8BlockExperts)):
+        for name, (E, H, I) in cfg.get(key, {}).items():
+            _take_experts(state, original_model, name, dev, is_fused_experts,
+                          lambda old: cls(E, H, I, act_fn=old.act_fn, device=dev, float_type=half_or_fp16(old.gate_up_proj.dtype)))
     original_model.load_state_dict(state, strict=False, assign=True)
     original_model.to(dev)
     original_model.eval()
