@@ -691,7 +691,25 @@ int inc_w8a8_gemm_rowscale(const int8_t* xq, const int8_t* wq, const float* row_
  *   INC_ERR_BAD_ARG unless limit > 0 and alpha == alpha, and for a bias that is not 4-byte aligned.  With a NaN accumulator (NaN
  *   codes or 0xFF scale bytes, which inc_mx_quant never writes for finite input) the output is unspecified.  bias is read after the
  *   LDS sum, by the lanes that store, for the columns they store.
- * All six validate their arguments before any HIP call.                                                                         */
+ * inc_mx_wo_gemv / inc_mx_wo_gemm (csrc/gemm_mx_wo.hip, K16w): the WEIGHT-ONLY cell -- MX weights against bf16 activations on the
+ *   bf16 MFMAs, the weights dequantised in registers by v_cvt_scalef32_pk_bf16_fp4 / _fp8 (profiles/mx/mx_cvt_lab.log).
+ *     y[m,n] = rd16( sum_{k < K} x[m,k] * W[n,k] + bias[n] ),   W[n,k] = value(code[n,k]) * 2^(ws[n, k/32] - 127)
+ *   fp32 accumulation (the order inside the matrix pipe is not documented), fp32 bias add, ONE rounding to ydtype.  Every W[n,k] is
+ *   exact in bf16, so this is the product of x with the dequantised weight in bfloat16.
+ *   x bf16 [M,K], row stride K, K % 8 == 0, 16-byte aligned.  wq [N, Kp] (e4m3) or [N, Kp/2] (e2m1, element 2i in the low nibble)
+ *   and ws [N, Kp/32] exactly as inc_mx_quant stores them (columns K .. Kp-1 are zero codes), Kp = K rounded up to 128; wq 16-byte
+ *   and ws 4-byte aligned.  bias [N] of ydtype or NULL; y [M,N] bf16 / fp16 with inc_mx_gemm's store rule.
+ *   Columns k >= K contribute nothing and x is not read there: what follows a row of x in memory may be anything, NaN included.
+ *   A zero code contributes exactly 0 for every scale byte 0 .. 254.  The product is exact for scale bytes 16 .. 240; below that a
+ *   nonzero code whose value falls under 2^-126 is flushed to zero or kept as the log states, above it 448 * 2^(byte - 127) may
+ *   pass bf16's range.  Byte 255 and the e4m3 codes 0x7f / 0xff (which inc_mx_quant never writes) give NaN.
+ *   inc_mx_wo_gemv: 1 <= M <= INC_MX_GEMV_MAX_M, the strip shape of inc_mx_gemv on v_mfma_f32_16x16x32_bf16: one workgroup per 16
+ *   weight rows, K split over its waves, the partials added in a fixed order through LDS: no workspace, repeated calls are
+ *   bit-identical.  inc_mx_wo_gemm: any M, 256 x 256 tiles on v_mfma_f32_32x32x16_bf16, x through LDS, the weights straight from
+ *   global memory into registers, no split-K and no workspace.
+ *   INC_ERR_BAD_ARG for a NULL operand, M, N or K < 1 or a misaligned x / wq / ws; INC_ERR_UNSUPPORTED for M > 16 (the GEMV),
+ *   Kp % 128 != 0, K % 8 != 0, K > Kp, Kp - K >= 128, an unknown wfmt or a ydtype other than bf16 / fp16.
+ * All eight validate their arguments before any HIP call.                                                                       */
 #define INC_MX_FP8_E4M3 0
 #define INC_MX_FP4_E2M1 4
 #define INC_MX_KTILE 128
@@ -705,6 +723,10 @@ int inc_mx_gemv(const uint8_t* xq, const uint8_t* xs, int xfmt, const uint8_t* w
 int inc_mx_gemv_multi(int n, const uint8_t* xq, const uint8_t* xs, int xfmt, const uint8_t* const* wq, const uint8_t* const* ws,
                       int wfmt, const void* const* bias, void* const* y, int ydtype, int64_t M, const int64_t* N, int64_t Kp,
                       inc_stream_t stream);
+int inc_mx_wo_gemv(const void* x, const uint8_t* wq, const uint8_t* ws, int wfmt, const void* bias, void* y, int ydtype, int64_t M,
+                   int64_t N, int64_t K, int64_t Kp, inc_stream_t stream);
+int inc_mx_wo_gemm(const void* x, const uint8_t* wq, const uint8_t* ws, int wfmt, const void* bias, void* y, int ydtype, int64_t M,
+                   int64_t N, int64_t K, int64_t Kp, inc_stream_t stream);
 int inc_mx_moe_gemm(int mode, const uint8_t* aq, const uint8_t* as, int afmt, const int32_t* route, const uint8_t* wq,
                     const uint8_t* ws, int wfmt, const void* routing_weights, int wdtype, void* out, int odtype, int64_t T, int top_k,
                     int64_t E, int64_t N, int64_t Kp, inc_stream_t stream);

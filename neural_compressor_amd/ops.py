@@ -1746,6 +1746,34 @@ def mx_gemv_multi(xq, xs, xfmt, wqs, wss, wfmt, biases, out_dtype):
     return ys
 
 
+def _mx_wo(entry, x, wq, ws, wfmt, bias, out_dtype):
+    """One launch of a weight-only MX product: x bf16 [M, K] (K % 8 == 0), wq / ws as mx_quant stores them for Kp = mx_padded_k(K)."""
+    dev = _dev(x, wq, ws, bias)
+    M, K = x.shape
+    N, Kp = wq.shape[0], ws.shape[1] * 32
+    assert x.dtype == torch.bfloat16 and x.is_contiguous() and wq.dtype == torch.uint8 and ws.dtype == torch.uint8
+    assert wq.shape[1] == (Kp if wfmt == MX_FP8_E4M3 else Kp // 2) and ws.shape[0] == N and wq.is_contiguous() and ws.is_contiguous()
+    if bias is not None and bias.dtype != out_dtype:
+        bias = bias.to(out_dtype)
+    y = torch.empty((M, N), dtype=out_dtype, device=dev)
+    with torch.cuda.device(dev):
+        check(getattr(lib, entry)(_ptr(x), _ptr(wq), _ptr(ws), int(wfmt), _ptr(bias), _ptr(y), dtype_code(out_dtype), M, N, K, Kp,
+                                  _stream()), entry)
+    return y
+
+
+def mx_wo_gemv(x, wq, ws, wfmt, bias, out_dtype):
+    """y = x @ dequant(wq, ws)^T + bias for up to MX_GEMV_MAX_M rows of bf16 x against MX weights (K16w, inc_mx_wo_gemv): the strip
+    shape of mx_gemv on v_mfma_f32_16x16x32_bf16, the weights converted in registers by v_cvt_scalef32_pk_bf16_fp4 / _fp8."""
+    return _mx_wo("inc_mx_wo_gemv", x, wq, ws, wfmt, bias, out_dtype)
+
+
+def mx_wo_gemm(x, wq, ws, wfmt, bias, out_dtype):
+    """mx_wo_gemv's product for any number of rows (inc_mx_wo_gemm): 256 x 256 tiles on v_mfma_f32_32x32x16_bf16, x through LDS, the
+    weights straight from global memory into registers."""
+    return _mx_wo("inc_mx_wo_gemm", x, wq, ws, wfmt, bias, out_dtype)
+
+
 def _moe_gemm_out(mode, out, out_dtype, S, N, dev, routing_weights, name):
     """(out, its dtype, the routing weights' dtype code) of a routed GEMM wrapper `name` (mx_moe_gemm, mx_moe_gemm_glu, fp8_moe_gemm):
     mode 0 writes [S, N/2] of out's dtype or `out_dtype` (bf16 / fp16), modes 1 and 2 fp32 [S, N]; `out` is allocated when None."""

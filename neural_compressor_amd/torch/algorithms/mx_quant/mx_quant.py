@@ -19,6 +19,7 @@ from ..base_algorithm import Quantizer
 
 FORMATS = {"fp8_e4m3": ops.MX_FP8_E4M3, "fp4": ops.MX_FP4_E2M1}
 PAIRS = (("fp8_e4m3", "fp8_e4m3"), ("fp4", "fp8_e4m3"), ("fp4", "fp4"))  # (w_dtype, act_dtype) the GEMM takes
+WEIGHT_ONLY_PAIRS = (("fp4", "bf16"), ("fp8_e4m3", "bf16"))  # the weight-only cell: MX weights, bf16 activations
 
 
 def _code_values(fmt):
@@ -104,6 +105,47 @@ class MXLinear(torch.nn.Module):
                 f"w_dtype={self.w_dtype}, act_dtype={self.act_dtype}, blocksize=32")
 
 
+class MXWeightOnlyLinear(MXLinear):
+    """nn.Linear with MX weights and bf16 activations (MXQuantConfig(weight_only=True, act_dtype="bf16")): MXLinear's buffers and
+    state-dict keys, its from_float (inc_mx_quant on the weight) and its recover; the activations are not quantised.
+    forward = inc_mx_wo_gemv up to DECODE_MAX_M rows, inc_mx_wo_gemm above (csrc/gemm_mx_wo.hip: the weights are dequantised in
+    registers, y = x @ recover(bfloat16)^T accumulated in fp32); nothing is read back to the host.  The product is computed in
+    bf16 whatever the input's type: fp16 and fp32 inputs are cast to bf16 and the output is returned in the input's type (the range
+    of an E8M0 scale does not fit fp16, so there is no fp16 product).  An in_features that is no multiple of 8 is zero-padded with
+    torch, once per call."""
+
+    # rows up to which the decode GEMV is taken: the measured crossover of the two kernels (profiles/mx/mx_wo_time.log)
+    DECODE_MAX_M = ops.MX_GEMV_MAX_M
+
+    def __init__(self, in_features, out_features, bias=False, w_dtype="fp4", act_dtype="bf16", device="cuda", float_type=torch.float16):
+        if (w_dtype, act_dtype) not in WEIGHT_ONLY_PAIRS:
+            raise NotImplementedError(f"MXQuant on MI355X, weight-only: (w_dtype, act_dtype) must be one of {WEIGHT_ONLY_PAIRS}, "
+                                      f"got {(w_dtype, act_dtype)}")
+        super().__init__(in_features, out_features, bias=bias, w_dtype=w_dtype, act_dtype="fp8_e4m3", device=device, float_type=float_type)
+        self.act_dtype, self.act_fmt = "bf16", None
+
+    @classmethod
+    def from_float(cls, linear, w_dtype="fp4", act_dtype="bf16", device="cuda"):
+        return super().from_float(linear, w_dtype=w_dtype, act_dtype=act_dtype, device=device)
+
+    def forward(self, input):
+        x = input
+        lead = x.shape[:-1]
+        out_dtype = x.dtype if x.dtype in (torch.float16, torch.bfloat16) else self.float_type
+        ret_dtype = torch.float32 if x.dtype == torch.float32 else out_dtype
+        x2d = x.reshape(-1, self.in_features)
+        if x2d.shape[0] == 0:
+            return torch.empty((*lead, self.out_features), dtype=ret_dtype, device=x.device)
+        x2d = x2d.to(torch.bfloat16)
+        if self.in_features % 8:
+            x2d = torch.nn.functional.pad(x2d, (0, 8 - self.in_features % 8))
+        product = ops.mx_wo_gemv if x2d.shape[0] <= min(self.DECODE_MAX_M, ops.MX_GEMV_MAX_M) else ops.mx_wo_gemm
+        y = product(x2d.contiguous(), self.qweight, self.w_scale, self.w_fmt, self.bias, out_dtype)
+        if x.dtype == torch.float32:
+            y = y.float()
+        return y.reshape(*lead, self.out_features)
+
+
 def mx_linear_group(x, modules):
     """[m(x) for m in modules], bit for bit, for MXLinear modules that multiply the SAME activation -- q / k / v of an attention block,
     gate / up of an MLP: x is quantised ONCE (each member's own forward quantises it again), and up to MXLinear.DECODE_MAX_M rows the
@@ -112,6 +154,8 @@ def mx_linear_group(x, modules):
     MXLinear, mixed formats or widths, fewer than 2 or more than 8 members, x elsewhere or empty, a decode-sized x with DECODE_GEMV off
     -- is the plain list of single forwards."""
     mods = list(modules)
+    if any(isinstance(m, MXWeightOnlyLinear) for m in mods):  # no one-launch group for the weight-only cell
+        return [m(x) for m in mods]
     plan = linear_group_plan(x, mods, MXLinear, ops.MX_GEMV_MAX_MEMBERS, ops.MX_GEMV_MAX_M,
                              lambda m: (m.in_features, m.qweight.device, m.w_dtype, m.act_dtype))
     if plan is None:
@@ -170,7 +214,10 @@ class MXQuantizer(Quantizer):
         for name in names:
             cfg = self.quant_config[name]
             mod = get_module(model, name)
-            cls = MXLinear if isinstance(mod, torch.nn.Linear) else MXGptOssExperts if is_gpt_oss_experts(mod) else MXExperts
+            if isinstance(mod, torch.nn.Linear):
+                cls = MXWeightOnlyLinear if cfg.get("weight_only") else MXLinear
+            else:
+                cls = MXGptOssExperts if is_gpt_oss_experts(mod) else MXExperts
             set_module(model, name, cls.from_float(mod, cfg["w_dtype"], cfg["act_dtype"], device=dev))
         model.mx_info = {"blocksize": 32, "round_method": "nearest"}
         return model

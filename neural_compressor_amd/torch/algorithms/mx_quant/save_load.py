@@ -1,6 +1,7 @@
 """save / load of an MX model (`model.save(output_dir)`, `load(output_dir, original_model)`), the files of smooth_quant/save_load.py:
   quantized_weight.pt   state_dict: uint8 `qweight`, uint8 `w_scale`, bias of every MXLinear; the float parameters of everything else
-  qconfig.json          {"mx_quant": {blocksize, round_method}, "mx_modules": {name: [w_dtype, act_dtype]},
+  qconfig.json          {"mx_quant": {blocksize, round_method}, "mx_modules": {name: [w_dtype, act_dtype]} (act_dtype "bf16": an
+                         MXWeightOnlyLinear),
                          "mx_experts": {name: [w_dtype, act_dtype, E, H, I]},
                          "mx_gpt_oss_experts": {name: [w_dtype, act_dtype, E, H, I, alpha, limit]}}
 MXExperts modules save their four uint8 buffers under their own names, MXGptOssExperts modules those and their two fp32 biases.  The
@@ -15,7 +16,7 @@ import torch
 
 from ...utils.utility import _take, _take_experts, get_module, half_or_fp16, is_fused_experts, is_gpt_oss_experts, set_module
 from .experts import MXExperts, MXGptOssExperts
-from .mx_quant import MXLinear
+from .mx_quant import MXLinear, MXWeightOnlyLinear
 
 WEIGHT_NAME = "quantized_weight.pt"
 QCONFIG_NAME = "qconfig.json"
@@ -55,7 +56,8 @@ def load(output_dir, original_model, device="cuda"):
         lin = get_module(original_model, name)
         assert isinstance(lin, torch.nn.Linear), f"{name}: expected nn.Linear in the float architecture, got {type(lin).__name__}"
         ft = state[name + ".bias"].dtype if (name + ".bias") in state else half_or_fp16(lin.weight.dtype)
-        new = MXLinear(lin.in_features, lin.out_features, bias=(name + ".bias") in state, w_dtype=w_dtype, act_dtype=act_dtype,
+        cls = MXWeightOnlyLinear if act_dtype == "bf16" else MXLinear  # the weight-only cell: same buffers, bf16 activations
+        new = cls(lin.in_features, lin.out_features, bias=(name + ".bias") in state, w_dtype=w_dtype, act_dtype=act_dtype,
                        device=dev, float_type=ft)
         _take(state, name, new, dev)
         set_module(original_model, name, new)

@@ -306,13 +306,15 @@ class MXQuantConfig(TorchBaseConfig):
     defaults to MX-INT8 (`w_dtype="int8", act_dtype="int8"`); the block-scaled matrix instruction of the MI355X has no INT8 operand,
     so the defaults here are `w_dtype="fp8_e4m3", act_dtype="fp8_e4m3"` -- a deliberate deviation.  Supported (w_dtype, act_dtype):
     ("fp8_e4m3", "fp8_e4m3"), ("fp4", "fp8_e4m3"), ("fp4", "fp4"), "fp4" being e2m1; `blocksize=32`, `round_method="nearest"`,
-    `weight_only=False`; `out_dtype` is accepted and unused (the output has the activation's type).  `w_dtype="fp32"` (through
+    `weight_only=False`; `weight_only=True` selects the weight-only cell and takes `act_dtype="bf16"` with `w_dtype` "fp4" or
+    "fp8_e4m3" (MXWeightOnlyLinear: MX weights against bf16 activations; experts modules stay float under it); `out_dtype` is accepted and unused (the output has the activation's type).  `w_dtype="fp32"` (through
     `set_local`) leaves a layer float; lm_head stays float unless `quant_lm_head=True`.  `quant_experts=True` (an extension of the
     reference's fields; off by default) also converts the fused MoE experts modules (is_fused_experts) to MXExperts."""
 
     name = MX_QUANT
     supported_configs: List = []
     PAIRS = (("fp8_e4m3", "fp8_e4m3"), ("fp4", "fp8_e4m3"), ("fp4", "fp4"))
+    WEIGHT_ONLY_PAIRS = (("fp4", "bf16"), ("fp8_e4m3", "bf16"))
 
     def __init__(
         self,
@@ -332,14 +334,19 @@ class MXQuantConfig(TorchBaseConfig):
                                  "quant_experts"])
         if w_dtype != "fp32":
             unsupported = []
-            if (w_dtype, act_dtype) not in self.PAIRS:
-                unsupported.append(f"(w_dtype, act_dtype) must be one of {self.PAIRS}, got {(w_dtype, act_dtype)}")
+            wo_pair = (w_dtype, act_dtype) in self.WEIGHT_ONLY_PAIRS
+            if wo_pair and not weight_only:
+                unsupported.append(f"{(w_dtype, act_dtype)} is the weight-only cell: pass weight_only=True")
+            elif not wo_pair and (w_dtype, act_dtype) not in self.PAIRS:
+                unsupported.append(f"(w_dtype, act_dtype) must be one of {self.PAIRS}, or one of {self.WEIGHT_ONLY_PAIRS} with "
+                                   f"weight_only=True, got {(w_dtype, act_dtype)}")
             if blocksize != 32:
                 unsupported.append("blocksize must be 32 (the block of the matrix instruction)")
             if round_method != "nearest":
                 unsupported.append('round_method must be "nearest"')
-            if weight_only:
-                unsupported.append("weight_only=True is not built (the instruction takes MX operands on both sides)")
+            if weight_only and not wo_pair:
+                unsupported.append("weight_only=True is not built (the instruction takes MX operands on both sides) with MX "
+                                   'activations: pass act_dtype="bf16" for MX weights against bf16 activations')
             if unsupported:
                 raise NotImplementedError("MXQuant on MI355X: " + "; ".join(unsupported))
         self._post_init()
