@@ -658,7 +658,7 @@ int inc_w8a8_gemm_rowscale(const int8_t* xq, const int8_t* wq, const float* row_
  *   members.  wq, ws, bias, y and N are HOST arrays of n entries (the convention of inc_woq_gemv_anyw_multi); bias may be NULL or hold
  *   NULL for a member without one; x, the format pair, ydtype and Kp are common.  y[i] is bit-identical to inc_mx_gemv on member i
  *   alone (the same strip body).  Rejections as for inc_mx_gemv, and INC_ERR_UNSUPPORTED for n outside 2 .. 8.
- * inc_mx_moe_gemm (csrc/gemm_strip_moe.hip, K16e): the product of inc_mx_gemm per expert over the rows inc_moe_route sorted -- the two
+ * inc_mx_moe_gemm (csrc/gemm_strip_moe.hip on csrc/strip_moe_frame.hpp, K16e): the product of inc_mx_gemm per expert over the rows inc_moe_route sorted -- the two
  *   F.linear of transformers' MixtralExperts.forward (also the Qwen2-MoE / Qwen3-MoE / OLMoE experts) for MX experts.  One forward is
  *   inc_moe_route -> inc_mx_quant(x) -> inc_mx_moe_gemm(0) -> inc_mx_quant(h) -> inc_mx_moe_gemm(1) -> inc_moe_combine on `stream`.
  *   `route` is K4e's buffer, unchanged ([0] tile count, offsets [E+1], order [S], pos [S], tiles of 64 rows; S = T * top_k).
@@ -780,7 +780,7 @@ int inc_mx_moe_gemm_glu(int mode, const uint8_t* aq, const uint8_t* as, int afmt
  *   to it.  Below g ~ -88.7 expf(-g) is +inf and silu(g) is -0, which is the rounded exact value; g = -inf gives NaN.  The store rule
  *   of y, the reads (nothing past row M - 1 of xq or row N - 1 of a weight) and the rejections are inc_fp8_gemv's.
  *   Both validate their arguments before any HIP call; no workspace, no counters, repeated calls are bit-identical.
- * inc_fp8_moe_gemm (csrc/gemm_strip_moe.hip, K17e): the product of inc_fp8_gemm per expert over the rows inc_moe_route sorted -- the two
+ * inc_fp8_moe_gemm (csrc/gemm_strip_moe.hip on csrc/strip_moe_frame.hpp, K17e): the product of inc_fp8_gemm per expert over the rows inc_moe_route sorted -- the two
  *   F.linear of transformers' MixtralExperts.forward (also the Qwen2-MoE / Qwen3-MoE / OLMoE experts) for FP8 experts.  One forward is
  *   inc_moe_route -> inc_fp8_quant_rows(x) -> inc_fp8_moe_gemm(0) -> inc_fp8_quant_rows(h) -> inc_fp8_moe_gemm(1) -> inc_moe_combine
  *   on `stream`.  `route` is K4e's buffer, unchanged ([0] tile count, offsets [E+1], order [S], pos [S], tiles of 64 rows; S = T *
@@ -855,7 +855,7 @@ int inc_fp8_moe_gemm(int mode, const uint8_t* aq, const float* a_scale, const in
  *   are bit-identical.  On operands whose every partial sum is exact in fp32 it equals inc_fp8_block_gemm bit for bit.
  * Both products: INC_ERR_UNSUPPORTED (nothing launched) for Kp % 128 != 0, a ydtype other than bf16 / fp16 or (gemv) M > 16;
  *   INC_ERR_BAD_ARG for a NULL operand, a size < 1 or a misaligned pointer.  All four validate their arguments before any HIP call.
- * inc_fp8_block_moe_gemm (csrc/gemm_fp8_block_moe.hip, K18e): the product of inc_fp8_block_gemv per expert over the rows inc_moe_route
+ * inc_fp8_block_moe_gemm (csrc/gemm_fp8_block_moe.hip on csrc/strip_moe_frame.hpp, K18e): the product of inc_fp8_block_gemv per expert over the rows inc_moe_route
  *   sorted -- the two F.linear of transformers' MixtralExperts.forward (also the Qwen3-MoE / DeepSeek-V3 shaped experts) for experts
  *   stored in this scheme.  One forward is
  *   inc_moe_route -> inc_fp8_quant_groups(x) -> inc_fp8_block_moe_gemm(0) -> inc_fp8_quant_groups(h) -> inc_fp8_block_moe_gemm(1) ->

@@ -1,5 +1,5 @@
 // strip_frame.hpp -- the frame every "strip" kernel on v_mfma_(scale_)f32_16x16x128_f8f6f4 is written against: the MX decode GEMV
-// (gemm_mx_gemv.hip: member table and fragments; its loop and sum are written out), the FP8 per-token decode GEMVs (gemm_fp8_group.hip) and the routed experts GEMM of both cells (gemm_strip_moe.hip).
+// (gemm_mx_gemv.hip: member table and fragments; its loop and sum are written out), the FP8 per-token decode GEMVs (gemm_fp8_group.hip) and the routed experts GEMMs (strip_moe_frame.hpp: the MX and per-token FP8 cells of gemm_strip_moe.hip on strip_partials, the block-scaled FP8 cell of gemm_fp8_block_moe.hip on its own K loop).
 // A kernel file keeps what is its own -- where its rows come from and what its epilogue multiplies -- and takes the rest from here.
 //
 //   workgroup   owns STRIP = 16 weight rows (one strip; gate AND up strip where NS = 2) over all of K against NB blocks of 16 rows of x.
@@ -21,7 +21,7 @@
 //               adjacent columns of one row (store_quad16 of tile256_frame.hpp for 16-bit outputs).
 // Every cross-kernel identity of the family (multi == gemv, gated == experts mode 0, fp8 == mx at scale bytes 127, one expert == gemv)
 // rests on the tile-to-wave map, the ascending K inside a wave and the wave-order sum; they are defined here and, written out for its
-// codegen, in mx_gemv_kernel (gemm_mx_gemv.hip), nowhere else.
+// codegen, in mx_gemv_kernel (gemm_mx_gemv.hip) and BlockCell::partials (gemm_fp8_block_moe.hip: its factor changes per K-tile), nowhere else.
 // SCALED = false issues the builtin with literal zero scale operands, which the compiler emits as the UNSCALED opcode (no scale
 // register); it equals the scaled opcode with both scale bytes 127 bit for bit (profiles/mx/mx_lab.log).
 #pragma once

@@ -19,7 +19,7 @@ import torch
 from .... import ops
 from ....common.utils import logger
 from ...utils.utility import half_or_fp16, is_fused_experts, set_module
-from ..fused_experts import MAX_EXPERTS, FusedExperts, is_silu
+from .experts import _FP8ExpertsBase, experts_unsupported_reason
 
 BLOCK = ops.FP8_BLOCK
 
@@ -28,7 +28,7 @@ def _blocks(n):
     return (n + BLOCK - 1) // BLOCK
 
 
-class FP8BlockExperts(FusedExperts):
+class FP8BlockExperts(_FP8ExpertsBase):
     """Buffers (Kp = K rounded up to 128; the padding columns are zero codes): gate_up_qweight uint8 [E, 2I, Kp(H)], gate_up_w_scale
     fp32 [E, 2, ceil(I/128), Kp(H)/128] (index 1: gate, up), down_qweight uint8 [E, H, Kp(I)], down_w_scale fp32 [E, ceil(H/128),
     Kp(I)/128].  bf16 / fp16 compute in their own dtype, fp32 computes in float_type and is cast back.  The dense route (the referee)
@@ -40,15 +40,12 @@ class FP8BlockExperts(FusedExperts):
     # Qwen3-30B-A3B experts (E 128, k 8) fused 14.5 x faster than dense at T = 4096 (256 rows per expert), a DeepSeek-V3 shaped layer
     # (E 256, k 8) 6.6 x at T = 4096 (128 per expert); the dense route wins at no measured point, and nothing above 256 was measured
     MOE_MAX_ROWS = 256
+    _quant = staticmethod(ops.fp8_quant_groups)
+    _moe_gemm = "fp8_block_moe_gemm"
 
     def __init__(self, num_experts, hidden_dim, intermediate_dim, act_fn=None, device="cuda", float_type=torch.float16):
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError(f"FP8BlockExperts needs a HIP device ('cuda[:N]'), got '{device}'. There is no CPU implementation.")
-        super().__init__(num_experts, hidden_dim, intermediate_dim, act_fn)
-        E, H, I = num_experts, hidden_dim, intermediate_dim
-        self.kp_h, self.kp_i = ops.mx_padded_k(H), ops.mx_padded_k(I)
-        self.float_type = float_type
+        super().__init__(num_experts, hidden_dim, intermediate_dim, act_fn, device, float_type)
+        E, H, I, dev = num_experts, hidden_dim, intermediate_dim, torch.device(device)
         self.register_buffer("gate_up_qweight", torch.zeros((E, 2 * I, self.kp_h), dtype=torch.uint8, device=dev))
         self.register_buffer("gate_up_w_scale", torch.zeros((E, 2, _blocks(I), self.kp_h // BLOCK), dtype=torch.float32, device=dev))
         self.register_buffer("down_qweight", torch.zeros((E, H, self.kp_i), dtype=torch.uint8, device=dev))
@@ -117,26 +114,6 @@ class FP8BlockExperts(FusedExperts):
             out.append(w if expert is None else w[0])
         return tuple(out)
 
-    def _fusable(self):
-        # inc_moe_combine stores four columns at a time
-        return is_silu(self.act_fn) and self.num_experts <= MAX_EXPERTS and self.hidden_dim % 4 == 0
-
-    def _compute_dtype(self, x):
-        return x.dtype if x.dtype in (torch.float16, torch.bfloat16) else self.float_type
-
-    def _fused_forward(self, x2d, idx, w, cdt):
-        """Six launches in stream order; every buffer is allocated per call and nothing is kept.  Rows of h past the route's valid
-        positions hold whatever torch.empty gave: the quantiser's contract for such a row is that every write stays in bounds, and
-        inc_fp8_block_moe_gemm reads neither the codes nor the factors of a row that no valid position names."""
-        T, k = idx.shape
-        E = self.num_experts
-        route = ops.moe_route(idx, E)
-        xq, xs = ops.fp8_quant_groups(x2d, self.kp_h)
-        h = ops.fp8_block_moe_gemm(0, xq, xs, route, self.gate_up_qweight, self.gate_up_w_scale, T, k, out_dtype=cdt)
-        hq, hs = ops.fp8_quant_groups(h, self.kp_i)
-        y = ops.fp8_block_moe_gemm(1, hq, hs, route, self.down_qweight, self.down_w_scale, T, k, routing_weights=w)
-        return ops.moe_combine(y, route, T, k, E, cdt)
-
     @staticmethod
     def _product(a, kp, wq, ws, cdt):
         aq, as_ = ops.fp8_quant_groups(a, kp)
@@ -156,12 +133,7 @@ class FP8BlockExperts(FusedExperts):
 
 def block_unsupported_reason(module):
     """Why convert_block_experts leaves the fused-experts `module` in floating point (None = it converts it)."""
-    if not is_silu(getattr(module, "act_fn", None)):
-        return f"activation {type(getattr(module, 'act_fn', None)).__name__} is not SiLU"
-    E = module.gate_up_proj.shape[0]
-    if E > MAX_EXPERTS:
-        return f"E={E} must be at most {MAX_EXPERTS}"
-    return None
+    return experts_unsupported_reason(module)
 
 
 @torch.no_grad()

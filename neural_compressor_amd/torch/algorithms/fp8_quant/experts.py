@@ -17,7 +17,43 @@ from ...utils.utility import half_or_fp16
 from ..fused_experts import MAX_EXPERTS, FusedExperts, is_silu
 
 
-class FP8Experts(FusedExperts):
+class _FP8ExpertsBase(FusedExperts):
+    """What FP8Experts and FP8BlockExperts (block_experts.py) share; a class names its activation quantiser `_quant(x, kp)` and its
+    routed GEMM `_moe_gemm`, a function of ops with fp8_moe_gemm's signature, by name (looked up at every call)."""
+
+    _quant = _moe_gemm = None
+
+    def __init__(self, num_experts, hidden_dim, intermediate_dim, act_fn, device, float_type):
+        if torch.device(device).type != "cuda":
+            raise RuntimeError(f"{type(self).__name__} needs a HIP device ('cuda[:N]'), got '{device}'. There is no CPU implementation.")
+        super().__init__(num_experts, hidden_dim, intermediate_dim, act_fn)
+        self.kp_h, self.kp_i = ops.mx_padded_k(hidden_dim), ops.mx_padded_k(intermediate_dim)
+        self.float_type = float_type
+
+    def _fusable(self):
+        # inc_moe_combine stores four columns at a time
+        return is_silu(self.act_fn) and self.num_experts <= MAX_EXPERTS and self.hidden_dim % 4 == 0
+
+    def _compute_dtype(self, x):
+        return x.dtype if x.dtype in (torch.float16, torch.bfloat16) else self.float_type
+
+    def _fused_forward(self, x2d, idx, w, cdt):
+        """Six launches in stream order; every buffer is allocated per call and nothing is kept.  Rows of h past the route's valid
+        positions hold whatever torch.empty gave, non-finite values included: the quantiser's contract for such a row is that every
+        write stays in bounds (include/inc_mi355x.h), and nothing reads those rows' codes or scales -- the routed GEMM reads neither
+        the codes nor the factors of a row that no valid position names."""
+        T, k = idx.shape
+        E = self.num_experts
+        route = ops.moe_route(idx, E)
+        xq, xs = self._quant(x2d, self.kp_h)
+        gemm = getattr(ops, self._moe_gemm)
+        h = gemm(0, xq, xs, route, self.gate_up_qweight, self.gate_up_w_scale, T, k, out_dtype=cdt)
+        hq, hs = self._quant(h, self.kp_i)
+        y = gemm(1, hq, hs, route, self.down_qweight, self.down_w_scale, T, k, routing_weights=w)
+        return ops.moe_combine(y, route, T, k, E, cdt)
+
+
+class FP8Experts(_FP8ExpertsBase):
     """Fused experts with e4m3 weights (one fp32 scale per output channel of every expert) and e4m3 activations (one fp32 scale per
     token, from the data of the call).  Buffers (Kp = K rounded up to 128): gate_up_qweight uint8 [E, 2I, Kp(H)], gate_up_w_scale fp32
     [E, 2I], down_qweight uint8 [E, H, Kp(I)], down_w_scale fp32 [E, H].  bf16 / fp16 compute in their own dtype, fp32 computes in
@@ -29,15 +65,12 @@ class FP8Experts(FusedExperts):
     # (E 8, k 2) fused 1.09 x faster than dense at T = 1024 (256 rows per expert), dense 2.4 x faster at T = 4096 (1024); Qwen3-MoE
     # (E 128, k 8) fused 12.5 x faster at T = 4096 (256 per expert)
     MOE_MAX_ROWS = 256
+    _quant = staticmethod(lambda x, kp: ops.fp8_quant_rows(x, None, kp))
+    _moe_gemm = "fp8_moe_gemm"
 
     def __init__(self, num_experts, hidden_dim, intermediate_dim, act_fn=None, device="cuda", float_type=torch.float16):
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError(f"FP8Experts needs a HIP device ('cuda[:N]'), got '{device}'. There is no CPU implementation.")
-        super().__init__(num_experts, hidden_dim, intermediate_dim, act_fn)
-        E, H, I = num_experts, hidden_dim, intermediate_dim
-        self.kp_h, self.kp_i = ops.mx_padded_k(H), ops.mx_padded_k(I)
-        self.float_type = float_type
+        super().__init__(num_experts, hidden_dim, intermediate_dim, act_fn, device, float_type)
+        E, H, I, dev = num_experts, hidden_dim, intermediate_dim, torch.device(device)
         for prefix, N, kp in (("gate_up", 2 * I, self.kp_h), ("down", H, self.kp_i)):
             self.register_buffer(f"{prefix}_qweight", torch.zeros((E, N, kp), dtype=torch.uint8, device=dev))
             self.register_buffer(f"{prefix}_w_scale", torch.zeros((E, N), dtype=torch.float32, device=dev))
@@ -70,27 +103,6 @@ class FP8Experts(FusedExperts):
             out.append(w if expert is None else w[0])
         return tuple(out)
 
-    def _fusable(self):
-        # inc_moe_combine stores four columns at a time
-        return is_silu(self.act_fn) and self.num_experts <= MAX_EXPERTS and self.hidden_dim % 4 == 0
-
-    def _compute_dtype(self, x):
-        return x.dtype if x.dtype in (torch.float16, torch.bfloat16) else self.float_type
-
-    def _fused_forward(self, x2d, idx, w, cdt):
-        """Six launches in stream order; every buffer is allocated per call and nothing is kept.  Rows of h past the route's valid
-        positions hold whatever torch.empty gave, non-finite values included: the quantiser's contract for such a row is that every
-        write stays in bounds (include/inc_mi355x.h), and nothing reads those rows' codes or scales -- inc_fp8_moe_gemm reads neither
-        the codes nor the a_scale entry of a row that no valid position names."""
-        T, k = idx.shape
-        E = self.num_experts
-        route = ops.moe_route(idx, E)
-        xq, xs = ops.fp8_quant_rows(x2d, None, self.kp_h)
-        h = ops.fp8_moe_gemm(0, xq, xs, route, self.gate_up_qweight, self.gate_up_w_scale, T, k, out_dtype=cdt)
-        hq, hs = ops.fp8_quant_rows(h, None, self.kp_i)
-        y = ops.fp8_moe_gemm(1, hq, hs, route, self.down_qweight, self.down_w_scale, T, k, routing_weights=w)
-        return ops.moe_combine(y, route, T, k, E, cdt)
-
     def _product(self, a, prefix, e, kp, cdt):
         aq, as_ = ops.fp8_quant_rows(a, None, kp)
         product = ops.fp8_gemv if a.shape[0] <= ops.FP8_GEMV_MAX_M else ops.fp8_gemm
@@ -105,13 +117,18 @@ class FP8Experts(FusedExperts):
                 f"fp8_config=E4M3, act_granularity=per_token, w_granularity=per_channel")
 
 
-def unsupported_reason(module, cfg):
-    """Why FP8Quantizer leaves the fused-experts `module` in float under `cfg` (None = it converts it)."""
-    E = module.gate_up_proj.shape[0]
-    if (cfg.get("act_granularity"), cfg.get("w_granularity")) == ("per_group", "per_block"):
-        return "block-scaled (per_group / per_block) experts are not wired into FP8Config yet: use convert_block_experts(model)"
+def experts_unsupported_reason(module):
+    """The refusals FP8Experts and FP8BlockExperts share (None = none applies)."""
     if not is_silu(getattr(module, "act_fn", None)):
         return f"activation {type(getattr(module, 'act_fn', None)).__name__} is not SiLU"
+    E = module.gate_up_proj.shape[0]
     if E > MAX_EXPERTS:
         return f"E={E} must be at most {MAX_EXPERTS}"
     return None
+
+
+def unsupported_reason(module, cfg):
+    """Why FP8Quantizer leaves the fused-experts `module` in float under `cfg` (None = it converts it)."""
+    if (cfg.get("act_granularity"), cfg.get("w_granularity")) == ("per_group", "per_block"):
+        return "block-scaled (per_group / per_block) experts are not wired into FP8Config yet: use convert_block_experts(model)"
+    return experts_unsupported_reason(module)

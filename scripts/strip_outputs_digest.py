@@ -12,10 +12,16 @@ depend on their order) those are used, the exact operands of the experts tables 
   fp8_gated       fp8_group_cases GATED_MS x GATED_NS x TILES on the random case and the exact case with both biases, one line (inc_fp8_gemv_gated)
   fp8_moe         every case and mode of fp8_moe_cases.CASES on its exact operands, the random case of every mode (inc_fp8_moe_gemm)
   fp8_gemm        fp8_cases GEMM_SHAPES (every GEMM_KPS in one line) on random codes: the 256 x 256 kernel, which is not on the frame -- a control
+  fp8_block_moe   every case and mode of fp8_block_cases.moe_exact (MOE_EXACT, MOE_EXACT_MODE0) and the random case of every mode of
+                  tests/test_gpu_fp8_block_moe.py (inc_fp8_block_moe_gemm)
+  mx_moe_glu      mx_gpt_oss_cases: mx_moe_cases' table x pairs with the bias (both scale rules and, in mode 0, every PARAMS in one line), and
+                  the random case of every mode x pairs (inc_mx_moe_gemm_glu)
+  fp8_block_gemv  fp8_block_cases GEMV_NS x GEMV_TILES (every GEMV_MS in one line) on random codes and scales with a bias (inc_fp8_block_gemv): its
+                  K loop is its own -- a control
 
 Every launch is made twice; the two outputs must agree before they enter the digest.  Outputs the experts kernels do not write (rows
 past the valid positions) hold a sentinel.
-usage: python scripts/strip_outputs_digest.py > listing.txt"""
+usage: python scripts/strip_outputs_digest.py [part ...] > listing.txt    (no part: all of them, in the order above)"""
 import hashlib
 import os
 import sys
@@ -24,12 +30,14 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from neural_compressor_amd import ops  # noqa: E402
+from tests import fp8_block_cases as B  # noqa: E402
 from tests import fp8_cases as F  # noqa: E402
 from tests import fp8_group_cases as G  # noqa: E402
 from tests import fp8_moe_cases as FM  # noqa: E402
 from tests import moe_stage_cases as S  # noqa: E402
 from tests import mx_cases as C  # noqa: E402
 from tests import mx_gemv_cases as V  # noqa: E402
+from tests import mx_gpt_oss_cases as GO  # noqa: E402
 from tests import mx_moe_cases as MM  # noqa: E402
 
 dev = torch.device("cuda:0")
@@ -172,7 +180,65 @@ def fp8_gemm():
         emit(f"fp8_gemm m{M} n{N}", *calls)
 
 
+def fp8_block_moe():
+    def call(mode, aq, as_, wq, ws, route, T, k, rw, out):
+        return ops.fp8_block_moe_gemm(mode, aq, as_, route, wq, ws, T, k, rw, out=out)
+
+    def case(ro, mode, N, operands):
+        return moe_calls(call, dict(ro=ro, mode=mode, N=N, rw=MM.routing_weights(ro["T"], ro["k"], torch.float32)), operands)
+
+    for routing, Nout, Kp in B.MOE_EXACT:
+        for mode in (2, 1):
+            ro, *operands, _ = B.moe_exact(routing, mode, Nout, Kp)
+            emit(f"fp8_block_moe {routing} n{Nout} k{Kp} mode{mode}", *case(ro, mode, Nout, operands))
+    for I, Kp in B.MOE_EXACT_MODE0:
+        ro, *operands, _ = B.moe_exact("edges3", 0, I, Kp)
+        emit(f"fp8_block_moe edges3 i{I} k{Kp} mode0", *case(ro, 0, 2 * I, operands))
+    for mode, Nout, Kp in ((2, 260, 640), (1, 260, 640), (0, 260, 640)):         # test_random_codes_and_scales' operands
+        ro = MM.route_of("edges3")
+        E, N, rows = ro["E"], (2 if mode == 0 else 1) * Nout, ro["S"] if mode == 1 else ro["T"]
+        aq, as_ = F.random_codes(rows, 1, Kp, 9100 + mode)["xq"], B.random_scales(rows, 1, Kp, 9300 + mode)[0]
+        wq = torch.stack([F.random_codes(1, N, Kp, 9200 + 10 * mode + e)["wq"] for e in range(E)])
+        ws = torch.stack([torch.cat([B.random_scales(1, Nout, Kp, 9400 + 100 * mode + 2 * e + h)[1] for h in range(N // Nout)]) for e in range(E)])
+        emit(f"fp8_block_moe random mode{mode}", *case(ro, mode, N, (aq, as_, wq, ws)))
+
+
+def mx_moe_glu():
+    for pair, pid in zip(C.PAIRS, C.PAIR_IDS):
+        def calls_of(d, operands, params):
+            bias = GO.bias_of(d["ro"]["E"], d["N"]).float().contiguous().to(dev)
+            return [c for _, alpha, limit in params for c in moe_calls(
+                lambda mode, aq, as_, wq, ws, route, T, k, rw, out, alpha=alpha, limit=limit: ops.mx_moe_gemm_glu(
+                    mode, aq, as_, pair[0], route, wq, ws, pair[1], T, k, bias=bias, alpha=alpha, limit=limit, routing_weights=rw, out=out),
+                d, operands)]
+
+        for c, mode in MM.CASE_MODES:
+            calls = []
+            for rule in MM.RULES:
+                d = MM.exact_case(c, mode, rule)
+                calls += calls_of(d, MM.stored_operands(d, pair[0], pair[1], poison=True), GO.PARAMS if mode == 0 else GO.PARAMS[:1])
+            emit(f"mx_moe_glu {pid} {c.name} mode{mode}", *calls)
+        for mode in (2, 1, 0):
+            d = MM.random_case(mode, pair[0], pair[1])
+            emit(f"mx_moe_glu {pid} random mode{mode}", *calls_of(d, (d["aq"], d["as_"], d["wq"], d["ws"]), GO.PARAMS[:1]))
+
+
+def fp8_block_gemv():
+    for N in B.GEMV_NS:
+        for tiles in B.GEMV_TILES:
+            calls = []
+            for M in B.GEMV_MS:
+                r = F.random_codes(M, N, 128 * tiles, seed=81)
+                xs, ws, bias = B.random_scales(M, N, 128 * tiles, 82)
+                xq, wq, xs, ws = to(r["xq"], r["wq"], xs, ws)
+                calls += [lambda xq=xq, xs=xs, wq=wq, ws=ws, bias=bias, dt=dt: ops.fp8_block_gemv(xq, xs, wq, ws, bias.to(dt).to(dev), dt)
+                          for dt in DTYPES]
+            emit(f"fp8_block_gemv n{N} k{tiles}tiles", *calls)
+
+
 if __name__ == "__main__":
+    parts = (mx_gemv, mx_moe, fp8_gemv, fp8_group, fp8_moe, fp8_gemm, fp8_block_moe, mx_moe_glu, fp8_block_gemv)
     with torch.no_grad():
-        for part in (mx_gemv, mx_moe, fp8_gemv, fp8_group, fp8_moe, fp8_gemm):
-            part()
+        for part in parts:
+            if len(sys.argv) == 1 or part.__name__ in sys.argv[1:]:
+                part()

@@ -9,6 +9,7 @@ import torch
 
 from tests.fp8_cases import DTYPE_IDS, DTYPES, OUT_DTYPES, SAT, SCALE_FLOOR, random_codes  # noqa: F401
 from tests.mx_cases import FP8, code_table, encode_values, padded_k, round_to_format, ulp_of  # noqa: F401
+from tests.mx_moe_cases import route_of
 
 B = 128
 
@@ -85,3 +86,48 @@ def random_scales(M, N, Kp, seed):
     xs = (torch.randn(M, Kp // B, generator=g).abs() * 2.0 ** -9 + 2.0 ** -12).float()
     ws = (torch.randn(-(-N // B), Kp // B, generator=g).abs() * 2.0 ** -9 + 2.0 ** -12).float()
     return xs, ws, (torch.randn(N, generator=g) * 4).to(torch.bfloat16).double()
+
+
+# ---- the routed experts GEMM (tests/test_gpu_fp8_block_moe.py, scripts/strip_outputs_digest.py) -----------------------------------------
+MOE_EXACT = [("edges3", 4, 128), ("edges3", 260, 1024), ("edges3", 264, 1152), ("edges", 264, 3328), ("one_slot", 20, 256),
+             ("all_invalid", 20, 256)]          # (routing, Nout, Kp) of modes 2 and 1
+MOE_EXACT_MODE0 = [(136, 1024), (7, 256)]      # (I, Kp) on "edges3"
+
+
+def moe_reference(ro, mode, ad, as_, wd, ws):
+    """float64 over the valid positions: (val, mass) [nvalid, N], the named source rows.  Mode 0: each half of ws is blocked from its row 0."""
+    nv, order, k, (E, N), KB = ro["nvalid"], ro["order"].long(), ro["k"], wd.shape[:2], as_.shape[1]
+    wse = ws.double().reshape(E, 2 if mode == 0 else 1, -1, KB).repeat_interleave(B, 2)[:, :, :N // 2 if mode == 0 else N].reshape(E, N, KB)
+    val, mass, named = torch.zeros(nv, N, dtype=torch.float64), torch.zeros(nv, N, dtype=torch.float64), torch.zeros(ad.shape[0], dtype=torch.bool)
+    for e in range(E):
+        lo, hi = int(ro["offsets"][e]), int(ro["offsets"][e + 1])
+        src = torch.arange(lo, hi) if mode == 1 else order[lo:hi] // k
+        named[src] = True
+        for kt in range(KB if lo < hi else 0):
+            f = as_[src, kt].double()[:, None] * wse[e, :, kt][None, :]
+            xk, wk = ad[src, B * kt:B * kt + B], wd[e][:, B * kt:B * kt + B]
+            val[lo:hi] += f * (xk @ wk.T)
+            mass[lo:hi] += f * (xk.abs() @ wk.abs().T)
+    return val, mass, named
+
+
+def moe_exact(routing, mode, Nout, Kp):
+    """Integers in -3..3 (per expert from its own seed; mode 0: gate rows from {-1, 0, 1}, two zeros in three), as[r, kt] =
+    2^((3r + kt) % 5 - 3), ws[e, nb, kt] = 2^((2(nb + 7e) + kt + 1) % 5 - 3) (mode 0: both exponents 3 lower); unnamed rows poisoned."""
+    ro = route_of(routing)
+    E, N, shift = ro["E"], (2 if mode == 0 else 1) * Nout, 6 if mode == 0 else 3
+    rows, kt, nblk = (ro["S"] if mode == 1 else ro["T"]), torch.arange(Kp // B), (2 if mode == 0 else 1) * -(-Nout // B)
+    a = torch.randint(-3, 4, (rows, Kp), generator=torch.Generator().manual_seed(5151 + 7 * Nout + Kp + mode))
+    as_ = torch.ldexp(torch.ones(()), (3 * torch.arange(rows)[:, None] + kt) % 5 - shift)
+    w = torch.empty((E, N, Kp), dtype=torch.int64)
+    for e in range(E):
+        ge = torch.Generator().manual_seed(800001 + 7919 * e + Nout + Kp + mode)
+        w[e] = torch.randint(-3, 4, (N, Kp), generator=ge)
+        if mode == 0:
+            w[e, :Nout] = torch.randint(-1, 2, (Nout, Kp), generator=ge) * torch.randint(0, 2, (Nout, Kp), generator=ge)
+    ws = torch.ldexp(torch.ones(()), (2 * (torch.arange(nblk)[None, :, None] + 7 * torch.arange(E)[:, None, None]) + kt + 1) % 5 - shift)
+    val, mass, named = moe_reference(ro, mode, a.double(), as_, w.double(), ws)
+    assert bool((val.float().double() == val).all()) and bool((mass < 2.0 ** 17 * float(as_.max() * ws.max())).all())
+    aq, wq = encode_values(a, FP8), encode_values(w.view(E * N, Kp), FP8).view(E, N, Kp)
+    aq[~named], as_[~named] = 0xFF, float("nan")
+    return ro, aq, as_, wq, ws, val

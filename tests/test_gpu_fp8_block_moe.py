@@ -15,23 +15,7 @@ DTYPES16 = [torch.bfloat16, torch.float16]
 PIPE = 2.0 ** -8                # the instruction's per-term allowance
 TAB = F.code_table(F.FP8)
 SENT = 0x7B5A
-
-
-def _reference(ro, mode, ad, as_, wd, ws):
-    """float64 over the valid positions: (val, mass) [nvalid, N], the named source rows.  Mode 0: each half of ws is blocked from its row 0."""
-    nv, order, k, (E, N), KB = ro["nvalid"], ro["order"].long(), ro["k"], wd.shape[:2], as_.shape[1]
-    wse = ws.double().reshape(E, 2 if mode == 0 else 1, -1, KB).repeat_interleave(B.B, 2)[:, :, :N // 2 if mode == 0 else N].reshape(E, N, KB)
-    val, mass, named = torch.zeros(nv, N, dtype=torch.float64), torch.zeros(nv, N, dtype=torch.float64), torch.zeros(ad.shape[0], dtype=torch.bool)
-    for e in range(E):
-        lo, hi = int(ro["offsets"][e]), int(ro["offsets"][e + 1])
-        src = torch.arange(lo, hi) if mode == 1 else order[lo:hi] // k
-        named[src] = True
-        for kt in range(KB if lo < hi else 0):
-            f = as_[src, kt].double()[:, None] * wse[e, :, kt][None, :]
-            xk, wk = ad[src, B.B * kt:B.B * kt + B.B], wd[e][:, B.B * kt:B.B * kt + B.B]
-            val[lo:hi] += f * (xk @ wk.T)
-            mass[lo:hi] += f * (xk.abs() @ wk.abs().T)
-    return val, mass, named
+_reference, _exact = B.moe_reference, B.moe_exact
 
 
 def _run(hip, mode, aq, as_, ro, wq, ws, rw=None, odtype=None):
@@ -49,31 +33,8 @@ def _run(hip, mode, aq, as_, ro, wq, ws, rw=None, odtype=None):
     return outs[0][:nv]
 
 
-def _exact(routing, mode, Nout, Kp):
-    """Integers in -3..3 (per expert from its own seed; mode 0: gate rows from {-1, 0, 1}, two zeros in three), as[r, kt] =
-    2^((3r + kt) % 5 - 3), ws[e, nb, kt] = 2^((2(nb + 7e) + kt + 1) % 5 - 3) (mode 0: both exponents 3 lower); unnamed rows poisoned."""
-    ro = route_of(routing)
-    E, N, shift = ro["E"], (2 if mode == 0 else 1) * Nout, 6 if mode == 0 else 3
-    rows, kt, nblk = (ro["S"] if mode == 1 else ro["T"]), torch.arange(Kp // B.B), (2 if mode == 0 else 1) * -(-Nout // B.B)
-    a = torch.randint(-3, 4, (rows, Kp), generator=torch.Generator().manual_seed(5151 + 7 * Nout + Kp + mode))
-    as_ = torch.ldexp(torch.ones(()), (3 * torch.arange(rows)[:, None] + kt) % 5 - shift)
-    w = torch.empty((E, N, Kp), dtype=torch.int64)
-    for e in range(E):
-        ge = torch.Generator().manual_seed(800001 + 7919 * e + Nout + Kp + mode)
-        w[e] = torch.randint(-3, 4, (N, Kp), generator=ge)
-        if mode == 0:
-            w[e, :Nout] = torch.randint(-1, 2, (Nout, Kp), generator=ge) * torch.randint(0, 2, (Nout, Kp), generator=ge)
-    ws = torch.ldexp(torch.ones(()), (2 * (torch.arange(nblk)[None, :, None] + 7 * torch.arange(E)[:, None, None]) + kt + 1) % 5 - shift)
-    val, mass, named = _reference(ro, mode, a.double(), as_, w.double(), ws)
-    assert bool((val.float().double() == val).all()) and bool((mass < 2.0 ** 17 * float(as_.max() * ws.max())).all())
-    aq, wq = F.encode_values(a, F.FP8), F.encode_values(w.view(E * N, Kp), F.FP8).view(E, N, Kp)
-    aq[~named], as_[~named] = 0xFF, float("nan")
-    return ro, aq, as_, wq, ws, val
-
-
 @pytest.mark.parametrize("mode", [2, 1])
-@pytest.mark.parametrize("routing,Nout,Kp", [("edges3", 4, 128), ("edges3", 260, 1024), ("edges3", 264, 1152), ("edges", 264, 3328),
-                                             ("one_slot", 20, 256), ("all_invalid", 20, 256)])
+@pytest.mark.parametrize("routing,Nout,Kp", B.MOE_EXACT)
 def test_exact_operands_are_bit_equal_to_float64(hip, routing, Nout, Kp, mode):
     ro, aq, as_, wq, ws, val = _exact(routing, mode, Nout, Kp)
     rw = routing_weights(ro["T"], ro["k"], torch.float64)
@@ -85,7 +46,7 @@ def test_exact_operands_are_bit_equal_to_float64(hip, routing, Nout, Kp, mode):
 
 
 @pytest.mark.parametrize("dtype", DTYPES16)
-@pytest.mark.parametrize("I,Kp", [(136, 1024), (7, 256)])
+@pytest.mark.parametrize("I,Kp", B.MOE_EXACT_MODE0)
 def test_exact_operands_mode0(hip, I, Kp, dtype):
     ro, aq, as_, wq, ws, val = _exact("edges3", 0, I, Kp)
     ref, tol = S.mode0_tolerance(val[:, :I], val[:, I:], torch.zeros(()), torch.zeros(()), dtype)
