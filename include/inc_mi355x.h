@@ -709,7 +709,27 @@ int inc_w8a8_gemm_rowscale(const int8_t* xq, const int8_t* wq, const float* row_
  *   global memory into registers, no split-K and no workspace.
  *   INC_ERR_BAD_ARG for a NULL operand, M, N or K < 1 or a misaligned x / wq / ws; INC_ERR_UNSUPPORTED for M > 16 (the GEMV),
  *   Kp % 128 != 0, K % 8 != 0, K > Kp, Kp - K >= 128, an unknown wfmt or a ydtype other than bf16 / fp16.
- * All eight validate their arguments before any HIP call.                                                                       */
+ * inc_mx_wo_moe_gemm / inc_mx_wo_moe_gemm_glu (csrc/gemm_mx_wo_moe.hip on csrc/strip_moe_frame.hpp, K16we): the WEIGHT-ONLY cell for the
+ *   fused MoE experts -- inc_mx_moe_gemm / inc_mx_moe_gemm_glu with bf16 activations in place of MX activations.  One forward is
+ *   inc_moe_route -> inc_mx_wo_moe_gemm[_glu](0) -> inc_mx_wo_moe_gemm[_glu](1) -> inc_moe_combine on `stream`: no quantiser launch.
+ *   x bf16, row stride K, 16-byte aligned: [T, K] in modes 0 and 2 (row p is token order[p] / top_k), [T * top_k, K] in sorted order
+ *   in mode 1.  wq [E, N, Kp] (e4m3) or [E, N, Kp/2] (e2m1) and ws [E, N, Kp/32] are inc_mx_moe_gemm's (slice e is what inc_mx_quant
+ *   writes for expert e's [N, K] matrix); `route` is inc_moe_route's buffer.  For position p of the sorted order and its expert e
+ *     val[p, n] = sum_{k < K} x[src(p), k] * value(code[e, n, k]) * 2^(ws[e, n, k/32] - 127)
+ *   in fp32, in a fixed order (wave w of 8 takes the K-tiles w, w + 8, ... ascending, the 8 partials are added in wave order:
+ *   repeated calls are bit-identical, and for one expert's rows val is inc_mx_wo_gemv's sum).  Every weight is exact in bf16; the
+ *   scale-byte range in which the product is exact is inc_mx_wo_gemv's.  x is not read at k >= K nor at rows no valid position names.
+ *     mode 2: out [S, N] fp32 = val (+ b(e, n) in the _glu entry)
+ *     mode 0 (N = 2I, gate rows 0 .. I-1, up rows I .. 2I-1): out [S, I] bf16 = rd_bf16(g / (1.f + expf(-g)) * u) with g = val[p, j],
+ *            u = val[p, I + j]; the _glu entry: inc_mx_moe_gemm_glu's mode 0 expression (bias, clamps, alpha) on the same g and u
+ *     mode 1: out [S, N] fp32 = w[order[p]] * val (the _glu entry: w[order[p]] * (val + b(e, n))), w of wdtype INC_F32 / BF16 / F16
+ *   Mode 0 stores bf16 only: h is the next product's operand and the range of an E8M0 scale does not fit fp16.  bias fp32 [E, N] or
+ *   NULL, alpha and limit as in inc_mx_moe_gemm_glu.  Store rule, untouched positions, no workspace and no counters: inc_mx_moe_gemm's.
+ *   INC_ERR_BAD_ARG for a mode outside 0 .. 2, a NULL operand (routing_weights: mode 1 only), a size < 1, a misaligned x / wq, and in
+ *   the _glu entry unless limit > 0 and alpha == alpha and for a bias that is not 4-byte aligned; INC_ERR_UNSUPPORTED (nothing
+ *   launched) for a wfmt other than e4m3 / e2m1, Kp % 128 != 0, K % 8 != 0, K > Kp, Kp - K >= 128, E > 512, S > 2^22, mode 0 with odd
+ *   N or an odtype other than INC_BF16 (INC_F16 included), another odtype than INC_F32 in modes 1 / 2, a bad wdtype (mode 1).
+ * All ten validate their arguments before any HIP call.                                                                         */
 #define INC_MX_FP8_E4M3 0
 #define INC_MX_FP4_E2M1 4
 #define INC_MX_KTILE 128
@@ -727,6 +747,12 @@ int inc_mx_wo_gemv(const void* x, const uint8_t* wq, const uint8_t* ws, int wfmt
                    int64_t N, int64_t K, int64_t Kp, inc_stream_t stream);
 int inc_mx_wo_gemm(const void* x, const uint8_t* wq, const uint8_t* ws, int wfmt, const void* bias, void* y, int ydtype, int64_t M,
                    int64_t N, int64_t K, int64_t Kp, inc_stream_t stream);
+int inc_mx_wo_moe_gemm(int mode, const void* x, const int32_t* route, const uint8_t* wq, const uint8_t* ws, int wfmt,
+                       const void* routing_weights, int wdtype, void* out, int odtype, int64_t T, int top_k, int64_t E, int64_t N,
+                       int64_t K, int64_t Kp, inc_stream_t stream);
+int inc_mx_wo_moe_gemm_glu(int mode, const void* x, const int32_t* route, const uint8_t* wq, const uint8_t* ws, int wfmt,
+                           const float* bias, float alpha, float limit, const void* routing_weights, int wdtype, void* out,
+                           int odtype, int64_t T, int top_k, int64_t E, int64_t N, int64_t K, int64_t Kp, inc_stream_t stream);
 int inc_mx_moe_gemm(int mode, const uint8_t* aq, const uint8_t* as, int afmt, const int32_t* route, const uint8_t* wq,
                     const uint8_t* ws, int wfmt, const void* routing_weights, int wdtype, void* out, int odtype, int64_t T, int top_k,
                     int64_t E, int64_t N, int64_t Kp, inc_stream_t stream);

@@ -101,6 +101,14 @@ SIGNATURES = {
     "inc_mx_gemv_multi": (c_int, [c_int, _P, _P, c_int, _P, _P, c_int, _P, _P, c_int, c_int64, _P, c_int64, _P]),
     "inc_mx_wo_gemv": (c_int, [_P, _P, _P, c_int, _P, _P, c_int, c_int64, c_int64, c_int64, c_int64, _P]),
     "inc_mx_wo_gemm": (c_int, [_P, _P, _P, c_int, _P, _P, c_int, c_int64, c_int64, c_int64, c_int64, _P]),
+    "inc_mx_wo_moe_gemm": (
+        c_int,
+        [c_int, _P, _P, _P, _P, c_int, _P, c_int, _P, c_int, c_int64, c_int, c_int64, c_int64, c_int64, c_int64, _P],
+    ),
+    "inc_mx_wo_moe_gemm_glu": (
+        c_int,
+        [c_int, _P, _P, _P, _P, c_int, _P, c_float, c_float, _P, c_int, _P, c_int, c_int64, c_int, c_int64, c_int64, c_int64, c_int64, _P],
+    ),
     "inc_mx_moe_gemm": (
         c_int,
         [c_int, _P, _P, c_int, _P, _P, _P, c_int, _P, c_int, _P, c_int, c_int64, c_int, c_int64, c_int64, c_int64, _P],

@@ -1,6 +1,7 @@
 // strip_moe_frame.hpp -- the one copy of what a routed strip experts GEMM is: the routed GEMM of the fused MoE experts, per expert over
 // the rows inc_moe_route sorted, on v_mfma_(scale_)f32_16x16x128_f8f6f4.  One kernel template; a cell type says what differs.  Readers:
-// gemm_strip_moe.hip (MxCell, Fp8Cell) and gemm_fp8_block_moe.hip (BlockCell).
+// gemm_strip_moe.hip (MxCell, Fp8Cell), gemm_fp8_block_moe.hip (BlockCell) and gemm_mx_wo_moe.hip (WoCell: bf16 activations on
+// v_mfma_f32_16x16x32_bf16, its own arguments and checks around moe_launch).
 //
 // Replaces the two F.linear of transformers' MixtralExperts.forward (also the Qwen2-MoE / Qwen3-MoE / OLMoE experts).  One forward of
 // MXExperts / FP8Experts / FP8BlockExperts is six launches and no host synchronisation, quant = the cell's activation quantiser:

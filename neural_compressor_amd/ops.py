@@ -1830,6 +1830,45 @@ def mx_moe_gemm_glu(mode, aq, as_, afmt, route, wq, ws, wfmt, T, top_k, bias=Non
     return out
 
 
+def _mx_wo_moe_check_operands(mode, x, wq, ws, wfmt, T, top_k):
+    """The operand checks of mx_wo_moe_gemm and mx_wo_moe_gemm_glu -> (E, N, K, Kp, S)."""
+    E, N = wq.shape[0], wq.shape[1]
+    Kp, S = ws.shape[2] * 32, T * top_k
+    assert x.dtype == torch.bfloat16 and wq.dtype == torch.uint8 and ws.dtype == torch.uint8
+    assert x.dim() == 2 and x.shape[0] == (S if mode == 1 else T) and ws.shape[:2] == (E, N)
+    assert wq.shape[2] == (Kp if wfmt == MX_FP8_E4M3 else Kp // 2)
+    assert x.is_contiguous() and wq.is_contiguous() and ws.is_contiguous()
+    return E, N, x.shape[1], Kp, S
+
+
+def mx_wo_moe_gemm(mode, x, route, wq, ws, wfmt, T, top_k, routing_weights=None, out=None):
+    """inc_mx_wo_moe_gemm (K16we): mx_wo_gemv's product per expert over the rows of the route's sorted order -- mx_moe_gemm with bf16
+    activations x [T or T*k, K] (K % 8 == 0, Kp = mx_padded_k(K)) in place of MX codes.  wq / ws as mx_moe_gemm's.  mode 0: gate_up +
+    SiLU product -> bf16 [T*k, N/2]; mode 1: down x routing weight -> fp32 [T*k, N] from x in sorted order; mode 2: plain -> fp32
+    [T*k, N].  Rows past the route's valid positions are not written."""
+    dev = _dev(x, route, wq, ws, routing_weights)
+    E, N, K, Kp, S = _mx_wo_moe_check_operands(mode, x, wq, ws, wfmt, T, top_k)
+    out, odt, wdt = _moe_gemm_out(mode, out, torch.bfloat16, S, N, dev, routing_weights, "mx_wo_moe_gemm")
+    with torch.cuda.device(dev):
+        check(lib.inc_mx_wo_moe_gemm(mode, _ptr(x), _ptr(route), _ptr(wq), _ptr(ws), int(wfmt), _ptr(routing_weights), wdt, _ptr(out),
+                                     dtype_code(odt), T, top_k, E, N, K, Kp, _stream()), "inc_mx_wo_moe_gemm")
+    return out
+
+
+def mx_wo_moe_gemm_glu(mode, x, route, wq, ws, wfmt, T, top_k, bias=None, alpha=1.702, limit=7.0, routing_weights=None, out=None):
+    """inc_mx_wo_moe_gemm_glu: mx_wo_moe_gemm with mx_moe_gemm_glu's epilogue -- a per-expert fp32 bias [E, N] (None: no add) in every
+    mode and the clamped SwiGLU of the GPT-OSS experts in mode 0."""
+    dev = _dev(x, route, wq, ws, routing_weights, bias)
+    E, N, K, Kp, S = _mx_wo_moe_check_operands(mode, x, wq, ws, wfmt, T, top_k)
+    assert bias is None or (bias.dtype == torch.float32 and tuple(bias.shape) == (E, N) and bias.is_contiguous())
+    out, odt, wdt = _moe_gemm_out(mode, out, torch.bfloat16, S, N, dev, routing_weights, "mx_wo_moe_gemm_glu")
+    with torch.cuda.device(dev):
+        check(lib.inc_mx_wo_moe_gemm_glu(mode, _ptr(x), _ptr(route), _ptr(wq), _ptr(ws), int(wfmt), _ptr(bias), float(alpha),
+                                         float(limit), _ptr(routing_weights), wdt, _ptr(out), dtype_code(odt), T, top_k, E, N, K, Kp,
+                                         _stream()), "inc_mx_wo_moe_gemm_glu")
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------
 # K17 FP8 per-token / per-channel: e4m3 codes with one fp32 scale per row (include/inc_mi355x.h has the specification)
 # ---------------------------------------------------------------------------------------------------

@@ -1,4 +1,5 @@
-"""The frame of the fused MoE experts modules (MI355XWeightOnlyExperts, FP8Experts, MXExperts, MXGptOssExperts).
+"""The frame of the fused MoE experts modules (MI355XWeightOnlyExperts, FP8Experts, MXExperts, MXGptOssExperts and the weight-only MX
+pair MXWeightOnlyExperts / MXWeightOnlyGptOssExperts).
 
 transformers (5.x) calls an experts module as `forward(hidden_states, top_k_index, top_k_weights)`.  `FusedExperts` holds the one copy
 of that contract -- shapes, the empty batch, the choice between the fused and the dense route, the types the kernels take for the ids
@@ -15,7 +16,7 @@ The frame never asks which subclass it serves.
 
 import torch
 
-MAX_EXPERTS = 512  # of inc_moe_route and the routed GEMMs (inc_woq_moe_gemm, inc_mx_moe_gemm, inc_fp8_moe_gemm)
+MAX_EXPERTS = 512  # of inc_moe_route and the routed GEMMs (inc_woq_moe_gemm, inc_mx_moe_gemm, inc_mx_wo_moe_gemm, inc_fp8_moe_gemm)
 
 
 def is_silu(act_fn):

@@ -11,6 +11,10 @@ with the routing weight (mode 1) -> combine (include/inc_mi355x.h, K16e; DESIGN 
 `MXGptOssExperts` does the same for transformers' `GptOssExperts` (`gate_up_proj [E, H, 2I]` with gate and up interleaved,
 `down_proj [E, I, H]`, two biases, a clamped SwiGLU) through `inc_mx_moe_gemm_glu`, and `from_mxfp4` takes the tensors of an MXFP4
 checkpoint as they are.  The forward contract and the dense route's loop are FusedExperts' (fused_experts.py).
+
+`MXWeightOnlyExperts` / `MXWeightOnlyGptOssExperts` are the two under `MXQuantConfig(weight_only=True, act_dtype="bf16",
+quant_experts=True)`: the same buffers against bf16 activations, four launches (route -> `inc_mx_wo_moe_gemm[_glu]` mode 0 -> mode 1
+-> combine) and no activation quantiser.
 """
 
 import torch
@@ -18,7 +22,7 @@ import torch
 from .... import ops
 from ...utils.utility import half_or_fp16, is_gpt_oss_experts
 from ..fused_experts import MAX_EXPERTS, FusedExperts, is_silu
-from .mx_quant import FORMATS, PAIRS, _code_values
+from .mx_quant import FORMATS, PAIRS, WEIGHT_ONLY_PAIRS, _code_values
 
 
 def _cols(fmt, kp):
@@ -130,8 +134,9 @@ def unsupported_reason(module, cfg):
     """Why MXQuant leaves the fused-experts `module` in float under `cfg` (None = it converts it)."""
     E = module.gate_up_proj.shape[0]
     pair = (cfg.get("w_dtype"), cfg.get("act_dtype"))
-    if pair not in PAIRS:
-        return f"(w_dtype, act_dtype)={pair} is not one of {PAIRS}"
+    pairs = WEIGHT_ONLY_PAIRS if cfg.get("weight_only") else PAIRS
+    if pair not in pairs:
+        return f"(w_dtype, act_dtype)={pair} is not one of {pairs}"
     if is_gpt_oss_experts(module):  # no act_fn: the clamped SwiGLU is the kernel's; there is no dense-only fall-back to keep
         if E > MAX_EXPERTS:
             return f"E={E} must be at most {MAX_EXPERTS}"
@@ -296,3 +301,100 @@ class MXGptOssExperts(MXExperts):
     def extra_repr(self):
         return super().extra_repr() + f", alpha={self.alpha}, limit={self.limit}"
 
+
+
+# ---- the weight-only cell: MX weights, bf16 activations -------------------------------------------------------------------------------
+class _WeightOnlyRoutes:
+    """What MXWeightOnlyExperts and MXWeightOnlyGptOssExperts share: bf16 products whatever the input's type (fp16 and fp32 inputs
+    are cast, FusedExperts.forward casts back: the range of an E8M0 scale does not fit fp16), the K % 8 rule of the routed kernel, and
+    the dense route's product -- inc_mx_wo_gemv / inc_mx_wo_gemm on expert e's slices, K zero-padded to a multiple of 8 as
+    MXWeightOnlyLinear.forward does.  The SiLU / _apply_gate arithmetic around the products is the parent's _expert_mlp."""
+
+    # Measured (scripts/mx_wo_moe_time.py, profiles/mx/mx_wo_moe_time.log; the rule is the script's last line): the fused route is
+    # 6.3 - 85 x faster than this dense route at every measured point of gpt-oss-20b / -120b / Qwen3-30B-A3B, up to 128 rows per expert
+    # (gpt-oss-20b, T = 1024), which is as far as the script goes; above 128 rows per expert it is not measured
+    MOE_MAX_ROWS = 128
+
+    @staticmethod
+    def _check_pair(w_dtype, act_dtype):
+        if (w_dtype, act_dtype) not in WEIGHT_ONLY_PAIRS:
+            raise NotImplementedError(f"MXQuant on MI355X, weight-only: (w_dtype, act_dtype) must be one of {WEIGHT_ONLY_PAIRS}, "
+                                      f"got {(w_dtype, act_dtype)}")
+
+    def _fusable(self):
+        # the routed kernel reads x and h in 16-byte chunks of 8 bf16
+        return super()._fusable() and self.hidden_dim % 8 == 0 and self.intermediate_dim % 8 == 0
+
+    def _compute_dtype(self, x):
+        return torch.bfloat16
+
+    def _bias_of(self, prefix, e):
+        return None
+
+    def _product(self, a, prefix, e, kp, cdt):
+        a = a.to(torch.bfloat16)
+        if a.shape[1] % 8:
+            a = torch.nn.functional.pad(a, (0, 8 - a.shape[1] % 8))
+        product = ops.mx_wo_gemv if a.shape[0] <= ops.MX_GEMV_MAX_M else ops.mx_wo_gemm
+        return product(a.contiguous(), self._buffers[f"{prefix}_qweight"][e], self._buffers[f"{prefix}_w_scale"][e], self.w_fmt,
+                       self._bias_of(prefix, e), torch.bfloat16)
+
+
+class MXWeightOnlyExperts(_WeightOnlyRoutes, MXExperts):
+    """Fused experts with MX weights and bf16 activations: MXExperts' buffers, state-dict keys, from_float and recover; forward is four
+    HIP launches with no host read (inc_moe_route -> inc_mx_wo_moe_gemm(0) -> inc_mx_wo_moe_gemm(1) -> inc_moe_combine), the weights
+    dequantised in registers (csrc/gemm_mx_wo_moe.hip).  hidden_dim or intermediate_dim that is no multiple of 8 takes the dense route."""
+
+    def __init__(self, num_experts, hidden_dim, intermediate_dim, w_dtype="fp4", act_dtype="bf16", act_fn=None, device="cuda",
+                 float_type=torch.float16):
+        self._check_pair(w_dtype, act_dtype)
+        super().__init__(num_experts, hidden_dim, intermediate_dim, w_dtype=w_dtype, act_dtype="fp8_e4m3", act_fn=act_fn, device=device,
+                         float_type=float_type)
+        self.act_dtype, self.act_fmt = "bf16", None
+
+    @classmethod
+    def from_float(cls, module, w_dtype="fp4", act_dtype="bf16", device="cuda"):
+        return super().from_float(module, w_dtype=w_dtype, act_dtype=act_dtype, device=device)
+
+    def _fused_forward(self, x2d, idx, w, cdt):
+        T, k = idx.shape
+        E, wf = self.num_experts, self.w_fmt
+        route = ops.moe_route(idx, E)
+        h = ops.mx_wo_moe_gemm(0, x2d.to(torch.bfloat16), route, self.gate_up_qweight, self.gate_up_w_scale, wf, T, k)
+        y = ops.mx_wo_moe_gemm(1, h, route, self.down_qweight, self.down_w_scale, wf, T, k, routing_weights=w)
+        return ops.moe_combine(y, route, T, k, E, cdt)
+
+
+class MXWeightOnlyGptOssExperts(_WeightOnlyRoutes, MXGptOssExperts):
+    """transformers' GptOssExperts with MX weights and bf16 activations -- how openai/gpt-oss-* is served: MXGptOssExperts' buffers,
+    state-dict keys, from_float, from_mxfp4 (the checkpoint's MXFP4 tensors byte for byte; there is no act_dtype to choose) and
+    recover; forward is four launches through inc_mx_wo_moe_gemm_glu, and nothing quantises an activation."""
+
+    def __init__(self, num_experts, hidden_dim, intermediate_dim, w_dtype="fp4", act_dtype="bf16", alpha=1.702, limit=7.0,
+                 device="cuda", float_type=torch.float16):
+        self._check_pair(w_dtype, act_dtype)
+        super().__init__(num_experts, hidden_dim, intermediate_dim, w_dtype=w_dtype, act_dtype="fp8_e4m3", alpha=alpha, limit=limit,
+                         device=device, float_type=float_type)
+        self.act_dtype, self.act_fmt = "bf16", None
+
+    @classmethod
+    def from_float(cls, module, w_dtype="fp4", act_dtype="bf16", device="cuda"):
+        return super().from_float(module, w_dtype=w_dtype, act_dtype=act_dtype, device=device)
+
+    @classmethod
+    def from_mxfp4(cls, gate_up_blocks, gate_up_scales, gate_up_bias, down_blocks, down_scales, down_bias, alpha=1.702, limit=7.0,
+                   device="cuda", float_type=torch.bfloat16):
+        return super().from_mxfp4(gate_up_blocks, gate_up_scales, gate_up_bias, down_blocks, down_scales, down_bias, act_dtype="bf16",
+                                  alpha=alpha, limit=limit, device=device, float_type=float_type)
+
+    def _bias_of(self, prefix, e):
+        return self._buffers[f"{prefix}_bias"][e].to(torch.bfloat16)
+
+    def _fused_forward(self, x2d, idx, w, cdt):
+        T, k = idx.shape
+        E, wf = self.num_experts, self.w_fmt
+        route = ops.moe_route(idx, E)
+        h = ops.mx_wo_moe_gemm_glu(0, x2d.to(torch.bfloat16), route, self.gate_up_qweight, self.gate_up_w_scale, wf, T, k,
+                                   bias=self.gate_up_bias, alpha=self.alpha, limit=self.limit)
+        y = ops.mx_wo_moe_gemm_glu(1, h, route, self.down_qweight, self.down_w_scale, wf, T, k, bias=self.down_bias, routing_weights=w)
+        return ops.moe_combine(y, route, T, k, E, cdt)

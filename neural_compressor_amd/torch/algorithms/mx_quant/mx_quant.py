@@ -178,7 +178,8 @@ class MXQuantizer(Quantizer):
     Besides nn.Linear the names may be fused MoE experts modules (is_fused_experts; they are in the mapping under
     MXQuantConfig(quant_experts=True)), which become MXExperts, and GPT-OSS experts modules (is_gpt_oss_experts), which become
     MXGptOssExperts when their dict carries "gpt_oss_experts": True (mx_quant_entry sets it under quant_experts=True; without the key
-    such a module stays float)."""
+    such a module stays float).  A dict with "weight_only" picks the weight-only class of each kind (MXWeightOnlyLinear,
+    MXWeightOnlyExperts, MXWeightOnlyGptOssExperts)."""
 
     def _selected(self, model):
         from .experts import unsupported_reason
@@ -203,7 +204,7 @@ class MXQuantizer(Quantizer):
 
     @torch.no_grad()
     def convert(self, model, *args, **kwargs):
-        from .experts import MXExperts, MXGptOssExperts
+        from .experts import MXExperts, MXGptOssExperts, MXWeightOnlyExperts, MXWeightOnlyGptOssExperts
 
         dev = torch.device("cuda", torch.cuda.current_device())
         model.to(dev)
@@ -216,6 +217,8 @@ class MXQuantizer(Quantizer):
             mod = get_module(model, name)
             if isinstance(mod, torch.nn.Linear):
                 cls = MXWeightOnlyLinear if cfg.get("weight_only") else MXLinear
+            elif cfg.get("weight_only"):
+                cls = MXWeightOnlyGptOssExperts if is_gpt_oss_experts(mod) else MXWeightOnlyExperts
             else:
                 cls = MXGptOssExperts if is_gpt_oss_experts(mod) else MXExperts
             set_module(model, name, cls.from_float(mod, cfg["w_dtype"], cfg["act_dtype"], device=dev))

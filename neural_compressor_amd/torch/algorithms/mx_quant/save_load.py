@@ -4,7 +4,9 @@
                          MXWeightOnlyLinear),
                          "mx_experts": {name: [w_dtype, act_dtype, E, H, I]},
                          "mx_gpt_oss_experts": {name: [w_dtype, act_dtype, E, H, I, alpha, limit]}}
-MXExperts modules save their four uint8 buffers under their own names, MXGptOssExperts modules those and their two fp32 biases.  The
+An experts entry whose act_dtype is "bf16" is the weight-only class of its kind (MXWeightOnlyExperts / MXWeightOnlyGptOssExperts: the
+same buffers).  MXExperts modules save their four uint8 buffers under their own names, MXGptOssExperts modules those and their two
+fp32 biases.  The
 "mx_experts" / "mx_gpt_oss_experts" keys are written only when the model has such modules; a directory without them (a model without
 them, or one written before the modules existed) loads as before.
 """
@@ -15,7 +17,7 @@ import os
 import torch
 
 from ...utils.utility import _take, _take_experts, get_module, half_or_fp16, is_fused_experts, is_gpt_oss_experts, set_module
-from .experts import MXExperts, MXGptOssExperts
+from .experts import MXExperts, MXGptOssExperts, MXWeightOnlyExperts, MXWeightOnlyGptOssExperts
 from .mx_quant import MXLinear, MXWeightOnlyLinear
 
 WEIGHT_NAME = "quantized_weight.pt"
@@ -63,12 +65,14 @@ def load(output_dir, original_model, device="cuda"):
         set_module(original_model, name, new)
     for name, (w_dtype, act_dtype, E, H, I) in cfg.get("mx_experts", {}).items():
         _take_experts(state, original_model, name, dev, is_fused_experts,
-                      lambda old: MXExperts(E, H, I, w_dtype=w_dtype, act_dtype=act_dtype, act_fn=old.act_fn, device=dev,
-                                            float_type=half_or_fp16(old.gate_up_proj.dtype)))
+                      lambda old: (MXWeightOnlyExperts if act_dtype == "bf16" else MXExperts)(
+                          E, H, I, w_dtype=w_dtype, act_dtype=act_dtype, act_fn=old.act_fn, device=dev,
+                          float_type=half_or_fp16(old.gate_up_proj.dtype)))
     for name, (w_dtype, act_dtype, E, H, I, alpha, limit) in cfg.get("mx_gpt_oss_experts", {}).items():
         _take_experts(state, original_model, name, dev, is_gpt_oss_experts,
-                      lambda old: MXGptOssExperts(E, H, I, w_dtype=w_dtype, act_dtype=act_dtype, alpha=alpha, limit=limit, device=dev,
-                                                  float_type=half_or_fp16(old.gate_up_proj.dtype)))
+                      lambda old: (MXWeightOnlyGptOssExperts if act_dtype == "bf16" else MXGptOssExperts)(
+                          E, H, I, w_dtype=w_dtype, act_dtype=act_dtype, alpha=alpha, limit=limit, device=dev,
+                          float_type=half_or_fp16(old.gate_up_proj.dtype)))
     original_model.load_state_dict(state, strict=False, assign=True)
     original_model.to(dev)
     original_model.eval()

@@ -307,7 +307,8 @@ class MXQuantConfig(TorchBaseConfig):
     so the defaults here are `w_dtype="fp8_e4m3", act_dtype="fp8_e4m3"` -- a deliberate deviation.  Supported (w_dtype, act_dtype):
     ("fp8_e4m3", "fp8_e4m3"), ("fp4", "fp8_e4m3"), ("fp4", "fp4"), "fp4" being e2m1; `blocksize=32`, `round_method="nearest"`,
     `weight_only=False`; `weight_only=True` selects the weight-only cell and takes `act_dtype="bf16"` with `w_dtype` "fp4" or
-    "fp8_e4m3" (MXWeightOnlyLinear: MX weights against bf16 activations; experts modules stay float under it); `out_dtype` is accepted and unused (the output has the activation's type).  `w_dtype="fp32"` (through
+    "fp8_e4m3" (MXWeightOnlyLinear: MX weights against bf16 activations; with `quant_experts=True` the experts modules become
+    MXWeightOnlyExperts / MXWeightOnlyGptOssExperts, without it they stay float); `out_dtype` is accepted and unused (the output has the activation's type).  `w_dtype="fp32"` (through
     `set_local`) leaves a layer float; lm_head stays float unless `quant_lm_head=True`.  `quant_experts=True` (an extension of the
     reference's fields; off by default) also converts the fused MoE experts modules (is_fused_experts) to MXExperts."""
 
