@@ -9,49 +9,38 @@ v_mfma_f32_32x32x64_f8f6f4 and promotes every K-tile's sum with `xs[m, kt] * ws[
 include/inc_mi355x.h.  The fused MoE experts of such checkpoints are FP8BlockExperts (block_experts.py), reached
 through `convert_block_experts`, not yet through FP8Config.  Not built: group launches and the gated pair (`fp8_linear_group` /
 `fp8_gated_pair` see a module that is not an FP8Linear and run the plain forwards), static scales, UE8M0 scales.
+The forward contract, `_decodes` and `from_float` are QuantLinear's (quant_linear.py).
 """
 
 import torch
 
 from .... import ops
-from ...utils.utility import half_or_fp16
+from ..quant_linear import QuantLinear, e4m3_table
 
 BLOCK = ops.FP8_BLOCK
 
 
-class FP8BlockLinear(torch.nn.Module):
+class FP8BlockLinear(QuantLinear):
     """Buffers: qweight uint8 [N, Kp], w_scale fp32 [ceil(N/128), Kp/128], bias.  Kp = in_features rounded up to 128; the padding
     columns are zero codes.  forward = inc_fp8_quant_groups(x) -> inc_fp8_block_gemv up to DECODE_MAX_M rows (while DECODE_GEMV is on),
     inc_fp8_block_gemm above; nothing is read back to the host."""
 
     # as FP8Linear's switch.  Times of both routes: profiles/fp8/fp8_block_time.log, DESIGN section 8c
     DECODE_GEMV = True
-    DECODE_MAX_M = ops.FP8_GEMV_MAX_M
+    DECODE_MAX_M, GEMV_LIMIT = ops.FP8_GEMV_MAX_M, "FP8_GEMV_MAX_M"
 
     def __init__(self, in_features, out_features, bias=False, device="cuda", float_type=torch.float16):
-        super().__init__()
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError(f"FP8BlockLinear needs a HIP device ('cuda[:N]'), got '{device}'. There is no CPU implementation.")
-        self.in_features, self.out_features = in_features, out_features
-        self.kp = ops.mx_padded_k(in_features)
-        self.float_type = float_type
+        dev = self._hip_device(device)
+        super().__init__(in_features, out_features, float_type)
         blocks = ((out_features + BLOCK - 1) // BLOCK, self.kp // BLOCK)
         self.register_buffer("qweight", torch.zeros((out_features, self.kp), dtype=torch.uint8, device=dev))
         self.register_buffer("w_scale", torch.zeros(blocks, dtype=torch.float32, device=dev))
-        self.register_buffer("bias", torch.zeros(out_features, dtype=float_type, device=dev) if bias else None)
+        self._register_bias(bias, dev)
 
-    @classmethod
-    @torch.no_grad()
-    def from_float(cls, linear, device="cuda"):
-        ft = half_or_fp16(linear.weight.dtype)
-        new = cls(linear.in_features, linear.out_features, bias=linear.bias is not None, device=device, float_type=ft)
-        codes, scale = ops.fp8_quant_blocks(linear.weight.detach().to(new.qweight.device), new.kp)
-        new.qweight.copy_(codes)
-        new.w_scale.copy_(scale)
-        if linear.bias is not None:
-            new.bias.copy_(linear.bias.detach().to(ft))
-        return new
+    def _quantize_weight(self, w):
+        codes, scale = ops.fp8_quant_blocks(w, self.kp)
+        self.qweight.copy_(codes)
+        self.w_scale.copy_(scale)
 
     @classmethod
     @torch.no_grad()
@@ -72,28 +61,15 @@ class FP8BlockLinear(torch.nn.Module):
             new.bias.copy_(bias.detach().to(float_type))
         return new
 
-    def forward(self, input):
-        x = input
-        lead = x.shape[:-1]
-        x2d = x.reshape(-1, self.in_features)
-        out_dtype = x.dtype if x.dtype in (torch.float16, torch.bfloat16) else self.float_type
-        if x2d.shape[0] == 0:
-            return torch.empty((*lead, self.out_features), dtype=torch.float32 if x.dtype == torch.float32 else out_dtype, device=x.device)
+    def _product(self, x2d, out_dtype):
         xq, xs = ops.fp8_quant_groups(x2d, self.kp)
         product = ops.fp8_block_gemv if self._decodes(x2d.shape[0]) else ops.fp8_block_gemm
-        y = product(xq, xs, self.qweight, self.w_scale, self.bias, out_dtype)
-        if x.dtype == torch.float32:  # an fp32 model keeps seeing fp32 activations (the kernel's epilogue emits 16-bit)
-            y = y.float()
-        return y.reshape(*lead, self.out_features)
-
-    def _decodes(self, rows):
-        return self.DECODE_GEMV and rows <= min(self.DECODE_MAX_M, ops.FP8_GEMV_MAX_M)
+        return product(xq, xs, self.qweight, self.w_scale, self.bias, out_dtype)
 
     def recover(self, dtype=None):
         """Dequantised weight [N, K]: the code table times the block's scale (one fp32 multiply per element), in `dtype` or float_type."""
-        table = torch.arange(256, dtype=torch.uint8).view(torch.float8_e4m3fn).float().to(self.qweight.device)
         scale = self.w_scale.repeat_interleave(BLOCK, 0)[: self.out_features].repeat_interleave(BLOCK, 1)
-        w = table[self.qweight.long()] * scale
+        w = e4m3_table(self.qweight.device)[self.qweight.long()] * scale
         return w[:, : self.in_features].to(self.float_type if dtype is None else dtype)
 
     def extra_repr(self):

@@ -19,6 +19,7 @@ import torch
 from .... import ops
 from ....common.utils import logger
 from ...utils.utility import half_or_fp16, is_fused_experts, set_module
+from ..quant_linear import e4m3_table
 from .experts import _FP8ExpertsBase, experts_unsupported_reason
 
 BLOCK = ops.FP8_BLOCK
@@ -105,7 +106,7 @@ class FP8BlockExperts(_FP8ExpertsBase):
         dtype = self.float_type if dtype is None else dtype
         sel = slice(None) if expert is None else slice(int(expert), int(expert) + 1)
         I, H = self.intermediate_dim, self.hidden_dim
-        table = torch.arange(256, dtype=torch.uint8).view(torch.float8_e4m3fn).float().to(self.gate_up_qweight.device)
+        table = e4m3_table(self.gate_up_qweight.device)
         gs = self.gate_up_w_scale[sel].repeat_interleave(BLOCK, 2)[:, :, :I].reshape(-1, 2 * I, self.kp_h // BLOCK)
         ds = self.down_w_scale[sel].repeat_interleave(BLOCK, 1)[:, :H]
         out = []

@@ -15,6 +15,7 @@ import torch
 from .... import ops
 from ...utils.utility import half_or_fp16
 from ..fused_experts import MAX_EXPERTS, FusedExperts, is_silu
+from ..quant_linear import e4m3_table
 
 
 class _FP8ExpertsBase(FusedExperts):
@@ -98,8 +99,7 @@ class FP8Experts(_FP8ExpertsBase):
         out = []
         for prefix, K in (("gate_up", self.hidden_dim), ("down", self.intermediate_dim)):
             q, s = self._buffers[f"{prefix}_qweight"][sel], self._buffers[f"{prefix}_w_scale"][sel]
-            table = torch.arange(256, dtype=torch.uint8).view(torch.float8_e4m3fn).float().to(q.device)
-            w = (table[q.long()] * s[..., None])[..., :K].to(dtype)
+            w = (e4m3_table(q.device)[q.long()] * s[..., None])[..., :K].to(dtype)
             out.append(w if expert is None else w[0])
         return tuple(out)
 

@@ -5,22 +5,16 @@
 "fp8_modules" lists FP8Linear and FP8BlockLinear alike; load tells them apart by the rank of `w_scale` ([N] against
 [ceil(N/128), Kp/128]), so one model may hold both.  FP8Experts modules save their four buffers under their own names.  The "fp8_experts" key is written only when the model has such
 modules; a directory without it (a model without them, or one written before FP8Experts existed) loads as before.  The same holds for
-FP8BlockExperts modules and the "fp8_block_experts" key.
+FP8BlockExperts modules and the "fp8_block_experts" key.  The file handling and the per-Linear rebuild are utils/utility.py's
+(save_quantized, open_saved, take_linear, finish_load), shared with the other two.
 """
 
-import json
-import os
-
-import torch
-
-from ...utils.utility import _take, _take_experts, get_module, half_or_fp16, is_fused_experts, set_module
+from ...utils.utility import QCONFIG_NAME, WEIGHT_NAME  # noqa: F401  (this module's names for the two files)
+from ...utils.utility import _take_experts, finish_load, half_or_fp16, is_fused_experts, open_saved, save_quantized, take_linear
 from .block import FP8BlockLinear
 from .block_experts import FP8BlockExperts
 from .experts import FP8Experts
 from .fp8_quant import FP8Linear
-
-WEIGHT_NAME = "quantized_weight.pt"
-QCONFIG_NAME = "qconfig.json"
 
 
 def qconfig_of(model):
@@ -37,34 +31,19 @@ def qconfig_of(model):
 
 
 def save(model, output_dir="./saved_results"):
-    os.makedirs(output_dir, exist_ok=True)
-    if torch.cuda.is_available():
-        torch.cuda.synchronize()
-    with open(os.path.join(output_dir, QCONFIG_NAME), "w") as f:
-        json.dump(qconfig_of(model), f, indent=2)
-    torch.save({k: v.detach().cpu() for k, v in model.state_dict().items()}, os.path.join(output_dir, WEIGHT_NAME))
+    save_quantized(model, output_dir, qconfig_of(model))
 
 
 def load(output_dir, original_model, device="cuda"):
     """Rebuild the FP8 model from the float architecture `original_model` (weights may be on any device, "meta" included)."""
-    with open(os.path.join(output_dir, QCONFIG_NAME)) as f:
-        cfg = json.load(f)
-    state = torch.load(os.path.join(output_dir, WEIGHT_NAME), map_location="cpu", weights_only=True)
-    dev = torch.device(device)
+    cfg, state, dev = open_saved(output_dir, device)
     for name in cfg["fp8_modules"]:
-        lin = get_module(original_model, name)
-        assert isinstance(lin, torch.nn.Linear), f"{name}: expected nn.Linear in the float architecture, got {type(lin).__name__}"
-        ft = state[name + ".bias"].dtype if (name + ".bias") in state else half_or_fp16(lin.weight.dtype)
         cls = FP8BlockLinear if state[name + ".w_scale"].dim() == 2 else FP8Linear  # [ceil(N/128), Kp/128] against [N]
-        new = cls(lin.in_features, lin.out_features, bias=(name + ".bias") in state, device=dev, float_type=ft)
-        _take(state, name, new, dev)
-        set_module(original_model, name, new)
+        take_linear(state, original_model, name, dev, cls)
     for key, cls in (("fp8_experts", FP8Experts), ("fp8_block_experts", FP8BlockExperts)):
         for name, (E, H, I) in cfg.get(key, {}).items():
             _take_experts(state, original_model, name, dev, is_fused_experts,
                           lambda old: cls(E, H, I, act_fn=old.act_fn, device=dev, float_type=half_or_fp16(old.gate_up_proj.dtype)))
-    original_model.load_state_dict(state, strict=False, assign=True)
-    original_model.to(dev)
-    original_model.eval()
+    finish_load(original_model, state, dev)
     original_model.fp8_info = cfg.get("fp8_quant", {})
     return original_model

@@ -22,7 +22,7 @@ import torch
 from .... import ops
 from ...utils.utility import half_or_fp16, is_gpt_oss_experts
 from ..fused_experts import MAX_EXPERTS, FusedExperts, is_silu
-from .mx_quant import FORMATS, PAIRS, WEIGHT_ONLY_PAIRS, _code_values
+from .mx_quant import FORMATS, PAIRS, WEIGHT_ONLY_PAIRS, _code_values, check_pair, mx_wo_product
 
 
 def _cols(fmt, kp):
@@ -41,18 +41,18 @@ class MXExperts(FusedExperts):
     # (E 8, k 2) fused 1.15 - 1.36 x faster than dense at T = 1024 (256 rows per expert), dense 2.1 - 2.5 x faster at T = 4096 (1024);
     # Qwen3-MoE (E 128, k 8) fused 10.8 - 13.8 x faster at T = 4096 (256 per expert)
     MOE_MAX_ROWS = 256
+    PAIRS, CELL = PAIRS, ""  # the (w_dtype, act_dtype) this class takes, and what check_pair's message calls the cell
 
     def __init__(self, num_experts, hidden_dim, intermediate_dim, w_dtype="fp8_e4m3", act_dtype="fp8_e4m3", act_fn=None, device="cuda",
                  float_type=torch.float16):
         dev = torch.device(device)
         if dev.type != "cuda":
             raise RuntimeError(f"MXExperts needs a HIP device ('cuda[:N]'), got '{device}'. There is no CPU implementation.")
-        if (w_dtype, act_dtype) not in PAIRS:
-            raise NotImplementedError(f"MXQuant on MI355X: (w_dtype, act_dtype) must be one of {PAIRS}, got {(w_dtype, act_dtype)}")
+        check_pair(self, w_dtype, act_dtype)
         super().__init__(num_experts, hidden_dim, intermediate_dim, act_fn)
         E, H, I = num_experts, hidden_dim, intermediate_dim
         self.w_dtype, self.act_dtype = w_dtype, act_dtype
-        self.w_fmt, self.act_fmt = FORMATS[w_dtype], FORMATS[act_dtype]
+        self.w_fmt, self.act_fmt = FORMATS[w_dtype], FORMATS.get(act_dtype)  # no format for "bf16": nothing quantises the activation
         self.kp_h, self.kp_i = ops.mx_padded_k(H), ops.mx_padded_k(I)
         self.float_type = float_type
         for prefix, N, kp in (("gate_up", 2 * I, self.kp_h), ("down", H, self.kp_i)):
@@ -115,11 +115,14 @@ class MXExperts(FusedExperts):
         y = ops.mx_moe_gemm(1, hq, hs, af, route, self.down_qweight, self.down_w_scale, wf, T, k, routing_weights=w)
         return ops.moe_combine(y, route, T, k, E, cdt)
 
+    def _bias_of(self, prefix, e, cdt):
+        return None
+
     def _product(self, a, prefix, e, kp, cdt):
         aq, as_ = ops.mx_quant(a, self.act_fmt, kp)
         product = ops.mx_gemv if a.shape[0] <= ops.MX_GEMV_MAX_M else ops.mx_gemm
         return product(aq, as_, self.act_fmt, self._buffers[f"{prefix}_qweight"][e], self._buffers[f"{prefix}_w_scale"][e], self.w_fmt,
-                       None, cdt)
+                       self._bias_of(prefix, e, cdt), cdt)
 
     def _expert_mlp(self, rows, e, cdt):
         gate, up = self._product(rows, "gate_up", e, self.kp_h, cdt).chunk(2, dim=-1)
@@ -283,11 +286,8 @@ class MXGptOssExperts(MXExperts):
                                 routing_weights=w)
         return ops.moe_combine(y, route, T, k, E, cdt)
 
-    def _product(self, a, prefix, e, kp, cdt):
-        aq, as_ = ops.mx_quant(a, self.act_fmt, kp)
-        product = ops.mx_gemv if a.shape[0] <= ops.MX_GEMV_MAX_M else ops.mx_gemm
-        return product(aq, as_, self.act_fmt, self._buffers[f"{prefix}_qweight"][e], self._buffers[f"{prefix}_w_scale"][e], self.w_fmt,
-                       self._buffers[f"{prefix}_bias"][e].to(cdt), cdt)
+    def _bias_of(self, prefix, e, cdt):
+        return self._buffers[f"{prefix}_bias"][e].to(cdt)
 
     def _expert_mlp(self, rows, e, cdt):
         """GptOssExperts.forward's MLP with MXLinear's products (and their bias add) on expert e's slices, and _apply_gate's
@@ -314,12 +314,7 @@ class _WeightOnlyRoutes:
     # 6.3 - 85 x faster than this dense route at every measured point of gpt-oss-20b / -120b / Qwen3-30B-A3B, up to 128 rows per expert
     # (gpt-oss-20b, T = 1024), which is as far as the script goes; above 128 rows per expert it is not measured
     MOE_MAX_ROWS = 128
-
-    @staticmethod
-    def _check_pair(w_dtype, act_dtype):
-        if (w_dtype, act_dtype) not in WEIGHT_ONLY_PAIRS:
-            raise NotImplementedError(f"MXQuant on MI355X, weight-only: (w_dtype, act_dtype) must be one of {WEIGHT_ONLY_PAIRS}, "
-                                      f"got {(w_dtype, act_dtype)}")
+    PAIRS, CELL = WEIGHT_ONLY_PAIRS, ", weight-only"
 
     def _fusable(self):
         # the routed kernel reads x and h in 16-byte chunks of 8 bf16
@@ -328,16 +323,9 @@ class _WeightOnlyRoutes:
     def _compute_dtype(self, x):
         return torch.bfloat16
 
-    def _bias_of(self, prefix, e):
-        return None
-
-    def _product(self, a, prefix, e, kp, cdt):
-        a = a.to(torch.bfloat16)
-        if a.shape[1] % 8:
-            a = torch.nn.functional.pad(a, (0, 8 - a.shape[1] % 8))
-        product = ops.mx_wo_gemv if a.shape[0] <= ops.MX_GEMV_MAX_M else ops.mx_wo_gemm
-        return product(a.contiguous(), self._buffers[f"{prefix}_qweight"][e], self._buffers[f"{prefix}_w_scale"][e], self.w_fmt,
-                       self._bias_of(prefix, e), torch.bfloat16)
+    def _product(self, a, prefix, e, kp, cdt):  # MXWeightOnlyLinear's chain, the bias (the GPT-OSS class's) in bf16
+        return mx_wo_product(a, a.shape[0] <= ops.MX_GEMV_MAX_M, self._buffers[f"{prefix}_qweight"][e],
+                             self._buffers[f"{prefix}_w_scale"][e], self.w_fmt, self._bias_of(prefix, e, torch.bfloat16), torch.bfloat16)
 
 
 class MXWeightOnlyExperts(_WeightOnlyRoutes, MXExperts):
@@ -347,10 +335,8 @@ class MXWeightOnlyExperts(_WeightOnlyRoutes, MXExperts):
 
     def __init__(self, num_experts, hidden_dim, intermediate_dim, w_dtype="fp4", act_dtype="bf16", act_fn=None, device="cuda",
                  float_type=torch.float16):
-        self._check_pair(w_dtype, act_dtype)
-        super().__init__(num_experts, hidden_dim, intermediate_dim, w_dtype=w_dtype, act_dtype="fp8_e4m3", act_fn=act_fn, device=device,
+        super().__init__(num_experts, hidden_dim, intermediate_dim, w_dtype=w_dtype, act_dtype=act_dtype, act_fn=act_fn, device=device,
                          float_type=float_type)
-        self.act_dtype, self.act_fmt = "bf16", None
 
     @classmethod
     def from_float(cls, module, w_dtype="fp4", act_dtype="bf16", device="cuda"):
@@ -372,10 +358,8 @@ class MXWeightOnlyGptOssExperts(_WeightOnlyRoutes, MXGptOssExperts):
 
     def __init__(self, num_experts, hidden_dim, intermediate_dim, w_dtype="fp4", act_dtype="bf16", alpha=1.702, limit=7.0,
                  device="cuda", float_type=torch.float16):
-        self._check_pair(w_dtype, act_dtype)
-        super().__init__(num_experts, hidden_dim, intermediate_dim, w_dtype=w_dtype, act_dtype="fp8_e4m3", alpha=alpha, limit=limit,
+        super().__init__(num_experts, hidden_dim, intermediate_dim, w_dtype=w_dtype, act_dtype=act_dtype, alpha=alpha, limit=limit,
                          device=device, float_type=float_type)
-        self.act_dtype, self.act_fmt = "bf16", None
 
     @classmethod
     def from_float(cls, module, w_dtype="fp4", act_dtype="bf16", device="cuda"):
@@ -386,9 +370,6 @@ class MXWeightOnlyGptOssExperts(_WeightOnlyRoutes, MXGptOssExperts):
                    device="cuda", float_type=torch.bfloat16):
         return super().from_mxfp4(gate_up_blocks, gate_up_scales, gate_up_bias, down_blocks, down_scales, down_bias, act_dtype="bf16",
                                   alpha=alpha, limit=limit, device=device, float_type=float_type)
-
-    def _bias_of(self, prefix, e):
-        return self._buffers[f"{prefix}_bias"][e].to(torch.bfloat16)
 
     def _fused_forward(self, x2d, idx, w, cdt):
         T, k = idx.shape

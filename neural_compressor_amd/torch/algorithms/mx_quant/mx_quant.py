@@ -7,30 +7,49 @@ executes: the weight is quantised once to e4m3 / e2m1 codes with one E8M0 scale 
 v_mfma_scale_f32_32x32x64_f8f6f4, which applies both block scales inside the matrix pipe; a decode-sized batch (up to 16 rows) takes
 `inc_mx_gemv` on the 16x16x128 form of the instruction, and `mx_linear_group` sends modules that share an activation out in one
 launch.  The specification in bits is the comment of the entry points in include/inc_mi355x.h.  The algorithm
-is data-free: `prepare` returns the model unchanged and `convert` swaps every selected nn.Linear.
+is data-free: `prepare` returns the model unchanged and `convert` swaps every selected nn.Linear.  The forward contract, `_decodes`
+and `from_float` are QuantLinear's, the group body is `linear_group` and the quantizer's `_selected` / `convert` are
+DataFreeQuantizer's (quant_linear.py); every class names the (w_dtype, act_dtype) it takes in its own `PAIRS`.
 """
 
 import torch
 
 from .... import ops
-from ....common.utils import logger
-from ...utils.utility import get_module, half_or_fp16, is_fused_experts, is_gpt_oss_experts, linear_group_plan, set_module
-from ..base_algorithm import Quantizer
+from ...utils.utility import is_fused_experts, is_gpt_oss_experts
+from ..quant_linear import DataFreeQuantizer, QuantLinear, e4m3_table, linear_group
 
 FORMATS = {"fp8_e4m3": ops.MX_FP8_E4M3, "fp4": ops.MX_FP4_E2M1}
 PAIRS = (("fp8_e4m3", "fp8_e4m3"), ("fp4", "fp8_e4m3"), ("fp4", "fp4"))  # (w_dtype, act_dtype) the GEMM takes
 WEIGHT_ONLY_PAIRS = (("fp4", "bf16"), ("fp8_e4m3", "bf16"))  # the weight-only cell: MX weights, bf16 activations
 
 
+def check_pair(owner, w_dtype, act_dtype):
+    """The one refusal of a (w_dtype, act_dtype) outside the table of `owner`: a class (or a module of it) that names the pairs it takes
+    as PAIRS and, beside them, the CELL its message carries (MXLinear, MXWeightOnlyLinear, MXExperts, ...)."""
+    if (w_dtype, act_dtype) not in owner.PAIRS:
+        raise NotImplementedError(f"MXQuant on MI355X{owner.CELL}: (w_dtype, act_dtype) must be one of {owner.PAIRS}, "
+                                  f"got {(w_dtype, act_dtype)}")
+
+
 def _code_values(fmt):
     """The value of every code: 256 entries for e4m3 (OCP e4m3fn; 0x7f / 0xff are NaN and never stored), 16 for e2m1."""
     if fmt == ops.MX_FP8_E4M3:
-        return torch.arange(256, dtype=torch.uint8).view(torch.float8_e4m3fn).float()
+        return e4m3_table()
     half = torch.tensor([0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0])
     return torch.cat([half, -half])
 
 
-class MXLinear(torch.nn.Module):
+def mx_wo_product(a, decode, qweight, w_scale, w_fmt, bias, out_dtype):
+    """The weight-only cell's chain on rows a [M, K]: the cast to bf16, K zero-padded to a multiple of 8, then inc_mx_wo_gemv if
+    `decode` else inc_mx_wo_gemm.  MXWeightOnlyLinear's forward and the dense routes of the two weight-only experts classes."""
+    a = a.to(torch.bfloat16)
+    if a.shape[1] % 8:
+        a = torch.nn.functional.pad(a, (0, 8 - a.shape[1] % 8))
+    product = ops.mx_wo_gemv if decode else ops.mx_wo_gemm
+    return product(a.contiguous(), qweight, w_scale, w_fmt, bias, out_dtype)
+
+
+class MXLinear(QuantLinear):
     """nn.Linear with MX weights and MX activations.  Buffers: qweight uint8 [N, Kp] (fp8) or [N, Kp/2] (fp4, element 2i in the low
     nibble), w_scale uint8 [N, Kp/32] (E8M0 bytes), bias.  Kp = in_features rounded up to 128; the padding columns are zero codes.
     forward = inc_mx_quant(x) -> inc_mx_gemv up to DECODE_MAX_M rows (while DECODE_GEMV is on), inc_mx_gemm above; nothing is read
@@ -39,56 +58,48 @@ class MXLinear(torch.nn.Module):
     # True = up to DECODE_MAX_M rows go through the decode GEMV (inc_mx_gemv: one workgroup per 16 weight rows, K split over its waves);
     # False = every batch takes the 256 x 256 tile kernel.  Times of both: profiles/mx/mx_gemv_time.log, DESIGN section 8b.
     DECODE_GEMV = True
-    DECODE_MAX_M = ops.MX_GEMV_MAX_M
+    DECODE_MAX_M, GEMV_LIMIT = ops.MX_GEMV_MAX_M, "MX_GEMV_MAX_M"
+    PAIRS, CELL = PAIRS, ""  # the (w_dtype, act_dtype) this class takes, and what check_pair's message calls the cell
 
     def __init__(self, in_features, out_features, bias=False, w_dtype="fp8_e4m3", act_dtype="fp8_e4m3", device="cuda",
                  float_type=torch.float16):
-        super().__init__()
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError(f"MXLinear needs a HIP device ('cuda[:N]'), got '{device}'. There is no CPU implementation.")
-        if (w_dtype, act_dtype) not in PAIRS:
-            raise NotImplementedError(f"MXQuant on MI355X: (w_dtype, act_dtype) must be one of {PAIRS}, got {(w_dtype, act_dtype)}")
-        self.in_features, self.out_features = in_features, out_features
+        dev = self._hip_device(device)
+        check_pair(self, w_dtype, act_dtype)
+        super().__init__(in_features, out_features, float_type)
         self.w_dtype, self.act_dtype = w_dtype, act_dtype
-        self.w_fmt, self.act_fmt = FORMATS[w_dtype], FORMATS[act_dtype]
-        self.kp = ops.mx_padded_k(in_features)
-        self.float_type = float_type
+        self.w_fmt, self.act_fmt = FORMATS[w_dtype], FORMATS.get(act_dtype)  # no format for "bf16": nothing quantises the activation
         cols = self.kp if self.w_fmt == ops.MX_FP8_E4M3 else self.kp // 2
         self.register_buffer("qweight", torch.zeros((out_features, cols), dtype=torch.uint8, device=dev))
         self.register_buffer("w_scale", torch.zeros((out_features, self.kp // 32), dtype=torch.uint8, device=dev))
-        self.register_buffer("bias", torch.zeros(out_features, dtype=float_type, device=dev) if bias else None)
+        self._register_bias(bias, dev)
 
     @classmethod
-    @torch.no_grad()
     def from_float(cls, linear, w_dtype="fp8_e4m3", act_dtype="fp8_e4m3", device="cuda"):
-        ft = half_or_fp16(linear.weight.dtype)
-        new = cls(linear.in_features, linear.out_features, bias=linear.bias is not None, w_dtype=w_dtype, act_dtype=act_dtype,
-                  device=device, float_type=ft)
-        dev = new.qweight.device
-        codes, scales = ops.mx_quant(linear.weight.detach().to(dev), new.w_fmt, new.kp)
-        new.qweight.copy_(codes)
-        new.w_scale.copy_(scales)
-        if linear.bias is not None:
-            new.bias.copy_(linear.bias.detach().to(ft))
-        return new
+        return super().from_float(linear, device=device, w_dtype=w_dtype, act_dtype=act_dtype)
 
-    def forward(self, input):
-        x = input
-        lead = x.shape[:-1]
-        x2d = x.reshape(-1, self.in_features)
-        out_dtype = x.dtype if x.dtype in (torch.float16, torch.bfloat16) else self.float_type
-        if x2d.shape[0] == 0:
-            return torch.empty((*lead, self.out_features), dtype=torch.float32 if x.dtype == torch.float32 else out_dtype, device=x.device)
+    def _quantize_weight(self, w):
+        codes, scales = ops.mx_quant(w, self.w_fmt, self.kp)
+        self.qweight.copy_(codes)
+        self.w_scale.copy_(scales)
+
+    def _product(self, x2d, out_dtype):
         xq, xs = ops.mx_quant(x2d, self.act_fmt, self.kp)
         product = ops.mx_gemv if self._decodes(x2d.shape[0]) else ops.mx_gemm
-        y = product(xq, xs, self.act_fmt, self.qweight, self.w_scale, self.w_fmt, self.bias, out_dtype)
-        if x.dtype == torch.float32:  # an fp32 model keeps seeing fp32 activations (the kernel's epilogue emits 16-bit)
-            y = y.float()
-        return y.reshape(*lead, self.out_features)
+        return product(xq, xs, self.act_fmt, self.qweight, self.w_scale, self.w_fmt, self.bias, out_dtype)
 
-    def _decodes(self, rows):
-        return self.DECODE_GEMV and rows <= min(self.DECODE_MAX_M, ops.MX_GEMV_MAX_M)
+    def _group_key(self):
+        return self.in_features, self.qweight.device, self.w_dtype, self.act_dtype
+
+    def _quantize_rows(self, x2d):
+        return ops.mx_quant(x2d, self.act_fmt, self.kp)
+
+    def _gemm(self, xq, xs, out_dtype):
+        return ops.mx_gemm(xq, xs, self.act_fmt, self.qweight, self.w_scale, self.w_fmt, self.bias, out_dtype)
+
+    @staticmethod
+    def _gemv_multi(xq, xs, mods, out_dtype):
+        return ops.mx_gemv_multi(xq, xs, mods[0].act_fmt, [m.qweight for m in mods], [m.w_scale for m in mods], mods[0].w_fmt,
+                                 [m.bias for m in mods], out_dtype)
 
     def recover(self, dtype=None):
         """Dequantised weight [N, K] (a table lookup times 2^(byte - 127); every value is exact in fp32), in `dtype` or float_type."""
@@ -116,34 +127,17 @@ class MXWeightOnlyLinear(MXLinear):
 
     # rows up to which the decode GEMV is taken: the measured crossover of the two kernels (profiles/mx/mx_wo_time.log)
     DECODE_MAX_M = ops.MX_GEMV_MAX_M
+    PAIRS, CELL = WEIGHT_ONLY_PAIRS, ", weight-only"
 
     def __init__(self, in_features, out_features, bias=False, w_dtype="fp4", act_dtype="bf16", device="cuda", float_type=torch.float16):
-        if (w_dtype, act_dtype) not in WEIGHT_ONLY_PAIRS:
-            raise NotImplementedError(f"MXQuant on MI355X, weight-only: (w_dtype, act_dtype) must be one of {WEIGHT_ONLY_PAIRS}, "
-                                      f"got {(w_dtype, act_dtype)}")
-        super().__init__(in_features, out_features, bias=bias, w_dtype=w_dtype, act_dtype="fp8_e4m3", device=device, float_type=float_type)
-        self.act_dtype, self.act_fmt = "bf16", None
+        super().__init__(in_features, out_features, bias=bias, w_dtype=w_dtype, act_dtype=act_dtype, device=device, float_type=float_type)
 
     @classmethod
     def from_float(cls, linear, w_dtype="fp4", act_dtype="bf16", device="cuda"):
         return super().from_float(linear, w_dtype=w_dtype, act_dtype=act_dtype, device=device)
 
-    def forward(self, input):
-        x = input
-        lead = x.shape[:-1]
-        out_dtype = x.dtype if x.dtype in (torch.float16, torch.bfloat16) else self.float_type
-        ret_dtype = torch.float32 if x.dtype == torch.float32 else out_dtype
-        x2d = x.reshape(-1, self.in_features)
-        if x2d.shape[0] == 0:
-            return torch.empty((*lead, self.out_features), dtype=ret_dtype, device=x.device)
-        x2d = x2d.to(torch.bfloat16)
-        if self.in_features % 8:
-            x2d = torch.nn.functional.pad(x2d, (0, 8 - self.in_features % 8))
-        product = ops.mx_wo_gemv if x2d.shape[0] <= min(self.DECODE_MAX_M, ops.MX_GEMV_MAX_M) else ops.mx_wo_gemm
-        y = product(x2d.contiguous(), self.qweight, self.w_scale, self.w_fmt, self.bias, out_dtype)
-        if x.dtype == torch.float32:
-            y = y.float()
-        return y.reshape(*lead, self.out_features)
+    def _product(self, x2d, out_dtype):
+        return mx_wo_product(x2d, self._decodes(x2d.shape[0]), self.qweight, self.w_scale, self.w_fmt, self.bias, out_dtype)
 
 
 def mx_linear_group(x, modules):
@@ -156,71 +150,37 @@ def mx_linear_group(x, modules):
     mods = list(modules)
     if any(isinstance(m, MXWeightOnlyLinear) for m in mods):  # no one-launch group for the weight-only cell
         return [m(x) for m in mods]
-    plan = linear_group_plan(x, mods, MXLinear, ops.MX_GEMV_MAX_MEMBERS, ops.MX_GEMV_MAX_M,
-                             lambda m: (m.in_features, m.qweight.device, m.w_dtype, m.act_dtype))
-    if plan is None:
-        return [m(x) for m in mods]
-    x2d, out_dtype, decode = plan
-    m0 = mods[0]
-    xq, xs = ops.mx_quant(x2d, m0.act_fmt, m0.kp)
-    if decode:
-        ys = ops.mx_gemv_multi(xq, xs, m0.act_fmt, [m.qweight for m in mods], [m.w_scale for m in mods], m0.w_fmt,
-                               [m.bias for m in mods], out_dtype)
-    else:
-        ys = [ops.mx_gemm(xq, xs, m.act_fmt, m.qweight, m.w_scale, m.w_fmt, m.bias, out_dtype) for m in mods]
-    if x.dtype == torch.float32:
-        ys = [y.float() for y in ys]
-    return [y.reshape(*x.shape[:-1], m.out_features) for y, m in zip(ys, mods)]
+    return linear_group(x, mods, MXLinear, ops.MX_GEMV_MAX_MEMBERS, ops.MX_GEMV_MAX_M)
 
 
-class MXQuantizer(Quantizer):
+class MXQuantizer(DataFreeQuantizer):
     """quant_config: {layer name: {"w_dtype", "act_dtype", ...}} (mx_quant_entry).  A layer whose w_dtype is "fp32" stays float.
     Besides nn.Linear the names may be fused MoE experts modules (is_fused_experts; they are in the mapping under
     MXQuantConfig(quant_experts=True)), which become MXExperts, and GPT-OSS experts modules (is_gpt_oss_experts), which become
     MXGptOssExperts when their dict carries "gpt_oss_experts": True (mx_quant_entry sets it under quant_experts=True; without the key
     such a module stays float).  A dict with "weight_only" picks the weight-only class of each kind (MXWeightOnlyLinear,
-    MXWeightOnlyExperts, MXWeightOnlyGptOssExperts)."""
+    MXWeightOnlyExperts, MXWeightOnlyGptOssExperts).  _selected / prepare / convert: DataFreeQuantizer's."""
 
-    def _selected(self, model):
+    LOG, STAYS_FLOAT = "MXQuant", ("w_dtype", "fp32")
+
+    def _is_experts(self, mod, cfg):
+        return is_fused_experts(mod) or (is_gpt_oss_experts(mod) and cfg.get("gpt_oss_experts"))
+
+    def _unsupported_reason(self, mod, cfg):
         from .experts import unsupported_reason
 
-        out = []
-        for name, cfg in self.quant_config.items():
-            if cfg.get("w_dtype", "fp32") == "fp32":
-                continue
-            mod = get_module(model, name)
-            if isinstance(mod, torch.nn.Linear):
-                out.append(name)
-            elif is_fused_experts(mod) or (is_gpt_oss_experts(mod) and cfg.get("gpt_oss_experts")):
-                why = unsupported_reason(mod, cfg)
-                if why is None:
-                    out.append(name)
-                else:
-                    logger.warning("MXQuant: experts module %s stays in floating point: %s", name, why)
-        return out
+        return unsupported_reason(mod, cfg)
 
-    def prepare(self, model, *args, **kwargs):
-        return model  # data-free: nothing to calibrate
-
-    @torch.no_grad()
-    def convert(self, model, *args, **kwargs):
+    def _quantized(self, mod, cfg, dev):
         from .experts import MXExperts, MXGptOssExperts, MXWeightOnlyExperts, MXWeightOnlyGptOssExperts
 
-        dev = torch.device("cuda", torch.cuda.current_device())
-        model.to(dev)
-        model.eval()
-        names = self._selected(model)
-        if not names:
-            logger.warning("MXQuant: no nn.Linear selected, the model is returned unchanged")
-        for name in names:
-            cfg = self.quant_config[name]
-            mod = get_module(model, name)
-            if isinstance(mod, torch.nn.Linear):
-                cls = MXWeightOnlyLinear if cfg.get("weight_only") else MXLinear
-            elif cfg.get("weight_only"):
-                cls = MXWeightOnlyGptOssExperts if is_gpt_oss_experts(mod) else MXWeightOnlyExperts
-            else:
-                cls = MXGptOssExperts if is_gpt_oss_experts(mod) else MXExperts
-            set_module(model, name, cls.from_float(mod, cfg["w_dtype"], cfg["act_dtype"], device=dev))
+        if isinstance(mod, torch.nn.Linear):
+            cls = MXWeightOnlyLinear if cfg.get("weight_only") else MXLinear
+        elif cfg.get("weight_only"):
+            cls = MXWeightOnlyGptOssExperts if is_gpt_oss_experts(mod) else MXWeightOnlyExperts
+        else:
+            cls = MXGptOssExperts if is_gpt_oss_experts(mod) else MXExperts
+        return cls.from_float(mod, cfg["w_dtype"], cfg["act_dtype"], device=dev)
+
+    def _leave_info(self, model, names):
         model.mx_info = {"blocksize": 32, "round_method": "nearest"}
-        return model

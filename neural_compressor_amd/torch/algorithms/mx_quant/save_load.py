@@ -8,20 +8,17 @@ An experts entry whose act_dtype is "bf16" is the weight-only class of its kind 
 same buffers).  MXExperts modules save their four uint8 buffers under their own names, MXGptOssExperts modules those and their two
 fp32 biases.  The
 "mx_experts" / "mx_gpt_oss_experts" keys are written only when the model has such modules; a directory without them (a model without
-them, or one written before the modules existed) loads as before.
+them, or one written before the modules existed) loads as before.  The file handling and the per-Linear rebuild are
+utils/utility.py's (save_quantized, open_saved, take_linear, finish_load), shared with the other two.
 """
 
-import json
-import os
+from functools import partial
 
-import torch
-
-from ...utils.utility import _take, _take_experts, get_module, half_or_fp16, is_fused_experts, is_gpt_oss_experts, set_module
+from ...utils.utility import QCONFIG_NAME, WEIGHT_NAME  # noqa: F401  (this module's names for the two files)
+from ...utils.utility import (_take_experts, finish_load, half_or_fp16, is_fused_experts, is_gpt_oss_experts, open_saved,
+                              save_quantized, take_linear)
 from .experts import MXExperts, MXGptOssExperts, MXWeightOnlyExperts, MXWeightOnlyGptOssExperts
 from .mx_quant import MXLinear, MXWeightOnlyLinear
-
-WEIGHT_NAME = "quantized_weight.pt"
-QCONFIG_NAME = "qconfig.json"
 
 
 def qconfig_of(model):
@@ -40,29 +37,15 @@ def qconfig_of(model):
 
 
 def save(model, output_dir="./saved_results"):
-    os.makedirs(output_dir, exist_ok=True)
-    if torch.cuda.is_available():
-        torch.cuda.synchronize()
-    with open(os.path.join(output_dir, QCONFIG_NAME), "w") as f:
-        json.dump(qconfig_of(model), f, indent=2)
-    torch.save({k: v.detach().cpu() for k, v in model.state_dict().items()}, os.path.join(output_dir, WEIGHT_NAME))
+    save_quantized(model, output_dir, qconfig_of(model))
 
 
 def load(output_dir, original_model, device="cuda"):
     """Rebuild the MX model from the float architecture `original_model` (weights may be on any device, "meta" included)."""
-    with open(os.path.join(output_dir, QCONFIG_NAME)) as f:
-        cfg = json.load(f)
-    state = torch.load(os.path.join(output_dir, WEIGHT_NAME), map_location="cpu", weights_only=True)
-    dev = torch.device(device)
+    cfg, state, dev = open_saved(output_dir, device)
     for name, (w_dtype, act_dtype) in cfg["mx_modules"].items():
-        lin = get_module(original_model, name)
-        assert isinstance(lin, torch.nn.Linear), f"{name}: expected nn.Linear in the float architecture, got {type(lin).__name__}"
-        ft = state[name + ".bias"].dtype if (name + ".bias") in state else half_or_fp16(lin.weight.dtype)
         cls = MXWeightOnlyLinear if act_dtype == "bf16" else MXLinear  # the weight-only cell: same buffers, bf16 activations
-        new = cls(lin.in_features, lin.out_features, bias=(name + ".bias") in state, w_dtype=w_dtype, act_dtype=act_dtype,
-                       device=dev, float_type=ft)
-        _take(state, name, new, dev)
-        set_module(original_model, name, new)
+        take_linear(state, original_model, name, dev, partial(cls, w_dtype=w_dtype, act_dtype=act_dtype))
     for name, (w_dtype, act_dtype, E, H, I) in cfg.get("mx_experts", {}).items():
         _take_experts(state, original_model, name, dev, is_fused_experts,
                       lambda old: (MXWeightOnlyExperts if act_dtype == "bf16" else MXExperts)(
@@ -73,8 +56,6 @@ def load(output_dir, original_model, device="cuda"):
                       lambda old: (MXWeightOnlyGptOssExperts if act_dtype == "bf16" else MXGptOssExperts)(
                           E, H, I, w_dtype=w_dtype, act_dtype=act_dtype, alpha=alpha, limit=limit, device=dev,
                           float_type=half_or_fp16(old.gate_up_proj.dtype)))
-    original_model.load_state_dict(state, strict=False, assign=True)
-    original_model.to(dev)
-    original_model.eval()
+    finish_load(original_model, state, dev)
     original_model.mx_info = cfg.get("mx_quant", {})
     return original_model

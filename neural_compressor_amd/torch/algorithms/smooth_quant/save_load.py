@@ -7,53 +7,36 @@ The files keep the reference's names where they mean the same thing:
                         W8A8Linear (a per-token module has no `alpha`, `corr`, `act_scale`, `act_zp`: that is how load tells the two
                         activation cells apart), the (possibly folded) float parameters of everything else
   qconfig.json          {"smooth_quant": {alpha, folding, absorb_to_layer}, "w8a8_modules": [names]}
+The file handling and the per-Linear rebuild are utils/utility.py's (save_quantized, open_saved, take_linear, finish_load), shared
+with mx_quant/save_load.py and fp8_quant/save_load.py.
 """
 
-import json
-import os
+from functools import partial
 
-import torch
-
-from ...utils.utility import get_module, half_or_fp16, set_module
+from ...utils.utility import QCONFIG_NAME, WEIGHT_NAME  # noqa: F401  (this module's names for the two files)
+from ...utils.utility import finish_load, open_saved, save_quantized, take_linear
 from .utility import W8A8Linear
 
-WEIGHT_NAME = "quantized_weight.pt"
-QCONFIG_NAME = "qconfig.json"
+
+def qconfig_of(model):
+    """The content of qconfig.json."""
+    info = dict(getattr(model, "sq_info", {}))
+    info["absorb_to_layer"] = {k: list(v) for k, v in (info.get("absorb_to_layer") or {}).items()}
+    return {"smooth_quant": info, "w8a8_modules": [n for n, m in model.named_modules() if isinstance(m, W8A8Linear)]}
 
 
 def save(model, output_dir="./saved_results"):
-    os.makedirs(output_dir, exist_ok=True)
-    if torch.cuda.is_available():
-        torch.cuda.synchronize()
-    names = [n for n, m in model.named_modules() if isinstance(m, W8A8Linear)]
-    info = dict(getattr(model, "sq_info", {}))
-    info["absorb_to_layer"] = {k: list(v) for k, v in (info.get("absorb_to_layer") or {}).items()}
-    with open(os.path.join(output_dir, QCONFIG_NAME), "w") as f:
-        json.dump({"smooth_quant": info, "w8a8_modules": names}, f, indent=2)
-    torch.save({k: v.detach().cpu() for k, v in model.state_dict().items()}, os.path.join(output_dir, WEIGHT_NAME))
+    save_quantized(model, output_dir, qconfig_of(model))
 
 
 def load(output_dir, original_model, device="cuda"):
     """Rebuild the W8A8 model from the float architecture `original_model` (weights may be on any device, "meta" included)."""
-    with open(os.path.join(output_dir, QCONFIG_NAME)) as f:
-        cfg = json.load(f)
-    state = torch.load(os.path.join(output_dir, WEIGHT_NAME), map_location="cpu", weights_only=True)
-    dev = torch.device(device)
+    cfg, state, dev = open_saved(output_dir, device)
     for name in cfg["w8a8_modules"]:
-        lin = get_module(original_model, name)
-        assert isinstance(lin, torch.nn.Linear), f"{name}: expected nn.Linear in the float architecture, got {type(lin).__name__}"
-        ft = state[name + ".bias"].dtype if (name + ".bias") in state else half_or_fp16(lin.weight.dtype)
-        new = W8A8Linear(lin.in_features, lin.out_features, bias=(name + ".bias") in state,
-                         has_input_scale=(name + ".input_scale") in state, device=dev, float_type=ft,
-                         act_quant="static" if (name + ".act_scale") in state else "per_token")
-        own = {k[len(name) + 1:]: v for k, v in state.items() if k.startswith(name + ".")}
-        new.load_state_dict({k: v.to(dev) for k, v in own.items()}, strict=True)
-        for k in own:
-            state.pop(name + "." + k)
-        set_module(original_model, name, new)
-    original_model.load_state_dict(state, strict=False, assign=True)
-    original_model.to(dev)
-    original_model.eval()
+        take_linear(state, original_model, name, dev,
+                    partial(W8A8Linear, has_input_scale=(name + ".input_scale") in state,
+                            act_quant="static" if (name + ".act_scale") in state else "per_token"))
+    finish_load(original_model, state, dev)
     original_model.sq_info = cfg.get("smooth_quant", {})
     original_model._smoothquant_optimized = True
     return original_model

@@ -18,6 +18,7 @@ import torch
 from .... import ops
 from ....common.utils import logger
 from ...utils.utility import get_module, half_or_fp16, set_module
+from ..quant_linear import QuantLinear
 
 LM_NORM_NAMES = ("LlamaRMSNorm", "T5LayerNorm", "MistralRMSNorm", "Qwen2RMSNorm", "RMSNorm")  # weight-only norms (:2049)
 
@@ -159,7 +160,7 @@ class SQLinearWrapper(torch.nn.Module):
             self.sq_linear.weight *= self.input_scale.view(1, -1).to(self.sq_linear.weight.dtype)
 
 
-class W8A8Linear(torch.nn.Module):
+class W8A8Linear(QuantLinear):
     """INT8 x INT8 Linear: per-output-channel symmetric int8 weights and one of two activation cells (`act_quant`).
 
     "static" (the default): per-tensor asymmetric uint8 activations, range frozen at calibration.
@@ -171,23 +172,19 @@ class W8A8Linear(torch.nn.Module):
     "per_token": dynamic per-token symmetric int8 activations, nothing calibrated.
     forward = inc_sq_quant_act_token (mul by input_scale, row abs-max, quantise) + inc_w8a8_gemm_rowscale (the same GEMM with
     row_scale[m] * w_scale[n] in the epilogue); no host read.  Buffers: qweight, w_scale, input_scale, bias only.
+
+    The forward contract around the two cells is QuantLinear's (quant_linear.py); there is no decode GEMV.
     """
 
-    K_ALIGN = 128
     ACT_QUANT = ("static", "per_token")
 
     def __init__(self, in_features, out_features, bias=False, has_input_scale=False, device="cuda", float_type=torch.float16,
                  act_quant="static"):
-        super().__init__()
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError(f"W8A8Linear needs a HIP device ('cuda[:N]'), got '{device}'. There is no CPU implementation.")
+        dev = self._hip_device(device)
         if act_quant not in self.ACT_QUANT:
             raise ValueError(f"act_quant must be one of {self.ACT_QUANT}, got {act_quant!r}")
+        super().__init__(in_features, out_features, float_type)
         self.act_quant = act_quant
-        self.in_features, self.out_features = in_features, out_features
-        self.kp = -(-in_features // self.K_ALIGN) * self.K_ALIGN
-        self.float_type = float_type
         self.register_buffer("qweight", torch.zeros((out_features, self.kp), dtype=torch.int8, device=dev))
         self.register_buffer("w_scale", torch.zeros(out_features, dtype=torch.float32, device=dev))
         if act_quant == "static":
@@ -196,7 +193,7 @@ class W8A8Linear(torch.nn.Module):
             self.register_buffer("act_scale", torch.ones(1, dtype=torch.float32, device=dev))
             self.register_buffer("act_zp", torch.zeros(1, dtype=torch.int32, device=dev))
         self.register_buffer("input_scale", torch.ones(in_features, dtype=torch.float32, device=dev) if has_input_scale else None)
-        self.register_buffer("bias", torch.zeros(out_features, dtype=float_type, device=dev) if bias else None)
+        self._register_bias(bias, dev)
         self._sx = self._zp = self._ver = None
 
     @classmethod
@@ -230,25 +227,15 @@ class W8A8Linear(torch.nn.Module):
             new.bias.copy_(lin.bias.detach().to(ft))
         return new
 
-    def forward(self, input):
-        x = input
-        lead = x.shape[:-1]
-        x2d = x.reshape(-1, self.in_features)
-        out_dtype = x.dtype if x.dtype in (torch.float16, torch.bfloat16) else self.float_type
-        if x2d.shape[0] == 0:
-            return torch.empty((*lead, self.out_features), dtype=torch.float32 if x.dtype == torch.float32 else out_dtype, device=x.device)
+    def _product(self, x2d, out_dtype):
         if self.act_quant == "per_token":
             xq, row_scale = ops.sq_quant_act_token(x2d, self.input_scale, self.kp)
-            y = ops.w8a8_gemm(xq, self.qweight, self.w_scale, None, self.bias, out_dtype, row_scale=row_scale)
-        else:
-            ver = (self.act_scale.data_ptr(), self.act_scale._version, self.act_zp._version)
-            if self._sx is None or self._ver != ver:  # one host read per (re)load: the static activation parameters are launch arguments
-                self._sx, self._zp, self._ver = float(self.act_scale.item()), float(self.act_zp.item()), ver
-            xq = ops.sq_quant_act(x2d, self.input_scale, self._sx, self._zp, self.kp)
-            y = ops.w8a8_gemm(xq, self.qweight, self.alpha, self.corr, self.bias, out_dtype)
-        if x.dtype == torch.float32:  # an fp32 model keeps seeing fp32 activations (the kernel's epilogue emits 16-bit)
-            y = y.float()
-        return y.reshape(*lead, self.out_features)
+            return ops.w8a8_gemm(xq, self.qweight, self.w_scale, None, self.bias, out_dtype, row_scale=row_scale)
+        ver = (self.act_scale.data_ptr(), self.act_scale._version, self.act_zp._version)
+        if self._sx is None or self._ver != ver:  # one host read per (re)load: the static activation parameters are launch arguments
+            self._sx, self._zp, self._ver = float(self.act_scale.item()), float(self.act_zp.item()), ver
+        xq = ops.sq_quant_act(x2d, self.input_scale, self._sx, self._zp, self.kp)
+        return ops.w8a8_gemm(xq, self.qweight, self.alpha, self.corr, self.bias, out_dtype)
 
     def recover(self):
         """Dequantised weight [N, K] fp32 (the `quant_dequant_w_v1` image of the smoothed weight)."""

@@ -6,6 +6,7 @@
   HIP accelerator                 reference auto_accelerator.py:220-268 ("cuda" device strings ARE HIP on ROCm)
 """
 
+import json
 import os
 
 import torch
@@ -121,28 +122,52 @@ def _take_experts(state, model, name, dev, recognise, build):
     set_module(model, name, new)
 
 
+def take_linear(state, model, name, dev, build):
+    """The quantised Linear `name` of a saved model, rebuilt from the float architecture `model`: `build(in_features, out_features,
+    bias=, device=, float_type=)` (a class, or a partial of one) makes the empty module -- with a bias if one was saved, float_type from
+    the saved bias or else the float weight -- _take fills it and it takes the nn.Linear's place."""
+    lin = get_module(model, name)
+    assert isinstance(lin, torch.nn.Linear), f"{name}: expected nn.Linear in the float architecture, got {type(lin).__name__}"
+    ft = state[name + ".bias"].dtype if (name + ".bias") in state else half_or_fp16(lin.weight.dtype)
+    new = build(lin.in_features, lin.out_features, bias=(name + ".bias") in state, device=dev, float_type=ft)
+    _take(state, name, new, dev)
+    set_module(model, name, new)
+
+
+WEIGHT_NAME = "quantized_weight.pt"
+QCONFIG_NAME = "qconfig.json"
+
+
+def save_quantized(model, output_dir, qconfig):
+    """The two files of a saved SmoothQuant / MX / FP8 model: `qconfig` as qconfig.json, the state dict (on the CPU) as
+    quantized_weight.pt."""
+    os.makedirs(output_dir, exist_ok=True)
+    if torch.cuda.is_available():
+        torch.cuda.synchronize()
+    with open(os.path.join(output_dir, QCONFIG_NAME), "w") as f:
+        json.dump(qconfig, f, indent=2)
+    torch.save({k: v.detach().cpu() for k, v in model.state_dict().items()}, os.path.join(output_dir, WEIGHT_NAME))
+
+
+def open_saved(output_dir, device):
+    """load's preamble: (the content of qconfig.json, the saved state dict on the CPU, torch.device(device))."""
+    with open(os.path.join(output_dir, QCONFIG_NAME)) as f:
+        cfg = json.load(f)
+    state = torch.load(os.path.join(output_dir, WEIGHT_NAME), map_location="cpu", weights_only=True)
+    return cfg, state, torch.device(device)
+
+
+def finish_load(model, state, dev):
+    """load's end: what the _take* calls left of `state` goes to the float modules; the model on `dev`, in eval mode."""
+    model.load_state_dict(state, strict=False, assign=True)
+    model.to(dev)
+    model.eval()
+    return model
+
+
 def half_or_fp16(dtype):
     """The float type a quantised module keeps for a float module of `dtype`: bf16 / fp16 as they are, fp16 for anything else."""
     return dtype if dtype in (torch.float16, torch.bfloat16) else torch.float16
-
-
-def linear_group_plan(x, mods, cls, max_members, max_rows, key):
-    """What `cls` members (FP8Linear / MXLinear) that multiply the same x share, or None where the group is the plain list of forwards:
-    (x2d, out_dtype, every member decodes).  2 .. max_members members of one `key(m)` (a tuple that starts with in_features and the
-    device), x there and not empty; an fp32 x needs one float_type; the row count decodes on every member or is above max_rows."""
-    m0 = mods[0] if mods else None
-    ok = (2 <= len(mods) <= max_members and all(isinstance(m, cls) for m in mods) and x.is_cuda and x.numel() > 0
-          and x.shape[-1] == m0.in_features and x.device == m0.qweight.device and all(key(m) == key(m0) for m in mods))
-    if not ok:
-        return None
-    half = x.dtype in (torch.float16, torch.bfloat16)
-    out_dtype = x.dtype if half else m0.float_type
-    x2d = x.reshape(-1, m0.in_features)
-    rows = x2d.shape[0]
-    decode = [m._decodes(rows) for m in mods]
-    if not (half or all(m.float_type == out_dtype for m in mods)) or not (all(decode) or rows > max_rows):
-        return None
-    return x2d, out_dtype, all(decode)
 
 
 get_attr = fetch_module
