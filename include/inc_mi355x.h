@@ -510,6 +510,29 @@ int inc_gptq_quantize_layer(float* w, const float* Hinv, float* scale, float* ze
                             int kernel_group_size, int block_size, int bits, int sym, int flags,
                             inc_stream_t stream, inc_stream_t aux_stream);
 
+/* == K6 on the MX grid: the same column loop with the OCP microscaling quantiser of inc_mx_quant (fmt INC_MX_FP8_E4M3 /
+ *   INC_MX_FP4_E2M1, blocks of 32 columns) in place of the integer one, emitting inc_mx_quant's storage.  Per 128 columns
+ *   [i1, i1 + count), count = min(128, K - i1):
+ *     byte  of each of its MX blocks = clamp(expfield(max|w|) - emax, 0, 254) on the block's columns of W AS THEY ARE WHEN THE
+ *           128 COLUMNS START (every earlier update applied, none of this chain's) -- always computed by the chain itself;
+ *     step  x = w[:, i]; v = x * 2^(127 - byte) (exact); code = RNE(v) onto the element grid, saturating, sign of x (the
+ *           rounding of inc_mx_quant); q = value(code) * 2^(byte - 127) (exact); e = (x - q) / Hinv[i,i];
+ *           w[:, j] -= e * Hinv[i,j] for the block's j >= i -- un-fused fp32 (true division, multiply then subtract);
+ *   then W[:, i1+count:] -= Err1 @ Hinv[i1:i1+count, i1+count:] by inc_gptq_lazy_update / _cols as they are.
+ *     w [N,K] fp32 working copy -- consumed; Hinv [K,K] fp32; wq uint8 [N,Kp] (e4m3) or [N,Kp/2] (e2m1, element 2i in the
+ *     low nibble), 16-byte aligned; ws uint8 [N,Kp/32], 4-byte aligned; Kp = K rounded up to 128: the columns K .. Kp-1 are
+ *     written too (zero codes; byte 0 for a block of padding alone); q_out [N,K] of q_dtype = the q of every column;
+ *     err_ws fp32 [2, N, 128].  With `aux_stream` != NULL (K a multiple of 128, K >= 384, no INC_GPTQ_NO_LOOKAHEAD in flags)
+ *     the bulk of every lazy update runs on it underneath the next chain; the results are bit-identical either way.
+ *   INC_ERR_BAD_ARG: a NULL operand, a size < 1, a misaligned wq / ws.  INC_ERR_UNSUPPORTED: another fmt or q_dtype, K % 32 != 0,
+ *   Kp != K rounded up to 128, K * 516 >= 2^32.  Both are decided before any HIP call.
+ *   inc_gptq_quant_block_mx is the chain of ONE block (i1 a multiple of 128, err fp32 [N,128] = Err1, 0 from `count` on).   */
+int inc_gptq_quant_block_mx(const float* w, const float* Hinv, uint8_t* wq, uint8_t* ws, void* q_out, int q_dtype,
+                            float* err, int64_t N, int64_t K, int64_t Kp, int64_t i1, int fmt, inc_stream_t stream);
+int inc_gptq_quantize_layer_mx(float* w, const float* Hinv, uint8_t* wq, uint8_t* ws, void* q_out, int q_dtype,
+                               float* err_ws, int64_t N, int64_t K, int64_t Kp, int fmt, int flags,
+                               inc_stream_t stream, inc_stream_t aux_stream);
+
 /* ---- K6': diagonal block of the blocked inverse-Cholesky factor -------------------------------- *
  * The reference builds Hinv = cholesky(cholesky_inverse(cholesky(H)), upper) (gptq.py:1228-1230) with
  * three LAPACK factorisations.  Here U = J Lr^-1 J with J H J = Lr Lr^T (see gptq.py: inverse_cholesky_upper):

@@ -152,6 +152,8 @@ SIGNATURES = {
     "inc_trace_marker": (c_int, [c_int, _P]),
     "inc_gptq_quantize_layer": (c_int, [_P, _P, _P, _P, c_int64, _P, _P, c_int64, _P, _P, c_int, _P, c_int64, c_int64, c_int, c_int, c_int,
                                         c_int, c_int, c_int, _P, _P]),
+    "inc_gptq_quant_block_mx": (c_int, [_P, _P, _P, _P, _P, c_int, _P, c_int64, c_int64, c_int64, c_int64, c_int, _P]),
+    "inc_gptq_quantize_layer_mx": (c_int, [_P, _P, _P, _P, _P, c_int, _P, c_int64, c_int64, c_int64, c_int, c_int, _P, _P]),
     "inc_chol_diag_block": (c_int, [_P, c_int64, c_int, _P, c_int64, _P, c_int, _P]),
     "inc_gptq_inverse_factor_workspace_bytes": (c_int64, [c_int64, c_int]),
     "inc_gptq_inverse_factor": (c_int, [_P, c_int64, _P, _P, c_int64, _P, c_int, _P, _P]),

@@ -1460,6 +1460,28 @@ def gptq_quantize_layer(w32, hinv, scale, zero, loop_scale, loop_zero, codes, q_
         )
 
 
+def gptq_quantize_layer_mx(w32, hinv, q_out, err_ws, fmt, flags=0, aux_stream=None):
+    """The column loop of GPTQ on the MX grid as ONE C-ABI call (include/inc_mi355x.h: inc_gptq_quantize_layer_mx): w32 [N,K] fp32
+    (consumed), K a multiple of 32 -> (codes, scales) in inc_mx_quant's storage for Kp = mx_padded_k(K), the padding written too;
+    `q_out` [N,K] receives the dequantised weight, `err_ws` is fp32 [2, N, 128].  Issued on the CURRENT stream, the bulk of the lazy
+    updates on `aux_stream` (a torch stream) when given."""
+    dev = _dev(w32, hinv, q_out, err_ws)
+    N, K = w32.shape
+    Kp = mx_padded_k(K)
+    assert w32.dtype == torch.float32 and hinv.dtype == torch.float32 and tuple(hinv.shape) == (K, K) and tuple(q_out.shape) == (N, K)
+    assert err_ws.dtype == torch.float32 and err_ws.numel() >= 2 * N * 128
+    codes = torch.empty((N, Kp if fmt == MX_FP8_E4M3 else Kp // 2), dtype=torch.uint8, device=dev)
+    scales = torch.empty((N, Kp // 32), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        check(
+            lib.inc_gptq_quantize_layer_mx(_ptr(w32), _ptr(hinv), _ptr(codes), _ptr(scales), _ptr(q_out), dtype_code(q_out.dtype),
+                                           _ptr(err_ws), N, K, Kp, int(fmt), int(flags), _stream(),
+                                           aux_stream.cuda_stream if aux_stream is not None else None),
+            "inc_gptq_quantize_layer_mx",
+        )
+    return codes, scales
+
+
 def chol_diag_block(A_view, Linv_view, info, tag):
     """In-place Cholesky of one <=128x128 diagonal block (a strided view into a larger fp32 matrix) + inverse of its
     factor into `Linv_view` (also a strided view).  See include/inc_mi355x.h: inc_chol_diag_block."""

@@ -499,6 +499,7 @@ class GPTQ:
         self.rows, self.columns = (shape[1], shape[0]) if self.is_conv1d else (shape[0], shape[1])
         self.acc = accumulator or HessianAccumulator(self.columns, device)
         self.perm = None
+        self.mx_codes = self.mx_scales = None  # left by an MX solve (fasterquant_mx)
         self.cfg = {}
         self.row_ctx = None  # distributed.CalibrationGroup: solve only this rank's weight rows, all-gather the results
 
@@ -535,6 +536,54 @@ class GPTQ:
 
     lookahead = True  # the column loop's second stream (bit-identical either way; tests compare)
 
+    # GPTQConfig(dtype=...) values that put the column loop on the MX grid -> the w_dtype of the MXWeightOnlyLinear they produce
+    MX_DTYPES = {"mx_fp4": "fp4", "mx_fp8_e4m3": "fp8_e4m3"}
+
+    @staticmethod
+    def check_mx(cfg, columns=None, is_conv1d=False, row_sharded=False):
+        """What an MX dtype cannot be combined with, one NotImplementedError each; nothing here needs a device.  `columns` / `is_conv1d`
+        describe the layer when there is one (RAWGPTQuantizer.check_layer_config has only the dict).  `bits` and `sym` are ignored: the
+        element format fixes both."""
+        def refuse(what):
+            raise NotImplementedError(f"GPTQ on the MX grid (dtype={cfg.get('dtype')!r}): {what}")
+
+        if cfg.get("group_size", 32) != 32:
+            refuse(f"group_size must be 32, the MX block (got {cfg.get('group_size')})")
+        for key, name in (("act_order", "act_order"), ("hybrid_order", "hybrid_order"), ("static_groups", "static_groups"),
+                          ("mse", "use_mse_search"), ("use_double_quant", "use_double_quant")):
+            if cfg.get(key, False):
+                refuse(f"{name} is not supported")
+        if is_conv1d:
+            refuse("Conv1D layers are not supported")
+        if columns is not None and columns % 32 != 0:
+            refuse(f"in_features must be a multiple of 32 (got {columns})")
+        if row_sharded:
+            refuse("the multi-GPU row-sharded solve is not supported")
+
+    def fasterquant_mx(self, W, percdamp):
+        """fasterquant for the MX dtypes: the same prologue (factor, fp32 working copy with dead columns zeroed), then the whole column
+        loop as ONE call (ops.gptq_quantize_layer_mx).  The E8M0 bytes are computed by the chain on the weights as they are when their
+        128 columns start, so `block_size` has no effect here.  Returns fasterquant's tuple with scale = zero = None; the packed codes and
+        the scale bytes (MXLinear's `qweight` / `w_scale`, padding included) are left in `self.mx_codes` / `self.mx_scales`."""
+        W = W.contiguous()
+        N, K = W.shape
+        Hinv, dead, _ = self.acc.inverse_factor(percdamp, False, 0)
+        w32 = ops.gptq_prepare_weight(W, dead)
+        Q = torch.empty((N, K), dtype=W.dtype, device=W.device)
+        err_ws = torch.empty((2, N, QBLOCK), dtype=torch.float32, device=W.device)
+        side = _lookahead_stream(W.device) if (self.lookahead and K % QBLOCK == 0 and K >= 3 * QBLOCK) else None
+        if side is not None:
+            for t in (w32, Hinv, err_ws):
+                t.record_stream(side)
+        from ..mx_quant.mx_quant import FORMATS
+
+        self.mx_codes, self.mx_scales = ops.gptq_quantize_layer_mx(w32, Hinv, Q, err_ws, FORMATS[self.MX_DTYPES[self.cfg["dtype"]]],
+                                                                   aux_stream=side)
+        self.codes, self.export_perm = None, None
+        if not self.defer_check:
+            self.acc.check()
+        return None, torch.tensor([-1]), None, Q
+
     def column_loop(self, w32, Hinv, scale, zero, loop_scale, loop_zero, codes, Q, gs, kernel_gs, blocksize, bits, sym, dynamic_groups, mse):
         """The loop of gptq.py:1250-1304 as ONE C-ABI call: per 128 columns `[find_params] -> chain -> next-128 update` on this
         stream and the rest of the trailing update on a second stream underneath the next chain (look-ahead: every column still
@@ -558,6 +607,11 @@ class GPTQ:
         the integer codes (uint8 [N,K], original column order) are left in `self.codes`."""
         if fp8_aware:
             raise NotImplementedError("fp8_aware (INT4 weights pre-scaled for Gaudi's fp8 matrix units) is a Gaudi W4A8 option outside the MI355X scope")
+        if self.cfg.get("dtype", "int") in self.MX_DTYPES:
+            # the arguments are what this solve runs with (the block driver passes the dict's own values)
+            self.check_mx(dict(self.cfg, group_size=groupsize, act_order=act_order, hybrid_order=hybrid_order, static_groups=static_groups),
+                          self.columns, self.is_conv1d, self.row_ctx is not None)
+            return self.fasterquant_mx(W, percdamp)
         if hybrid_order:
             self.check_hybrid_order(self.columns, groupsize, act_order, static_groups)
         bits = int(self.cfg.get("bits", 4))
@@ -655,7 +709,7 @@ class GPTQ:
 
     def free(self):
         self.acc = None
-        self.codes = None
+        self.codes = self.mx_codes = self.mx_scales = None
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -745,6 +799,9 @@ class RAWGPTQuantizer(object):
             self.dist_ctx = CalibrationGroup(None if self.row_shard_solve is True else self.row_shard_solve)
             if self.dist_ctx.world == 1 and not SINGLE_RANK_GROUP:
                 self.dist_ctx = None
+        self.mx = any(config["dtype"] in GPTQ.MX_DTYPES for config in self.weight_config.values())
+        if self.mx and (self.dist_ctx is not None or (self.layer_ctx is not None and self.layer_ctx.world > 1)):
+            raise NotImplementedError("GPTQ on the MX grid: the multi-GPU row-sharded and block-per-rank modes are not supported")
 
     # -- config handling (reference :330-398) --------------------------------------------------------
     _DEFAULTS = dict(
@@ -761,6 +818,10 @@ class RAWGPTQuantizer(object):
             if config["dtype"] != "int" and "int" in config["dtype"]:
                 config["bits"] = int(config["dtype"].lstrip("int"))
                 config["dtype"] = "int"
+            if config["dtype"] in GPTQ.MX_DTYPES:
+                GPTQ.check_mx(config)
+        if len({config["dtype"] in GPTQ.MX_DTYPES for config in self.weight_config.values()}) > 1:
+            raise NotImplementedError("GPTQ on the MX grid: a model mixes MX and integer layers (one saved format per model)")
 
     def get_layer_config(self, layer_name):
         import re
@@ -1444,6 +1505,20 @@ class RAWGPTQuantizer(object):
                 set_module(block, name, mod)
 
     @torch.no_grad()
+    def _mx_module(self, layer, cfg, mx_codes, mx_scales):
+        """The packed module of an MX solve: an MXWeightOnlyLinear that takes the chain's two buffers as they are (no re-quantisation) and
+        the bias, with the float_type `from_float` would give it."""
+        from ...utils.utility import half_or_fp16
+        from ..mx_quant.mx_quant import MXWeightOnlyLinear
+
+        new = MXWeightOnlyLinear(layer.in_features, layer.out_features, bias=layer.bias is not None, w_dtype=GPTQ.MX_DTYPES[cfg["dtype"]],
+                                 act_dtype="bf16", device=self.device, float_type=half_or_fp16(layer.weight.dtype))
+        new.qweight.copy_(mx_codes)
+        new.w_scale.copy_(mx_scales)
+        if layer.bias is not None:
+            new.bias.copy_(layer.bias.detach().to(new.float_type))
+        return new
+
     def quantize_post_layer(self):
         """Step 2.7 (reference :887-1080): GPTQ on the layer that follows the transformer stack (lm_head).
 
@@ -1490,11 +1565,14 @@ class RAWGPTQuantizer(object):
         else:
             in_features, out_features = layer.weight.shape[0], layer.weight.shape[1]
         zero = None if cfg["sym"] else zp
-        new_module = MI355XWeightOnlyLinear(
-            in_features, out_features, dtype=cfg["dtype"], bits=cfg["bits"], group_size=cfg["group_size"],
-            zp=zero is not None, bias=layer.bias is not None, g_idx=solver.export_perm is not None, device=self.device,
-        )
-        new_module.pack_codes(solver.codes, scale, zero, layer.bias, g_idx=solver.export_perm)
+        if cfg["dtype"] in GPTQ.MX_DTYPES:
+            new_module = self._mx_module(layer, cfg, solver.mx_codes, solver.mx_scales)
+        else:
+            new_module = MI355XWeightOnlyLinear(
+                in_features, out_features, dtype=cfg["dtype"], bits=cfg["bits"], group_size=cfg["group_size"],
+                zp=zero is not None, bias=layer.bias is not None, g_idx=solver.export_perm is not None, device=self.device,
+            )
+            new_module.pack_codes(solver.codes, scale, zero, layer.bias, g_idx=solver.export_perm)
         solver.acc.check()
         solver.free()
         set_module(self.model, full, new_module)
@@ -1523,6 +1601,8 @@ class RAWGPTQuantizer(object):
                 solvers[name].defer_check = True  # checked once per group of solves below
                 solvers[name].configure(self.get_layer_config(self.get_full_layer_name(name, block_idx)))
                 cfg_ = solvers[name].cfg
+                if cfg_.get("dtype") in GPTQ.MX_DTYPES:  # refused before the capture pass too
+                    GPTQ.check_mx(cfg_, solvers[name].columns, solvers[name].is_conv1d, self.dist_ctx is not None)
                 if cfg_.get("hybrid_order", False):  # before the capture pass, the factorisations and (multi-GPU) the factor exchange
                     GPTQ.check_hybrid_order(solvers[name].columns, cfg_.get("group_size", -1), cfg_.get("act_order", False), cfg_.get("static_groups", False))
             # Step 2.3: hooks feeding the Hessians (reference :670-688).  Layers that receive the very same input
@@ -1696,7 +1776,8 @@ class RAWGPTQuantizer(object):
                     act_order=cfg["act_order"], hybrid_order=cfg["hybrid_order"], fp8_aware=cfg["fp8_aware"],
                     static_groups=cfg["static_groups"],
                 )
-                return scale, zp, Q, sv.codes, sv.export_perm
+                # an MX solve has no (scale, zero) tables; its `codes` are the pair (packed codes, E8M0 bytes) -- row-wise like the rest
+                return scale, zp, Q, sv.codes if sv.mx_codes is None else (sv.mx_codes, sv.mx_scales), sv.export_perm
 
             def scatter(names, stacked):
                 """Hand the rows of a solved batch back to its Linears."""
@@ -1708,10 +1789,14 @@ class RAWGPTQuantizer(object):
                     sl = slice(r0, r0 + rows)
                     r0 += rows
                     one = len(names) == 1
-                    layers[n].weight.data = Q if one else Q[sl].contiguous()
-                    results[n] = dict(scale=scale if one else scale[sl].contiguous(),
-                                      zero=None if cfg["sym"] else (zp if one else zp[sl].contiguous()), perm=perm,
-                                      codes=codes if one else codes[sl].contiguous())
+
+                    def cut(t):  # this member's rows of a stacked result
+                        if isinstance(t, tuple):
+                            return tuple(cut(u) for u in t)
+                        return t if (one or t is None) else t[sl].contiguous()
+
+                    layers[n].weight.data = cut(Q)
+                    results[n] = dict(scale=cut(scale), zero=None if cfg["sym"] else cut(zp), perm=perm, codes=cut(codes))
                     solvers[n].perm = perm
 
             def solve(names):
@@ -1728,7 +1813,9 @@ class RAWGPTQuantizer(object):
                         solve(late)
                         late_event = self._late_stream.record_event()
                     for n in late:
-                        for t in (layers[n].weight.data, results[n]["scale"], results[n]["zero"], results[n]["codes"], results[n]["perm"]):
+                        codes_ = results[n]["codes"]
+                        for t in (layers[n].weight.data, results[n]["scale"], results[n]["zero"], results[n]["perm"],
+                                  *(codes_ if isinstance(codes_, tuple) else (codes_,))):
                             if isinstance(t, torch.Tensor):
                                 t.record_stream(main)
                 if plan2d is not None:
@@ -1779,6 +1866,9 @@ class RAWGPTQuantizer(object):
             for name, layer in layers.items():
                 cfg = self.get_layer_config(self.get_full_layer_name(name, block_idx))
                 r = results[name]
+                if cfg["dtype"] in GPTQ.MX_DTYPES:
+                    set_module(block, name, self._mx_module(layer, cfg, *r["codes"]))
+                    continue
                 if isinstance(layer, nn.Linear):
                     in_features, out_features = layer.in_features, layer.out_features
                 else:
@@ -1818,5 +1908,7 @@ class GPTQuantizer(INCQuantizer):
         self.gptq_quantizer.model = model
         self.gptq_quantizer.remove_prepare_for_calibration()
         q_model = self.gptq_quantizer.execute_quantization()
+        if self.gptq_quantizer.mx:  # what mx_quant.save_load writes beside the modules' own (w_dtype, act_dtype) records
+            q_model.mx_info = {"blocksize": 32, "round_method": "gptq"}
         logger.info("GPTQ quantizing done.")
         return q_model

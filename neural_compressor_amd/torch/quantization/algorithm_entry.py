@@ -14,6 +14,10 @@ from ..utils.utility import get_quantizer, postprocess_model, register_algo
 
 
 def _save(self, output_dir="./saved_results", format="default", **kwargs):
+    if getattr(self, "mx_info", None):  # GPTQConfig(dtype="mx_*"): the modules are MXWeightOnlyLinear, the files mx_quant's
+        from ..algorithms.mx_quant.save_load import save as mx_save
+
+        return mx_save(self, output_dir)
     from ..algorithms.weight_only.save_load import save
 
     return save(self, output_dir, format=format, **kwargs)
@@ -67,6 +71,8 @@ def gptq_entry(model, configs_mapping, mode=Mode.QUANTIZE, *args, **kwargs):
     for (op_name, op_type), quant_config in configs_mapping.items():
         if quant_config.name != GPTQ or quant_config.dtype == "fp32":
             continue
+        if str(quant_config.dtype).startswith("mx_") and getattr(quant_config, "quant_experts", False):
+            raise NotImplementedError("GPTQ on the MX grid: quant_experts=True is not supported (the fused experts solve is integer only)")
         weight_config[op_name] = {
             "dtype": quant_config.dtype,
             "bits": quant_config.bits,

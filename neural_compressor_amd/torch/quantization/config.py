@@ -107,7 +107,15 @@ def get_default_rtn_config(processor_type=None) -> RTNConfig:
 
 @register_config(framework_name=FRAMEWORK_NAME, algo_name=GPTQ, priority=PRIORITY_GPTQ)
 class GPTQConfig(TorchBaseConfig):
-    """GPTQ (reference config.py:322)."""
+    """GPTQ (reference config.py:322).
+
+    `dtype="mx_fp4"` / `dtype="mx_fp8_e4m3"` (an extension of the reference's values) put the column loop on the OCP microscaling grid:
+    E8M0 scales per 32 columns, e2m1 / e4m3 elements, and every selected Linear becomes the MXWeightOnlyLinear that
+    MXQuantConfig(weight_only=True) produces, with error feedback instead of round-to-nearest.  `bits` and `use_sym` are ignored
+    there (the element format fixes both) and `block_size` has no effect: the scale of an MX block is taken from the weights as they
+    are when the block's 128 columns start.  group_size must be 32; act_order, hybrid_order, static_groups, use_mse_search,
+    use_double_quant, quant_experts, Conv1D layers, an in_features that is no multiple of 32 and the multi-GPU row-sharded modes
+    raise NotImplementedError."""
 
     name = GPTQ
     supported_configs: List = []
