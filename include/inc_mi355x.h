@@ -661,12 +661,24 @@ int inc_w8a8_gemm_rowscale(const int8_t* xq, const int8_t* wq, const float* row_
  *             (the instruction's own order: no permutation in the kernel); scales [rows, Kp/32] uint8.
  *   Product:  y[m,n] = sum_blocks 2^(sx + sw - 254) * sum_{k in block} a_k * b_k  +  bias[n], accumulated in fp32 inside the
  *             matrix pipe (its summation order is not documented), fp32 bias add, one rounding to bf16 / fp16.
+ *   MXFP6:    fmt INC_MX_FP6_E2M3 (emax 2, 3 mantissa bits, bias 1, subnormals m * 2^-3, saturating to +-7.5) and INC_MX_FP6_E3M2
+ *             (emax 4, 2 mantissa bits, bias 3, subnormals m * 2^-4, saturating to +-28): sign in bit 5, no NaN / Inf codes; scale
+ *             rule, multiplier and rounding as above.  Storage: codes [rows, Kp * 3/4] uint8 -- block b of a row is the 24 bytes at
+ *             24 b and element j of the block sits in bits 6 j .. 6 j + 5 of that little-endian 192-bit string (the instruction's
+ *             own order, pinned on the device: tools/mx_lab.hip) -- scales [rows, Kp/32].  Rows stay 16-byte aligned (Kp % 128 == 0),
+ *             blocks are 8-byte aligned.  Served by inc_mx_quant_fp6, inc_mx_gemm, inc_mx_gemv and inc_mx_gemv_multi only: every
+ *             other MX entry point (experts, weight-only, GPTQ) rejects fp6 with INC_ERR_UNSUPPORTED.
  * `fmt` values are the instruction's own format codes.
  * inc_mx_quant: the row quantiser above.  x bf16 / fp16 / fp32 [M,K] contiguous, of any alignment (16-byte loads when K is a
  *   multiple of 8 (fp32: 4) and x is 16-byte aligned); codes 16-byte aligned.  One lane per block: each row is read from HBM once.
  *   Writes every code byte and scale byte, the padding included, and nothing else.  Serves activations at run time and weights at
  *   convert time.  INC_ERR_UNSUPPORTED (nothing launched) for an unknown fmt / dtype or Kp % 128 != 0.
- * inc_mx_gemm: the product above for (xfmt, wfmt) = (fp8, fp8), (fp8, fp4), (fp4, fp4); any other pair is INC_ERR_UNSUPPORTED.
+ *   Formats INC_MX_FP6_* are INC_ERR_UNSUPPORTED here: they have the entry point below.
+ * inc_mx_quant_fp6: inc_mx_quant for fmt INC_MX_FP6_E2M3 / INC_MX_FP6_E3M2 (any other fmt is INC_ERR_UNSUPPORTED): the same
+ *   arguments, checks and kernel shape; a lane's 32 codes leave as six dwords, one 16-byte and one 8-byte store.
+ * inc_mx_gemm: the product above for (xfmt, wfmt) = (fp8, fp8), (fp8, fp4), (fp4, fp4), (e2m3, e2m3), (e3m2, e3m2), (fp8, e2m3),
+ *   (e2m3, fp4) -- the activation is never narrower than the weight; any other pair (mixed e2m3 / e3m2 and fp8 weights under fp6
+ *   activations among them) is INC_ERR_UNSUPPORTED.  An fp6 operand is [rows, Kp * 3/4].
  *   xq [M, Kp or Kp/2], xs [M, Kp/32], wq [N, Kp or Kp/2], ws [N, Kp/32] as stored by inc_mx_quant, xq / wq 16-byte and xs / ws
  *   4-byte aligned; bias [N] in ydtype or NULL; y [M,N] bf16 / fp16, any M >= 1 and N >= 1 (8-byte stores when N % 4 == 0 and y is
  *   8-byte aligned, 2-byte stores otherwise).  256 x 256 x 128 tiles, one workgroup per tile, no split-K tail; the decode route for
@@ -752,13 +764,17 @@ int inc_w8a8_gemm_rowscale(const int8_t* xq, const int8_t* wq, const float* row_
  *   the _glu entry unless limit > 0 and alpha == alpha and for a bias that is not 4-byte aligned; INC_ERR_UNSUPPORTED (nothing
  *   launched) for a wfmt other than e4m3 / e2m1, Kp % 128 != 0, K % 8 != 0, K > Kp, Kp - K >= 128, E > 512, S > 2^22, mode 0 with odd
  *   N or an odtype other than INC_BF16 (INC_F16 included), another odtype than INC_F32 in modes 1 / 2, a bad wdtype (mode 1).
- * All ten validate their arguments before any HIP call.                                                                         */
+ * All eleven validate their arguments before any HIP call.                                                                         */
 #define INC_MX_FP8_E4M3 0
+#define INC_MX_FP6_E2M3 2
+#define INC_MX_FP6_E3M2 3
 #define INC_MX_FP4_E2M1 4
 #define INC_MX_KTILE 128
 #define INC_MX_GEMV_MAX_M 16
 int inc_mx_quant(const void* x, int xdtype, int64_t M, int64_t K, int64_t Kp, int fmt, uint8_t* codes, uint8_t* scales,
                  inc_stream_t stream);
+int inc_mx_quant_fp6(const void* x, int xdtype, int64_t M, int64_t K, int64_t Kp, int fmt, uint8_t* codes, uint8_t* scales,
+                     inc_stream_t stream);
 int inc_mx_gemm(const uint8_t* xq, const uint8_t* xs, int xfmt, const uint8_t* wq, const uint8_t* ws, int wfmt, const void* bias,
                 void* y, int ydtype, int64_t M, int64_t N, int64_t Kp, inc_stream_t stream);
 int inc_mx_gemv(const uint8_t* xq, const uint8_t* xs, int xfmt, const uint8_t* wq, const uint8_t* ws, int wfmt, const void* bias,

@@ -96,6 +96,7 @@ SIGNATURES = {
     "inc_sq_quant_act_token": (c_int, [_P, c_int, c_int64, c_int64, c_int64, _P, _P, _P, _P]),
     "inc_w8a8_gemm_rowscale": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int64, c_int64, c_int64, _P, c_int64, _P]),
     "inc_mx_quant": (c_int, [_P, c_int, c_int64, c_int64, c_int64, c_int, _P, _P, _P]),
+    "inc_mx_quant_fp6": (c_int, [_P, c_int, c_int64, c_int64, c_int64, c_int, _P, _P, _P]),
     "inc_mx_gemm": (c_int, [_P, _P, c_int, _P, _P, c_int, _P, _P, c_int, c_int64, c_int64, c_int64, _P]),
     "inc_mx_gemv": (c_int, [_P, _P, c_int, _P, _P, c_int, _P, _P, c_int, c_int64, c_int64, c_int64, _P]),
     "inc_mx_gemv_multi": (c_int, [c_int, _P, _P, c_int, _P, _P, c_int, _P, _P, c_int, c_int64, _P, c_int64, _P]),

@@ -1,4 +1,4 @@
-// gemm_mx.hip -- K16: MXFP8 / MXFP4 GEMM on v_mfma_scale_f32_32x32x64_f8f6f4 (the block-scaled matrix instruction of gfx950).
+// gemm_mx.hip -- K16: MXFP8 / MXFP6 / MXFP4 GEMM on v_mfma_scale_f32_32x32x64_f8f6f4 (the block-scaled matrix instruction of gfx950).
 //
 //   y[m, n] = sum_blocks 2^(xs[m,b] + ws[n,b] - 254) * sum_{k in block b} x[m,k] * w[n,k]  +  bias[n]
 //
@@ -8,7 +8,9 @@
 //   lane l holds row / column l & 31; h = l >> 5.  fp4: the 32 elements of block h of the 64-wide K step, element j in nibble j of
 //   the first 4 dwords (element 2i in the low nibble of byte i -- the stored order; dwords 4 .. 7 are not read).  fp8: dwords 0 .. 3
 //   are bytes 16 h .. 16 h + 15 and dwords 4 .. 7 bytes 32 + 16 h .. of the step (two back-to-back 8-bit MFMAs of K = 32), so a
-//   block is spread over both lane halves.  For either format lane half h supplies the scale of block h of its row, in the byte of
+//   block is spread over both lane halves.  fp6 (e2m3 / e3m2): the fp4 map -- the 32 elements of block h, element j in bits 6 j ..
+//   6 j + 5 of the little-endian 192-bit string in dwords 0 .. 5 (the stored order; dwords 6 and 7 are not read); its K-tile row is
+//   96 bytes, staged and read back by MxStage<96> (mx_stage.hpp has the image and its bank arithmetic).  For every format lane half h supplies the scale of block h of its row, in the byte of
 //   the scale register that opsel names; C/D is the 32 x 32 map of every other 32x32 MFMA (tile256_frame.hpp).
 //
 // The kernel stands on the wave frame of tile256_frame.hpp (wave grid, operand roles, swizzled LDS image, C/D map) with a K-tile of 128
@@ -28,7 +30,9 @@ typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 constexpr int XM = 256, XN = 256, XK = INC_MX_KTILE;
 
-__host__ __device__ constexpr int mx_row_bytes(int fmt) { return fmt == INC_MX_FP8_E4M3 ? XK : XK / 2; }  // of one K-tile
+// of one K-tile: 128 (fp8), 96 (fp6: e2m3 / e3m2) or 64 (fp4)
+__host__ __device__ constexpr int mx_row_bytes(int fmt) { return fmt == INC_MX_FP8_E4M3 ? XK : fmt == INC_MX_FP4_E2M1 ? XK / 2 : XK / 4 * 3; }
+__host__ __device__ constexpr int64_t mx_ld(int fmt, int64_t Kp) { return fmt == INC_MX_FP8_E4M3 ? Kp : fmt == INC_MX_FP4_E2M1 ? Kp / 2 : Kp / 4 * 3; }
 
 template <bool IS_BF16, int XF, int WF>
 __global__ __launch_bounds__(512) void mx_gemm_kernel(const uint8_t* __restrict__ xq, const uint8_t* __restrict__ xs,
@@ -50,7 +54,7 @@ __global__ __launch_bounds__(512) void mx_gemm_kernel(const uint8_t* __restrict_
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 2, wn = wave & 3;
   const uint32_t lds0 = (uint32_t)(uintptr_t)smem;
-  const int64_t ldx = XF == INC_MX_FP8_E4M3 ? Kp : Kp / 2, ldw = WF == INC_MX_FP8_E4M3 ? Kp : Kp / 2;
+  const int64_t ldx = mx_ld(XF, Kp), ldw = mx_ld(WF, Kp);
   const int64_t lds_ = Kp / 32;  // scale bytes per row
 
   uint32_t xoff[SX::NI], woff[SW::NI];
@@ -180,7 +184,7 @@ __global__ __launch_bounds__(512) void mx_gemm_kernel(const uint8_t* __restrict_
 template <int XF, int WF>
 int mx_launch(const uint8_t* xq, const uint8_t* xs, const uint8_t* wq, const uint8_t* ws, const void* bias, void* y, int ydtype,
               int64_t M, int64_t N, int64_t Kp, inc_stream_t stream) {
-  const size_t smem = (size_t)2 * 256 * (mx_row_bytes(XF) + mx_row_bytes(WF));  // 128 / 96 / 64 KiB
+  const size_t smem = (size_t)2 * 256 * (mx_row_bytes(XF) + mx_row_bytes(WF));  // 128 / 96 / 64 KiB; with fp6: 96 (a6w6), 112 (a8w6), 80 (a6w4)
   static std::atomic<uint64_t> attr_set{0};
   if (inc_attr_needed(attr_set)) {
     (void)hipFuncSetAttribute((const void*)mx_gemm_kernel<true, XF, WF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
@@ -206,12 +210,21 @@ extern "C" int inc_mx_gemm(const uint8_t* xq, const uint8_t* xs, int xfmt, const
   const bool p88 = xfmt == INC_MX_FP8_E4M3 && wfmt == INC_MX_FP8_E4M3;
   const bool p84 = xfmt == INC_MX_FP8_E4M3 && wfmt == INC_MX_FP4_E2M1;
   const bool p44 = xfmt == INC_MX_FP4_E2M1 && wfmt == INC_MX_FP4_E2M1;
-  if (!p88 && !p84 && !p44) return INC_ERR_UNSUPPORTED;
+  // the fp6 pairs: (e2m3, e2m3), (e3m2, e3m2), e4m3 x over e2m3 w, e2m3 x over e2m1 w
+  const bool p66a = xfmt == INC_MX_FP6_E2M3 && wfmt == INC_MX_FP6_E2M3;
+  const bool p66b = xfmt == INC_MX_FP6_E3M2 && wfmt == INC_MX_FP6_E3M2;
+  const bool p86 = xfmt == INC_MX_FP8_E4M3 && wfmt == INC_MX_FP6_E2M3;
+  const bool p64 = xfmt == INC_MX_FP6_E2M3 && wfmt == INC_MX_FP4_E2M1;
+  if (!p88 && !p84 && !p44 && !p66a && !p66b && !p86 && !p64) return INC_ERR_UNSUPPORTED;
   INC_CHECK_ARG(((reinterpret_cast<uintptr_t>(xq) | reinterpret_cast<uintptr_t>(wq)) & 15) == 0);
   INC_CHECK_ARG(((reinterpret_cast<uintptr_t>(xs) | reinterpret_cast<uintptr_t>(ws)) & 3) == 0);
   INC_CHECK_ARG((int64_t)XM * Kp < ((int64_t)1 << 32));          // 32-bit DMA offsets inside a tile
   INC_CHECK_ARG(ceil_div64(M, XM) * ceil_div64(N, XN) < ((int64_t)1 << 31));
   if (p88) return mx_launch<INC_MX_FP8_E4M3, INC_MX_FP8_E4M3>(xq, xs, wq, ws, bias, y, ydtype, M, N, Kp, stream);
   if (p84) return mx_launch<INC_MX_FP8_E4M3, INC_MX_FP4_E2M1>(xq, xs, wq, ws, bias, y, ydtype, M, N, Kp, stream);
+  if (p66a) return mx_launch<INC_MX_FP6_E2M3, INC_MX_FP6_E2M3>(xq, xs, wq, ws, bias, y, ydtype, M, N, Kp, stream);
+  if (p66b) return mx_launch<INC_MX_FP6_E3M2, INC_MX_FP6_E3M2>(xq, xs, wq, ws, bias, y, ydtype, M, N, Kp, stream);
+  if (p86) return mx_launch<INC_MX_FP8_E4M3, INC_MX_FP6_E2M3>(xq, xs, wq, ws, bias, y, ydtype, M, N, Kp, stream);
+  if (p64) return mx_launch<INC_MX_FP6_E2M3, INC_MX_FP4_E2M1>(xq, xs, wq, ws, bias, y, ydtype, M, N, Kp, stream);
   return mx_launch<INC_MX_FP4_E2M1, INC_MX_FP4_E2M1>(xq, xs, wq, ws, bias, y, ydtype, M, N, Kp, stream);
 }

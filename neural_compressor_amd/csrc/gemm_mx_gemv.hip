@@ -6,7 +6,7 @@
 // Operands, storage and arithmetic are inc_mx_gemm's (include/inc_mi355x.h has the specification).  This is the strip scheme of
 // strip_frame.hpp with block scales (SCALED = true), one weight strip and one block of x rows: a workgroup owns one strip of 16 weight
 // rows over all of K; a lane loads what the instruction wants of its row straight from global memory into VGPRs -- two (fp8) or one
-// (fp4) 16-byte loads and one scale byte per operand and K-tile, non-temporal for the weights (streamed once), plain for x (every
+// (fp4) 16-byte loads, or a 16-byte and an 8-byte load of its block's 24 bytes (fp6), and one scale byte per operand and K-tile, non-temporal for the weights (streamed once), plain for x (every
 // strip re-reads it from L2) -- with no LDS round trip and no shuffle.  K is split over the W waves of the workgroup, UNROLL tiles per
 // round and the cascade tail; wave 0 adds the W partials in wave order, adds the bias in fp32 and rounds once.  No global hand-off, no
 // counters, no workspace: repeated calls are bit-identical.
@@ -14,7 +14,7 @@
 // inc_mx_gemv_multi is the same kernel over the strips of up to 8 weight matrices one after another: a workgroup finds its member in
 // a table passed by value (StripMembers) and then runs the same strip, so member i's output is inc_mx_gemv's bit for bit; inc_mx_gemv
 // is the launch with a table of one member.
-// Algorithmic bytes per launch: N * Kp * (1 or 1/2) + N * Kp / 32 + M * Kp * (1 or 1/2) + M * Kp / 32 + 2 * M * N.
+// Algorithmic bytes per launch: N * Kp * (1, 3/4 or 1/2) + N * Kp / 32 + M * Kp * (1, 3/4 or 1/2) + M * Kp / 32 + 2 * M * N.
 #include "strip_frame.hpp"
 
 #ifndef INC_MX_GEMV_WAVES
@@ -52,8 +52,8 @@ __global__ __launch_bounds__(GW * 64) void mx_gemv_kernel(const uint8_t* __restr
   if (wrow > N - 1) wrow = N - 1;
   const int xrow = r < M ? r : M - 1;
   const int xkeep = r < M ? -1 : 0;
-  const uint8_t* const wp = mem.wq[mi] + wrow * (Kp / XK * TW) + 16 * g;
-  const uint8_t* const xp = xq + (int64_t)xrow * (Kp / XK * TX) + 16 * g;
+  const uint8_t* const wp = mem.wq[mi] + wrow * (Kp / XK * TW) + mx_lane_bytes(WF) * g;
+  const uint8_t* const xp = xq + (int64_t)xrow * (Kp / XK * TX) + mx_lane_bytes(XF) * g;
   const uint8_t* const wsp = mem.ws[mi] + wrow * sld + g;
   const uint8_t* const xsp = xs + (int64_t)xrow * sld + g;
   const int nk = (int)(Kp / XK);
@@ -137,13 +137,22 @@ int gemv_run(int n, const uint8_t* xq, const uint8_t* xs, int xfmt, const uint8_
   const bool p88 = xfmt == INC_MX_FP8_E4M3 && wfmt == INC_MX_FP8_E4M3;
   const bool p84 = xfmt == INC_MX_FP8_E4M3 && wfmt == INC_MX_FP4_E2M1;
   const bool p44 = xfmt == INC_MX_FP4_E2M1 && wfmt == INC_MX_FP4_E2M1;
-  if (!p88 && !p84 && !p44) return INC_ERR_UNSUPPORTED;
+  // the fp6 pairs of inc_mx_gemm: (e2m3, e2m3), (e3m2, e3m2), e4m3 x over e2m3 w, e2m3 x over e2m1 w
+  const bool p66a = xfmt == INC_MX_FP6_E2M3 && wfmt == INC_MX_FP6_E2M3;
+  const bool p66b = xfmt == INC_MX_FP6_E3M2 && wfmt == INC_MX_FP6_E3M2;
+  const bool p86 = xfmt == INC_MX_FP8_E4M3 && wfmt == INC_MX_FP6_E2M3;
+  const bool p64 = xfmt == INC_MX_FP6_E2M3 && wfmt == INC_MX_FP4_E2M1;
+  if (!p88 && !p84 && !p44 && !p66a && !p66b && !p86 && !p64) return INC_ERR_UNSUPPORTED;
   INC_CHECK_ARG((reinterpret_cast<uintptr_t>(xq) & 15) == 0 && (reinterpret_cast<uintptr_t>(xs) & 3) == 0);
   MxGemvMembers mem = {};
   const int rc = strip_members_fill(mem, n, wq, ws, bias, y, N);
   if (rc != INC_OK) return rc;
   if (p88) return gemv_launch<INC_MX_FP8_E4M3, INC_MX_FP8_E4M3>(xq, xs, mem, ydtype, M, Kp, stream);
   if (p84) return gemv_launch<INC_MX_FP8_E4M3, INC_MX_FP4_E2M1>(xq, xs, mem, ydtype, M, Kp, stream);
+  if (p66a) return gemv_launch<INC_MX_FP6_E2M3, INC_MX_FP6_E2M3>(xq, xs, mem, ydtype, M, Kp, stream);
+  if (p66b) return gemv_launch<INC_MX_FP6_E3M2, INC_MX_FP6_E3M2>(xq, xs, mem, ydtype, M, Kp, stream);
+  if (p86) return gemv_launch<INC_MX_FP8_E4M3, INC_MX_FP6_E2M3>(xq, xs, mem, ydtype, M, Kp, stream);
+  if (p64) return gemv_launch<INC_MX_FP6_E2M3, INC_MX_FP4_E2M1>(xq, xs, mem, ydtype, M, Kp, stream);
   return gemv_launch<INC_MX_FP4_E2M1, INC_MX_FP4_E2M1>(xq, xs, mem, ydtype, M, Kp, stream);
 }
 

@@ -1,4 +1,4 @@
-// mx.hip -- K15: OCP microscaling (MX) row quantiser, MXFP8 (e4m3) and MXFP4 (e2m1).  HBM-bound streaming kernel.
+// mx.hip -- K15: OCP microscaling (MX) row quantiser, MXFP8 (e4m3), MXFP6 (e2m3 / e3m2) and MXFP4 (e2m1).  HBM-bound streaming kernel.
 //
 // The specification is the comment of inc_mx_quant in include/inc_mi355x.h; the reference emulates the formats
 // with fake quantisation in float (torch/algorithms/mx_quant/utils.py), here the codes are the operands of
@@ -8,10 +8,15 @@
 //   code  = RNE(v) onto the element grid, saturating, with the sign bit of x
 // One lane owns one block, so max|x| needs no exchange between lanes and every code has one right answer, bit for bit: the row is
 // read once (16-byte loads where K and the pointer allow it), the 32 codes leave as two (fp8) or one (fp4) 16-byte store.
+// fp6 (inc_mx_quant_fp6): the 32 six-bit codes are one little-endian 192-bit string, element j in bits 6 j .. 6 j + 5, assembled in
+// six dwords in registers (every shift is a compile-time constant; 5 of the 32 codes straddle two dwords) and stored as 16 + 8 bytes:
+// block b of a row sits at byte 24 b, which is 8-byte aligned only, so neither store is written as a 16-byte-aligned access.
 // The element rounding is mx_encode of mx_format.hpp (shared with the per-token FP8 quantiser).
 #include "mx_format.hpp"
 
 namespace {
+
+typedef uint32_t u32x4_a8 __attribute__((ext_vector_type(4), aligned(8)));  // a 16-byte access at an 8-byte-aligned address
 
 template <int FMT>
 __device__ __forceinline__ uint32_t mx_code(float x, float mult) {
@@ -87,6 +92,17 @@ __global__ __launch_bounds__(256) void mx_quant_kernel(const void* __restrict__ 
     uint4* dst = reinterpret_cast<uint4*>(codes + m * Kp + b * 32);
     dst[0] = make_uint4(w[0], w[1], w[2], w[3]);
     dst[1] = make_uint4(w[4], w[5], w[6], w[7]);
+  } else if constexpr (FMT == INC_MX_FP6_E2M3 || FMT == INC_MX_FP6_E3M2) {
+    uint32_t w[6] = {0, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (int j = 0; j < 32; ++j) {
+      const uint32_t c = mx_code<FMT>(v[j], mult);
+      w[(6 * j) >> 5] |= c << ((6 * j) & 31);
+      if (((6 * j) & 31) > 26) w[((6 * j) >> 5) + 1] |= c >> (32 - ((6 * j) & 31));
+    }
+    uint8_t* dst = codes + m * (Kp / 4 * 3) + b * 24;
+    *reinterpret_cast<u32x4_a8*>(dst) = u32x4_a8{w[0], w[1], w[2], w[3]};
+    *reinterpret_cast<uint2*>(dst + 16) = make_uint2(w[4], w[5]);
   } else {
     uint32_t w[4];
 #pragma unroll
@@ -99,20 +115,31 @@ __global__ __launch_bounds__(256) void mx_quant_kernel(const void* __restrict__ 
   }
 }
 
-}  // namespace
-
-extern "C" int inc_mx_quant(const void* x, int xdtype, int64_t M, int64_t K, int64_t Kp, int fmt, uint8_t* codes, uint8_t* scales,
-                            inc_stream_t stream) {
+// the checks and the launch of both entry points; FA / FB: the two formats the entry point takes
+template <int FA, int FB>
+int mx_quant_run(const void* x, int xdtype, int64_t M, int64_t K, int64_t Kp, int fmt, uint8_t* codes, uint8_t* scales, inc_stream_t stream) {
   INC_CHECK_ARG(x && codes && scales && M > 0 && K > 0 && Kp >= K);
-  if (fmt != INC_MX_FP8_E4M3 && fmt != INC_MX_FP4_E2M1) return INC_ERR_UNSUPPORTED;
+  if (fmt != FA && fmt != FB) return INC_ERR_UNSUPPORTED;
   if (xdtype != INC_F32 && xdtype != INC_F16 && xdtype != INC_BF16) return INC_ERR_UNSUPPORTED;
   if ((Kp % INC_MX_KTILE) != 0) return INC_ERR_UNSUPPORTED;
   INC_CHECK_ARG((reinterpret_cast<uintptr_t>(codes) & 15) == 0);
   INC_CHECK_ARG(M * (Kp / 32) < ((int64_t)1 << 31) * 256);
   const unsigned grid = (unsigned)ceil_div64(M * (Kp / 32), 256);
   INC_DISPATCH_DTYPE(xdtype, DT, {
-    if (fmt == INC_MX_FP8_E4M3) mx_quant_kernel<DT, INC_MX_FP8_E4M3><<<grid, 256, 0, inc_s(stream)>>>(x, M, K, Kp, codes, scales);
-    else mx_quant_kernel<DT, INC_MX_FP4_E2M1><<<grid, 256, 0, inc_s(stream)>>>(x, M, K, Kp, codes, scales);
+    if (fmt == FA) mx_quant_kernel<DT, FA><<<grid, 256, 0, inc_s(stream)>>>(x, M, K, Kp, codes, scales);
+    else mx_quant_kernel<DT, FB><<<grid, 256, 0, inc_s(stream)>>>(x, M, K, Kp, codes, scales);
   })
   INC_LAUNCH_RETURN();
+}
+
+}  // namespace
+
+extern "C" int inc_mx_quant(const void* x, int xdtype, int64_t M, int64_t K, int64_t Kp, int fmt, uint8_t* codes, uint8_t* scales,
+                            inc_stream_t stream) {
+  return mx_quant_run<INC_MX_FP8_E4M3, INC_MX_FP4_E2M1>(x, xdtype, M, K, Kp, fmt, codes, scales, stream);
+}
+
+extern "C" int inc_mx_quant_fp6(const void* x, int xdtype, int64_t M, int64_t K, int64_t Kp, int fmt, uint8_t* codes, uint8_t* scales,
+                                inc_stream_t stream) {
+  return mx_quant_run<INC_MX_FP6_E2M3, INC_MX_FP6_E3M2>(x, xdtype, M, K, Kp, fmt, codes, scales, stream);
 }

@@ -1,5 +1,5 @@
-// mx_format.hpp -- the element rounding of the e4m3 / e2m1 quantisers: one device function for the MX row quantiser (mx.hip) and the
-// per-token FP8 quantiser (sq.hip, inc_fp8_quant_rows), so both put a value on the same code, bit for bit.
+// mx_format.hpp -- the element rounding of the e4m3 / e2m3 / e3m2 / e2m1 quantisers: one device function for the MX row quantisers
+// (mx.hip) and the per-token FP8 quantiser (sq.hip, inc_fp8_quant_rows), so all put a value on the same code, bit for bit.
 // The rounding is done in fp32 arithmetic, not with v_cvt_scalef32_pk_*: with e = max(expfield(|v|), expfield(min normal)) the
 // grid step at |v| is 2^(e - 127 - MB) (MB mantissa bits), t = rint(|v| / step) is an integer in [0, 2^(MB+1)] and
 // ((e - expfield(min normal)) << MB) + t is the code -- the carry of t = 2^(MB+1) lands in the exponent field by itself and the
@@ -7,9 +7,12 @@
 #pragma once
 #include "common.hpp"
 
+// EMAX: of the scale rule; MB: mantissa bits; EMINF: expfield of the smallest normal; SIGN: the sign's bit; SAT: largest magnitude
 template <int FMT> struct MxFmt;
-template <> struct MxFmt<INC_MX_FP8_E4M3> { static constexpr int EMAX = 8, MB = 3, EMINF = 127 - 6; static constexpr float SAT = 448.f; };
-template <> struct MxFmt<INC_MX_FP4_E2M1> { static constexpr int EMAX = 2, MB = 1, EMINF = 127; static constexpr float SAT = 6.f; };
+template <> struct MxFmt<INC_MX_FP8_E4M3> { static constexpr int EMAX = 8, MB = 3, EMINF = 127 - 6, SIGN = 7; static constexpr float SAT = 448.f; };
+template <> struct MxFmt<INC_MX_FP6_E2M3> { static constexpr int EMAX = 2, MB = 3, EMINF = 127, SIGN = 5; static constexpr float SAT = 7.5f; };
+template <> struct MxFmt<INC_MX_FP6_E3M2> { static constexpr int EMAX = 4, MB = 2, EMINF = 127 - 2, SIGN = 5; static constexpr float SAT = 28.f; };
+template <> struct MxFmt<INC_MX_FP4_E2M1> { static constexpr int EMAX = 2, MB = 1, EMINF = 127, SIGN = 3; static constexpr float SAT = 6.f; };
 
 // the code of the already scaled value v: RNE onto the element grid, saturating at +-SAT (a NaN saturates too: no NaN code is
 // produced), with `sign` (0 / 1) in the sign bit
@@ -22,5 +25,5 @@ __device__ __forceinline__ uint32_t mx_encode(float v, uint32_t sign) {
   const float inv_step = __uint_as_float((uint32_t)(254 + F::MB - e) << 23);
   const uint32_t t = (uint32_t)(int)rintf(a * inv_step);
   const uint32_t mag = ((uint32_t)(e - F::EMINF) << F::MB) + t;
-  return mag | (sign << (FMT == INC_MX_FP8_E4M3 ? 7 : 3));
+  return mag | (sign << F::SIGN);
 }

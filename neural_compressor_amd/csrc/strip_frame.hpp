@@ -7,7 +7,8 @@
 //               (strip, block) and the accumulator's rows are output columns.
 //   operands    lane l holds row r = l & 15, lane group g = l >> 4 (tools/mx_lab.hip).  fp8: registers 0 .. 3 are
 //               the 16 bytes at 16 g of the K-tile and 4 .. 7 the 16 bytes at 64 + 16 g; fp4: registers 0 .. 3 are the 16 bytes of
-//               block g (4 .. 7 are not read); either format: the scale byte of block g.  A lane loads that straight from global
+//               block g (4 .. 7 are not read); fp6: registers 0 .. 5 are the 24 bytes of block g, a 16-byte and an 8-byte load at an
+//               8-byte-aligned address (6, 7 are zero and not read); every format: the scale byte of block g.  A lane loads that straight from global
 //               memory into the instruction's registers (mx_frag): non-temporal for the weights, plain for x.  A weight row past N
 //               re-reads row N - 1; what it produces is never stored.
 //   K loop      strip_partials: K is split INSIDE the workgroup, wave w of W takes the K-tiles w, w + W, ... in ascending order, U of
@@ -37,11 +38,27 @@ constexpr int XK = INC_MX_KTILE;
 constexpr int STRIP = 16;  // weight rows of a workgroup: the instruction's M
 constexpr int STRIP_MAX_MEMBERS = 8;
 
-__host__ __device__ constexpr int mx_tile_bytes(int fmt) { return fmt == INC_MX_FP8_E4M3 ? XK : XK / 2; }  // of one row and K-tile
+// of one row and K-tile: 128 (fp8), 96 (fp6: e2m3 / e3m2; decode GEMV only) or 64 (fp4)
+__host__ __device__ constexpr int mx_tile_bytes(int fmt) { return fmt == INC_MX_FP8_E4M3 ? XK : fmt == INC_MX_FP4_E2M1 ? XK / 2 : XK / 4 * 3; }
+// where lane group g starts inside the K-tile of its row, per g: fp8 / fp4 16 bytes, fp6 the 24 bytes of a block
+__host__ __device__ constexpr int mx_lane_bytes(int fmt) { return fmt == INC_MX_FP6_E2M3 || fmt == INC_MX_FP6_E3M2 ? 24 : 16; }
 
-// what a lane supplies of its row for the K-tile at `p` (= row + tile + 16 g), as the instruction wants it
+typedef int i32x4_a8 __attribute__((ext_vector_type(4), aligned(8)));  // a 16-byte load at an 8-byte-aligned address
+typedef __attribute__((ext_vector_type(2))) int i32x2;
+
+// what a lane supplies of its row for the K-tile at `p` (= row + tile + mx_lane_bytes g), as the instruction wants it
 template <int F, bool NT>
 __device__ __forceinline__ i32x8 mx_frag(const uint8_t* p) {
+  if constexpr (F == INC_MX_FP6_E2M3 || F == INC_MX_FP6_E3M2) {  // block g: 24 bytes, 8-byte aligned; registers 6, 7 are not read
+    const i32x4_a8* q = reinterpret_cast<const i32x4_a8*>(p);
+    const i32x2* t = reinterpret_cast<const i32x2*>(p + 16);
+    const i32x4 lo = NT ? __builtin_nontemporal_load(q) : q[0];
+    const i32x2 hi = NT ? __builtin_nontemporal_load(t) : t[0];
+    i32x8 f;
+    f[0] = lo[0]; f[1] = lo[1]; f[2] = lo[2]; f[3] = lo[3];
+    f[4] = hi[0]; f[5] = hi[1]; f[6] = 0; f[7] = 0;
+    return f;
+  }
   const i32x4* q = reinterpret_cast<const i32x4*>(p);
   const i32x4 lo = NT ? __builtin_nontemporal_load(q) : q[0];
   i32x4 hi = {0, 0, 0, 0};
@@ -73,14 +90,14 @@ __device__ __forceinline__ StripLane strip_lane(int64_t n0, int64_t N, int M = S
   return L;
 }
 
-// a lane's row of one operand at K-tile 0: its codes (+ 16 g) and, where the cell has block scales, its scale bytes (+ g)
+// a lane's row of one operand at K-tile 0: its codes (+ 16 g; fp6 + 24 g) and, where the cell has block scales, its scale bytes (+ g)
 struct StripRow {
   const uint8_t* q;
   const uint8_t* s;
 };
 template <int F, bool SCALED>
 __device__ __forceinline__ StripRow strip_row(const uint8_t* q, const uint8_t* s, int64_t row, int nk, int g) {
-  return {q + row * ((int64_t)nk * mx_tile_bytes(F)) + 16 * g, SCALED ? s + row * ((int64_t)nk * (XK / 32)) + g : nullptr};
+  return {q + row * ((int64_t)nk * mx_tile_bytes(F)) + mx_lane_bytes(F) * g, SCALED ? s + row * ((int64_t)nk * (XK / 32)) + g : nullptr};
 }
 
 // ---- the K loop ----------------------------------------------------------------------------------------------------------------------

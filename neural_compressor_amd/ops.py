@@ -1683,7 +1683,7 @@ def _workspace_i8(dev, nbytes):
 # ---------------------------------------------------------------------------------------------------
 # K15/K16 OCP microscaling: MXFP8 / MXFP4 on the block-scaled matrix instruction (include/inc_mi355x.h has the specification)
 # ---------------------------------------------------------------------------------------------------
-MX_FP8_E4M3, MX_FP4_E2M1 = 0, 4  # the instruction's own format codes
+MX_FP8_E4M3, MX_FP6_E2M3, MX_FP6_E3M2, MX_FP4_E2M1 = 0, 2, 3, 4  # the instruction's own format codes
 MX_KTILE = 128
 
 
@@ -1692,16 +1692,24 @@ def mx_padded_k(K):
     return (int(K) + MX_KTILE - 1) // MX_KTILE * MX_KTILE
 
 
+def mx_code_cols(fmt, Kp):
+    """Bytes of one row of Kp codes: Kp (fp8), Kp * 3/4 (fp6: blocks of 24 bytes) or Kp / 2 (fp4).  The linears' formats; the experts,
+    weight-only and GPTQ cells take fp8 / fp4 only and size their buffers themselves."""
+    return Kp if fmt == MX_FP8_E4M3 else Kp // 4 * 3 if fmt in (MX_FP6_E2M3, MX_FP6_E3M2) else Kp // 2
+
+
 def mx_quant(x2d, fmt, Kp=None):
-    """The MX row quantiser: x [M,K] bf16 / fp16 / fp32 -> (codes uint8 [M,Kp] (fp8) or [M,Kp/2] (fp4), scales uint8 [M,Kp/32])."""
+    """The MX row quantiser: x [M,K] bf16 / fp16 / fp32 -> (codes uint8 [M,Kp] (fp8), [M,Kp*3/4] (fp6) or [M,Kp/2] (fp4), scales uint8
+    [M,Kp/32]).  fp8 / fp4 are inc_mx_quant, the fp6 formats inc_mx_quant_fp6."""
     x2d = x2d.contiguous()
     dev = _dev(x2d)
     M, K = x2d.shape
     Kp = mx_padded_k(K) if Kp is None else int(Kp)
-    codes = torch.empty((M, Kp if fmt == MX_FP8_E4M3 else Kp // 2), dtype=torch.uint8, device=dev)
+    codes = torch.empty((M, mx_code_cols(fmt, Kp)), dtype=torch.uint8, device=dev)
     scales = torch.empty((M, Kp // 32), dtype=torch.uint8, device=dev)
+    entry = "inc_mx_quant_fp6" if fmt in (MX_FP6_E2M3, MX_FP6_E3M2) else "inc_mx_quant"
     with torch.cuda.device(dev):
-        check(lib.inc_mx_quant(_ptr(x2d), dtype_code(x2d.dtype), M, K, Kp, int(fmt), _ptr(codes), _ptr(scales), _stream()), "inc_mx_quant")
+        check(getattr(lib, entry)(_ptr(x2d), dtype_code(x2d.dtype), M, K, Kp, int(fmt), _ptr(codes), _ptr(scales), _stream()), entry)
     return codes, scales
 
 
@@ -1709,7 +1717,7 @@ def _mx_check_operands(xq, xs, xfmt, wq, ws, wfmt):
     """The shapes the MX products take -> Kp."""
     Kp = xs.shape[1] * 32
     assert ws.shape[1] * 32 == Kp and xq.dtype == torch.uint8 and wq.dtype == torch.uint8
-    assert xq.shape[1] == (Kp if xfmt == MX_FP8_E4M3 else Kp // 2) and wq.shape[1] == (Kp if wfmt == MX_FP8_E4M3 else Kp // 2)
+    assert xq.shape[1] == mx_code_cols(xfmt, Kp) and wq.shape[1] == mx_code_cols(wfmt, Kp)
     assert xq.is_contiguous() and xs.is_contiguous() and wq.is_contiguous() and ws.is_contiguous()
     return Kp
 

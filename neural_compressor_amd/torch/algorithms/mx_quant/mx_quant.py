@@ -18,8 +18,11 @@ from .... import ops
 from ...utils.utility import is_fused_experts, is_gpt_oss_experts
 from ..quant_linear import DataFreeQuantizer, QuantLinear, e4m3_table, linear_group
 
-FORMATS = {"fp8_e4m3": ops.MX_FP8_E4M3, "fp4": ops.MX_FP4_E2M1}
-PAIRS = (("fp8_e4m3", "fp8_e4m3"), ("fp4", "fp8_e4m3"), ("fp4", "fp4"))  # (w_dtype, act_dtype) the GEMM takes
+FORMATS = {"fp8_e4m3": ops.MX_FP8_E4M3, "fp6_e2m3": ops.MX_FP6_E2M3, "fp6_e3m2": ops.MX_FP6_E3M2, "fp4": ops.MX_FP4_E2M1}
+PAIRS = (("fp8_e4m3", "fp8_e4m3"), ("fp4", "fp8_e4m3"), ("fp4", "fp4"))  # (w_dtype, act_dtype) every MX cell takes: linears and experts
+# the MXFP6 pairs, which only MXLinear takes (inc_mx_gemm / inc_mx_gemv); the activation is never narrower than the weight.  They are a
+# table of their own because PAIRS is shared with the experts classes, which reject fp6
+FP6_PAIRS = (("fp6_e2m3", "fp6_e2m3"), ("fp6_e3m2", "fp6_e3m2"), ("fp6_e2m3", "fp8_e4m3"), ("fp4", "fp6_e2m3"))
 WEIGHT_ONLY_PAIRS = (("fp4", "bf16"), ("fp8_e4m3", "bf16"))  # the weight-only cell: MX weights, bf16 activations
 
 
@@ -32,9 +35,16 @@ def check_pair(owner, w_dtype, act_dtype):
 
 
 def _code_values(fmt):
-    """The value of every code: 256 entries for e4m3 (OCP e4m3fn; 0x7f / 0xff are NaN and never stored), 16 for e2m1."""
+    """The value of every code: 256 entries for e4m3 (OCP e4m3fn; 0x7f / 0xff are NaN and never stored), 64 for e2m3 / e3m2 (sign in
+    bit 5, no NaN / Inf codes), 16 for e2m1."""
     if fmt == ops.MX_FP8_E4M3:
         return e4m3_table()
+    if fmt in (ops.MX_FP6_E2M3, ops.MX_FP6_E3M2):
+        mb, bias = (3, 1) if fmt == ops.MX_FP6_E2M3 else (2, 3)
+        mag = torch.arange(32)
+        e, m = mag >> mb, (mag & ((1 << mb) - 1)).float()
+        half = torch.where(e == 0, m * 2.0 ** (1 - bias - mb), torch.ldexp(1 + m / (1 << mb), e - bias))
+        return torch.cat([half, -half])
     half = torch.tensor([0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0])
     return torch.cat([half, -half])
 
@@ -50,8 +60,9 @@ def mx_wo_product(a, decode, qweight, w_scale, w_fmt, bias, out_dtype):
 
 
 class MXLinear(QuantLinear):
-    """nn.Linear with MX weights and MX activations.  Buffers: qweight uint8 [N, Kp] (fp8) or [N, Kp/2] (fp4, element 2i in the low
-    nibble), w_scale uint8 [N, Kp/32] (E8M0 bytes), bias.  Kp = in_features rounded up to 128; the padding columns are zero codes.
+    """nn.Linear with MX weights and MX activations.  Buffers: qweight uint8 [N, Kp] (fp8), [N, Kp*3/4] (fp6_e2m3 / fp6_e3m2: 24 bytes
+    per block, element j in bits 6j .. 6j+5) or [N, Kp/2] (fp4, element 2i in the low nibble), w_scale uint8 [N, Kp/32] (E8M0 bytes),
+    bias.  Beside PAIRS the class takes the MXFP6 pairs FP6_PAIRS (inc_mx_quant_fp6 and the same two products).  Kp = in_features rounded up to 128; the padding columns are zero codes.
     forward = inc_mx_quant(x) -> inc_mx_gemv up to DECODE_MAX_M rows (while DECODE_GEMV is on), inc_mx_gemm above; nothing is read
     back to the host."""
 
@@ -60,15 +71,17 @@ class MXLinear(QuantLinear):
     DECODE_GEMV = True
     DECODE_MAX_M, GEMV_LIMIT = ops.MX_GEMV_MAX_M, "MX_GEMV_MAX_M"
     PAIRS, CELL = PAIRS, ""  # the (w_dtype, act_dtype) this class takes, and what check_pair's message calls the cell
+    FP6_PAIRS = FP6_PAIRS    # taken too, by this class only (subclasses and the experts classes set it empty or do not have it)
 
     def __init__(self, in_features, out_features, bias=False, w_dtype="fp8_e4m3", act_dtype="fp8_e4m3", device="cuda",
                  float_type=torch.float16):
         dev = self._hip_device(device)
-        check_pair(self, w_dtype, act_dtype)
+        if (w_dtype, act_dtype) not in self.FP6_PAIRS:
+            check_pair(self, w_dtype, act_dtype)
         super().__init__(in_features, out_features, float_type)
         self.w_dtype, self.act_dtype = w_dtype, act_dtype
         self.w_fmt, self.act_fmt = FORMATS[w_dtype], FORMATS.get(act_dtype)  # no format for "bf16": nothing quantises the activation
-        cols = self.kp if self.w_fmt == ops.MX_FP8_E4M3 else self.kp // 2
+        cols = ops.mx_code_cols(self.w_fmt, self.kp)
         self.register_buffer("qweight", torch.zeros((out_features, cols), dtype=torch.uint8, device=dev))
         self.register_buffer("w_scale", torch.zeros((out_features, self.kp // 32), dtype=torch.uint8, device=dev))
         self._register_bias(bias, dev)
@@ -106,6 +119,10 @@ class MXLinear(QuantLinear):
         q = self.qweight
         if self.w_fmt == ops.MX_FP4_E2M1:
             q = torch.stack([q & 0xF, q >> 4], dim=2).reshape(q.shape[0], -1)
+        elif self.w_fmt in (ops.MX_FP6_E2M3, ops.MX_FP6_E3M2):  # 3 bytes = one 24-bit little-endian word = 4 codes
+            b = q.view(q.shape[0], -1, 3).to(torch.int32)
+            word = b[:, :, 0] | (b[:, :, 1] << 8) | (b[:, :, 2] << 16)
+            q = torch.stack([(word >> (6 * i)) & 0x3F for i in range(4)], dim=2).reshape(q.shape[0], -1)
         vals = _code_values(self.w_fmt).to(q.device)[q.long()]
         scale = torch.ldexp(torch.ones((), dtype=torch.float32, device=q.device), self.w_scale.to(torch.int32) - 127)
         w = (vals.view(self.out_features, self.kp // 32, 32) * scale[:, :, None]).view(self.out_features, self.kp)
@@ -127,7 +144,7 @@ class MXWeightOnlyLinear(MXLinear):
 
     # rows up to which the decode GEMV is taken: the measured crossover of the two kernels (profiles/mx/mx_wo_time.log)
     DECODE_MAX_M = ops.MX_GEMV_MAX_M
-    PAIRS, CELL = WEIGHT_ONLY_PAIRS, ", weight-only"
+    PAIRS, CELL, FP6_PAIRS = WEIGHT_ONLY_PAIRS, ", weight-only", ()  # no fp6 in the weight-only cell
 
     def __init__(self, in_features, out_features, bias=False, w_dtype="fp4", act_dtype="bf16", device="cuda", float_type=torch.float16):
         super().__init__(in_features, out_features, bias=bias, w_dtype=w_dtype, act_dtype=act_dtype, device=device, float_type=float_type)

@@ -313,7 +313,11 @@ class MXQuantConfig(TorchBaseConfig):
     """OCP microscaling linears (reference config.py MXQuantConfig: same fields).  The reference emulates the formats in float and
     defaults to MX-INT8 (`w_dtype="int8", act_dtype="int8"`); the block-scaled matrix instruction of the MI355X has no INT8 operand,
     so the defaults here are `w_dtype="fp8_e4m3", act_dtype="fp8_e4m3"` -- a deliberate deviation.  Supported (w_dtype, act_dtype):
-    ("fp8_e4m3", "fp8_e4m3"), ("fp4", "fp8_e4m3"), ("fp4", "fp4"), "fp4" being e2m1; `blocksize=32`, `round_method="nearest"`,
+    ("fp8_e4m3", "fp8_e4m3"), ("fp4", "fp8_e4m3"), ("fp4", "fp4"), "fp4" being e2m1, and for nn.Linear layers the MXFP6 pairs
+    ("fp6_e2m3", "fp6_e2m3"), ("fp6_e3m2", "fp6_e3m2"), ("fp6_e2m3", "fp8_e4m3"), ("fp4", "fp6_e2m3") -- the activation is never
+    narrower than the weight, so fp8 weights under fp6 activations (a6w8) raise, as do mixed e2m3 / e3m2, fp6 with
+    `weight_only=True` and fp6 through GPTQ-on-MX; under `quant_experts=True` an fp6 pair converts the Linears and leaves the experts
+    modules float with the usual warning; `blocksize=32`, `round_method="nearest"`,
     `weight_only=False`; `weight_only=True` selects the weight-only cell and takes `act_dtype="bf16"` with `w_dtype` "fp4" or
     "fp8_e4m3" (MXWeightOnlyLinear: MX weights against bf16 activations; with `quant_experts=True` the experts modules become
     MXWeightOnlyExperts / MXWeightOnlyGptOssExperts, without it they stay float); `out_dtype` is accepted and unused (the output has the activation's type).  `w_dtype="fp32"` (through
@@ -322,7 +326,8 @@ class MXQuantConfig(TorchBaseConfig):
 
     name = MX_QUANT
     supported_configs: List = []
-    PAIRS = (("fp8_e4m3", "fp8_e4m3"), ("fp4", "fp8_e4m3"), ("fp4", "fp4"))
+    PAIRS = (("fp8_e4m3", "fp8_e4m3"), ("fp4", "fp8_e4m3"), ("fp4", "fp4"),
+             ("fp6_e2m3", "fp6_e2m3"), ("fp6_e3m2", "fp6_e3m2"), ("fp6_e2m3", "fp8_e4m3"), ("fp4", "fp6_e2m3"))
     WEIGHT_ONLY_PAIRS = (("fp4", "bf16"), ("fp8_e4m3", "bf16"))
 
     def __init__(

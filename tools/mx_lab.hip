@@ -14,9 +14,11 @@
 //        -- the layout of two back-to-back 8-bit MFMAs of half the K -- so a 32-element block is spread over two lane groups;
 //   scales: lane group g supplies the scale of block g (k = 32 g .. 32 g + 31) of its row, in the byte of its scale register that
 //        opsel (0 .. 3) names (the lab puts wrong values in the other three bytes).
+//   fp6 (e2m3 = format 2, e3m2 = format 3): the fp4 map -- the lane holds the 32 elements of block g, element j in bits 6 j .. 6 j + 5
+//        of the little-endian 192-bit string in dwords 0 .. 5; dwords 6 and 7 are not read (the lab fills them with ones);
 // H0, the first guess for fp8 (a lane's 8 dwords are the 32 consecutive bytes of block g), also runs and must FAIL.
-// A mixed fp4 x fp8 product also runs with the fp4 nibbles swapped (hypothesis N'), which must FAIL: it shows the data tells the two
-// nibble orders apart.  A same-format product cannot see the element order inside a lane, and no product can see a relabelling of
+// A mixed-format product also runs with neighbouring elements of its sub-byte operand swapped (fp4 nibbles, fp6 fields: hypothesis
+// N'), which must FAIL: it shows the data tells the two element orders apart.  A same-format product cannot see the element order inside a lane, and no product can see a relabelling of
 // the blocks applied to A, B and both scales alike: H is established up to those, which is all a kernel can depend on.
 // Last case (for gemm_fp8.hip): the UNSCALED opcode v_mfma_f32_*_f8f6f4 against the scaled one with every scale byte
 // 127, fp8 x fp8 on the same data, both shapes -- they must agree bit for bit and with the exact product.
@@ -72,11 +74,15 @@ struct Variant { int R, cb, bl, oa, ob; kern_t k; };
 #define V(R, CB, BL, OA, OB) {R, CB, BL, OA, OB, one_mfma<R, CB, BL, OA, OB>}
 static const Variant variants[] = {
     V(32, 0, 0, 0, 0), V(32, 4, 4, 0, 0), V(32, 4, 0, 0, 0), V(32, 0, 4, 0, 0), V(32, 0, 0, 0, 3), V(32, 0, 0, 1, 2), V(32, 0, 0, 2, 1),
-    V(32, 0, 0, 3, 0), V(32, 4, 0, 2, 2), V(16, 0, 0, 0, 0), V(16, 4, 0, 0, 0), V(16, 4, 4, 2, 1), V(16, 0, 4, 1, 3)};
+    V(32, 0, 0, 3, 0), V(32, 4, 0, 2, 2), V(16, 0, 0, 0, 0), V(16, 4, 0, 0, 0), V(16, 4, 4, 2, 1), V(16, 0, 4, 1, 3),
+    // fp6, as the A and as the B operand of both shapes: the pairs gemm_mx.hip / gemm_mx_gemv.hip issue (A = weight, B = activation)
+    V(32, 2, 2, 0, 2), V(32, 3, 3, 2, 0), V(32, 2, 0, 0, 0), V(32, 0, 2, 1, 3), V(32, 4, 2, 2, 2), V(32, 3, 0, 0, 2), V(32, 0, 3, 0, 0),
+    V(16, 2, 2, 0, 0), V(16, 3, 3, 1, 2), V(16, 2, 0, 0, 0), V(16, 0, 2, 3, 1), V(16, 4, 2, 0, 0), V(16, 3, 0, 2, 0), V(16, 0, 3, 0, 1)};
 
 static int code_of(int v, int fmt) {
-  static const int c8[4] = {0x00, 0x38, 0x40, 0x44}, c4[4] = {0, 2, 4, 5};
+  static const int c8[4] = {0x00, 0x38, 0x40, 0x44}, c4[4] = {0, 2, 4, 5}, c23[4] = {0x00, 0x08, 0x10, 0x14}, c32[4] = {0x00, 0x0C, 0x10, 0x12};
   const int m = v < 0 ? -v : v;
+  if (fmt == 2 || fmt == 3) return (fmt == 2 ? c23[m] : c32[m]) | (v < 0 ? 0x20 : 0);
   return fmt == 0 ? (c8[m] | (v < 0 ? 0x80 : 0)) : (c4[m] | (v < 0 ? 8 : 0));
 }
 
@@ -88,16 +94,21 @@ struct Problem {
 
 static bool contiguous_fp8 = false;  // pack fp8 under H0
 static void pack(const Problem& p, bool isA, int fmt, int opsel, bool swap_nibbles, int* regs, int* sc) {
+  const bool fp6 = fmt == 2 || fmt == 3;
   for (int l = 0; l < 64; ++l) {
     const int row = l % p.R, blk = l / p.R;
     uint32_t w[8];
-    for (int d = 0; d < 8; ++d) w[d] = fmt == 0 ? 0u : (d < 4 ? 0u : 0xffffffffu);
+    for (int d = 0; d < 8; ++d) w[d] = fmt == 0 ? 0u : (d < (fp6 ? 6 : 4) ? 0u : 0xffffffffu);
     for (int j = 0; j < 32; ++j) {
       const int d = j >> 2, b = j & 3;
       const int k = (fmt == 0 && !contiguous_fp8) ? (p.R == 32 ? 32 : 64) * (d >> 2) + 16 * blk + 4 * (d & 3) + b : 32 * blk + j;
       const uint32_t cde = (uint32_t)code_of(isA ? p.A[row][k] : p.B[k][row], fmt);
       if (fmt == 0) w[j >> 2] |= cde << (8 * (j & 3));
-      else w[j >> 3] |= cde << (4 * ((swap_nibbles ? (j ^ 1) : j) & 7));
+      else if (fp6) {
+        const int bit = 6 * (swap_nibbles ? (j ^ 1) : j);
+        w[bit >> 5] |= cde << (bit & 31);
+        if ((bit & 31) > 26) w[(bit >> 5) + 1] |= cde >> (32 - (bit & 31));
+      } else w[j >> 3] |= cde << (4 * ((swap_nibbles ? (j ^ 1) : j) & 7));
     }
     memcpy(regs + l * 8, w, 32);
     const int s = isA ? p.SA[row][blk] : p.SB[row][blk];
@@ -168,7 +179,7 @@ int main() {
   static float out[1024];
   static Problem p;
   int failures = 0;
-  const char* fn[5] = {"fp8", "?", "?", "?", "fp4"};
+  const char* fn[5] = {"fp8", "?", "e2m3", "e3m2", "fp4"};
   for (const Variant& v : variants) {
     fill(p, v.R);
     if (run(p, v, false, false, out)) return 2;
@@ -185,10 +196,10 @@ int main() {
              alt ? "ok (H0 refuted)" : "FAIL (data cannot tell)");
       failures += alt == 0;
     }
-    if (v.cb != v.bl) {  // the nibble order matters only against the other format's byte order
-      if (run(p, v, v.cb == 4, v.bl == 4, out)) return 2;
+    if (v.cb != v.bl) {  // the element order matters only against the other format's order: swap one sub-byte operand's pairs
+      if (run(p, v, v.cb != 0, v.cb == 0, out)) return 2;
       const int alt = mismatches(p, out);
-      printf("        same with the fp4 nibbles swapped (N'):          %4d / %d differ  %s\n", alt, v.R * v.R,
+      printf("        same with the %4s pairs swapped (N'):            %4d / %d differ  %s\n", fn[v.cb != 0 ? v.cb : v.bl], alt, v.R * v.R,
              alt ? "ok (N' refuted)" : "FAIL (data cannot tell)");
       failures += alt == 0;
     }
